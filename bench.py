@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- rays/s of the TransHuman rendering hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload real|dense]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload real|dense] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -322,6 +322,30 @@ def fused_vs_fp32(renderer, b, hip):
             "vs": "per-layer fp32 MFMA path (th_set_mlp_mode 0), same kernels otherwise; bar 5e-5 (half the 1e-4 budget)"}
 
 
+DUMP_BYTES = 60 * 10**6          # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per array in float32, so that two
+    builds can be compared output for output.  Past DUMP_BYTES in all, every array keeps the same fraction of the entries
+    along its longest axis (rays, voxels), a sorted sample drawn with a fixed seed: the same entries on every run with the
+    same arguments, and the same rays in arrays of the same length."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    for k, a in out.items():
+        if total > DUMP_BYTES:
+            ax = int(np.argmax(a.shape))
+            n = a.shape[ax] * DUMP_BYTES // total
+            a = np.take(a, np.sort(np.random.default_rng(0).choice(a.shape[ax], size=n, replace=False)), axis=ax)
+        np.save(os.path.join(path, f"{k}.npy"), a)
+
+
+def split_image(img):
+    """[R, 5] rgb | acc | depth of a frame -> the arrays Renderer.render_fast returns ([1, R, 3], [1, R], [1, R])"""
+    return {"rgb_map": img[None, :, :3], "acc_map": img[None, :, 3], "depth_map": img[None, :, 4]}
+
+
 def time_steps(fn, steps, warmup=1):
     for _ in range(warmup):
         fn()
@@ -511,7 +535,12 @@ def main():
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="developer aid: on ONE GPU render rank 0's shard of an N-rank job (no collectives); the JSON "
                          "line is then per-rank time, not a bench result")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, "
+                         "at most 64 MB in all: a fixed, seeded sample of larger outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -672,6 +701,8 @@ def main():
     if rank == 0 and os.environ.get("TH_SAVE_IMAGE"):     # developer aid: the last timed frame [R, 5] (rgb, acc, depth)
         import numpy as _np
         _np.save(os.environ["TH_SAVE_IMAGE"], img.detach().cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, split_image(img))
     prof = hip.profile_read()
     hip.profile_enable(False)
     step_ms = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]) if args.steps > 0 else np.zeros(1)
@@ -949,6 +980,8 @@ def run_secondary(args, world, rank, dev, dist_on, renderer, net, batch, batch_c
     dt = time.perf_counter() - t0
     if rank == 0 and os.environ.get("TH_SAVE_IMAGE"):     # developer aid: the last frame [R, 5] / sigma grid [grid^3]
         np.save(os.environ["TH_SAVE_IMAGE"], res.detach().cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, split_image(res) if args.workload == "orbit" else {"sigma": res})
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if dist_on:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

@@ -214,3 +214,24 @@ def test_bench_reads_the_committed_hbm_traffic():
     blk4 = bench.roofline_block(1, 5.0e14, 9.4e12, 17.9, 4.0, n_valid=n)
     assert abs(blk4["traffic"] - 0.5 * t["mlp_fused_bytes_per_launch"]) < 1.0
     assert blk["traffic_per_frame"]["measured_K4_K5_K6_bytes"] > 2 * t["mlp_fused_bytes_per_launch"]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the frame's rgb / acc / depth as render_fast returns them, float32, bit for bit; outputs past
+    the size cap are cut to the same seeded sample on every run, and arrays of one length keep the same rows"""
+    import os
+    import bench
+    img = torch.rand(4096, 5, generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(str(tmp_path / "a"), bench.split_image(img))
+    d = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("rgb_map", "acc_map", "depth_map")}
+    assert d["rgb_map"].shape == (1, 4096, 3) and d["acc_map"].shape == d["depth_map"].shape == (1, 4096)
+    assert all(v.dtype == np.float32 for v in d.values())
+    assert np.array_equal(np.concatenate([d["rgb_map"][0], d["acc_map"][0][:, None], d["depth_map"][0][:, None]], 1), img.numpy())
+    big = {"x": torch.arange(bench.DUMP_BYTES // 4 + 4096, dtype=torch.float32), "y": torch.arange(1000, dtype=torch.float64)}
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    sizes = [os.path.getsize(tmp_path / "b" / f"{k}.npy") for k in big]
+    assert sum(sizes) <= 64 * 10**6
+    for k in big:
+        b, c = np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "c" / f"{k}.npy")
+        assert b.dtype == np.float32 and np.array_equal(b, c) and 0 < len(b) < len(big[k]) and np.all(np.diff(b) > 0)
