@@ -454,6 +454,19 @@ int th_marching_cubes_emit(th_ctx* ctx, const float* cube, int X, int Y, int Z, 
                            int x0, int x1, const double* scale_host /* [3] */, const double* origin_host /* [3] */,
                            double* verts, int32_t* tris, th_stream stream);
 
+/* ---- evaluator metrics: SSIM ------------------------------------------------ */
+/* lib/evaluators/if_nerf.py:108: skimage's structural_similarity(img_pred, img_gt, multichannel=True) of the evaluator's
+ * cropped H x W x 3 float64 images, read as skimage 0.19 computes it for a float64 image without data_range: per channel a
+ * 7 x 7 uniform window with sample covariance (49 / 48), data_range 2 (C1 = 4e-4, C2 = 3.6e-3), the mean of the SSIM map over
+ * the pixels whose window lies inside the image (rows / columns 3 .. n - 4), then the mean over the channels.  (Pinned by the
+ * formula, not by a run of skimage, which is third-party and absent.)
+ * a, b: fp32 images [h][w][c] channel-last, rows `pitch` floats apart (>= w * c; a crop of a larger frame is a pointer offset
+ * into it); all arithmetic in fp64.  out: ONE double on the device, bit-identical from run to run (fixed-order reduction, no
+ * atomics).  Two launches on `stream`.  h < 7 or w < 7: error (skimage raises ValueError); the workspace query then gives 0. */
+size_t th_ssim_workspace_bytes(int h, int w, int c);
+int th_ssim(th_ctx* ctx, const float* a, const float* b, int h, int w, int c, int pitch, double* out, void* workspace,
+            size_t workspace_bytes, th_stream stream);
+
 /* ---- K10: SMPL linear blend skinning ------------------------------------ */
 /* SMPL._call, lib/utils/SMPL.py:114-186, float64 like the reference.  Model arrays (DEVICE pointers, the fields
  * the reference reads from the SMPL pickle, :83-89): v_template [nv,3], shapedirs [nv,3,10], posedirs [nv,3,207],

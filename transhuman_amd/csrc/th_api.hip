@@ -694,6 +694,16 @@ int th_bound_mask(th_ctx* c, const int32_t* corners_xy_host, int H, int W, uint8
     return th_bound_mask_launch(corners_xy_host, H, W, mask, (hipStream_t)stream);
 }
 
+size_t th_ssim_workspace_bytes(int h, int w, int c) { return th_ssim_ws(h, w, c); }
+
+int th_ssim(th_ctx* c, const float* a, const float* b, int h, int w, int ch, int pitch, double* out, void* ws, size_t ws_bytes,
+            th_stream stream) {
+    TH_REQUIRE(c && a && b && out && ws, "null argument");
+    TH_REQUIRE(h >= 7 && w >= 7, "image is " + std::to_string(h) + " x " + std::to_string(w) +
+                                     ": SSIM needs at least 7 x 7 pixels (skimage raises ValueError)");
+    return th_ssim_launch(a, b, h, w, ch, pitch, out, ws, ws_bytes, (hipStream_t)stream);
+}
+
 size_t th_marching_cubes_workspace_bytes(int X, int Y, int Z) { return th_mc_ws(X, Y, Z) + 256; }
 
 int th_marching_cubes_count(th_ctx* c, const float* cube, int X, int Y, int Z, float iso, void* ws, size_t ws_bytes,

@@ -519,5 +519,9 @@ int th_bn_act_launch(const float* x, const float* res, int N, int C, int HW, con
                      size_t ws_bytes, hipStream_t s, int eval = 0, const void* conv_stats = nullptr, int conv_np = 0);
 int th_fold_color_launch(const float* W /*[N,384]*/, const float* b, const float* wc /*[128,3]*/, const float* bc,
                          int N, float* Wo /*[N,260]*/, float* bo /*[N]*/, hipStream_t s);
+// k_metrics.hip: SSIM of two channel-last fp32 images (skimage 0.19 structural_similarity, 7 x 7 uniform window), fp64
+size_t th_ssim_ws(int h, int w, int c);
+int th_ssim_launch(const float* a, const float* b, int h, int w, int c, long long pitch, double* out, void* ws,
+                   size_t ws_bytes, hipStream_t s);
 int th_segmean_masked_launch(const float* rows, int V, int width, const uint8_t* viz, int nv, const int32_t* off,
                              const int32_t* mem, int nc, float* out, hipStream_t s);

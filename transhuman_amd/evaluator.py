@@ -4,17 +4,26 @@
 Mirrors /root/reference/lib/evaluators/if_nerf.py: ``evaluate(output, batch)`` appends the frame's MSE and PSNR
 (:34-37, :121-130), rebuilds the H x W image from the rays inside the body box (`mask_at_box`, :41-57), crops it to the
 mask's bounding rectangle (:60-62) and writes `pred/frame{i}_view{v}.png` and `gt/..._gt.png` under
-`<result_dir>/<human>/` (:64-99); ``summarize()`` stores `mse.npy` / `psnr.npy` and returns the means (:146-170).
+`<result_dir>/<human>/` (:64-99); ``summarize()`` stores `mse.npy` / `psnr.npy` / `ssim.npy` and returns the means
+(:146-175; `lpips.npy` is not written).
 PNG files are written with PIL (cv2 is absent; `cv2.imwrite` of a float image = round-to-nearest, saturate to uint8,
-and the reference's RGB -> BGR swap followed by cv2's BGR file order is the identity on the stored RGB).  SSIM
-(skimage) and LPIPS (a VGG network download) are third-party, absent here and not part of the rendering path:
-``ssim`` / ``lpips`` stay empty lists.
+and the reference's RGB -> BGR swap followed by cv2's BGR file order is the identity on the stored RGB).
+
+SSIM (:108, `structural_similarity(img_pred, img_gt, multichannel=True)` on the cropped float64 images) is computed on
+the device by `hip.ssim` (csrc/k_metrics.hip) from cropped float32 images assembled on the device with the same fill and
+crop as ``images()``.  skimage is third-party and absent, so the metric is pinned by its formula -- skimage 0.19's, the
+releases that take data_range from the float64 dtype: 7 x 7 uniform window, sample covariance, data_range 2, mean over the
+window-interior pixels of each channel, then over the channels -- not by a run of skimage.  Like skimage, a crop smaller
+than 7 x 7 raises ValueError.  Without a visible HIP device SSIM is skipped (the list stays empty: there is no CPU path).
+LPIPS needs torchvision's pretrained VGG16 (a download) and a VGG conv stack the project does not build: ``lpips`` stays
+an empty list.
 """
 import os
 
 import numpy as np
 import torch
 
+from . import hip
 from .config import get_cfg
 from .mesh import psnr_metric
 
@@ -61,6 +70,23 @@ class Evaluator:
         x, y, w, h = bounding_rect(m)
         return pred[y:y + h, x:x + w], gt[y:y + h, x:x + w]
 
+    def ssim_metric(self, rgb_pred, rgb_gt, batch, H=None, W=None):
+        """(:39-62, :108) SSIM of the cropped images of ``images()``, assembled as float32 on the device -> hip.ssim"""
+        cfg = get_cfg()
+        if H is None:
+            H, W = int(cfg.H * cfg.ratio), int(cfg.W * cfg.ratio)
+        dev = rgb_pred.device if torch.is_tensor(rgb_pred) and rgb_pred.is_cuda else \
+            torch.device("cuda", torch.cuda.current_device())
+        m = torch.as_tensor(batch["mask_at_box"][0], device=dev).reshape(H, W).bool()
+        x, y, w, h = bounding_rect(_np(m))
+        m = m[y:y + h, x:x + w]
+        fill = 1.0 if cfg.white_bkgd else 0.0
+        pred = torch.full((h, w, 3), fill, dtype=torch.float32, device=dev)
+        gt = torch.full((h, w, 3), fill, dtype=torch.float32, device=dev)
+        pred[m] = torch.as_tensor(rgb_pred, device=dev).to(torch.float32)
+        gt[m] = torch.as_tensor(rgb_gt, device=dev).to(torch.float32)
+        return hip.ssim(pred, gt)
+
     def evaluate(self, output, batch, H=None, W=None, save=True):
         from PIL import Image
         rgb_pred = _np(output["rgb_map"][0])
@@ -68,6 +94,10 @@ class Evaluator:
         mse = float(np.mean((rgb_pred - rgb_gt) ** 2))                     # :124
         self.mse.append(mse)
         self.psnr.append(self.psnr_metric(rgb_pred, rgb_gt))               # :127
+        out = {"mse": mse, "psnr": self.psnr[-1]}
+        if "mask_at_box" in batch and hip._gpu_visible():
+            self.ssim.append(self.ssim_metric(output["rgb_map"][0], batch["rgb"][0], batch, H, W))   # :131-133
+            out["ssim"] = self.ssim[-1]
         if save and "mask_at_box" in batch:
             pred, gt = self.images(rgb_pred, rgb_gt, batch, H, W)
             human = batch["human_name"][0] if "human_name" in batch else "human"
@@ -77,13 +107,15 @@ class Evaluator:
                 d = os.path.join(self.result_dir, human, sub)
                 os.makedirs(d, exist_ok=True)
                 Image.fromarray(to_uint8(img)).save(os.path.join(d, f"frame{frame}_view{view}{suffix}.png"))
-        return {"mse": mse, "psnr": self.psnr[-1]}
+        return out
 
     def summarize(self):
         os.makedirs(self.result_dir, exist_ok=True)
         np.save(os.path.join(self.result_dir, "mse.npy"), self.mse)
         np.save(os.path.join(self.result_dir, "psnr.npy"), self.psnr)
+        np.save(os.path.join(self.result_dir, "ssim.npy"), self.ssim)
         out = {"mse": float(np.mean(self.mse)) if self.mse else float("nan"),
-               "psnr": float(np.mean(self.psnr)) if self.psnr else float("nan")}
+               "psnr": float(np.mean(self.psnr)) if self.psnr else float("nan"),
+               "ssim": float(np.mean(self.ssim)) if self.ssim else float("nan")}
         self.mse, self.psnr, self.ssim, self.lpips = [], [], [], []
         return out

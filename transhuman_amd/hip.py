@@ -138,6 +138,9 @@ SYMBOLS = {
     "th_gen_rays": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_int, C.c_int, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "th_bound_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "th_ssim_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                          C.c_size_t, C.c_void_p]),
     "th_marching_cubes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "th_marching_cubes_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                           C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),
@@ -1137,6 +1140,28 @@ def bound_2d_mask(bounds, K, pose, H, W, device=None):
     mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
     _check(lib.th_bound_mask(ctx(dev), c2.ctypes.data_as(C.POINTER(C.c_int32)), H, W, _p(mask), _stream()))
     return mask
+
+
+def ssim(a, b):
+    """th_ssim: skimage 0.19's structural_similarity(a, b, multichannel=True) as lib/evaluators/if_nerf.py:108 calls it on
+    float64 images (7 x 7 uniform window, sample covariance, data_range 2, mean over the window-interior pixels, then over
+    the channels), computed in fp64 on the device.  a, b: float32 [H, W, C] device tensors or strided views of larger
+    frames (channels contiguous, pixels C floats apart); runs on the current stream and returns a Python float (waits for
+    it).  ValueError below 7 x 7, like skimage."""
+    if a.dim() != 3 or a.shape != b.shape:
+        raise ValueError(f"ssim expects two images of the same [H, W, C] shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    H, W, Cc = (int(n) for n in a.shape)
+    if H < 7 or W < 7:
+        raise ValueError(f"ssim: a {H} x {W} image is smaller than the 7 x 7 window")
+    assert a.is_cuda and b.is_cuda and a.device == b.device, "expected two tensors on the same device"
+    assert a.dtype is torch.float32 and b.dtype is torch.float32, "expected float32 images"
+    if not (a.stride() == b.stride() and a.stride(2) == 1 and a.stride(1) == Cc and a.stride(0) >= W * Cc):
+        a, b = a.contiguous(), b.contiguous()
+    lib = load_library()
+    ws = _ws(lib.th_ssim_workspace_bytes(H, W, Cc), a.device)
+    out = torch.empty(1, dtype=torch.float64, device=a.device)
+    _check(lib.th_ssim(ctx(a.device), _p(a), _p(b), H, W, Cc, int(a.stride(0)), _p(out), _p(ws), ws.numel(), _stream()))
+    return float(out.item())
 
 
 def marching_cubes(cube, iso, scale=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), x_range=None):
