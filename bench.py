@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- rays/s of the TransHuman rendering hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload real|dense] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload real|dense] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,15 +16,19 @@ diagonal 8x8-pixel tiles, the encoder's constants are recomputed on every rank
 j mod N and its tokens are broadcast, and the image is assembled with one RCCL
 all_gather -- "strong" scaling: total work fixed, value = rays of the frame /
 max-over-ranks time.  The timed loop runs Renderer.render_sequence (the frame
-constants of frame i+1 on a second stream under the shading of frame i); the
-reference's own call pattern, render_fast per frame, is timed after it and
-reported as render_fast_ms_per_step, followed by the `extra` block (the other
-configurations of BASELINE.json, each with an oracle spot check).
+constants of frame i+1 on a second stream under the shading of frame i).
 
-Rank 0 prints ONE JSON line; `roofline` is for the dominant kernel (the fused per-point MLP: fp32-class arithmetic
-as three fp16 MFMA products per MAC), measured live with HIP events on the launch stream;
-`cpu_baseline` is the CPU oracle (oracle/th_oracle.py, a port of the reference
-arithmetic) timed on this host on a bounded sample of the same frame.
+Rank 0 prints ONE JSON line.  A plain run reports only what the timed steps
+themselves measured (rays/s, per-step spread, stage spans, host cost, shader
+clock) and exits.  With --full, what needs runs of its own follows the timed
+steps: the sigma > 0 count behind `roofline` for the dominant kernel (the fused
+per-point MLP: fp32-class arithmetic as three fp16 MFMA products per MAC,
+measured live with HIP events on the launch stream), the fused kernel's cycles
+from inside, the reference's own call pattern (render_fast per frame,
+render_fast_ms_per_step), fused vs fp32 over a whole frame, `cpu_baseline` (the
+CPU oracle, oracle/th_oracle.py, a port of the reference arithmetic, timed on
+this host on a bounded sample of the same frame) and the `extra` block (the
+other configurations of BASELINE.json, each with an oracle spot check).
 """
 import argparse
 import itertools
@@ -508,7 +512,7 @@ def run_extras(dev, net, args, H, W, V):
     return extra
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)          # (1.5 s of timed frames at N = 1)
@@ -520,9 +524,14 @@ def main():
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--nc", type=int, default=500)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the short post-run measurements of the other configurations")
-    ap.add_argument("--cpu-stride", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's own measurements, everything that needs runs of its own: the sigma > 0 "
+                         "count and the roofline, the fused kernel's cycles, render_fast per frame, fused vs fp32, the CPU "
+                         "baseline and the extras (the other configurations, each with an oracle spot check)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (and the extras)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the short post-run measurements of the other "
+                                                             "configurations")
+    ap.add_argument("--cpu-stride", type=int, default=128, help="with --full: the CPU baseline renders every CPU_STRIDE-th ray")
     ap.add_argument("--dense-oracle-rays", type=int, default=1024,
                     help="extras: rays of the all-valid S_dense_full frame checked against the CPU oracle")
     ap.add_argument("--mlp-mode", type=int, default=1, help="1 fused fp16-split MFMA kernel, 0 per-layer fp32 MFMA")
@@ -538,9 +547,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, "
                          "at most 64 MB in all: a fixed, seeded sample of larger outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -713,20 +727,21 @@ def main():
 
     # algorithmic work of the dominant stage on this rank (counts from the rendered frames themselves: the mean over the
     # alternating frames)
-    per_frame = []
-    for k, sh in enumerate(frames):
-        st_k = stats_of.get(k, stats)
-        pts = hip.Points(sh["ray_o"][0], sh["ray_d"][0], sh["near"][0], sh["far"][0], args.samples)
-        frame = renderer.prepare_frame(batches[k])
-        nv_k = st_k["valid_samples"]
-        per_frame.append({"hit_rays": int(st_k["hit_rays"]), "valid_samples": int(nv_k),
-                          "sigma_pos_samples": int(count_sigma_positive(hip, net, frame, pts) if st_k["unmasked"] == 0 else nv_k)})
+    per_frame = [{"hit_rays": int(stats_of.get(k, stats)["hit_rays"]), "valid_samples": int(stats_of.get(k, stats)["valid_samples"])}
+                 for k in range(len(frames))]
     n_valid = int(round(sum(f["valid_samples"] for f in per_frame) / len(per_frame)))
-    n_pos = int(round(sum(f["sigma_pos_samples"] for f in per_frame) / len(per_frame)))
+    if args.full:
+        # the RGB branch's work: the samples with sigma_raw > 0, from a sigma evaluation of every frame of its own
+        for k, sh in enumerate(frames):
+            pts = hip.Points(sh["ray_o"][0], sh["ray_d"][0], sh["near"][0], sh["far"][0], args.samples)
+            frame = renderer.prepare_frame(batches[k])
+            per_frame[k]["sigma_pos_samples"] = int(count_sigma_positive(hip, net, frame, pts)
+                                                    if stats_of.get(k, stats)["unmasked"] == 0 else per_frame[k]["valid_samples"])
+        n_pos = int(round(sum(f["sigma_pos_samples"] for f in per_frame) / len(per_frame)))
     # the fused kernel from inside (th_fused_cycles): cycles per phase and per tile, and the shader clock UNDER the kernel, over
     # one un-pipelined frame of each kind after the timed region
     fused_inside = None
-    if args.mlp_mode == 1 and world == 1 and os.environ.get("TH_NO_PROF") != "1":
+    if args.full and args.mlp_mode == 1 and world == 1 and os.environ.get("TH_NO_PROF") != "1":
         cnt = torch.zeros(64, dtype=torch.int64, device=dev)
         hip.fused_cycles(cnt)
         try:
@@ -745,9 +760,6 @@ def main():
                             "note": "thread 0 of every 16th tile, one frame of each kind through render_fast after the timed region; "
                                     "mfma cycles = the tile's MFMA instructions x their issue interval on one SIMD (2 988 x 16.6 / 1 494 x 32)"}
     mlp_ms, mlp_launches = prof["mlp"]
-    flops_step = algorithmic_mlp_flops(V, n_valid, n_pos)
-    mlp_s_per_step = mlp_ms * 1e-3 / max(args.steps, 1)
-    achieved = flops_step / max(mlp_s_per_step, 1e-12)
 
     if rank == 0:
         res = {
@@ -776,15 +788,11 @@ def main():
                             f"hull mask + DPaRF + pixel gather + MLP + compositing",
                 "frames_alternating": per_frame,
                 "rays": R, "hit_rays_rank0": stats["hit_rays"], "valid_samples_rank0": n_valid,
-                "sigma_pos_samples_rank0": n_pos, "parallelism": f"ray-tile x{world}" if world > 1 else "single",
+                "parallelism": f"ray-tile x{world}" if world > 1 else "single",
                 "frame_pipeline": "off" if seq is None else "constants(i+1) on a 2nd HIP stream under shading(i)",
                 "stem_exchange": stem_x is not None,
                 "map_crop": os.environ.get("TH_MAP_CROP") != "0",      # pixel map written inside the hull's texel box only
             },
-            "roofline": roofline_block(args.mlp_mode, achieved, flops_step, mlp_ms / max(args.steps, 1),
-                                       mlp_launches / max(args.steps, 1), executed_mlp_flops(V, n_valid, n_pos, map_fold=args.mlp_mode == 1 and hip.tex_rows_enabled(dev)), n_valid=n_valid,
-                                       folded_flops=(2.0 * V * (98304.0 * n_valid + 147456.0 * n_pos)) if (args.mlp_mode == 1 and hip.tex_rows_enabled(dev)) else 0.0,
-                                       fold_ms=prof["fold"][0] / max(args.steps, 1)),
             "gather": (texel_handover_block if hip.tex_rows_enabled(dev) else gather_block)(V, n_valid, prof["gather"][0] / max(args.steps, 1)),
             # what the range guard of the fp16 hi/lo split has switched on this device (every entry false = the fast paths
             # ran; a tripped MLP guard means per-layer fp32 launches, ~7x slower frames) + the last table read (fp16 bit
@@ -803,6 +811,14 @@ def main():
                           "other stages (their spans are stretched by the overlap and do not add to the frame time); vit = 0: "
                           "TransHE is a replayed hipGraph in the frame paths, its launches carry no stage events",
         }
+        if args.full:
+            flops_step = algorithmic_mlp_flops(V, n_valid, n_pos)
+            achieved = flops_step / max(mlp_ms * 1e-3 / max(args.steps, 1), 1e-12)
+            res["config"]["sigma_pos_samples_rank0"] = n_pos
+            res["roofline"] = roofline_block(args.mlp_mode, achieved, flops_step, mlp_ms / max(args.steps, 1),
+                                             mlp_launches / max(args.steps, 1), executed_mlp_flops(V, n_valid, n_pos, map_fold=args.mlp_mode == 1 and hip.tex_rows_enabled(dev)), n_valid=n_valid,
+                                             folded_flops=(2.0 * V * (98304.0 * n_valid + 147456.0 * n_pos)) if (args.mlp_mode == 1 and hip.tex_rows_enabled(dev)) else 0.0,
+                                             fold_ms=prof["fold"][0] / max(args.steps, 1))
         if fused_inside is not None:
             # the roofline priced at the clock the chip holds under the kernel (the peaks above assume 2.4 GHz)
             g = fused_inside["clock_GHz_inside_the_launch"]
@@ -818,7 +834,7 @@ def main():
                                   "headline_reserved": torch.cuda.max_memory_reserved(dev) / 2**30}
         if emu:
             res["config"]["emulated_rank0_of"] = emu
-        if world == 1 and not emu:
+        if args.full and world == 1 and not emu:
             # the reference's own call pattern (run.py:96-118 calls renderer.render_fast per item, no look-ahead):
             # measured after the timed region on the same device
             ms_rf, _ = time_steps(lambda: renderer.render_fast(shard), max(3, args.steps // 2), warmup=1)
@@ -830,9 +846,9 @@ def main():
             res["dropin_rays_per_s"] = R / ms_rf * 1e3
             if args.mlp_mode == 1 and not args.no_extras:
                 res["fused_vs_fp32_full_frame"] = fused_vs_fp32(renderer, batch, hip)
-        if world == 1 and not args.no_cpu_baseline and not emu:
+        if args.full and world == 1 and not args.no_cpu_baseline and not emu:
             res["cpu_baseline"] = cpu_baseline(batch_cpu, assign, args.samples, stride=args.cpu_stride, gpu_img=img)
-        if world == 1 and not args.no_extras and not args.no_cpu_baseline and not emu and args.workload == "real":
+        if args.full and world == 1 and not args.no_extras and not args.no_cpu_baseline and not emu and args.workload == "real":
             try:        # secondary numbers must never cost the headline line
                 res["extra"] = run_extras(dev, net, args, H, W, V)
             except Exception as e:        # noqa: BLE001

@@ -235,3 +235,11 @@ def test_bench_dump_outputs(tmp_path):
     for k in big:
         b, c = np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "c" / f"{k}.npy")
         assert b.dtype == np.float32 and np.array_equal(b, c) and 0 < len(b) < len(big[k]) and np.all(np.diff(b) > 0)
+
+
+def test_bench_full_is_opt_in():
+    """a plain bench.py run measures the headline only; the measurements that need runs of their own come with --full"""
+    import bench
+    a = bench.parse_args([])
+    assert not a.full and a.steps == 100 and a.warmup == 5 and a.dump_outputs is None
+    assert bench.parse_args(["--full", "--steps", "3"]).full

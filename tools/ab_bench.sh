@@ -1,12 +1,12 @@
 #!/bin/bash
 # A/B of library variants / env switches on ONE box: tools/ab_bench.sh OUTDIR "name|ENV=.. ENV=.." ...
-# each case: bench.py --steps 8 --warmup 3 with TH_FUSED_DBG=1 -> one summary line (frame ms, MLP ms, gather, dparf, tile cycles)
+# each case: bench.py --full --steps 8 --warmup 3 with TH_FUSED_DBG=1 -> one summary line (frame ms, MLP ms, gather, dparf, tile cycles)
 out=$GRAFT_REPO_ROOT/$1; shift
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
 for case in "$@"; do
   name=${case%%|*}; envs=${case#*|}
-  env $envs TH_FUSED_DBG=1 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-extras > $out/$name.json 2> $out/$name.err
+  env $envs TH_FUSED_DBG=1 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-extras > $out/$name.json 2> $out/$name.err
   python - "$name" "$out/$name.json" "$out/$name.err" <<'PY'
 import json, sys
 name, j, e = sys.argv[1:4]

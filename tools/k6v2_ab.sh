@@ -6,7 +6,7 @@ mkdir -p $out
 cd $GRAFT_REPO_ROOT
 for w in 4 8 4 8; do
   n=w$w; [ -e $out/$n.json ] && n=${n}b
-  TH_FUSED_WAVES=$w TH_FUSED_DBG=1 TH_SAVE_IMAGE=$out/img_w$w.npy timeout 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $out/$n.json 2> $out/$n.err
+  TH_FUSED_WAVES=$w TH_FUSED_DBG=1 TH_SAVE_IMAGE=$out/img_w$w.npy timeout 600 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $out/$n.json 2> $out/$n.err
   python - "$n" "$out/$n.json" "$out/$n.err" <<'PY'
 import json, sys
 name, j, e = sys.argv[1:4]

@@ -5,7 +5,7 @@ mkdir -p $out
 cd $GRAFT_REPO_ROOT
 for case in "$@"; do
   name=${case%%|*}; envs=${case#*|}
-  env $envs timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras > $out/$name.json 2> $out/$name.err
+  env $envs timeout 600 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras > $out/$name.json 2> $out/$name.err
   python - "$name" "$out/$name.json" <<'PY'
 import json, sys
 name, j = sys.argv[1:3]
