@@ -243,3 +243,20 @@ def test_bench_full_is_opt_in():
     a = bench.parse_args([])
     assert not a.full and a.steps == 100 and a.warmup == 5 and a.dump_outputs is None
     assert bench.parse_args(["--full", "--steps", "3"]).full
+
+
+def test_readme_lists_every_environment_switch():
+    """README's switch table names exactly the TH_* environment variables that the package, bench.py and
+    __graft_entry__.py read (getenv("..."), os.environ.get("...", os.environ["..."], "..." in os.environ)"""
+    import glob
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    files = [p for ext in ("py", "hip", "h") for p in glob.glob(os.path.join(root, "transhuman_amd", "**", "*." + ext), recursive=True)]
+    files += [os.path.join(root, "bench.py"), os.path.join(root, "__graft_entry__.py")]
+    read = re.compile(r'(?:getenv\(|os\.environ\.get\(|os\.environ\[)"(TH_[A-Z0-9_]+)"|"(TH_[A-Z0-9_]+)" in os\.environ')
+    used = {a or b for p in files for a, b in read.findall(open(p).read())}
+    readme = open(os.path.join(root, "README.md")).read()
+    table = readme.split("## Environment switches", 1)[1].split("\n\n", 2)[1]
+    listed = {n for row in table.splitlines() if row.startswith("| `TH_") for n in re.findall(r"TH_[A-Z0-9_]+", row.split("|")[1])}
+    assert used and used == listed, (sorted(used - listed), sorted(listed - used))

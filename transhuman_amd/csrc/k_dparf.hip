@@ -20,8 +20,6 @@
 // fp32 [sample][view][256] (64 lanes x float4: every lane busy), and pe_out = the blended 63-wide positional
 // encoding, ONE split-f16 row (64 hi + 64 lo halves) per sample -- it is the same for every view.
 // Bound: L2 gather of 7*V*768 B per sample; HBM write 3 KB per sample.
-#include <stdlib.h>
-
 #include "th_internal.h"
 
 #define DP_K 7
@@ -548,14 +546,13 @@ int th_dparf_launch(const float* pts_smpl, const ThPointSrc* ps, const float* Rh
         cnt = ar.take<int>(DPG_MAXCELLS);
         cand = ar.take<int>((size_t)DPG_MAXCELLS * DPG_STRIDE);
     }
-    static const bool per_view = getenv("TH_DPARF_PER_VIEW") != nullptr;       // A/B switch
     if (fmt == TH_ROWS_NBR) {
         static unsigned long long attrn = 0ull;
         if (th_lds_attr_needed(&attrn))
             TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<true, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL((dparf_kernel<true, -1>), dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
                            Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gi, cnt, cand);
-    } else if (fmt == TH_ROWS_FOLDED && V == 3 && !per_view) {
+    } else if (fmt == TH_ROWS_FOLDED && V == 3) {
         static unsigned long long attr3 = 0ull;
         if (th_lds_attr_needed(&attr3))
             TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

@@ -15,8 +15,6 @@
 //   image, so one coalesced 1 KiB global_load_dwordx4 per wave fetches a whole
 //   16(k) x 16(n) block straight into the MFMA operand registers (weights are
 //   <= 1.2 MB per layer and stay L2-resident; no LDS round trip for them).
-#include <stdlib.h>
-
 #include "th_internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -273,8 +271,7 @@ static int gemm_launch(const float* A, int lda, int M, const ThPacked& W, int fl
     // the chip several times over (these launches are latency-bound: co-resident workgroups hide the L2 round
     // trips of each other's weight fragments)
     const bool small = M <= 8192;
-    static const int small_nt = getenv("TH_GEMM_SMALL_NT") ? atoi(getenv("TH_GEMM_SMALL_NT")) : 1;
-    int nt = small ? (small_nt >= 1 && small_nt <= 4 ? small_nt : pick_nt(W.NB)) : pick_nt(W.NB);
+    const int nt = small ? 1 : pick_nt(W.NB);
     const int bm = small ? 16 : GEMM_BM;
     dim3 grid(th_cdiv(M, bm), th_cdiv(W.NB, 4 * nt));
     size_t lds = (size_t)bm * GEMM_LDS_STRIDE * sizeof(float);
@@ -370,10 +367,10 @@ int th_pack_linear_h3(const th_linear& lin, void* storage_h3, ThPacked* out, hip
 }
 
 #define H3_RING 6
-// RT row tiles of 16 per workgroup.  A workgroup streams its 64 columns of the weight image (4 K bytes per column) once per
-// 16 RT rows: with RT = 1 the V N_c = 1500 rows of the ViT re-read every layer's weights 94 times (41-55 MB of L2 traffic
-// per GEMM: that, not latency, bounded the 9-10 us launches); RT = 2 / 4 halves / quarters it and gives a wave 2 / 4
-// independent accumulators per product term.
+// RT row tiles of 16 per workgroup; only RT = 1 is instantiated (th_gemm_h3 says why).  A workgroup streams its 64 columns of
+// the weight image (4 K bytes per column) once per 16 RT rows: with RT = 1 the V N_c = 1500 rows of the ViT re-read every
+// layer's weights 94 times (41-55 MB of L2 traffic per GEMM: that, not latency, bounded the 9-10 us launches); RT = 2 / 4
+// halves / quarters it and gives a wave 2 / 4 independent accumulators per product term.
 template <bool LN, int RT>
 __global__ __launch_bounds__(256) void gemm_h3_kernel(const float* __restrict__ A, int lda, int M, int Kreal,
                                                       const uint4* __restrict__ W16, const float* __restrict__ inv_scale,
@@ -584,30 +581,20 @@ int th_gemm_h3(const float* A, int lda, int M, const ThPacked& W, const float* l
     const int KP = W.KB32 * 32;
     static unsigned long long attr = 0ull;
     if (th_lds_attr_needed(&attr)) {
-        const int mx = 2 * 16 * 4 * (2 * 256 + 16), mx2 = 2 * 16 * 2 * (2 * 768 + 16);
-        TH_HIP(hipFuncSetAttribute((const void*)gemm_h3_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, mx2));
-        TH_HIP(hipFuncSetAttribute((const void*)gemm_h3_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, mx2));
-        TH_HIP(hipFuncSetAttribute((const void*)gemm_h3_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, mx2));
-        TH_HIP(hipFuncSetAttribute((const void*)gemm_h3_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, mx2));
-        TH_HIP(hipFuncSetAttribute((const void*)gemm_h3_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-        TH_HIP(hipFuncSetAttribute((const void*)gemm_h3_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
+        const int mx = 2 * 16 * (2 * 768 + 16);
+        TH_HIP(hipFuncSetAttribute((const void*)gemm_h3_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
+        TH_HIP(hipFuncSetAttribute((const void*)gemm_h3_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
     }
     // rows per workgroup: 16 (RT = 1).  Larger tiles re-read the weights less often (RT = 2 / 4: half / a quarter of the
     // 41-55 MB of L2 traffic per GEMM of the ViT) but were measured SLOWER at V N_c = 900 .. 4500 rows (0.79 / 0.86 /
     // 0.91 ms per forward at RT = 1 / 2 / 4, N_c = 500): these launches are bound by the length of the per-workgroup
-    // dependency chain, not by bandwidth.  TH_GEMM_H3_RT = 2 | 4 selects the larger tiles (A/B switch).
-    static const int rt_env = getenv("TH_GEMM_H3_RT") ? atoi(getenv("TH_GEMM_H3_RT")) : 0;
-    const int gy = th_cdiv(W.NB, 4);
-    int rt = 1;
-    if (rt_env == 2 || (rt_env == 4 && KP <= 256)) rt = rt_env;
-    const size_t lds = (size_t)2 * 16 * rt * (2 * KP + 16);
-    dim3 grid(th_cdiv(M, 16 * rt), gy);
-#define H3_LAUNCH(LN_, RT_)                                                                                              \
-    hipLaunchKernelGGL((gemm_h3_kernel<LN_, RT_>), grid, dim3(256), lds, s, A, lda, M, W.K, W.w16, W.scale16, W.b, W.N, W.NB, \
-                       W.KB32, C, ldc, flags, ln_w, ln_b, eps, range, qs)
-    if (ln) { if (rt == 4) H3_LAUNCH(true, 4); else if (rt == 2) H3_LAUNCH(true, 2); else H3_LAUNCH(true, 1); }
-    else    { if (rt == 4) H3_LAUNCH(false, 4); else if (rt == 2) H3_LAUNCH(false, 2); else H3_LAUNCH(false, 1); }
-#undef H3_LAUNCH
+    // dependency chain, not by bandwidth.
+    const size_t lds = (size_t)2 * 16 * (2 * KP + 16);
+    dim3 grid(th_cdiv(M, 16), th_cdiv(W.NB, 4));
+    if (ln) hipLaunchKernelGGL((gemm_h3_kernel<true, 1>), grid, dim3(256), lds, s, A, lda, M, W.K, W.w16, W.scale16, W.b, W.N,
+                               W.NB, W.KB32, C, ldc, flags, ln_w, ln_b, eps, range, qs);
+    else hipLaunchKernelGGL((gemm_h3_kernel<false, 1>), grid, dim3(256), lds, s, A, lda, M, W.K, W.w16, W.scale16, W.b, W.N,
+                            W.NB, W.KB32, C, ldc, flags, ln_w, ln_b, eps, range, qs);
     TH_LAUNCH_CHECK();
     return 0;
 }

@@ -30,55 +30,6 @@ __device__ __forceinline__ int cell_coord(float x, float gmin, float inv_h) {
     return (int)floorf((x - gmin) * inv_h);
 }
 
-// one block: AABB of the vertices -> GridInfo, and zero the counters
-__global__ __launch_bounds__(1024) void grid_setup_kernel(const float* __restrict__ verts, int nv, float h0,
-                                                          GridInfo* __restrict__ gi, int* __restrict__ counts) {
-    __shared__ float smin[3][16], smax[3][16];
-    float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    for (int i = threadIdx.x; i < nv; i += blockDim.x)
-        for (int a = 0; a < 3; ++a) {
-            float v = verts[3 * i + a];
-            mn[a] = fminf(mn[a], v);
-            mx[a] = fmaxf(mx[a], v);
-        }
-    for (int a = 0; a < 3; ++a) {
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], o));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            smin[a][threadIdx.x >> 6] = mn[a];
-            smax[a][threadIdx.x >> 6] = mx[a];
-        }
-    }
-    __syncthreads();
-    __shared__ GridInfo g;
-    if (threadIdx.x == 0) {
-        float ext = 0.f;
-        int nw = blockDim.x >> 6;
-        for (int a = 0; a < 3; ++a) {
-            float lo = smin[a][0], hi = smax[a][0];
-            for (int w = 1; w < nw; ++w) { lo = fminf(lo, smin[a][w]); hi = fmaxf(hi, smax[a][w]); }
-            g.gmin[a] = lo;
-            smax[a][0] = hi;
-            ext = fmaxf(ext, hi - lo);
-        }
-        float h = fmaxf(h0, ext / (float)(GRID_MAX_DIM - 2));
-        g.inv_h = 1.0f / h;
-        int nc = 1;
-        for (int a = 0; a < 3; ++a) {
-            int d = cell_coord(smax[a][0], g.gmin[a], g.inv_h) + 1;
-            d = d < 1 ? 1 : (d > GRID_MAX_DIM ? GRID_MAX_DIM : d);
-            g.dim[a] = d;
-            nc *= d;
-        }
-        g.ncell = nc;
-        *gi = g;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < g.ncell + 1; i += blockDim.x) counts[i] = 0;
-}
-
 __device__ __forceinline__ int vert_cell(const GridInfo& g, float x, float y, float z) {
     int cx = cell_coord(x, g.gmin[0], g.inv_h), cy = cell_coord(y, g.gmin[1], g.inv_h),
         cz = cell_coord(z, g.gmin[2], g.inv_h);
@@ -86,71 +37,6 @@ __device__ __forceinline__ int vert_cell(const GridInfo& g, float x, float y, fl
     cy = min(max(cy, 0), g.dim[1] - 1);
     cz = min(max(cz, 0), g.dim[2] - 1);
     return (cz * g.dim[1] + cy) * g.dim[0] + cx;
-}
-
-__global__ void grid_count_kernel(const float* __restrict__ verts, int nv, const GridInfo* __restrict__ gi,
-                                  int* __restrict__ counts) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv) return;
-    GridInfo g = *gi;
-    atomicAdd(&counts[vert_cell(g, verts[3 * i], verts[3 * i + 1], verts[3 * i + 2])], 1);
-}
-
-// single block exclusive scan counts[0..ncell) -> starts[0..ncell]; cursor := starts
-__global__ __launch_bounds__(1024) void grid_scan_kernel(const GridInfo* __restrict__ gi, int* __restrict__ counts,
-                                                         int* __restrict__ starts, int* __restrict__ cursor) {
-    __shared__ int wsum[16];
-    __shared__ int carry;
-    int n = gi->ncell;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        int i = base + threadIdx.x;
-        int v = (i < n) ? counts[i] : 0;
-        int x = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            int t = __shfl_up(x, o);
-            if ((threadIdx.x & 63) >= o) x += t;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = x;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < (threadIdx.x >> 6); ++w) woff += wsum[w];
-        int excl = carry + woff + x - v;
-        if (i < n) { starts[i] = excl; cursor[i] = excl; }
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = excl + v;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) starts[n] = carry;
-}
-
-__global__ void grid_fill_kernel(const float* __restrict__ verts, int nv, const GridInfo* __restrict__ gi,
-                                 int* __restrict__ cursor, float* __restrict__ sorted) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv) return;
-    GridInfo g = *gi;
-    float x = verts[3 * i], y = verts[3 * i + 1], z = verts[3 * i + 2];
-    int pos = atomicAdd(&cursor[vert_cell(g, x, y, z)], 1);
-    sorted[3 * pos] = x; sorted[3 * pos + 1] = y; sorted[3 * pos + 2] = z;
-}
-
-// bounding box of the vertices of every cell (empty cell: inverted box): lets the mask kernel skip a whole cell
-// whose content is provably farther than the threshold -- at 6890 vertices a 0.1 m cell that touches the surface
-// holds ~40 of them, and a sample just outside the hull used to test all ~400 vertices of its 27 cells
-__global__ void grid_bbox_kernel(const GridInfo* __restrict__ gi, const int* __restrict__ starts,
-                                 const float* __restrict__ sorted, float* __restrict__ bbox) {
-    // 8 lanes per cell (a surface cell holds ~40 vertices: one thread per cell was a 40-deep dependent load chain)
-    const int c = (blockIdx.x * blockDim.x + threadIdx.x) >> 3, sub = threadIdx.x & 7;
-    const bool live = c < gi->ncell;
-    float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    if (live)
-        for (int v = starts[c] + sub, e = starts[c + 1]; v < e; v += 8)
-            for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], sorted[3 * v + a]); mx[a] = fmaxf(mx[a], sorted[3 * v + a]); }
-    for (int o = 1; o < 8; o <<= 1)
-        for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o)); }
-    if (live && sub == 0)
-        for (int a = 0; a < 3; ++a) { bbox[6 * c + a] = mn[a]; bbox[6 * c + 3 + a] = mx[a]; }
 }
 
 // Per cell of the grid EXTENDED by one layer (a sample one cell outside still reaches the boundary cells): the 27-bit
@@ -174,16 +60,16 @@ __device__ __forceinline__ void grid_nbr_phase(const GridInfo& g, const int* __r
         nbr[e] = m;
     }
 }
-__global__ void grid_nbr_kernel(const GridInfo* __restrict__ gi, const int* __restrict__ starts, unsigned* __restrict__ nbr) {
-    grid_nbr_phase(*gi, starts, nbr, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-}
 
 // The whole grid build as ONE single-workgroup launch (6890 vertices: 7 per thread): AABB -> GridInfo, zeroed counters,
-// per-cell counts, exclusive scan, bucket fill, per-cell bounding boxes -- the five launches above cost ~30 us alone
-// but ~80 us EACH when they have to squeeze in between the MLP tiles of a concurrent frame (frame pipeline, sharded
-// frames).  Also clears the per-ray hit flags and the 16-int info block of the caller (two memset launches less).
-// Same arithmetic per phase as the separate kernels; the order of the vertices inside a cell is as arbitrary as before
-// (atomics) and does not matter to the predicate.
+// per-cell counts, exclusive scan, bucket fill, per-cell bounding boxes, neighbour words.  As five separate launches the
+// build cost ~30 us alone but ~80 us EACH when they had to squeeze in between the MLP tiles of a concurrent frame (frame
+// pipeline, sharded frames).  Also clears the per-ray hit flags and the 16-int info block of the caller (two memset
+// launches less).  The order of the vertices inside a cell is arbitrary (atomics) and does not matter to the predicate.
+// The bounding box of the vertices of every cell (empty cell: inverted box) lets the mask kernel skip a whole cell whose
+// content is provably farther than the threshold -- at 6890 vertices a 0.1 m cell that touches the surface holds ~40 of
+// them, and a sample just outside the hull used to test all ~400 vertices of its 27 cells; 8 lanes per cell, since one
+// thread per cell was a 40-deep dependent load chain.
 __global__ __launch_bounds__(1024) void grid_build_kernel(const float* __restrict__ verts, int nv, float h0,
                                                           GridInfo* __restrict__ gi, int* __restrict__ counts,
                                                           int* __restrict__ starts, int* __restrict__ cursor,
@@ -457,20 +343,8 @@ int th_hull_mask_launch(const ThPointSrc& ps, long long P, const float* verts, i
     // cell size: thresh plus 5 % so fp rounding of the cell index can never
     // separate a vertex within `thresh` from the 3x3x3 neighbourhood
     float h0 = thresh * 1.05f;
-    static const bool split_build = getenv("TH_HULL_SPLIT_BUILD") != nullptr;     // A/B switch: the five-launch build
-    if (split_build) {
-        hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(1024), 0, s, verts, nv, h0, gi, counts);
-        hipLaunchKernelGGL(grid_count_kernel, dim3(th_cdiv(nv, 256)), dim3(256), 0, s, verts, nv, gi, counts);
-        hipLaunchKernelGGL(grid_scan_kernel, dim3(1), dim3(1024), 0, s, gi, counts, starts, cursor);
-        hipLaunchKernelGGL(grid_fill_kernel, dim3(th_cdiv(nv, 256)), dim3(256), 0, s, verts, nv, gi, cursor, sorted);
-        hipLaunchKernelGGL(grid_bbox_kernel, dim3(th_cdiv(GRID_MAX_CELLS * 8, 256)), dim3(256), 0, s, gi, starts, sorted, bbox);
-        hipLaunchKernelGGL(grid_nbr_kernel, dim3(64), dim3(256), 0, s, gi, starts, nbr);
-        if (ray_hit) TH_HIP(hipMemsetAsync(ray_hit, 0, sizeof(int32_t) * (size_t)ps.R, s));
-        if (info_zero) TH_HIP(hipMemsetAsync(info_zero, 0, 16 * sizeof(int32_t), s));
-    } else {
-        hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, s, verts, nv, h0, gi, counts, starts, cursor, sorted, bbox,
-                           ray_hit, ray_hit ? ps.R : 0, info_zero, nbr);
-    }
+    hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, s, verts, nv, h0, gi, counts, starts, cursor, sorted, bbox,
+                       ray_hit, ray_hit ? ps.R : 0, info_zero, nbr);
     const bool seq = getenv("TH_HULL_SEQ") != nullptr;          // A/B switch, read per launch: one lane per sample throughout
     if (seq)
         hipLaunchKernelGGL(hull_mask_seq_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, ps, P, gi, starts, sorted, bbox, thresh,

@@ -519,46 +519,6 @@ int th_mlp_fused_forward(const FusedParams& base, const ThMlpPacked& heads, int 
         default: FM_LAUNCH(3, 1); break;
     }
 #undef FM_LAUNCH
-    // developer aid: TH_FUSED_CHECK=1 -> the first big 8-wave launch is repeated by the 4-wave kernel into a scratch buffer and the two
-    // raw outputs are compared on the host (per channel: max difference, worst sample)
-    static int chk_state = getenv("TH_FUSED_CHECK") ? 1 : 0;
-    if (eight && chk_state == 1 && P >= 4096) {
-        chk_state = 2;
-        float* raw4 = nullptr;
-        TH_HIP(hipMalloc((void**)&raw4, (size_t)P * 16));
-        FusedParams q = p;
-        q.raw_c = raw4; q.dbg = nullptr; q.range = nullptr;
-        if (V == 1) hipLaunchKernelGGL((mlp_fused_kernel<1, 1, true>), grid, dim3(256), FUSED_LDS_BYTES, s, q);
-        else if (V == 2) hipLaunchKernelGGL((mlp_fused_kernel<2, 1, true>), grid, dim3(256), FUSED_LDS_BYTES, s, q);
-        else hipLaunchKernelGGL((mlp_fused_kernel<3, 1, true>), grid, dim3(256), FUSED_LDS_BYTES, s, q);
-        TH_HIP(hipStreamSynchronize(s));
-        float* h8v = (float*)malloc((size_t)P * 16);
-        float* h4v = (float*)malloc((size_t)P * 16);
-        TH_HIP(hipMemcpy(h8v, raw_c, (size_t)P * 16, hipMemcpyDeviceToHost));
-        TH_HIP(hipMemcpy(h4v, raw4, (size_t)P * 16, hipMemcpyDeviceToHost));
-        double mx[4] = {0, 0, 0, 0};
-        long long wi[4] = {0, 0, 0, 0}, nbad[4] = {0, 0, 0, 0};
-        for (long long i = 0; i < P; ++i)
-            for (int ch = 0; ch < 4; ++ch) {
-                const double d = fabs((double)h8v[i * 4 + ch] - (double)h4v[i * 4 + ch]);
-                if (!(d <= mx[ch])) { mx[ch] = d; wi[ch] = i; }
-                if (!(d <= 1e-4)) ++nbad[ch];
-            }
-        for (int ch = 0; ch < 4; ++ch)
-            fprintf(stderr, "[TH_FUSED_CHECK] raw ch %d: max |8w - 4w| = %.3e at sample %lld (tile %lld, row %lld): %.6f vs %.6f; %lld of %d above 1e-4\n", ch,
-                    mx[ch], wi[ch], wi[ch] / 32, wi[ch] % 32, h8v[wi[ch] * 4 + ch], h4v[wi[ch] * 4 + ch], nbad[ch], P);
-        // the first tile with a bad green value, row by row
-        for (long long i = 0; i < P; ++i)
-            if (fabs(h8v[i * 4 + 1] - h4v[i * 4 + 1]) > 1e-4) {
-                const long long t0 = i / 32 * 32;
-                for (long long r = t0; r < t0 + 32 && r < P; ++r)
-                    fprintf(stderr, "   row %2lld  8w %9.5f %9.5f %9.5f %9.5f   4w %9.5f %9.5f %9.5f %9.5f\n", r - t0, h8v[r * 4], h8v[r * 4 + 1], h8v[r * 4 + 2],
-                            h8v[r * 4 + 3], h4v[r * 4], h4v[r * 4 + 1], h4v[r * 4 + 2], h4v[r * 4 + 3]);
-                break;
-            }
-        free(h8v); free(h4v);
-        TH_HIP(hipFree(raw4));
-    }
 #undef FM_LAUNCH_T
 #undef FM_LAUNCH_8
     TH_LAUNCH_CHECK();

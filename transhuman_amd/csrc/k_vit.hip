@@ -4,13 +4,13 @@
 // x += PE; depth x [ pre-LN (eps 1e-6) -> fused qkv Linear -> 3-head
 // softmax(q k^T * 0.125) v -> proj -> residual ; pre-LN -> FC 192->768 ->
 // GELU(erf) -> FC 768->192 -> residual ] ; final LN   (:257-307).
-// Dense layers: th_gemm (fp32 MFMA).  Attention: flash-style, one workgroup =
-// 64 queries (16 per wave) of one (view, head); K/V tiles of 64 keys staged in
-// LDS; q k^T and p v on v_mfma_f32_16x16x4_f32; online softmax in registers with
-// 16-lane shuffle reductions.  The [V,3,N,N] probability tensor the reference
-// materialises (81 MB at N_c = 1500) never exists.
+// Dense layers: th_gemm_h3 (fp16-split MFMA; th_gemm_ln / th_gemm outside its range).
+// Attention: flash-style on fp16-split MFMA operands, online softmax in registers;
+// attn2_kernel (one wave = 16 queries, K / V^T fragments from L2) up to N = 700,
+// attn3_kernel (64 queries share K / V^T tiles staged in LDS) above.  The
+// [V,3,N,N] probability tensor the reference materialises (81 MB at N_c = 1500)
+// never exists.
 // Per-frame cost 12/23/110 GFLOP at N_c = 300/500/1500 (fp32 MFMA bound).
-#include <stdlib.h>
 
 #include "th_internal.h"
 
@@ -63,14 +63,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 // split into fp16 hi + lo (x = hi + lo to 2^-22; three products hi*hi + hi*lo + lo*hi, fp32 accumulate -- the
 // same fp32-class scheme as the fused MLP): 48 MFMAs of 16 cycles per tile and wave instead of the
 // 128 fp32 MFMAs of 32 cycles the 16x16x4 form needs.
-//   S = Q K^T : A = Q [16 q][k = d]   (registers, split once per workgroup)
-//               B = K^T: lane (key = nt*16 + lane&15, d = 32 s + 8 (lane>>4) ..+7) -> 16 bytes of a K row in LDS
-//   O = P V   : A = P [16 q][k = key] (softmax output, C layout -> LDS -> A layout, split)
-//               B = V  : lane (d = dt*16 + lane&15, key = 32 s + 8 (lane>>4) ..+7) -> V is staged TRANSPOSED
-// One workgroup = 4 waves = 64 queries; K / V tiles are fetched into registers one tile ahead.
-#define AT_Q 64
 #define AT_K 64
-#define AT_HS 144      // LDS row stride in bytes of a 64-half row (+16: an odd number of 16-byte slots)
 
 typedef _Float16 at_h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 at_h4 __attribute__((ext_vector_type(4)));
@@ -80,176 +73,10 @@ __device__ __forceinline__ void at_split(float x, _Float16& hi, _Float16& lo) {
     lo = (_Float16)(x - (float)hi);
 }
 
-__global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv, int N, int dim, float scale,
-                                                   float* __restrict__ out) {
-    // planes: [hi | lo][64 rows][AT_HS bytes]
-    __shared__ __attribute__((aligned(16))) char Ks[2 * AT_K * AT_HS];      // K  [key][d]
-    __shared__ __attribute__((aligned(16))) char Vt[2 * 64 * AT_HS];        // V^T [d][key]
-    __shared__ __attribute__((aligned(16))) char Ps[4][2 * 16 * AT_HS];     // P  [q][key] per wave
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int head = blockIdx.y, view = blockIdx.z;
-    const int q0 = blockIdx.x * AT_Q + wave * 16;
-    const int ld = 3 * dim;
-    const float* base = qkv + (long long)view * N * ld;
-    const int qcol = head * 64, kcol = dim + head * 64, vcol = 2 * dim + head * 64;
-
-    // Q fragments (A operand): row q0 + (lane&15), d = 32 s + 8 (lane>>4) .. +7
-    at_h8 qh[2], ql[2];
-    {
-        const int qi = q0 + (lane & 15);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            float v8[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v8[e] = 0.f;
-            if (qi < N) {
-                const float* src = base + (long long)qi * ld + qcol + 32 * s2 + 8 * (lane >> 4);
-                float4 a = *reinterpret_cast<const float4*>(src), b4 = *reinterpret_cast<const float4*>(src + 4);
-                v8[0] = a.x; v8[1] = a.y; v8[2] = a.z; v8[3] = a.w; v8[4] = b4.x; v8[5] = b4.y; v8[6] = b4.z; v8[7] = b4.w;
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                _Float16 x, y;
-                at_split(v8[e], x, y);
-                qh[s2][e] = x; ql[s2][e] = y;
-            }
-        }
-    }
-    f32x4 oacc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) oacc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float mrun[4], lrun[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { mrun[r] = -3.0e38f; lrun[r] = 0.f; }
-
-    // K / V tiles (64 keys x 64 floats each = 1024 float4 per tile): fetched into registers one tile ahead
-    float4 kreg[4], vreg[4];
-    auto fetch_kv = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int idx = tid + 256 * i;
-            int row = idx >> 4, c4 = idx & 15;
-            int key = k0 + row;
-            kreg[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            vreg[i] = kreg[i];
-            if (key < N) {
-                kreg[i] = *reinterpret_cast<const float4*>(base + (long long)key * ld + kcol + 4 * c4);
-                vreg[i] = *reinterpret_cast<const float4*>(base + (long long)key * ld + vcol + 4 * c4);
-            }
-        }
-    };
-    fetch_kv(0);
-    char* Pw = Ps[wave];
-    for (int k0 = 0; k0 < N; k0 += AT_K) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int idx = tid + 256 * i;
-            int row = idx >> 4, c4 = idx & 15;                  // key row, 4 consecutive d
-            const float kv[4] = {kreg[i].x, kreg[i].y, kreg[i].z, kreg[i].w};
-            const float vv[4] = {vreg[i].x, vreg[i].y, vreg[i].z, vreg[i].w};
-            at_h4 kh, kl;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                _Float16 x, y;
-                at_split(kv[e], x, y);
-                kh[e] = x; kl[e] = y;
-                at_split(vv[e], x, y);
-                *reinterpret_cast<_Float16*>(Vt + (4 * c4 + e) * AT_HS + 2 * row) = x;                     // V^T[d][key]
-                *reinterpret_cast<_Float16*>(Vt + 64 * AT_HS + (4 * c4 + e) * AT_HS + 2 * row) = y;
-            }
-            *reinterpret_cast<at_h4*>(Ks + row * AT_HS + 8 * c4) = kh;
-            *reinterpret_cast<at_h4*>(Ks + AT_K * AT_HS + row * AT_HS + 8 * c4) = kl;
-        }
-        __syncthreads();
-        if (k0 + AT_K < N) fetch_kv(k0 + AT_K);
-        // ---- S = Q K^T (C layout: row q = 4*(lane>>4)+r, col key = nt*16 + (lane&15)) ----
-        f32x4 sacc[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            sacc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const int off = (nt * 16 + (lane & 15)) * AT_HS + 64 * s2 + 16 * (lane >> 4);
-                const at_h8 bh = *reinterpret_cast<const at_h8*>(Ks + off);
-                const at_h8 bl = *reinterpret_cast<const at_h8*>(Ks + AT_K * AT_HS + off);
-                sacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ql[s2], bh, sacc[nt], 0, 0, 0);
-                sacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qh[s2], bl, sacc[nt], 0, 0, 0);
-                sacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qh[s2], bh, sacc[nt], 0, 0, 0);
-            }
-        }
-        float mnew[4], corr[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float m = -3.0e38f;
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                int key = k0 + nt * 16 + (lane & 15);
-                float sv = (key < N) ? sacc[nt][r] * scale : -3.0e38f;
-                sacc[nt][r] = sv;
-                m = fmaxf(m, sv);
-            }
-            m = th_row16_max(m);
-            mnew[r] = fmaxf(mrun[r], m);
-            corr[r] = expf(mrun[r] - mnew[r]);
-            mrun[r] = mnew[r];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float ls = 0.f;
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                int key = k0 + nt * 16 + (lane & 15);
-                float pv = (key < N) ? expf(sacc[nt][r] - mnew[r]) : 0.f;
-                ls += pv;
-                _Float16 x, y;
-                at_split(pv, x, y);
-                const int po = (4 * (lane >> 4) + r) * AT_HS + 2 * (nt * 16 + (lane & 15));
-                *reinterpret_cast<_Float16*>(Pw + po) = x;
-                *reinterpret_cast<_Float16*>(Pw + 16 * AT_HS + po) = y;
-            }
-            ls = th_row16_sum(ls);
-            lrun[r] = lrun[r] * corr[r] + ls;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) oacc[j][r] *= corr[r];
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): P tile of this wave is written
-        __builtin_amdgcn_wave_barrier();
-        // ---- O += P V ----
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const int pof = (lane & 15) * AT_HS + 64 * s2 + 16 * (lane >> 4);
-            const at_h8 ph = *reinterpret_cast<const at_h8*>(Pw + pof);
-            const at_h8 pl = *reinterpret_cast<const at_h8*>(Pw + 16 * AT_HS + pof);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int vof = (j * 16 + (lane & 15)) * AT_HS + 64 * s2 + 16 * (lane >> 4);
-                const at_h8 vh = *reinterpret_cast<const at_h8*>(Vt + vof);
-                const at_h8 vl = *reinterpret_cast<const at_h8*>(Vt + 64 * AT_HS + vof);
-                oacc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pl, vh, oacc[j], 0, 0, 0);
-                oacc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, vl, oacc[j], 0, 0, 0);
-                oacc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, vh, oacc[j], 0, 0, 0);
-            }
-        }
-    }
-    // out[t][head*64 + d] = O / l      (x = (attn @ v).transpose(1,2).reshape(B,N,C), :278)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        int qi = q0 + 4 * (lane >> 4) + r;
-        if (qi < N) {
-            float inv = 1.0f / lrun[r];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                out[((long long)view * N + qi) * dim + head * 64 + j * 16 + (lane & 15)] = oacc[j][r] * inv;
-        }
-    }
-}
-
-
 // ---- attention, second form: operands split ONCE per layer, no LDS staging ------------------------------------
-// attn_kernel converts every K / V tile fp32 -> fp16 hi/lo inside every workgroup (the V tile transposed with
-// 2-byte LDS stores) between two block barriers: 8 q-blocks repeat the conversion of the same (view, head) and
-// the 8-tile loop is a 31 us dependent chain.  Here kv_split_kernel writes, once per layer,
+// The first form (round 2, since retired) converted every K / V tile fp32 -> fp16 hi/lo inside every workgroup (the V
+// tile transposed with 2-byte LDS stores) between two block barriers: 8 q-blocks repeated the conversion of the same
+// (view, head) and the 8-tile loop was a 31 us dependent chain.  Here kv_split_kernel writes, once per layer,
 //   Kp [V][heads][2 planes][Npad][64]   K rows as fp16 hi | lo          (rows >= N zero)
 //   Vp [V][heads][2 planes][64][Npad]   V^T rows (one d; keys in the fragment order of attn2_kernel) as fp16 hi | lo
 // -- exactly the 16-byte B-operand fragments of the two products -- and attn2_kernel (ONE wave = 16 queries per
@@ -450,8 +277,8 @@ __global__ __launch_bounds__(64) void attn2_kernel(const float* __restrict__ qkv
 
 // ---- attention, third form (round 6): attn2's arithmetic, K / V^T tiles shared by four waves through LDS ---------------------------
 // attn2_kernel (one wave = 16 queries per workgroup) streams the whole K / V^T planes of its (view, head) from L2 per wave: at
-// N = 1500 that is 650 MB per layer and the launch takes 172 us (3.8 TB/s: the L2's rate for this pattern); the LDS-staged
-// attn_kernel converts and transposes every tile inside every workgroup (134 us).  Here one workgroup = 4 waves = 64 queries; a
+// N = 1500 that is 650 MB per layer and the launch takes 172 us (3.8 TB/s: the L2's rate for this pattern); the retired round-2
+// form converted and transposed every tile inside every workgroup (134 us).  Here one workgroup = 4 waves = 64 queries; a
 // 64-key tile of the PRE-SPLIT planes (the qkv GEMM's epilogue writes them in fragment order) is copied into LDS by LDS-DMA, one
 // plane per wave (K hi, K lo, V^T hi, V^T lo: 8 KB = 8 wave instructions each), double-buffered, ONE barrier per tile; every wave
 // reads its fragments with ds_read_b128 and runs attn2's transposed products / online softmax in registers.  A quarter of the L2
@@ -632,28 +459,22 @@ int th_vit_launch(const ThVitPacked& W, const float* x, const float* pe, int V, 
     // few tokens: the register-fed form (more, shorter workgroups); many: the LDS-staged form (64 queries share every K / V
     // tile: a quarter of the L2 traffic, which is what bounds the register-fed form from N ~ 1000 on).
     // Measured ViT forward, N_c = 300 / 500 / 1500: 0.80 / 0.99 / 2.15 ms register-fed, 0.86 / 1.07 / 2.06 ms LDS-staged.
-    static const char* attn_env = getenv("TH_ATTN_FORM");               // "lds" | "reg": A/B switch
     // (transposed register-fed form, late round 2: 0.77 / 0.95 / 1.19 / 2.06 ms at N_c = 500 / 800 / 1000 / 1500 against 0.93 / 1.16 /
     // 1.27 / 1.76 ms LDS-staged)
-    // (round 6: from N ~ 700 on the third form -- attn2's arithmetic on K / V^T tiles shared through LDS, attn3_kernel; "lds": the
-    // round-2 form that converts inside the workgroup, "reg" / "tile": force the register-fed / the tiled form)
-    const bool attn_lds = attn_env ? attn_env[0] == 'l' : false;
-    const bool attn_tile = attn_env ? attn_env[0] == 't' : N > 700;
+    // (round 6: from N ~ 700 on the third form -- attn2's arithmetic on K / V^T tiles shared through LDS, attn3_kernel)
+    const bool attn_tile = N > 700;
     TH_REQUIRE(Q != nullptr, "workspace carve failed");
     long long n = (long long)T * dim;
     hipLaunchKernelGGL(add_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, x, pe, n, X);
     const float scale = 0.125f;   // head_dim ** -0.5
-    // the two pre-LayerNorms of a block run inside the GEMM that consumes them (TH_VIT_SEPARATE_LN=1: own launches)
-    static const bool separate_ln = getenv("TH_VIT_SEPARATE_LN") != nullptr;
-    const bool fuse_ln = !separate_ln && th_gemm_ln_ok(T, W.blocks[0].qkv) && th_gemm_ln_ok(T, W.blocks[0].fc1);
-    // dense layers on the fp16-split MFMA path (th_gemm_h3; TH_VIT_GEMM_F32=1: the fp32 MFMA GEMMs)
-    static const bool f32_gemm = getenv("TH_VIT_GEMM_F32") != nullptr;
-    const bool h3 = allow_h3 && !f32_gemm && !separate_ln && th_gemm_h3_ok(T, W.blocks[0].qkv, true) && th_gemm_h3_ok(T, W.blocks[0].fc1, true) &&
+    // the two pre-LayerNorms of a block run inside the GEMM that consumes them
+    const bool fuse_ln = th_gemm_ln_ok(T, W.blocks[0].qkv) && th_gemm_ln_ok(T, W.blocks[0].fc1);
+    // dense layers on the fp16-split MFMA path (th_gemm_h3)
+    const bool h3 = allow_h3 && th_gemm_h3_ok(T, W.blocks[0].qkv, true) && th_gemm_h3_ok(T, W.blocks[0].fc1, true) &&
                     th_gemm_h3_ok(T, W.blocks[0].proj, false) && th_gemm_h3_ok(T, W.blocks[0].fc2, false);
     // the K / V^T operand planes of the register-fed attention are written by the qkv GEMM's epilogue (no kv_split launch);
     // the padding keys (N .. Npad) of the planes must read as zero: cleared once per forward
-    static const bool no_fuse_split = getenv("TH_VIT_KV_SPLIT") != nullptr;       // A/B switch: the separate launch
-    const bool fuse_split = h3 && !attn_lds && !no_fuse_split;
+    const bool fuse_split = h3;
     const ThQkvSplit qs{Kp, Vp, N, Npad, heads, dim};
     if (fuse_split && Npad != N)
     {
@@ -671,14 +492,10 @@ int th_vit_launch(const ThVitPacked& W, const float* x, const float* pe, int V, 
             hipLaunchKernelGGL(layernorm_kernel, dim3(th_cdiv(T, 4)), dim3(256), 0, s, X, T, dim, B.ln1_w, B.ln1_b, 1e-6f, Y);
             TH_TRY(th_gemm(Y, dim, T, B.qkv, TH_ACT_NONE, Q, 3 * dim, s));
         }
-        if (attn_lds) {
-            hipLaunchKernelGGL(attn_kernel, dim3(th_cdiv(N, AT_Q), heads, V), dim3(256), 0, s, Q, N, dim, scale, Y);
-        } else {
-            if (!(h3 && fuse_split))
-                hipLaunchKernelGGL(kv_split_kernel, dim3(Npad / 64, heads, V), dim3(256), 0, s, Q, N, Npad, dim, Kp, Vp);
-            if (attn_tile) hipLaunchKernelGGL(attn3_kernel, dim3(th_cdiv(N, 64), heads, V), dim3(256), 0, s, Q, Kp, Vp, N, Npad, dim, scale, Y);
-            else hipLaunchKernelGGL(attn2_kernel, dim3(th_cdiv(N, 16), heads, V), dim3(64), 0, s, Q, Kp, Vp, N, Npad, dim, scale, Y);
-        }
+        if (!fuse_split)
+            hipLaunchKernelGGL(kv_split_kernel, dim3(Npad / 64, heads, V), dim3(256), 0, s, Q, N, Npad, dim, Kp, Vp);
+        if (attn_tile) hipLaunchKernelGGL(attn3_kernel, dim3(th_cdiv(N, 64), heads, V), dim3(256), 0, s, Q, Kp, Vp, N, Npad, dim, scale, Y);
+        else hipLaunchKernelGGL(attn2_kernel, dim3(th_cdiv(N, 16), heads, V), dim3(64), 0, s, Q, Kp, Vp, N, Npad, dim, scale, Y);
         if (h3) {
             TH_TRY(th_gemm_h3(Y, dim, T, B.proj, nullptr, nullptr, 0.f, TH_ACT_NONE | TH_GEMM_ACCUM, X, dim, range, s));
             TH_TRY(th_gemm_h3(X, dim, T, B.fc1, B.ln2_w, B.ln2_b, 1e-6f, TH_ACT_GELU, Q, 4 * dim, range, s));

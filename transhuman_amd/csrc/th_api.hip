@@ -1131,38 +1131,33 @@ static int shade_points(th_ctx* c, const th_frame* f, const ThPointSrc& ps, long
         const bool grid = getenv("TH_DPARF_NOGRID") == nullptr && th_dparf_grid_ok(f->n_clusters);
         // K4 on the context's second stream, K5 on `s`: the two producers share nothing but the sample list -- K5 sits on
         // the texture path (TA busy 80-90 %, VALU 43 %), K4 since TH_ROWS_NBR is a 7-NN scan out of LDS (no row gather) --
-        // so their waves co-reside on the CUs instead of running back to back (TH_K4_SIDE=0: one stream, K4 then K5).
-        static const bool k4_side = !(getenv("TH_K4_SIDE") && getenv("TH_K4_SIDE")[0] == '0');
-        hipStream_t s4 = s, s5 = s;
-        if (k4_side) {
-            if (!c->aux) {
-                TH_HIP(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-                TH_HIP(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
-                TH_HIP(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
-                TH_HIP(hipStreamCreateWithFlags(&c->aux2, hipStreamNonBlocking));
-                TH_HIP(hipEventCreateWithFlags(&c->aux2_join, hipEventDisableTiming));
-            }
-            // th_render_pregather_early: K4 is ordered behind the per-sample stage of the previous th_render_rays on this
-            // stream and pool (the last user of the pool's record regions) instead of behind everything queued on `s` since
-            // -- that frame's compositing and whatever the caller queued after it run beside K4, not in front of it
-            const bool early = c->pregather_early && c->after_shade_valid && c->after_shade_stream == s &&
-                               c->after_shade_pool == pool;
-            c->after_shade_valid = false;
-            // K5t (the texel hand-over's producer: rays, cameras, sample list -- no map) gets a stream of its own under the same
-            // rule: in the early form it starts with K4 behind the previous frame's per-sample stage, beside that frame's
-            // compositing and the consumer's image assembly, instead of behind them on `s` (the window between two launches of
-            // the fused kernel of a rank of 8: 360 -> 240 us)
-            if (early) {
-                TH_HIP(hipStreamWaitEvent(c->aux, c->after_shade, 0));
-                if (tex) TH_HIP(hipStreamWaitEvent(c->aux2, c->after_shade, 0));
-            } else {
-                TH_HIP(hipEventRecord(c->aux_fork, s));      // sample list, candidate grid and every earlier user of the pool
-                TH_HIP(hipStreamWaitEvent(c->aux, c->aux_fork, 0));
-                if (tex) TH_HIP(hipStreamWaitEvent(c->aux2, c->aux_fork, 0));
-            }
-            s4 = c->aux;
-            if (tex) s5 = c->aux2;
+        // so their waves co-reside on the CUs instead of running back to back.
+        if (!c->aux) {
+            TH_HIP(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
+            TH_HIP(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
+            TH_HIP(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
+            TH_HIP(hipStreamCreateWithFlags(&c->aux2, hipStreamNonBlocking));
+            TH_HIP(hipEventCreateWithFlags(&c->aux2_join, hipEventDisableTiming));
         }
+        // th_render_pregather_early: K4 is ordered behind the per-sample stage of the previous th_render_rays on this
+        // stream and pool (the last user of the pool's record regions) instead of behind everything queued on `s` since
+        // -- that frame's compositing and whatever the caller queued after it run beside K4, not in front of it
+        const bool early = c->pregather_early && c->after_shade_valid && c->after_shade_stream == s &&
+                           c->after_shade_pool == pool;
+        c->after_shade_valid = false;
+        // K5t (the texel hand-over's producer: rays, cameras, sample list -- no map) gets a stream of its own under the same
+        // rule: in the early form it starts with K4 behind the previous frame's per-sample stage, beside that frame's
+        // compositing and the consumer's image assembly, instead of behind them on `s` (the window between two launches of
+        // the fused kernel of a rank of 8: 360 -> 240 us)
+        if (early) {
+            TH_HIP(hipStreamWaitEvent(c->aux, c->after_shade, 0));
+            if (tex) TH_HIP(hipStreamWaitEvent(c->aux2, c->after_shade, 0));
+        } else {
+            TH_HIP(hipEventRecord(c->aux_fork, s));      // sample list, candidate grid and every earlier user of the pool
+            TH_HIP(hipStreamWaitEvent(c->aux, c->aux_fork, 0));
+            if (tex) TH_HIP(hipStreamWaitEvent(c->aux2, c->aux_fork, 0));
+        }
+        hipStream_t s4 = c->aux, s5 = tex ? c->aux2 : s;
         // From here on work may be in flight on the second stream: whatever happens, `s` waits for it before this call
         // returns (a caller that frees or reuses the pool after an error must not race with K4).
         int rc = 0;
@@ -1190,15 +1185,13 @@ static int shade_points(th_ctx* c, const th_frame* f, const ThPointSrc& ps, long
             rc = token_table(c, f->tokens, V, f->n_clusters, tprime, &table, s);
             if (rc == 0) t.pre_tokens = f->tokens;
         }
-        if (k4_side) {
-            const hipError_t e1 = hipEventRecord(c->aux_join, c->aux);
-            const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s, c->aux_join, 0) : e1;
-            if (e2 != hipSuccess) (void)hipStreamSynchronize(c->aux);      // last resort: nothing left in flight
-            if (s5 != s) {
-                const hipError_t e3 = hipEventRecord(c->aux2_join, c->aux2);
-                const hipError_t e4 = e3 == hipSuccess ? hipStreamWaitEvent(s, c->aux2_join, 0) : e3;
-                if (e4 != hipSuccess) (void)hipStreamSynchronize(c->aux2);
-            }
+        const hipError_t e1 = hipEventRecord(c->aux_join, c->aux);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s, c->aux_join, 0) : e1;
+        if (e2 != hipSuccess) (void)hipStreamSynchronize(c->aux);      // last resort: nothing left in flight
+        if (s5 != s) {
+            const hipError_t e3 = hipEventRecord(c->aux2_join, c->aux2);
+            const hipError_t e4 = e3 == hipSuccess ? hipStreamWaitEvent(s, c->aux2_join, 0) : e3;
+            if (e4 != hipSuccess) (void)hipStreamSynchronize(c->aux2);
         }
         if (rc != 0) return rc;
         if (!t.ev2) TH_HIP(hipEventCreateWithFlags(&t.ev2, hipEventDisableTiming));

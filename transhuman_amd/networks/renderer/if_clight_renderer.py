@@ -187,7 +187,7 @@ class Renderer:
             # :316, :334, :346) are applied to the map's texels here, once per frame -- bilinear sampling commutes with them
             if (isinstance(map_nhwc, hip.SplitMap) and hip.tex_rows_enabled(dev) and V <= 3 and V * H * W < (1 << 22)
                     and hip.mlp_is_fused(dev)):
-                if pregather is not None and os.environ.get("TH_FOLD_STREAM", "1") != "0":
+                if pregather is not None:
                     # a single frame (render_fast) is bound by its chain of dependent stages: stem -> map -> paint / group ->
                     # TransHE -> fused MLP.  The fold (0.35 ms) is needed by the fused MLP only: beside that chain on a stream
                     # of its own, not inside it.  (A stream of frames is bound by the chip's total work: render_sequence keeps
@@ -311,8 +311,8 @@ class Renderer:
         the null stream; on a stream of our own they start when their inputs are ready (render_fast 18.3 -> 17.6 ms on one box,
         17.85 -> 17.65 on another, profiles/r05_m).  render_sequence stays on the caller's stream: its steady state was 0.17 ms per
         frame SLOWER on a stream of its own (14.79 -> 14.96 ms, same profile).  None = stay on the caller's stream (it is not the
-        default stream, or TH_OWN_STREAM=0)."""
-        if not torch.cuda.is_available() or os.environ.get("TH_OWN_STREAM", "1") == "0":
+        default stream)."""
+        if not torch.cuda.is_available():
             return None
         if torch.cuda.current_stream(dev) != torch.cuda.default_stream(dev):
             return None
@@ -357,8 +357,6 @@ class Renderer:
                 side = self._dev.get(("hull_stream", str(dev)))
                 if side is None:
                     side = self._dev[("hull_stream", str(dev))] = torch.cuda.Stream(dev)
-                if os.environ.get("TH_HULL_SAME_STREAM") == "1":       # A/B switch: the ray-only stage in front, same stream
-                    side = torch.cuda.current_stream(dev)
                 side.wait_stream(torch.cuda.current_stream(dev))
                 with torch.cuda.stream(side):
                     hip.render_prepass(pts, batch["tar_smpl_vertice"][0], V, cfg_hull(), small_frame_rays,
@@ -454,19 +452,19 @@ class Renderer:
         cfg = get_cfg()
         sl = slice(None) if ray_slice is None else ray_slice
         it = iter(batches)
-        lookahead = max(1, min(int(os.environ.get("TH_LOOKAHEAD", lookahead)), 3))    # (th_render_prepass keeps at most 4 tokens)
+        lookahead = max(1, min(int(lookahead), 3))    # (th_render_prepass keeps at most 4 tokens)
         if lookahead >= 3 and hip.graphs_enabled():
             # the stem / TransHE graph rings hold 4 instances = pipeline depth 2 + the frame being shaded + the frame just handed
             # out: at depth 3 the instance `last_frame` points at has been replayed for a later frame by the time it is yielded
             lookahead = 2
-        # split front (single rank, TH_SPLIT_FRONT=0 switches it off): the front of a frame is issued in two pieces -- A =
-        # hull stage, encoder, paint, group (chip-filling kernels) and B = TransHE (63 small dependent launches).  In the
+        # split front (single rank): the front of a frame is issued in two pieces -- A = hull stage, encoder, paint, group
+        # (chip-filling kernels) and B = TransHE (63 small dependent launches).  In the
         # shading window of frame i the side stream runs B(i+1) FIRST and then A(i+2): the latency-bound launches of
         # TransHE find free CUs beside the producers of frame i instead of queueing, one by one, behind MLP tiles.
-        split = token_exchange is None and os.environ.get("TH_SPLIT_FRONT", "1") != "0"
+        split = token_exchange is None
         if split:
             lookahead = max(lookahead, 2)
-        elif os.environ.get("TH_PREGATHER_EARLY", "1") != "0" and "TH_LOOKAHEAD" not in os.environ:
+        elif os.environ.get("TH_PREGATHER_EARLY", "1") != "0":
             # multi-rank job: two frames ahead as well, so that the front of frame i+1 is complete before the shading of
             # frame i is queued and its neighbour records can start beside frame i's compositing and image gather
             # (th_render_pregather_early below; emulated rank of 8: 2.835 -> 2.80 ms per frame)
@@ -487,21 +485,19 @@ class Renderer:
                     # the ray-only hull stage (grid, hull test, compaction: ~10 dependent launches, 0.3 ms) shares nothing with
                     # the frame constants: on a stream of its own beside them, not in front of them -- the side stream's chain of
                     # ~55 dependent launches is what bounds a rank of 8 (2.7 ms against a 2.3 ms shard of the fused MLP)
-                    hs = hull_side if hull_side is not None else side
-                    hs.wait_stream(side)
-                    with torch.cuda.stream(hs):
+                    hull_side.wait_stream(side)
+                    with torch.cuda.stream(hull_side):
                         hip.render_prepass(pts, b["tar_smpl_vertice"][0], V, cfg_hull(), small_frame_rays,
                                            n_clusters=len(self.csr_offsets) - 1, slot=1 + j % nslots)
                         dm = self.predemand(b, pts, token_exchange, sharded=token_exchange is not None or ray_slice is not None)
                     for t in (pts.ray_o, pts.ray_d, pts.near, pts.far):
-                        t.record_stream(hs)
+                        t.record_stream(hull_side)
                 else:
                     dm = None
                 frame = self.prepare_frame(b, token_exchange=token_exchange, defer_tokens=split, stem_exchange=stem_exchange,
                                            demand=dm, stem_graph=True)
                 if V <= 4 and pts.R > 0:
-                    side.wait_stream(hs)
-                if V <= 4 and pts.R > 0 and os.environ.get("TH_PREGRID", "1") != "0":
+                    side.wait_stream(hull_side)
                     hip.render_pregrid(frame, pts)         # K4's candidate grid: here, not in front of K4
                 ready = torch.cuda.Event()
                 ready.record(side)
@@ -524,15 +520,12 @@ class Renderer:
         dev = first["ray_o"].device
         side = self._dev.get(("side_stream", str(dev)))
         if side is None:
-            # TH_SIDE_PRIORITY=-1: high-priority side stream (A/B switch; measured: see DESIGN.md 6)
-            side = self._dev[("side_stream", str(dev))] = torch.cuda.Stream(dev, priority=int(os.environ.get("TH_SIDE_PRIORITY", "0")))
+            side = self._dev[("side_stream", str(dev))] = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
-        hull_side = None
-        if os.environ.get("TH_HULL_STREAM", "1") != "0":
-            hull_side = self._dev.get(("hull_side_stream", str(dev)))
-            if hull_side is None:
-                hull_side = self._dev[("hull_side_stream", str(dev))] = torch.cuda.Stream(dev)
-        if token_exchange is not None and os.environ.get("TH_GRAPH_PRIME", "1") != "0":
+        hull_side = self._dev.get(("hull_side_stream", str(dev)))
+        if hull_side is None:
+            hull_side = self._dev[("hull_side_stream", str(dev))] = torch.cuda.Stream(dev)
+        if token_exchange is not None:
             # multi-rank job: a rank runs TransHE (and, with the stem exchange, the stem) only for the frames it owns, so the
             # first-call capture of their graphs (a device synchronisation + a garbage collection per instance: tens of
             # milliseconds) would land on its first OWNED frame -- frame r of rank r, inside a short run's timed frames.  One
