@@ -467,6 +467,26 @@ size_t th_ssim_workspace_bytes(int h, int w, int c);
 int th_ssim(th_ctx* ctx, const float* a, const float* b, int h, int w, int c, int pitch, double* out, void* workspace,
             size_t workspace_bytes, th_stream stream);
 
+/* ---- evaluator metrics: LPIPS (VGG16) ---------------------------------------- */
+/* lib/evaluators/if_nerf.py:110-117: lpips.LPIPS(net="vgg") (version 0.1, lpips=True, spatial=False, eval mode;
+ * third_parties/lpips/lpips.py:81-124) of the evaluator's crops mapped to [-1, 1]: ScalingLayer, VGG16 features[0:30]
+ * (13 conv3x3 + ReLU, 4 max pools 2x2 floor), the taps relu1_2 .. relu5_3, per tap normalize_tensor (x / (sqrt(sum_c x^2 +
+ * 1e-10) + 1e-10)) of both images, (f0 - f1)^2, the 1x1 lin_k dot (no bias), the spatial mean, then the sum of the taps.
+ * Convolutions on the fp32-input MFMA (an fp32 fmaf chain, no reduced precision), the head and the means in fp64.
+ * th_lpips_pack: conv_w[l] / conv_b[l] are DEVICE pointers to torchvision's features.{0,2,5,...,28}.weight [COUT][CIN][3][3]
+ * / .bias [COUT], fp32; lin_w[k] to lin{k}.model.1.weight [1][C][1][1].  The packed image (th_lpips_pack_bytes() bytes,
+ * caller-owned device memory) is written on `stream`.
+ * th_lpips: in0, in1: NCHW [n][3][h][w] fp32 in [-1, 1] (device).  out: doubles [n][6] on the device: the five tap values
+ * and their sum.  Both images go through the same launches (lpips(a, a) == 0 exactly); fixed-order reductions, no atomics:
+ * bit-identical from run to run.  h < 16 or w < 16 (the fifth tap would be empty): error before any device work, and the
+ * workspace query gives 0. */
+size_t th_lpips_pack_bytes(void);
+int th_lpips_pack(th_ctx* ctx, const float* const* conv_w /* [13] */, const float* const* conv_b /* [13] */,
+                  const float* const* lin_w /* [5] */, void* packed, size_t bytes, th_stream stream);
+size_t th_lpips_workspace_bytes(int n, int h, int w);
+int th_lpips(th_ctx* ctx, const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out,
+             void* workspace, size_t workspace_bytes, th_stream stream);
+
 /* ---- K10: SMPL linear blend skinning ------------------------------------ */
 /* SMPL._call, lib/utils/SMPL.py:114-186, float64 like the reference.  Model arrays (DEVICE pointers, the fields
  * the reference reads from the SMPL pickle, :83-89): v_template [nv,3], shapedirs [nv,3,10], posedirs [nv,3,207],

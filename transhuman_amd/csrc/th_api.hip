@@ -704,6 +704,24 @@ int th_ssim(th_ctx* c, const float* a, const float* b, int h, int w, int ch, int
     return th_ssim_launch(a, b, h, w, ch, pitch, out, ws, ws_bytes, (hipStream_t)stream);
 }
 
+size_t th_lpips_pack_bytes(void) { return th_lpips_pack_bytes_internal(); }
+
+int th_lpips_pack(th_ctx* c, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w,
+                  void* packed, size_t bytes, th_stream stream) {
+    TH_REQUIRE(c && conv_w && conv_b && lin_w && packed, "null argument");
+    return th_lpips_pack_launch(conv_w, conv_b, lin_w, packed, bytes, (hipStream_t)stream);
+}
+
+size_t th_lpips_workspace_bytes(int n, int h, int w) { return th_lpips_ws(n, h, w); }
+
+int th_lpips(th_ctx* c, const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out,
+             void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(h >= 16 && w >= 16, "image is " + std::to_string(h) + " x " + std::to_string(w) +
+                                       ": LPIPS (VGG16) needs at least 16 x 16 pixels (the fifth tap would be empty)");
+    TH_REQUIRE(c && in0 && in1 && packed && out && ws, "null argument");
+    return th_lpips_launch(in0, in1, n, h, w, packed, out, ws, ws_bytes, (hipStream_t)stream);
+}
+
 size_t th_marching_cubes_workspace_bytes(int X, int Y, int Z) { return th_mc_ws(X, Y, Z) + 256; }
 
 int th_marching_cubes_count(th_ctx* c, const float* cube, int X, int Y, int Z, float iso, void* ws, size_t ws_bytes,

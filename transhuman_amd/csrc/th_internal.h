@@ -523,5 +523,12 @@ int th_fold_color_launch(const float* W /*[N,384]*/, const float* b, const float
 size_t th_ssim_ws(int h, int w, int c);
 int th_ssim_launch(const float* a, const float* b, int h, int w, int c, long long pitch, double* out, void* ws,
                    size_t ws_bytes, hipStream_t s);
+// k_lpips.hip: LPIPS (VGG16, v0.1) of two NCHW fp32 image batches, fp32-input MFMA convolutions, fp64 head
+size_t th_lpips_pack_bytes_internal();
+size_t th_lpips_ws(int n, int h, int w);
+int th_lpips_pack_launch(const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* packed,
+                         size_t bytes, hipStream_t s);
+int th_lpips_launch(const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out, void* ws,
+                    size_t ws_bytes, hipStream_t s);
 int th_segmean_masked_launch(const float* rows, int V, int width, const uint8_t* viz, int nv, const int32_t* off,
                              const int32_t* mem, int nc, float* out, hipStream_t s);

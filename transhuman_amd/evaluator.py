@@ -4,8 +4,8 @@
 Mirrors /root/reference/lib/evaluators/if_nerf.py: ``evaluate(output, batch)`` appends the frame's MSE and PSNR
 (:34-37, :121-130), rebuilds the H x W image from the rays inside the body box (`mask_at_box`, :41-57), crops it to the
 mask's bounding rectangle (:60-62) and writes `pred/frame{i}_view{v}.png` and `gt/..._gt.png` under
-`<result_dir>/<human>/` (:64-99); ``summarize()`` stores `mse.npy` / `psnr.npy` / `ssim.npy` and returns the means
-(:146-175; `lpips.npy` is not written).
+`<result_dir>/<human>/` (:64-99); ``summarize()`` stores `mse.npy` / `psnr.npy` / `ssim.npy` (and `lpips.npy` when
+LPIPS runs, below) and returns the means (:146-175).
 PNG files are written with PIL (cv2 is absent; `cv2.imwrite` of a float image = round-to-nearest, saturate to uint8,
 and the reference's RGB -> BGR swap followed by cv2's BGR file order is the identity on the stored RGB).
 
@@ -15,8 +15,16 @@ crop as ``images()``.  skimage is third-party and absent, so the metric is pinne
 releases that take data_range from the float64 dtype: 7 x 7 uniform window, sample covariance, data_range 2, mean over the
 window-interior pixels of each channel, then over the channels -- not by a run of skimage.  Like skimage, a crop smaller
 than 7 x 7 raises ValueError.  Without a visible HIP device SSIM is skipped (the list stays empty: there is no CPU path).
-LPIPS needs torchvision's pretrained VGG16 (a download) and a VGG conv stack the project does not build: ``lpips`` stays
-an empty list.
+
+LPIPS (:110-117, `lpips.LPIPS(net="vgg")` of the same crops mapped to [-1, 1] with `2 x - 1`) is computed on the device
+by `transhuman_amd.lpips.LPIPS` (csrc/k_lpips.hip) from the same device-side crops, permuted to [1, 3, h, w].  It needs two
+weight files, which are never downloaded: torchvision's VGG16 (`lpips_vgg16` / `cfg.lpips_vgg16_path`, by default
+`<torch.hub.get_dir()>/checkpoints/vgg16-397923af.pth` when that file exists) and LPIPS's `weights/v0.1/vgg.pth`
+(`lpips_lin` / `cfg.lpips_lin_path`, no default).  It runs when both are found and a HIP device is visible; then
+``evaluate`` returns ``"lpips"`` and ``summarize`` writes `lpips.npy`.  A configured path that does not exist raises
+FileNotFoundError; a crop smaller than 16 x 16 raises ValueError.  Without the weights nothing changes: no ``"lpips"`` key
+and no `lpips.npy`.  The metric is the vendored third_parties/lpips (see transhuman_amd/lpips.py for how it may differ
+from the PyPI package the reference's evaluator imports).
 """
 import os
 
@@ -24,7 +32,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .config import get_cfg
+from .config import cfg_get, get_cfg
 from .mesh import psnr_metric
 
 
@@ -45,13 +53,29 @@ def to_uint8(img):
     return np.clip(np.rint(img * 255.0), 0, 255).astype(np.uint8)
 
 
+def _weight_path(given, key, default=None):
+    """an explicitly given or configured path must exist; the default is used only when it does"""
+    p = given if given is not None else cfg_get(key)
+    if p is not None:
+        p = os.path.expanduser(str(p))
+        if not os.path.isfile(p):
+            raise FileNotFoundError(f"LPIPS weights: {key} = {p!r} does not exist")
+        return p
+    return default if default is not None and os.path.isfile(default) else None
+
+
 class Evaluator:
-    def __init__(self, result_dir=None):
+    def __init__(self, result_dir=None, lpips_vgg16=None, lpips_lin=None):
         cfg = get_cfg()
         self.result_dir = result_dir if result_dir is not None else os.path.join(
             getattr(cfg, "result_dir", "data/result"), "epoch_" + str(getattr(getattr(cfg, "test", None), "epoch", -1)),
             str(getattr(getattr(cfg, "test", None), "exp_folder_name", "debug")))
         self.mse, self.psnr, self.ssim, self.lpips = [], [], [], []
+        self.lpips_vgg16 = _weight_path(lpips_vgg16, "lpips_vgg16_path",
+                                        os.path.join(torch.hub.get_dir(), "checkpoints", "vgg16-397923af.pth"))
+        self.lpips_lin = _weight_path(lpips_lin, "lpips_lin_path")
+        self.lpips_on = self.lpips_vgg16 is not None and self.lpips_lin is not None
+        self._lpips_net = None
 
     def psnr_metric(self, img_pred, img_gt):
         return psnr_metric(img_pred, img_gt)
@@ -70,8 +94,8 @@ class Evaluator:
         x, y, w, h = bounding_rect(m)
         return pred[y:y + h, x:x + w], gt[y:y + h, x:x + w]
 
-    def ssim_metric(self, rgb_pred, rgb_gt, batch, H=None, W=None):
-        """(:39-62, :108) SSIM of the cropped images of ``images()``, assembled as float32 on the device -> hip.ssim"""
+    def device_images(self, rgb_pred, rgb_gt, batch, H=None, W=None):
+        """(:39-62) the cropped images of ``images()``, assembled as float32 [h, w, 3] on the device"""
         cfg = get_cfg()
         if H is None:
             H, W = int(cfg.H * cfg.ratio), int(cfg.W * cfg.ratio)
@@ -85,7 +109,22 @@ class Evaluator:
         gt = torch.full((h, w, 3), fill, dtype=torch.float32, device=dev)
         pred[m] = torch.as_tensor(rgb_pred, device=dev).to(torch.float32)
         gt[m] = torch.as_tensor(rgb_gt, device=dev).to(torch.float32)
-        return hip.ssim(pred, gt)
+        return pred, gt
+
+    def ssim_metric(self, rgb_pred, rgb_gt, batch, H=None, W=None):
+        """(:108) SSIM of the cropped images of ``images()``, assembled on the device -> hip.ssim"""
+        return hip.ssim(*self.device_images(rgb_pred, rgb_gt, batch, H, W))
+
+    def lpips_metric(self, rgb_pred, rgb_gt, batch, H=None, W=None):
+        """(:110-117) LPIPS (VGG16) of the cropped images of ``images()`` mapped to [-1, 1], [1, 3, h, w] -> th_lpips"""
+        return self._lpips_of(*self.device_images(rgb_pred, rgb_gt, batch, H, W))
+
+    def _lpips_of(self, pred, gt):
+        if self._lpips_net is None:
+            from .lpips import LPIPS
+            self._lpips_net = LPIPS(net="vgg", vgg16_path=self.lpips_vgg16, model_path=self.lpips_lin, device=pred.device)
+        p, g = (t.permute(2, 0, 1)[None] * 2.0 - 1.0 for t in (pred, gt))
+        return float(self._lpips_net(p, g).item())
 
     def evaluate(self, output, batch, H=None, W=None, save=True):
         from PIL import Image
@@ -96,8 +135,12 @@ class Evaluator:
         self.psnr.append(self.psnr_metric(rgb_pred, rgb_gt))               # :127
         out = {"mse": mse, "psnr": self.psnr[-1]}
         if "mask_at_box" in batch and hip._gpu_visible():
-            self.ssim.append(self.ssim_metric(output["rgb_map"][0], batch["rgb"][0], batch, H, W))   # :131-133
+            crops = self.device_images(output["rgb_map"][0], batch["rgb"][0], batch, H, W)
+            self.ssim.append(hip.ssim(*crops))                              # :108, :131-133
             out["ssim"] = self.ssim[-1]
+            if self.lpips_on:
+                self.lpips.append(self._lpips_of(*crops))                  # :110-117
+                out["lpips"] = self.lpips[-1]
         if save and "mask_at_box" in batch:
             pred, gt = self.images(rgb_pred, rgb_gt, batch, H, W)
             human = batch["human_name"][0] if "human_name" in batch else "human"
@@ -117,5 +160,8 @@ class Evaluator:
         out = {"mse": float(np.mean(self.mse)) if self.mse else float("nan"),
                "psnr": float(np.mean(self.psnr)) if self.psnr else float("nan"),
                "ssim": float(np.mean(self.ssim)) if self.ssim else float("nan")}
+        if self.lpips_on:                                                   # (like ssim: empty without a device)
+            np.save(os.path.join(self.result_dir, "lpips.npy"), self.lpips)
+            out["lpips"] = float(np.mean(self.lpips)) if self.lpips else float("nan")
         self.mse, self.psnr, self.ssim, self.lpips = [], [], [], []
         return out

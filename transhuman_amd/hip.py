@@ -141,6 +141,11 @@ SYMBOLS = {
     "th_ssim_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "th_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                           C.c_size_t, C.c_void_p]),
+    "th_lpips_pack_bytes": (C.c_size_t, []),
+    "th_lpips_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_lpips_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_lpips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                           C.c_void_p, C.c_size_t, C.c_void_p]),
     "th_marching_cubes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "th_marching_cubes_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                           C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),
@@ -1162,6 +1167,58 @@ def ssim(a, b):
     out = torch.empty(1, dtype=torch.float64, device=a.device)
     _check(lib.th_ssim(ctx(a.device), _p(a), _p(b), H, W, Cc, int(a.stride(0)), _p(out), _p(ws), ws.numel(), _stream()))
     return float(out.item())
+
+
+LPIPS_CONV_SHAPES = [(64, 3), (64, 64), (128, 64), (128, 128), (256, 128), (256, 256), (256, 256), (512, 256),
+                     (512, 512), (512, 512), (512, 512), (512, 512), (512, 512)]    # (COUT, CIN) of VGG16 features[0:30]
+LPIPS_TAP_CHANNELS = [64, 128, 256, 512, 512]
+
+
+def lpips_pack(conv_w, conv_b, lin_w, device=None):
+    """th_lpips_pack: the 13 VGG16 conv weights [COUT, CIN, 3, 3] / biases [COUT] and the 5 LPIPS lin weights [1, C, 1, 1]
+    -> the packed device image th_lpips reads (a uint8 tensor; the packing runs on the current stream)."""
+    assert len(conv_w) == 13 and len(conv_b) == 13 and len(lin_w) == 5
+    dev = torch.device(device) if device is not None else conv_w[0].device
+    ws = [w.detach().to(dev, torch.float32).contiguous() for w in conv_w]
+    bs = [b.detach().to(dev, torch.float32).contiguous() for b in conv_b]
+    ls = [w.detach().to(dev, torch.float32).contiguous() for w in lin_w]
+    for i, (w, b) in enumerate(zip(ws, bs)):
+        co, ci = LPIPS_CONV_SHAPES[i]
+        if tuple(w.shape) != (co, ci, 3, 3) or tuple(b.shape) != (co,):
+            raise ValueError(f"conv {i}: expected weight {(co, ci, 3, 3)} and bias {(co,)}, got {tuple(w.shape)} and "
+                             f"{tuple(b.shape)}")
+    for k, w in enumerate(ls):
+        if w.numel() != LPIPS_TAP_CHANNELS[k]:
+            raise ValueError(f"lin{k}: expected {LPIPS_TAP_CHANNELS[k]} weights, got shape {tuple(w.shape)}")
+    lib = load_library()
+    packed = torch.empty(int(lib.th_lpips_pack_bytes()), dtype=torch.uint8, device=dev)
+    arr13, arr5 = C.c_void_p * 13, C.c_void_p * 5
+    _check(lib.th_lpips_pack(ctx(dev), arr13(*[t.data_ptr() for t in ws]), arr13(*[t.data_ptr() for t in bs]),
+                             arr5(*[t.data_ptr() for t in ls]), _p(packed), packed.numel(), _stream()))
+    torch.cuda.current_stream(dev).synchronize()             # (the sources are temporaries)
+    return packed
+
+
+def lpips(in0, in1, packed):
+    """th_lpips: LPIPS (VGG16, v0.1, lpips=True, spatial=False) of in0 vs in1, NCHW float32 device tensors in [-1, 1]
+    ([N, 3, H, W] or [3, H, W]), with the image of lpips_pack.  Returns a float64 device tensor [N, 6]: the five tap values
+    (relu1_2 .. relu5_3, each already the spatial mean of lin_k((f0 - f1)^2)) and their sum.  Runs on the current stream.
+    ValueError below 16 x 16 (the fifth tap would be empty)."""
+    if in0.dim() == 3:
+        in0, in1 = in0[None], in1[None]
+    if in0.dim() != 4 or in0.shape != in1.shape or in0.shape[1] != 3:
+        raise ValueError(f"lpips expects two [N, 3, H, W] batches of the same shape, got {tuple(in0.shape)} and "
+                         f"{tuple(in1.shape)}")
+    N, _, H, W = (int(n) for n in in0.shape)
+    if H < 16 or W < 16:
+        raise ValueError(f"lpips: a {H} x {W} image is smaller than 16 x 16 (VGG16's fifth tap would be empty)")
+    assert in0.is_cuda and in1.is_cuda and in0.device == in1.device == packed.device, "expected tensors on one device"
+    a, b = _f32(in0), _f32(in1)
+    lib = load_library()
+    ws = _ws(lib.th_lpips_workspace_bytes(N, H, W), a.device)
+    out = torch.empty((N, 6), dtype=torch.float64, device=a.device)
+    _check(lib.th_lpips(ctx(a.device), _p(a), _p(b), N, H, W, _p(packed), _p(out), _p(ws), ws.numel(), _stream()))
+    return out
 
 
 def marching_cubes(cube, iso, scale=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), x_range=None):
