@@ -487,6 +487,36 @@ size_t th_lpips_workspace_bytes(int n, int h, int w);
 int th_lpips(th_ctx* ctx, const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out,
              void* workspace, size_t workspace_bytes, th_stream stream);
 
+/* ---- K14: mesh rasteriser, vertex visibility maps and SMPL depth maps -------------------------- */
+/* batch['input_vizmaps'] ([1, V, 6890], the mask paint_neural_human applies at if_clight_renderer.py:176-182) and
+ * batch['input_depthmaps'] are LOADED by the reference from the .npy files of rasterize_root/<human>/{visibility,depth} (can_smpl.py:439-475);
+ * no program of the reference writes those files, so the rasteriser below is defined by this project (DESIGN.md 4 K14,
+ * restated in numpy by transhuman_amd.visibility.rasterize_oracle):
+ *   float64 projection of :123-126 without contraction; pixel centre (col, row) at (u, v) = (col, row); vertices snapped to 1/256
+ *   pixel round-half-even; int64 edge functions with the top-left rule (y down), either winding, no back-face culling; a triangle
+ *   is skipped for a view when a vertex has z <= 1e-3 or |u| or |v| >= 2^20, or when its snapped area is 0 -- there is NO
+ *   clipping; depth = 1 / sum(w_i / z_i) in float64 rounded once to fp32; z-buffer of uint64 keys (depth bits << 32 | face)
+ *   under a 64-bit atomicMin: nearest fragment, then lowest face index -- deterministic, independent of launch shape.
+ * th_rasterize_mesh: verts_world fp32 [nv][3], faces int32 [nf][3] (either winding), cams [V][21] (R[9] T[3] K[9] row-major, as
+ * everywhere here) -> depth fp32 [V][H][W] (`background` where nothing landed) and pix_to_face int32 [V][H][W] (-1 there).  Five
+ * operations on `stream`, then ONE host wait on it: a face index outside [0, nv) is never dereferenced, its triangle is skipped
+ * and the call returns an error.  1 <= H, W <= 16384; V H W, V nf, V nv < 2^31 (the workspace query gives 0 otherwise).
+ * th_vertex_visibility: vis uint8 [V][nv] (the format th_paint_group* takes) = 1 iff the vertex is a corner of a face that owns
+ * at least one pixel of pix_to_face[v]; entries of pix_to_face / faces outside the mesh are ignored.  No host wait.
+ * th_depth_visibility: get_relative_depth, if_clight_renderer.py:75-93 as :129-133 calls it, in fp32: depthmaps fp32 [V][H][W]
+ * sampled at uv / H * 2 - 1 (both coordinates over H, :85) by F.grid_sample's defaults (bilinear, zeros, align_corners=False)
+ * -> surface_depth [V][nv]; vis_mask uint8 [V][nv] = depth <= surface + det; relative_depth [V][nv] = depth - (surface + det),
+ * depth = the fp32 p_2 of :123-125.  No host wait. */
+size_t th_rasterize_workspace_bytes(int V, int n_verts, int n_faces, int H, int W);
+int th_rasterize_mesh(th_ctx* ctx, const float* verts_world, int n_verts, const int32_t* faces, int n_faces, const float* cams,
+                      int V, int H, int W, float background, float* depth, int32_t* pix_to_face, void* workspace,
+                      size_t workspace_bytes, th_stream stream);
+int th_vertex_visibility(th_ctx* ctx, const int32_t* pix_to_face, const int32_t* faces, int n_faces, int n_verts, int V, int H,
+                         int W, uint8_t* vis, th_stream stream);
+int th_depth_visibility(th_ctx* ctx, const float* verts_world, int n_verts, const float* cams, int V, const float* depthmaps,
+                        int H, int W, float det, float* surface_depth, uint8_t* vis_mask, float* relative_depth,
+                        th_stream stream);
+
 /* ---- K10: SMPL linear blend skinning ------------------------------------ */
 /* SMPL._call, lib/utils/SMPL.py:114-186, float64 like the reference.  Model arrays (DEVICE pointers, the fields
  * the reference reads from the SMPL pickle, :83-89): v_template [nv,3], shapedirs [nv,3,10], posedirs [nv,3,207],

@@ -29,6 +29,9 @@ def _defaults():
         rasterize=True,
         depth_map=False,
         depth_vizmap=False,
+        # where the vertex mask of painting comes from: "batch" (input_vizmaps, as the reference) or "device" (rasterised here
+        # from input_smpl_vertice, the input cameras and the renderer's faces; transhuman_amd/visibility.py)
+        vizmap_source="batch",
         # architecture (train_or_eval.yaml:51-56)
         embed_size=192,
         img_feat_size=384,

@@ -704,6 +704,27 @@ int th_ssim(th_ctx* c, const float* a, const float* b, int h, int w, int ch, int
     return th_ssim_launch(a, b, h, w, ch, pitch, out, ws, ws_bytes, (hipStream_t)stream);
 }
 
+size_t th_rasterize_workspace_bytes(int V, int nv, int nf, int H, int W) { return th_raster_ws(V, nv, nf, H, W); }
+
+int th_rasterize_mesh(th_ctx* c, const float* verts, int nv, const int32_t* faces, int nf, const float* cams, int V, int H, int W,
+                      float background, float* depth, int32_t* pix_to_face, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && verts && faces && cams && depth && pix_to_face && ws, "null argument");
+    return th_raster_launch(verts, nv, faces, nf, cams, V, H, W, background, depth, pix_to_face, ws, ws_bytes,
+                            (hipStream_t)stream);
+}
+
+int th_vertex_visibility(th_ctx* c, const int32_t* pix_to_face, const int32_t* faces, int nf, int nv, int V, int H, int W,
+                         uint8_t* vis, th_stream stream) {
+    TH_REQUIRE(c && pix_to_face && faces && vis, "null argument");
+    return th_vertex_visibility_launch(pix_to_face, faces, nf, nv, V, H, W, vis, (hipStream_t)stream);
+}
+
+int th_depth_visibility(th_ctx* c, const float* verts, int nv, const float* cams, int V, const float* depthmaps, int H, int W,
+                        float det, float* surface, uint8_t* vis, float* relative, th_stream stream) {
+    TH_REQUIRE(c && verts && cams && depthmaps && surface && vis && relative, "null argument");
+    return th_depth_visibility_launch(verts, nv, cams, V, depthmaps, H, W, det, surface, vis, relative, (hipStream_t)stream);
+}
+
 size_t th_lpips_pack_bytes(void) { return th_lpips_pack_bytes_internal(); }
 
 int th_lpips_pack(th_ctx* c, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w,

@@ -530,5 +530,13 @@ int th_lpips_pack_launch(const float* const* conv_w, const float* const* conv_b,
                          size_t bytes, hipStream_t s);
 int th_lpips_launch(const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out, void* ws,
                     size_t ws_bytes, hipStream_t s);
+// k_raster.hip: z-buffer rasteriser of a triangle mesh into V views, and the two vertex-visibility rules on top of it
+size_t th_raster_ws(int V, int nv, int nf, int H, int W);
+int th_raster_launch(const float* verts, int nv, const int32_t* faces, int nf, const float* cams, int V, int H, int W,
+                     float background, float* depth, int32_t* pix_to_face, void* ws, size_t ws_bytes, hipStream_t s);
+int th_vertex_visibility_launch(const int32_t* pix_to_face, const int32_t* faces, int nf, int nv, int V, int H, int W,
+                                uint8_t* vis, hipStream_t s);
+int th_depth_visibility_launch(const float* verts, int nv, const float* cams, int V, const float* depthmaps, int H, int W,
+                               float det, float* surface, uint8_t* vis, float* relative, hipStream_t s);
 int th_segmean_masked_launch(const float* rows, int V, int width, const uint8_t* viz, int nv, const int32_t* off,
                              const int32_t* mem, int nc, float* out, hipStream_t s);

@@ -141,6 +141,13 @@ SYMBOLS = {
     "th_ssim_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "th_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                           C.c_size_t, C.c_void_p]),
+    "th_rasterize_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "th_rasterize_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_vertex_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
+    "th_depth_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "th_lpips_pack_bytes": (C.c_size_t, []),
     "th_lpips_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "th_lpips_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

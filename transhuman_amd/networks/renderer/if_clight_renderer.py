@@ -30,15 +30,17 @@ import pickle                                                       # noqa: E402
 import numpy as np                                                  # noqa: E402
 import torch                                                        # noqa: E402
 
-from transhuman_amd.config import get_cfg                           # noqa: E402
+from transhuman_amd.config import cfg_get, get_cfg                  # noqa: E402
 from transhuman_amd import hip, synth                               # noqa: E402
 
 
 class Renderer:
-    def __init__(self, net, vertex_can=None, pc2voxel_ind=None):
+    def __init__(self, net, vertex_can=None, pc2voxel_ind=None, faces=None):
         """``vertex_can`` (float64 [6890,3]) / ``pc2voxel_ind`` (int [6890]) may be
         injected; otherwise they are read from the reference's cwd-relative files
-        (./data/smplx/smpl/SMPL_NEUTRAL.pkl :43-48, ./kmeans_dict/kmeans_dict_{N}.npy :55)."""
+        (./data/smplx/smpl/SMPL_NEUTRAL.pkl :43-48, ./kmeans_dict/kmeans_dict_{N}.npy :55).
+        ``faces`` (int [nf,3]): the triangles of the vertices in ``batch['input_smpl_vertice']``, used only with
+        cfg.vizmap_source == "device" (prepare_frame); default: the SMPL pickle's ``f`` when that file is read."""
         cfg = get_cfg()
         self.net = net
         self.faces = None
@@ -47,6 +49,8 @@ class Renderer:
                 data = pickle.load(f, encoding="latin1")
             vertex_can = np.asarray(data["v_template"])
             self.faces = data["f"]
+        if faces is not None:
+            self.faces = faces
         self.vertex_can = torch.as_tensor(np.asarray(vertex_can)).contiguous()      # float64 like :48
         self.CR = torch.tensor([-1.5, -1.5, -1.5, 1.5, 1.5, 1.5])                  # :50
         voxel2pc = None
@@ -149,7 +153,10 @@ class Renderer:
                              batch["input_K"][t].reshape(-1, 3, 3))
         image_shape = batch["input_imgs"][t].shape[-2:]
         off, mem = self._csr(dev)
-        viz = batch["input_vizmaps"][t][0] if cfg.rasterize else None               # :103-119
+        if cfg.rasterize and cfg_get("vizmap_source", "batch") == "device":
+            viz = self._device_vizmap(batch, t)              # (a callable: evaluated where the frame paints, once)
+        else:
+            viz = batch["input_vizmaps"][t][0] if cfg.rasterize else None           # :103-119
         enc = self.net.encoder
         fold_done = None
         if fused_encoder_tail and hasattr(enc, "trunk"):
@@ -210,7 +217,8 @@ class Renderer:
                     hip.map_fold(self.net, map_nhwc)
 
             def group():
-                return hip.paint_group_nhwc(map_nhwc, batch["input_smpl_vertice"][t][0], cams, scale, viz,
+                return hip.paint_group_nhwc(map_nhwc, batch["input_smpl_vertice"][t][0], cams, scale,
+                                            viz() if callable(viz) else viz,
                                             enc.reduction_layer.weight, enc.reduction_layer.bias, off, mem,
                                             color_w=cw if compact_map else None, color_b=cb if compact_map else None)
             pix_scale = scale
@@ -220,7 +228,8 @@ class Renderer:
 
             def group():
                 return hip.paint_group(holder_map, batch["input_smpl_vertice"][t][0], cams,
-                                       hip.feat_scale(holder_scale, image_shape, dev), viz, off, mem)
+                                       hip.feat_scale(holder_scale, image_shape, dev), viz() if callable(viz) else viz,
+                                       off, mem)
             map_nhwc = hip.nchw_to_nhwc(pixel_map)
             pix_scale = hip.feat_scale(pixel_scale, image_shape, dev)
 
@@ -272,6 +281,43 @@ class Renderer:
         # (device bool: the stem latents this frame was built from were not finite -- dist.StemExchange; read in finish())
         frame.stem_flag = stem_flag if (fused_encoder_tail and hasattr(enc, "trunk")) else None
         return frame
+
+    def _device_vizmap(self, batch, t):
+        """cfg.vizmap_source == "device": the mask of :103-119 / :129-133 computed here instead of read from
+        ``batch['input_vizmaps']`` (which may be absent).  Returns a callable: prepare_frame's ``group()`` calls it, so the mask is
+        made only on the rank that paints this frame (the token owner of a multi-rank job), on the stream that paints, outside
+        the captured stem / TransHE graphs.  The mesh is rasterised into the input views (transhuman_amd.visibility, K14); with
+        cfg.depth_map and cfg.depth_vizmap the mask is get_relative_depth's (:75-93) on ``batch['input_depthmaps'][t]`` when
+        the batch has them, else on the rasterised depth.  The uint8 [V, nv] mask is kept in ``self.last_vizmap``."""
+        from transhuman_amd import visibility
+        cfg = get_cfg()
+        if self.faces is None:
+            raise ValueError('cfg.vizmap_source == "device" needs the mesh triangles: Renderer(net, ..., faces=[nf,3]) '
+                             "(or the SMPL pickle's f, read when vertex_can is not injected)")
+        verts = batch["input_smpl_vertice"][t][0]
+        dev = verts.device
+        key = ("faces", str(dev))
+        if key not in self._dev:
+            self._dev[key] = visibility._faces_dev(self.faces, dev)
+        faces = self._dev[key]
+        R, T, K = batch["input_R"][t], batch["input_T"][t], batch["input_K"][t]
+        H, W = batch["input_imgs"][t].shape[-2:]
+        done = []
+
+        def make():
+            if not done:
+                if cfg.depth_map and cfg.depth_vizmap:                              # :129-133
+                    dm = batch["input_depthmaps"][t] if "input_depthmaps" in batch else None
+                    if dm is None:
+                        dm, _ = visibility.rasterize_mesh(verts, faces, R, T, K, H, W)
+                    mask = visibility.depth_visibility(verts, dm, R, T, K, det=0.07)[1].to(torch.uint8)
+                else:
+                    _, p2f = visibility.rasterize_mesh(verts, faces, R, T, K, H, W)
+                    mask = visibility.visibility_from_faces(p2f, faces, verts.shape[0])
+                self.last_vizmap = mask
+                done.append(mask)
+            return done[0]
+        return make
 
     def predemand(self, batch, pts, token_exchange=None, sharded=False):
         """Behind ``hip.render_prepass(pts, ...)``, on the current stream (the prepass's): the demand buffer of the frame's map
