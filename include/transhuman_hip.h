@@ -517,6 +517,38 @@ int th_depth_visibility(th_ctx* ctx, const float* verts_world, int n_verts, cons
                         int H, int W, float det, float* surface_depth, uint8_t* vis_mask, float* relative_depth,
                         th_stream stream);
 
+/* ---- K15: vertex normals and normal-coloured Phong frames of a mesh ---------------------------- */
+/* render_mesh_dynamic.py:182-276 of the reference renders each extracted mesh with pytorch3d (MeshRasterizer, faces_per_pixel 1,
+ * blur_radius 0; SoftPhongShader, PointLights at (0, 3, 0), default Materials; verts_rgb = 0.7 n + 0.7 with n the normals of the
+ * mesh in the camera frame with y and z flipped).  pytorch3d is third-party and absent: parity with it is UNPINNED; the image
+ * below is defined by this project after those settings and restated in float64 / int64 numpy by
+ * transhuman_amd.mesh_render.vertex_normals_oracle / render_mesh_oracle.  Float64 on the exactly promoted fp32 inputs, no
+ * contraction, every output rounded once to fp32.
+ * th_vertex_normals: verts fp32 [nv][3], faces int32 [nf][3] -> normals fp32 [nv][3], pytorch3d's area-weighted rule: every corner
+ * of a face receives c = (v1 - v0) x (v2 - v0), as the int64 q = rint(c 2^40) summed with 64-bit vector atomics (exact: the
+ * result does not depend on the order of the faces or the launch shape, bit for bit), n = s / max(|s|, 1e-6), (0, 0, 0) for a
+ * vertex without faces or with cancelling ones; flip != 0 negates.  Faces the rasteriser would skip count.  Two memsets and two
+ * kernels on `stream`, NO host wait -- so what only the device can see is reported in `status`, ONE int32 on the device, valid
+ * once the stream has passed the call: bit 0: a face index outside [0, nv) (never dereferenced, the face adds nothing); bit 1: a
+ * face with |c_k| 2^40 > 2^62 / nf or not finite (outside the range in which no sum can leave int64; it adds nothing -- nothing
+ * ever wraps).  0: the normals are valid.  transhuman_amd.mesh_render reads the word and raises.  The workspace holds the int64
+ * sums [nv][3] at its start when the call has run.
+ * th_shade_mesh: pix_to_face int32 [V][H][W] as th_rasterize_mesh wrote it for the same verts, faces and cams; vertex_normals as
+ * above -> image fp32 [V][H][W][3], unclamped.  At a covered pixel the perspective-correct weights b_i = (w_i / z_i) / sum(w_j / z_j)
+ * from the same snapped int64 edge functions as the rasteriser, p = sum b_i v_i, nh = unit(sum b_i n_i), texel t = sum b_i (0.7 F R n_i
+ * + 0.7) with F = diag(1, -1, -1), lh = unit(light - p), vh = unit(-R^T T - p), d = nh . lh,
+ * colour = (ambient + diffuse max(d, 0)) t + specular [d > 0] max(vh . (2 d nh - lh), 0)^shininess (unit(x) = x / max(|x|, 1e-6);
+ * shininess a power of two, taken by squaring; the reference's settings: 0.5, 0.3, 0.2, 64).  Elsewhere, and where pix_to_face
+ * names no face of the mesh: `background`, exactly.  light_host / background_host: 3 floats each on the HOST.  One kernel, no
+ * host wait, no workspace.  V <= 65535; the rasteriser's limits on H, W otherwise. */
+size_t th_vertex_normals_workspace_bytes(int n_verts, int n_faces);
+int th_vertex_normals(th_ctx* ctx, const float* verts, int n_verts, const int32_t* faces, int n_faces, int flip, float* normals,
+                      int32_t* status, void* workspace, size_t workspace_bytes, th_stream stream);
+int th_shade_mesh(th_ctx* ctx, const float* verts_world, const float* vertex_normals, int n_verts, const int32_t* faces,
+                  int n_faces, const float* cams, int V, int H, int W, const int32_t* pix_to_face, const float* light_host /* [3] */,
+                  const float* background_host /* [3] */, float ambient, float diffuse, float specular, int shininess, float* image,
+                  th_stream stream);
+
 /* ---- K10: SMPL linear blend skinning ------------------------------------ */
 /* SMPL._call, lib/utils/SMPL.py:114-186, float64 like the reference.  Model arrays (DEVICE pointers, the fields
  * the reference reads from the SMPL pickle, :83-89): v_template [nv,3], shapedirs [nv,3,10], posedirs [nv,3,207],

@@ -725,6 +725,22 @@ int th_depth_visibility(th_ctx* c, const float* verts, int nv, const float* cams
     return th_depth_visibility_launch(verts, nv, cams, V, depthmaps, H, W, det, surface, vis, relative, (hipStream_t)stream);
 }
 
+size_t th_vertex_normals_workspace_bytes(int nv, int nf) { return th_vertex_normals_ws(nv, nf); }
+
+int th_vertex_normals(th_ctx* c, const float* verts, int nv, const int32_t* faces, int nf, int flip, float* normals,
+                      int32_t* status, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && verts && faces && normals && status && ws, "null argument");
+    return th_vertex_normals_launch(verts, nv, faces, nf, flip, normals, status, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int th_shade_mesh(th_ctx* c, const float* verts, const float* normals, int nv, const int32_t* faces, int nf, const float* cams,
+                  int V, int H, int W, const int32_t* pix_to_face, const float* light_host, const float* background_host,
+                  float ambient, float diffuse, float specular, int shininess, float* image, th_stream stream) {
+    TH_REQUIRE(c && verts && normals && faces && cams && pix_to_face && light_host && background_host && image, "null argument");
+    return th_shade_mesh_launch(verts, normals, nv, faces, nf, cams, V, H, W, pix_to_face, light_host, background_host, ambient,
+                                diffuse, specular, shininess, image, (hipStream_t)stream);
+}
+
 size_t th_lpips_pack_bytes(void) { return th_lpips_pack_bytes_internal(); }
 
 int th_lpips_pack(th_ctx* c, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w,

@@ -538,5 +538,12 @@ int th_vertex_visibility_launch(const int32_t* pix_to_face, const int32_t* faces
                                 uint8_t* vis, hipStream_t s);
 int th_depth_visibility_launch(const float* verts, int nv, const float* cams, int V, const float* depthmaps, int H, int W,
                                float det, float* surface, uint8_t* vis, float* relative, hipStream_t s);
+// k_meshshade.hip: area-weighted vertex normals (exact integer sums) and the normal-coloured Phong image on K14's pix_to_face
+size_t th_vertex_normals_ws(int nv, int nf);
+int th_vertex_normals_launch(const float* verts, int nv, const int32_t* faces, int nf, int flip, float* normals, int32_t* status,
+                             void* ws, size_t ws_bytes, hipStream_t s);
+int th_shade_mesh_launch(const float* verts, const float* normals, int nv, const int32_t* faces, int nf, const float* cams, int V,
+                         int H, int W, const int32_t* pix_to_face, const float* light, const float* background, float ambient,
+                         float diffuse, float specular, int shininess, float* image, hipStream_t s);
 int th_segmean_masked_launch(const float* rows, int V, int width, const uint8_t* viz, int nv, const int32_t* off,
                              const int32_t* mem, int nc, float* out, hipStream_t s);
