@@ -549,6 +549,32 @@ int th_shade_mesh(th_ctx* ctx, const float* verts_world, const float* vertex_nor
                   const float* background_host /* [3] */, float ambient, float diffuse, float specular, int shininess, float* image,
                   th_stream stream);
 
+/* ---- K16: the input views from the raw camera pictures (undistort, resize, mask) ---------------- */
+/* The reference's dataset prepares every input view on the host with OpenCV (lib/datasets/light_stage/can_smpl.py:118-200 get_mask /
+ * get_input_mask, :629-660 process_loaded: / 255, cv2.undistort, cv2.resize INTER_AREA / INTER_NEAREST, black-out under the mask,
+ * 5 x 5 erode / dilate border marked 100).  OpenCV is absent: parity with cv2 is UNPINNED (its SIMD paths may fuse the four-tap
+ * sum; its 15-bit weight table has a saturation fix-up that is not reproduced); the image below is defined by this project after
+ * OpenCV's documented algorithm and restated in numpy by transhuman_amd.preprocess.prepare_views_oracle /
+ * combine_masks_oracle, which the device equals bit for bit: every step is one correctly rounded IEEE operation in a fixed order.
+ * th_prep_views: img uint8 [V][H0][W0][3], msk uint8 [V][H0][W0], K fp32 [V][9] row-major, D fp32 [V][5] = (k1, k2, p1, p2, k3), lut
+ * fp32 [256] = float(i) / 255.0f -- all DEVICE pointers -- n = 1 / ratio in {1, 2, 4} dividing H0 and W0, H = H0 / n, W = W0 / n
+ * -> out_img fp32 [V][3][H][W], out_msk uint8 [V][H][W].  For source pixel (col j, row i), in float64 on the promoted K, D:
+ * x = (j - cx) / fx, y = (i - cy) / fy, r2 = x x + y y, t = (2 x) y, kr = 1 + ((k3 r2 + k2) r2 + k1) r2,
+ * xd = (x kr + p1 t) + p2 (r2 + 2 x x), yd = (y kr + p1 (r2 + 2 y y)) + p2 t, u = fx xd + cx, v = fy yd + cy, iu = rint(32 u),
+ * iv = rint(32 v) (|32 u| >= 2^30 or not finite: every tap outside), X = iu >> 5, a = iu & 31 (Y, b alike); taps (X,Y) (X+1,Y) (X,Y+1)
+ * (X+1,Y+1) with integer weights (32-b)(32-a), (32-b) a, b (32-a), b a, a tap outside the image being 0; picture in fp32
+ * o = ((s00 w00 + s01 w01) + s10 w10) + s11 w11 with s = lut[u8], w = W / 1024; mask (W00 m00 + ... + 512) >> 10 in integers.  Resize:
+ * the n x n block of o summed in row-major order from 0, times 1 / (n n); mask at [n y][n x].  mask_bkgd != 0: where the resized
+ * mask is 0 the picture is 0 (1 with white_bkgd != 0).  One kernel, no host wait, no workspace.
+ * th_prep_mask: a, b_or_null uint8 [V][H0][W0] -> out uint8 [V][H0][W0] (not in place): m = (a != 0) | (b != 0); border = 0: that;
+ * border odd <= 15: 100 where the maximum and minimum of m over the border x border window (the pixels of it inside the image)
+ * differ.  One kernel, no host wait.  1 <= H0, W0 <= 16384, V <= 65535 for both. */
+int th_prep_views(th_ctx* ctx, const uint8_t* img_u8, const uint8_t* msk_u8, int V, int H0, int W0, const float* K /* [V][9] */,
+                  const float* D /* [V][5] */, int n, int mask_bkgd, int white_bkgd, const float* lut /* [256] */, float* out_img,
+                  uint8_t* out_msk, th_stream stream);
+int th_prep_mask(th_ctx* ctx, const uint8_t* a, const uint8_t* b_or_null, int V, int H0, int W0, int border, uint8_t* out,
+                 th_stream stream);
+
 /* ---- K10: SMPL linear blend skinning ------------------------------------ */
 /* SMPL._call, lib/utils/SMPL.py:114-186, float64 like the reference.  Model arrays (DEVICE pointers, the fields
  * the reference reads from the SMPL pickle, :83-89): v_template [nv,3], shapedirs [nv,3,10], posedirs [nv,3,207],

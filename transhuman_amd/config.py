@@ -32,6 +32,10 @@ def _defaults():
         # where the vertex mask of painting comes from: "batch" (input_vizmaps, as the reference) or "device" (rasterised here
         # from input_smpl_vertice, the input cameras and the renderer's faces; transhuman_amd/visibility.py)
         vizmap_source="batch",
+        # where batch['input_imgs'] / batch['input_K'] come from: "batch" (as the reference: its dataset prepares them on the host)
+        # or "device" (made here from the raw camera frames input_imgs_raw / input_msks_raw / input_K_raw / input_D: undistort,
+        # resize by `ratio`, background under the mask; transhuman_amd/preprocess.py, Renderer.frame_inputs)
+        input_prep="batch",
         # architecture (train_or_eval.yaml:51-56)
         embed_size=192,
         img_feat_size=384,

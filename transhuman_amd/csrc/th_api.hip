@@ -741,6 +741,18 @@ int th_shade_mesh(th_ctx* c, const float* verts, const float* normals, int nv, c
                                 diffuse, specular, shininess, image, (hipStream_t)stream);
 }
 
+int th_prep_views(th_ctx* c, const uint8_t* img, const uint8_t* msk, int V, int H0, int W0, const float* K, const float* D, int n,
+                  int mask_bkgd, int white_bkgd, const float* lut, float* out_img, uint8_t* out_msk, th_stream stream) {
+    TH_REQUIRE(c && img && msk && K && D && lut && out_img && out_msk, "null argument");
+    return th_prep_views_launch(img, msk, V, H0, W0, K, D, n, mask_bkgd, white_bkgd, lut, out_img, out_msk, (hipStream_t)stream);
+}
+
+int th_prep_mask(th_ctx* c, const uint8_t* a, const uint8_t* b, int V, int H0, int W0, int border, uint8_t* out, th_stream stream) {
+    TH_REQUIRE(c && a && out, "null argument");
+    TH_REQUIRE(out != a && out != b, "th_prep_mask does not work in place");
+    return th_prep_mask_launch(a, b, V, H0, W0, border, out, (hipStream_t)stream);
+}
+
 size_t th_lpips_pack_bytes(void) { return th_lpips_pack_bytes_internal(); }
 
 int th_lpips_pack(th_ctx* c, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w,

@@ -545,5 +545,9 @@ int th_vertex_normals_launch(const float* verts, int nv, const int32_t* faces, i
 int th_shade_mesh_launch(const float* verts, const float* normals, int nv, const int32_t* faces, int nf, const float* cams, int V,
                          int H, int W, const int32_t* pix_to_face, const float* light, const float* background, float ambient,
                          float diffuse, float specular, int shininess, float* image, hipStream_t s);
+// k_prep.hip: the input views from the raw camera pictures (undistort, area resize, background) and the raw masks' union / border
+int th_prep_views_launch(const uint8_t* img, const uint8_t* msk, int V, int H0, int W0, const float* K, const float* D, int n,
+                         int mask_bkgd, int white_bkgd, const float* lut, float* out_img, uint8_t* out_msk, hipStream_t s);
+int th_prep_mask_launch(const uint8_t* a, const uint8_t* b, int V, int H0, int W0, int border, uint8_t* out, hipStream_t s);
 int th_segmean_masked_launch(const float* rows, int V, int width, const uint8_t* viz, int nv, const int32_t* off,
                              const int32_t* mem, int nc, float* out, hipStream_t s);

@@ -34,6 +34,12 @@ from transhuman_amd.config import cfg_get, get_cfg                  # noqa: E402
 from transhuman_amd import hip, synth                               # noqa: E402
 
 
+class _PreparedBatch(dict):
+    """a shallow copy of a batch whose ``input_imgs`` / ``input_K`` were made on the device (Renderer.frame_inputs);
+    ``source`` is the caller's batch"""
+    source = None
+
+
 class Renderer:
     def __init__(self, net, vertex_can=None, pc2voxel_ind=None, faces=None):
         """``vertex_can`` (float64 [6890,3]) / ``pc2voxel_ind`` (int [6890]) may be
@@ -105,6 +111,32 @@ class Renderer:
         return self._dev[key]
 
     # ---- per-frame constants ---------------------------------------------------------
+    def frame_inputs(self, batch):
+        """The batch the frame paths read ``input_imgs`` / ``input_K`` from.  cfg.input_prep == "batch" (default): ``batch`` itself,
+        raw keys ignored.  "device": the input views are made here from the raw camera frames (transhuman_amd.preprocess, K16:
+        undistort, resize by cfg.ratio, background under the mask) -- ``batch['input_imgs_raw']`` (list[T] of uint8 [1,V,H0,W0,3]),
+        ``batch['input_msks_raw']`` (list[T] of uint8 [1,V,H0,W0]), ``batch['input_K_raw']`` ([1,V,3,3]) and ``batch['input_D']``
+        ([1,V,5]; the last two also as list[T]) -- on the current stream, without a host wait; ``input_imgs`` / ``input_K`` of the
+        batch, if any, are not read.  Returns a shallow copy with the two keys filled: ``batch`` is not mutated.  A batch that
+        came from here is returned as it is."""
+        mode = cfg_get("input_prep", "batch")
+        if mode == "batch" or isinstance(batch, _PreparedBatch):
+            return batch
+        if mode != "device":
+            raise ValueError(f'cfg.input_prep is {mode!r}: "batch" or "device"')
+        from transhuman_amd import preprocess
+        per_t = lambda x, t: x[t] if isinstance(x, (list, tuple)) else x
+        imgs, Ks = [], []
+        for t, (raw, raw_msk) in enumerate(zip(batch["input_imgs_raw"], batch["input_msks_raw"])):
+            im, _, K = preprocess.prepare_views(raw[0], raw_msk[0], per_t(batch["input_K_raw"], t)[0], per_t(batch["input_D"], t)[0],
+                                                 mask_bkgd=bool(cfg_get("mask_bkgd", True)))
+            imgs.append(im[None])
+            Ks.append(K[None])
+        out = _PreparedBatch(batch)
+        out.source = batch
+        out["input_imgs"], out["input_K"] = imgs, Ks
+        return out
+
     def prepare_frame(self, batch, hull_thresh=None, fused_encoder_tail=True, compact_map=True, token_exchange=None,
                       pregather=None, defer_tokens=False, stem_exchange=None, crop_map=None, demand=None, stem_graph=False):
         """paint -> group -> TransHE -> DPaRF tables (:531-547).  Returns hip.Frame.
@@ -142,6 +174,7 @@ class Renderer:
         cfg = get_cfg()
         assert cfg.time_steps == 1                                                  # :412
         t = 0
+        batch = self.frame_inputs(batch)
         # the weight image (and with it the sticky range slot of the stem convolutions, which belongs to the same
         # parameter set) is brought up to date BEFORE the stem runs and on the stream that runs it: a frame's own
         # convolutions are then never queued in front of the clear that new weights trigger
@@ -331,6 +364,7 @@ class Renderer:
         if mode == "0" or (mode != "1" and not sharded) or not hasattr(self.net.encoder, "trunk"):
             return None
         t = 0
+        batch = self.frame_inputs(batch)
         imgs = batch["input_imgs"][t]
         V, H, W = int(np.prod(imgs.shape[:-3])), int(imgs.shape[-2]), int(imgs.shape[-1])
         dev = imgs.device
@@ -394,6 +428,7 @@ class Renderer:
         pts = hip.Points(batch["ray_o"][0][sl], batch["ray_d"][0][sl], batch["near"][0][sl], batch["far"][0][sl],
                          n_samples=cfg.N_samples, **self._sampling_randoms(batch, sl, cfg))
         if frame is None:
+            batch = self.frame_inputs(batch)
             V = batch["input_imgs"][0].reshape(-1, *batch["input_imgs"][0].shape[2:]).shape[0]
             if V <= 4 and pts.R > 0:
                 # the ray-only stage (hull mask, compaction: ~10 launches, 0.85 ms) runs on a second stream beside the
@@ -523,7 +558,9 @@ class Renderer:
             # the range-guard epoch these constants are built under: a frame whose front was issued before the guard
             # switched a path (fp32 MLP, stock convolutions, fp32 TransHE GEMMs) is rebuilt before it is handed out
             ep = hip.range_epoch(b["ray_o"].device)
+            given = getattr(b, "source", None) or b        # (what the caller handed in: ``self.last_batch``)
             with torch.cuda.stream(side):
+                b = self.frame_inputs(b)
                 pts = hip.Points(b["ray_o"][0][sl], b["ray_d"][0][sl], b["near"][0][sl], b["far"][0][sl],
                                  n_samples=cfg.N_samples, **self._sampling_randoms(b, sl, cfg))
                 V = b["input_imgs"][0].reshape(-1, *b["input_imgs"][0].shape[2:]).shape[0]
@@ -547,7 +584,7 @@ class Renderer:
                     hip.render_pregrid(frame, pts)         # K4's candidate grid: here, not in front of K4
                 ready = torch.cuda.Event()
                 ready.record(side)
-            return [b, pts, frame, ready, ep, ready, False]      # [5]: piece A's event (tokens() replaces [3]); [6]: see below
+            return [given, pts, frame, ready, ep, ready, False]      # [5]: piece A's event (tokens() replaces [3]); [6]: see below
 
         def tokens(ent, side):
             """side stream: piece B of an entry whose piece A has been issued"""
@@ -578,6 +615,8 @@ class Renderer:
             # local set of frame constants up front (no exchange, result dropped) captures both rings on every rank at once.
             # (Train-mode BatchNorm running statistics advance by this one extra frame; they do not enter the rendering.)
             # (keyed on the shape AND the graph epoch: instances dropped for new weights are captured again the same way)
+            with torch.cuda.stream(side):
+                first = self.frame_inputs(first)           # (made once: front() below takes it as it is)
             shape = (tuple(first["input_imgs"][0].shape), hip.graph_epoch())
             primed = self._dev.setdefault(("graphs_primed", str(dev)), set())
             if shape not in primed and hip.graphs_enabled():
