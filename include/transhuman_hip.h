@@ -407,6 +407,27 @@ int th_network_forward(th_ctx* ctx, const float* pixel_feat, const float* viewdi
 int th_composite(th_ctx* ctx, const float* raw, const float* z, const th_points* rays, int white_bkgd,
                  float* rgb, float* acc, float* depth, float* weights_out, th_stream stream);
 
+/* ---- K17: training -- the adjoints of K4, K5 and K7 (additions, ABI 12) ----------------- */
+/* Backward of th_dparf_encode with respect to the tokens: grad_out [P,V,256] (columns 192..255 -- positional encoding and
+ * pad -- do not depend on the tokens and are ignored) -> grad_tokens [V,N_c,192],
+ *   grad_tokens[v,c,:] = sum over (p,k) with idx_k(p) = c of w_k(p) grad_out[p,v,:192],
+ * with the 7 neighbours and weights of th_dparf_encode on the same pts_smpl / centres (the forward's own selection code).
+ * Every element is written (zeros for a centre nobody selected; P = 0 writes zeros); no float atomics: bit-identical from
+ * run to run.  Points, centres and rotations get no gradient.  workspace: th_dparf_encode_bwd_workspace_bytes(P, V, N_c). */
+size_t th_dparf_encode_bwd_workspace_bytes(int P, int V, int n_clusters);
+int th_dparf_encode_bwd(th_ctx* ctx, const float* pts_smpl, int P, const float* centres, const float* rot, int V,
+                        int n_clusters, const float* grad_out, float* grad_tokens, void* workspace, size_t workspace_bytes,
+                        th_stream stream);
+/* Backward of th_pixel_gather (sel = NULL) with respect to the map: grad_out [P,V,ldo] (columns C.. ignored) ->
+ * grad_map_nhwc [V,H,W,C], every element written (the call clears the map, then adds with float atomics: results can differ
+ * in the last bits from run to run).  C a multiple of 4. */
+int th_pixel_gather_bwd(th_ctx* ctx, int V, int C, int H, int W, const float* pts_world, int P, const float* cams,
+                        const float* scale_xy, const float* grad_out, int ldo, float* grad_map_nhwc, th_stream stream);
+/* Backward of th_composite with respect to raw: g_rgb [R,3], g_acc [R], g_depth [R] -> g_raw [R,S,4], S <= 256.  z, rays,
+ * near and far get no gradient.  Bit-identical from run to run. */
+int th_composite_bwd(th_ctx* ctx, const float* raw, const float* z, const th_points* rays, int white_bkgd,
+                     const float* g_rgb, const float* g_acc, const float* g_depth, float* g_raw, th_stream stream);
+
 /* ---- K9: ray generation for a target camera --------------------------- */
 /* lib/utils/if_nerf/if_nerf_data_utils.py:11-30 (get_rays) + :65-97 (get_near_far) as the test split of
  * sample_ray_h36m uses them (:271-283): one ray per pixel of an H x W camera (K [3,3], R [3,3], T [3] float32,

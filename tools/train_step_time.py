@@ -1,0 +1,138 @@
+"""Time one training step (forward + loss.backward() of Renderer.render under autograd) at the reference's training shape --
+2 400 rays x 64 samples, V = 3 input views of 512 x 512, N_c = 500 -- in both modes of cfg.train_kernels on the same box in
+the same job: "torch" (every stage composed from torch operators) and "device" (K4, K5 and K7 through the HIP forwards with
+the HIP adjoints of K17, transhuman_amd/networks/train_ops.py).
+
+    timeout -k 10 900 python tools/train_step_time.py [--steps 10] [--warmup 2] [--rocprof DIR]
+
+Prints one JSON line.  Per mode: median and minimum wall time of a step over --steps steps after --warmup (host clock around
+forward + backward with a device synchronisation at both ends) and torch.cuda.max_memory_allocated of the timed steps; the
+largest difference of the outputs and of every parameter gradient between the two modes; and, with --rocprof DIR, the device
+time of the K17 kernels per step from `rocprofv3 --kernel-trace --stats` over a short run of the "device" mode in a fresh child
+process (DIR keeps the trace).  No threshold on any figure."""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import time
+from collections import defaultdict
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+RAYS, SAMPLES, VIEWS, NC, SIZE = 2400, 64, 3, 500, 512
+K17 = ("dpb_", "dparf_kernel<false, -2>", "dparf_kernelILb0ELin2E", "pixgather_bwd_kernel", "composite_bwd_kernel")
+
+
+def setup(dev):
+    import torch
+    from transhuman_amd import synth
+    from transhuman_amd.config import get_cfg
+    from transhuman_amd.networks.cross_transformer import Network
+    from transhuman_amd.networks.renderer.if_clight_renderer import Renderer
+    cfg = get_cfg()
+    cfg.N_samples, cfg.num_class, cfg.vit_depth, cfg.perturb, cfg.raw_noise_std = SAMPLES, NC, 12, 0.0, 0.0
+    torch.manual_seed(0)
+    net = Network()
+    net.load_state_dict(synth.det_state_dict(net.state_dict(), seed=0, sigma_bias=-1.7))
+    net.train()
+    net = net.to(dev)
+    body, _ = synth.make_body(0)
+    d = np.load(os.path.join(ROOT, "tests", "golden", "synth_assign.npz"))
+    assign = d[f"assign_{NC}"].astype(np.int64) if f"assign_{NC}" in d.files else synth.kmeans_assign(body, NC).astype(np.int64)
+    r = Renderer(net, vertex_can=body.astype(np.float64) * 1.02 + 0.001, pc2voxel_ind=assign)
+    b = synth.make_batch(SIZE, SIZE, VIEWS, seed=0, all_rays=False)
+    n = b["ray_o"].shape[1]
+    pick = torch.from_numpy(np.sort(np.random.RandomState(0).choice(n, RAYS, replace=n < RAYS)))
+    for k in ("ray_o", "ray_d", "near", "far"):
+        b[k] = b[k][:, pick].contiguous()
+    return cfg, net, r, synth.batch_to(b, dev)
+
+
+def step(net, r, b, target):
+    import torch
+    for p in net.parameters():
+        p.grad = None
+    ret = r.render(b)
+    loss = torch.mean((ret["rgb_map"] - target) ** 2) + 0.1 * ret["acc_map"].mean() + 0.01 * ret["depth_map"].mean()
+    loss.backward()
+    return ret
+
+
+def run_mode(mode, cfg, net, r, b, target, steps, warmup):
+    import torch
+    cfg.train_kernels = mode
+    for _ in range(warmup):
+        step(net, r, b, target)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    ms = []
+    for _ in range(steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ret = step(net, r, b, target)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    peak = torch.cuda.max_memory_allocated()
+    outs = {k: v.detach().clone() for k, v in ret.items()}
+    grads = {k: p.grad.detach().clone() for k, p in net.named_parameters() if p.grad is not None}
+    return {"step_ms_median": round(float(np.median(ms)), 2), "step_ms_min": round(float(np.min(ms)), 2), "steps": steps,
+            "peak_allocated_MiB": round(peak / 2 ** 20, 1)}, outs, grads
+
+
+def kernel_times(out_dir, steps):
+    """per-step device time of the K17 kernels from the child's kernel trace"""
+    agg = defaultdict(lambda: [0, 0])
+    for path in glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True):
+        for row in csv.DictReader(open(path)):
+            name = row["Kernel_Name"]
+            if any(t in name for t in K17):
+                key = name.split("(")[0][:60]
+                agg[key][0] += 1
+                agg[key][1] += int(row["End_Timestamp"]) - int(row["Start_Timestamp"])
+    return {k: {"calls_per_step": round(c / steps, 2), "us_per_step": round(t / 1e3 / steps, 1)} for k, (c, t) in sorted(agg.items())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--modes", default="torch,device")
+    ap.add_argument("--rocprof", default=None, metavar="DIR", help="also trace a short 'device' run under rocprofv3 into DIR")
+    args = ap.parse_args()
+    res = {"shape": {"rays": RAYS, "samples": SAMPLES, "views": VIEWS, "n_clusters": NC, "image": [SIZE, SIZE]}}
+    if args.rocprof:
+        # (first, before this process opens the GPU; the traced program is a fresh child behind `--`)
+        os.makedirs(args.rocprof, exist_ok=True)
+        n = 3
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", args.rocprof, "-o", "train_step", "--",
+               sys.executable, os.path.abspath(__file__), "--modes", "device", "--steps", str(n), "--warmup", "0"]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        res["k17_kernels"] = kernel_times(args.rocprof, n) if p.returncode == 0 else {"error": p.stderr[-400:]}
+    import torch
+    dev = torch.device("cuda:0")
+    res["device"] = torch.cuda.get_device_name(0)
+    cfg, net, r, b = setup(dev)
+    target = torch.rand((1, RAYS, 3), device=dev)
+    seen = {}
+    try:
+        for mode in args.modes.split(","):
+            res[mode], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
+            seen[mode] = (outs, grads)
+    finally:
+        cfg.train_kernels = "torch"
+    if len(seen) == 2:
+        (o0, g0), (o1, g1) = seen["torch"], seen["device"]
+        res["device_vs_torch"] = {
+            "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
+            "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -62,6 +62,9 @@ def _defaults():
         hull_dist=0.1,
         small_frame_rays=2400,
         chunk_points=1024 * 32,
+        # the training entry (autograd_path.render): "torch" composes every stage from torch operators; "device" runs the token
+        # blend, the pixel-aligned gather and the compositing through the HIP forwards with HIP adjoints (networks/train_ops.py)
+        train_kernels="torch",
     )
 
 

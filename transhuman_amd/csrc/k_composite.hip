@@ -125,3 +125,99 @@ int th_view_embed_launch(const float* d, int R, int res, float* out, hipStream_t
     TH_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- K7 backward ----------------------------------------------------------------------------------------------------------
+// raw2outputs' adjoint with respect to raw [R,S,4], term by term as torch differentiates nerf_net_utils.py:14-59.  With
+//   c = sigmoid(raw_rgb), s = relu(raw_sigma), e = exp(-s delta), a = 1 - e, t = 1 - a + 1e-10, T_i = prod_{j<i} t_j, w = a T:
+//   G_i      = g_rgb . c_i + g_acc' + g_depth z_i          (dL/dw_i; white background: g_acc' = g_acc - sum(g_rgb), else g_acc)
+//   d raw_rgb = w_i g_rgb c_i (1 - c_i)                     (sigmoid')
+//   dL/da_i  = G_i T_i - (sum_{j>i} G_j w_j) / t_i          (cumprod's backward: the reversed cumulative sum over the input)
+//   d raw_sigma = [raw_sigma > 0] dL/da_i delta_i e_i       (relu'(0) = 0; delta_last = 1e10 |d|)
+// One wave per ray, like the forward: the transmittance is the forward's own product scan (same statements, same carry across
+// 64-sample passes), then the passes run in reverse with a wave suffix-sum scan for sum_{j>i} G_j w_j and its carry.  Every
+// step is a fixed function of the inputs: bit-identical from run to run.  z, ray_d, near and far get no gradient.
+#define CB_MAXPASS 4          // S <= 256
+__global__ __launch_bounds__(256) void composite_bwd_kernel(const float4* __restrict__ raw, const float* __restrict__ zin,
+                                                            ThPointSrc ps, int white, const float* __restrict__ g_rgb,
+                                                            const float* __restrict__ g_acc, const float* __restrict__ g_depth,
+                                                            float4* __restrict__ g_raw) {
+    const int lane = threadIdx.x & 63;
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= ps.R) return;
+    const int S = ps.S;
+    const float dx = ps.ray_d[3 * ray], dy = ps.ray_d[3 * ray + 1], dz = ps.ray_d[3 * ray + 2];
+    float nd = dx * dx + dy * dy;
+    nd = __fsqrt_rn(nd + dz * dz);
+    const float gr = g_rgb[3 * ray], gg = g_rgb[3 * ray + 1], gb = g_rgb[3 * ray + 2], gd = g_depth[ray];
+    float ga = g_acc[ray];
+    if (white) ga = ga - ((gr + gg) + gb);
+    const int npass = (S + 63) / 64;
+    float carryT[CB_MAXPASS + 1];
+    carryT[0] = 1.0f;
+    float suffix = 0.f;                                  // sum of G_j w_j over the passes behind the current one
+#pragma unroll
+    for (int dir = 0; dir < 2; ++dir) {
+        // dir 0: the forward's transmittance carried into every pass; dir 1: the passes in reverse
+#pragma unroll
+        for (int it = 0; it < CB_MAXPASS; ++it) {
+            const int pass = dir == 0 ? it : CB_MAXPASS - 1 - it;
+            if (pass >= npass) continue;
+            const int s = pass * 64 + lane;
+            const bool ok = s < S;
+            float z = 0.f, zn = 0.f;
+            if (ok) {
+                z = zin ? zin[(long long)ray * S + s] : th_sample_z(ps, ray, s);
+                if (s + 1 < S) zn = zin ? zin[(long long)ray * S + s + 1] : th_sample_z(ps, ray, s + 1);
+            }
+            float delta = (s + 1 < S) ? (zn - z) : 1e10f;
+            delta = delta * nd;
+            const float4 r = ok ? raw[(long long)ray * S + s] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float e = expf(-fmaxf(r.w, 0.0f) * delta);
+            const float alpha = ok ? 1.0f - e : 0.0f;
+            float t = (1.0f - alpha) + 1e-10f;
+            if (!ok) t = 1.0f;
+            float inc = t;
+            for (int o = 1; o < 64; o <<= 1) {
+                const float u = __shfl_up(inc, o);
+                if (lane >= o) inc = inc * u;
+            }
+            if (dir == 0) {
+                carryT[pass + 1] = carryT[pass] * __shfl(inc, 63);
+                continue;
+            }
+            float excl = __shfl_up(inc, 1);
+            if (lane == 0) excl = 1.0f;
+            const float T = carryT[pass] * excl;
+            const float w = alpha * T;
+            const float cr = 1.0f / (1.0f + expf(-r.x)), cg = 1.0f / (1.0f + expf(-r.y)), cb = 1.0f / (1.0f + expf(-r.z));
+            const float G = ((gr * cr + gg * cg) + gb * cb) + ga + gd * z;
+            const float x = ok ? G * w : 0.f;
+            float sfx = x;                               // inclusive suffix sum over the wave
+            for (int o = 1; o < 64; o <<= 1) {
+                const float u = __shfl_down(sfx, o);
+                if (lane + o < 64) sfx = sfx + u;
+            }
+            float after = __shfl_down(sfx, 1);
+            if (lane == 63) after = 0.f;
+            after = after + suffix;
+            suffix = suffix + __shfl(sfx, 0);
+            const float g_a = G * T - after / t;
+            float4 o4;
+            o4.x = (w * gr) * ((1.0f - cr) * cr);
+            o4.y = (w * gg) * ((1.0f - cg) * cg);
+            o4.z = (w * gb) * ((1.0f - cb) * cb);
+            o4.w = r.w > 0.0f ? (g_a * e) * delta : 0.0f;
+            if (ok) g_raw[(long long)ray * S + s] = o4;
+        }
+    }
+}
+
+int th_composite_bwd_launch(const float* raw, const float* z, const ThPointSrc& ps, int white, const float* g_rgb,
+                            const float* g_acc, const float* g_depth, float* g_raw, hipStream_t s) {
+    TH_REQUIRE(ps.R >= 0 && ps.S >= 1 && ps.S <= 64 * CB_MAXPASS, "need 1 <= S <= 256 samples per ray");
+    if (ps.R == 0) return 0;
+    hipLaunchKernelGGL(composite_bwd_kernel, dim3(th_cdiv(ps.R, 4)), dim3(256), 0, s, (const float4*)raw, z, ps, white, g_rgb,
+                       g_acc, g_depth, (float4*)g_raw);
+    TH_LAUNCH_CHECK();
+    return 0;
+}

@@ -338,6 +338,21 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
         }
         __syncthreads();
     }
+    if constexpr (!FOLDED && VT == -2) {
+        // TH_ROWS_REC (the backward, k_dparf_bwd.hip): phase 1 above IS the selection -- the same statements, compiled without
+        // contraction, as every other form of this kernel -- and nothing else is produced: one 64-byte record per sample,
+        // int idx[7], 0, float w[7], 0
+        for (int i = threadIdx.x; i < DP_SAMPLES * 16; i += DP_THREADS) {
+            const int lp = i >> 4, j = i & 15;
+            const long long gp = (long long)blockIdx.x * DP_SAMPLES + lp;
+            if (gp >= P) break;
+            unsigned rec = 0u;
+            if (j < DP_K) rec = (unsigned)nb[lp].idx[j];
+            else if (j >= 8 && j < 8 + DP_K) rec = __builtin_bit_cast(unsigned, nb[lp].w[j - 8]);
+            reinterpret_cast<unsigned*>(out)[gp * 16 + j] = rec;
+        }
+        return;
+    }
     const float PI_F = 3.14159274101257324219f;          // fp32(pi)
     const float HALF_PI_F = 1.57079637050628662109f;     // fp32(pi/2)
     if constexpr (FOLDED && VT < 0) {
@@ -535,7 +550,7 @@ int th_dparf_launch(const float* pts_smpl, const ThPointSrc* ps, const float* Rh
         TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
-    TH_REQUIRE(fmt == TH_ROWS_F32 || ((fmt == TH_ROWS_FOLDED || fmt == TH_ROWS_NBR) && pe_out != nullptr),
+    TH_REQUIRE(fmt == TH_ROWS_F32 || fmt == TH_ROWS_REC || ((fmt == TH_ROWS_FOLDED || fmt == TH_ROWS_NBR) && pe_out != nullptr),
                "K4 writes fp32 rows, the folded form or neighbour records");
     // optional candidate grid (th_dparf_grid_build into grid_ws): same carve as the builder
     const DpGrid* gi = nullptr;
@@ -546,7 +561,13 @@ int th_dparf_launch(const float* pts_smpl, const ThPointSrc* ps, const float* Rh
         cnt = ar.take<int>(DPG_MAXCELLS);
         cand = ar.take<int>((size_t)DPG_MAXCELLS * DPG_STRIDE);
     }
-    if (fmt == TH_ROWS_NBR) {
+    if (fmt == TH_ROWS_REC) {
+        static unsigned long long attrr = 0ull;
+        if (th_lds_attr_needed(&attrr))
+            TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<false, -2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL((dparf_kernel<false, -2>), dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
+                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gi, cnt, cand);
+    } else if (fmt == TH_ROWS_NBR) {
         static unsigned long long attrn = 0ull;
         if (th_lds_attr_needed(&attrn))
             TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<true, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

@@ -680,6 +680,31 @@ int th_composite(th_ctx* c, const float* raw, const float* z, const th_points* r
     return th_composite_launch(raw, z, th_src(rays), white, rgb, acc, depth, wout, nullptr, (hipStream_t)stream);
 }
 
+// ---- training: the adjoints of K4, K5 and K7 (transhuman_amd/networks/train_ops.py) ----
+size_t th_dparf_encode_bwd_workspace_bytes(int P, int V, int nc) { return th_dparf_bwd_ws(P, V, nc); }
+
+int th_dparf_encode_bwd(th_ctx* c, const float* pts, int P, const float* centres, const float* rot, int V, int nc,
+                        const float* grad_out, float* grad_tokens, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && centres && rot && grad_tokens, "null argument");
+    TH_REQUIRE(P == 0 || (pts && grad_out && ws), "null argument");
+    return th_dparf_bwd_launch(pts, P, centres, rot, V, nc, 0.5f, grad_out, grad_tokens, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int th_pixel_gather_bwd(th_ctx* c, int V, int C, int H, int W, const float* pts, int P, const float* cams, const float* scale,
+                        const float* grad_out, int ldo, float* grad_map, th_stream stream) {
+    TH_REQUIRE(c && cams && scale && grad_map, "null argument");
+    TH_REQUIRE(P == 0 || (pts && grad_out), "null argument");
+    return th_pixgather_bwd_launch(V, C, H, W, pts, P, cams, scale, grad_out, ldo, grad_map, (hipStream_t)stream);
+}
+
+int th_composite_bwd(th_ctx* c, const float* raw, const float* z, const th_points* rays, int white, const float* g_rgb,
+                     const float* g_acc, const float* g_depth, float* g_raw, th_stream stream) {
+    TH_REQUIRE(c && raw && rays && g_rgb && g_acc && g_depth && g_raw, "null argument");
+    TH_REQUIRE(rays->ray_d != nullptr, "ray_d required");
+    TH_REQUIRE(z || (rays->near && rays->far && rays->t_vals && rays->one_minus_t), "need z or near/far/t_vals");
+    return th_composite_bwd_launch(raw, z, th_src(rays), white, g_rgb, g_acc, g_depth, g_raw, (hipStream_t)stream);
+}
+
 int th_gen_rays(th_ctx* c, const float* K_host, const float* R_host, const float* T_host, const float* bounds_host, int H,
                 int W, float* ray_o, float* ray_d, float* near_out, float* far_out, uint8_t* mask_at_box,
                 th_stream stream) {

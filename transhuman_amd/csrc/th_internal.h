@@ -441,7 +441,9 @@ int th_nchw_to_nhwc_launch(const float* src, int V, int C, int H, int W, float* 
 //                  float w[7], 0 (the 7 nearest token centres in (distance, index) order and their softmax weights) --
 //                  and `pe_out` the split-f16 positional encoding like TH_ROWS_FOLDED.  The fused kernel then forms the
 //                  blend of T' rows itself, on the matrix pipe, from the L2-resident table (k_mlp_fused_kernel.h)
-enum { TH_ROWS_F32 = 0, TH_ROWS_SPLIT = 1, TH_ROWS_FOLDED = 2, TH_ROWS_NBR = 3 };
+//   TH_ROWS_REC    (K4 only) the selection alone, for the backward (k_dparf_bwd.hip): `out` gets one 64-byte record per
+//                  sample -- int idx[7] (token-centre indices in (distance, index) order), 0, float w[7], 0 -- nothing else
+enum { TH_ROWS_F32 = 0, TH_ROWS_SPLIT = 1, TH_ROWS_FOLDED = 2, TH_ROWS_NBR = 3, TH_ROWS_REC = 4 };
 // k_dparf.hip
 int th_dparf_launch(const float* pts_smpl, const ThPointSrc* ps, const float* Rh, const float* Th,
                     const int32_t* sel, int P, const float* centres, const float* rot, const float* tokens,
@@ -452,6 +454,14 @@ int th_dparf_launch(const float* pts_smpl, const ThPointSrc* ps, const float* Rh
 static inline bool th_dparf_grid_ok(int nc) { return nc >= 7 && (size_t)nc * 16 <= 64 * 1024; }
 size_t th_dparf_grid_ws(int nc);
 int th_dparf_grid_build(const float* centres, int nc, void* ws, size_t ws_bytes, hipStream_t s);
+// k_dparf_bwd.hip: grad_tokens [V,nc,192] = adjoint of the token blend applied to grad_out [P,V,256] (columns 192.. ignored);
+// every element is written; bit-identical from run to run
+size_t th_dparf_bwd_ws(int P, int V, int nc);
+int th_dparf_bwd_launch(const float* pts_smpl, int P, const float* centres, const float* rot, int V, int nc, float alpha,
+                        const float* grad_out, float* grad_tokens, void* ws, size_t ws_bytes, hipStream_t s);
+// k_pixfeat_bwd.hip: grad_map [V,H,W,C] = adjoint of the fp32-row gather applied to grad_out [P,V,ldo]; clears the map itself
+int th_pixgather_bwd_launch(int V, int C, int H, int W, const float* pts_world, int P, const float* cams, const float* scale,
+                            const float* grad_out, int ldo, float* grad_map, hipStream_t s);
 // k_pixfeat.hip
 int th_pixgather_launch(const float* map, int V, int C, int H, int W, const float* pts_world,
                         const ThPointSrc* ps, const int32_t* sel, int P, const float* cams, const float* scale,
@@ -471,6 +481,8 @@ int th_scatter_raw_launch(const float* raw_c, const int32_t* sel, int P, int rgb
 // mask (optional, uint8 per sample): raw is only read where mask != 0, elsewhere it counts as zero
 int th_composite_launch(const float* raw, const float* z, const ThPointSrc& ps, int white, float* rgb, float* acc,
                         float* depth, float* wout, const uint8_t* mask, hipStream_t s, const int32_t* ray_hit = nullptr);
+int th_composite_bwd_launch(const float* raw, const float* z, const ThPointSrc& ps, int white, const float* g_rgb,
+                            const float* g_acc, const float* g_depth, float* g_raw, hipStream_t s);
 int th_view_embed_launch(const float* d, int R, int res, float* out, hipStream_t s, const int32_t* hit = nullptr);
 // k_vit.hip
 size_t th_vit_ws(int V, int N, int dim, int heads);

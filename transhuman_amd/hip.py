@@ -133,6 +133,13 @@ SYMBOLS = {
     "th_network_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    "th_dparf_encode_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_dparf_encode_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_pixel_gather_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "th_composite_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ThPoints), C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "th_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ThPoints), C.c_int, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "th_gen_rays": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_int, C.c_int, C.c_void_p,
@@ -1104,6 +1111,50 @@ def composite(raw, z, ray_d, white_bkgd=False, return_weights=False):
     _check(lib.th_composite(ctx(raw.device), _p(raw), _p(z), C.byref(pts), int(white_bkgd), _p(rgb), _p(acc), _p(dep),
                             _p(w), _stream()))
     return (rgb, acc, dep, w) if return_weights else (rgb, acc, dep)
+
+
+def dparf_encode_bwd(pts_smpl, centres, rot, grad_out, out=None):
+    """th_dparf_encode_bwd: grad_out [P,V,256] -> grad_tokens [V,N_c,192], the adjoint of dparf_encode with respect to the
+    tokens.  ``out`` (optional) is written in full."""
+    lib = load_library()
+    p, c, r, g = _f32(pts_smpl).reshape(-1, 3), _f32(centres).reshape(-1, 3), _f32(rot).reshape(-1, 9), _f32(grad_out)
+    P, V = g.shape[0], g.shape[1]
+    assert g.shape == (P, V, 256) and p.shape[0] == P
+    nc = c.shape[0]
+    if out is None:
+        out = torch.empty((V, nc, 192), dtype=torch.float32, device=c.device)
+    assert out.shape == (V, nc, 192) and out.dtype is torch.float32 and out.is_contiguous()
+    ws = _ws(lib.th_dparf_encode_bwd_workspace_bytes(P, V, nc), c.device)
+    _check(lib.th_dparf_encode_bwd(ctx(c.device), _p(p), P, _p(c), _p(r), V, nc, _p(g), _p(out), _p(ws), ws.numel(), _stream()))
+    return out
+
+
+def pixel_gather_bwd(map_shape, pts_world, cams, scale_xy, grad_out, out=None):
+    """th_pixel_gather_bwd: grad_out [P,V,ldo] -> grad_map [V,H,W,C] (map_shape), the adjoint of pixel_gather with respect
+    to the map.  ``out`` (optional) is written in full."""
+    lib = load_library()
+    V, H, W, Cc = (int(x) for x in map_shape)
+    p, g = _f32(pts_world).reshape(-1, 3), _f32(grad_out)
+    P, ldo = p.shape[0], g.shape[-1]
+    assert g.shape == (P, V, ldo)
+    if out is None:
+        out = torch.empty((V, H, W, Cc), dtype=torch.float32, device=g.device)
+    assert out.shape == (V, H, W, Cc) and out.dtype is torch.float32 and out.is_contiguous()
+    _check(lib.th_pixel_gather_bwd(ctx(g.device), V, Cc, H, W, _p(p), P, _p(cams), _p(scale_xy), _p(g), ldo, _p(out), _stream()))
+    return out
+
+
+def composite_bwd(raw, z, ray_d, g_rgb, g_acc, g_depth, white_bkgd=False):
+    """th_composite_bwd: the gradients of composite's three outputs -> g_raw [R,S,4]"""
+    lib = load_library()
+    raw, z, d = _f32(raw), _f32(z), _f32(ray_d).reshape(-1, 3)
+    R, S = z.shape
+    gr, ga, gd = _f32(g_rgb).reshape(R, 3), _f32(g_acc).reshape(R), _f32(g_depth).reshape(R)
+    pts = ThPoints(None, None, _p(d), None, None, None, None, R, S)
+    out = torch.empty((R, S, 4), dtype=torch.float32, device=raw.device)
+    _check(lib.th_composite_bwd(ctx(raw.device), _p(raw), _p(z), C.byref(pts), int(white_bkgd), _p(gr), _p(ga), _p(gd), _p(out),
+                                _stream()))
+    return out
 
 
 def gen_rays(K, R, T, bounds, H, W, device=None, compact=True):

@@ -6,7 +6,12 @@ autograd, so a call with gradients enabled (or with the training-time randomisat
 ``cfg.raw_noise_std``) is served by this module instead: the same forward composed from differentiable torch operators
 on the module's own parameters, on the device the batch lives on (torch's ROCm kernels on an MI355X).  It is NOT the
 rendering hot path and not a fallback of it -- inference calls (``render_fast``, ``render_sequence``, ``render`` under
-``no_grad``) never come here; SURVEY 7 hard-part 6 planned exactly this split.  No backward HIP kernels exist.
+``no_grad``) never come here; SURVEY 7 hard-part 6 planned exactly this split.
+
+``cfg.train_kernels`` selects how the three non-GEMM stages around the per-point network run: "torch" (default) composes
+them from torch operators like everything else; "device" runs the token blend (K4), the pixel-aligned gather (K5) and the
+compositing (K7) through the HIP forwards with HIP adjoints (``train_ops``), once over all samples before
+the chunk loop.  The encoder, TransHE and the per-point network stay on torch autograd in both modes.
 
 Pinned by ``oracle/gen_golden_train.py`` (the real reference imported in the survey container: outputs and parameter
 gradients of one training step's forward/backward on a synthetic patch -> ``tests/golden/g18_train_step.npz``) and
@@ -169,6 +174,13 @@ def render(renderer, batch, chunk=32768):
     net = renderer.net
     assert cfg.time_steps == 1
     ray_o, ray_d = batch["ray_o"][0], batch["ray_d"][0]
+    mode = str(getattr(cfg, "train_kernels", "torch"))
+    if mode not in ("torch", "device"):
+        raise ValueError(f"cfg.train_kernels must be 'torch' or 'device', not {mode!r}")
+    if mode == "device" and not ray_o.is_cuda:
+        from .. import hip
+        raise hip.HipError("cfg.train_kernels = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
+                           "use 'torch' for a CPU batch")
     near, far = batch["near"][0], batch["far"][0]
     dev = ray_o.device
     S = int(cfg.N_samples)
@@ -194,12 +206,30 @@ def render(renderer, batch, chunk=32768):
     M64 = pooling_matrix_cached(renderer, nv, dev, blend.dtype)        # (float64 mean, :544)
     rot = (M64 @ blend.reshape(nv, 16)).reshape(-1, 4, 4)[:, :3, :3].to(torch.float32)             # cross_transformer.py:185
 
+    noise_std = float(getattr(cfg, "raw_noise_std", 0.0))
     raws = []
+    if mode == "device":
+        from .. import hip
+        from . import train_ops
+        if int(cfg.KNN) != 7 or float(cfg.KNN_DIST_ALPHA) != 0.5:
+            raise hip.HipError("cfg.train_kernels = 'device': K4 is built for KNN = 7, KNN_DIST_ALPHA = 0.5")
+        # K5 and K4 once over all P samples: one map-sized gradient per step, nothing of the blends kept for backward
+        scale = hip.feat_scale(net.encoder.feat_scale(*pix.shape[2:]), image_shape, dev)
+        f_all = train_ops.PixelGatherFn.apply(pix.permute(0, 2, 3, 1).contiguous(), xyz, hip.pack_cams(R_in, T_in, K_in), scale)
+        h_all = train_ops.HumanRepresentationFn.apply(tokens.contiguous(), pts_s, centres, rot)
+        for f, h, vd in zip(f_all.split(chunk), h_all.split(chunk), viewdir.split(chunk)):
+            raws.append(point_network(net, h[..., :255], f, vd))
+        raw = torch.cat(raws, 0).view(-1, S, 4)
+        if noise_std > 0.0:                                        # nerf_net_utils.py:39-44, drawn by torch
+            noise = torch.randn(raw[..., 3].shape).to(raw) * noise_std
+            raw = torch.cat([raw[..., :3], (raw[..., 3] + noise)[..., None]], -1)
+        rgb, acc, depth = train_ops.CompositeFn.apply(raw.contiguous(), z, ray_d, bool(cfg.white_bkgd))
+        return {"rgb_map": rgb[None], "acc_map": acc[None], "depth_map": depth[None]}
     for s0 in range(0, xyz.shape[0], chunk):                       # batchify_rays :607-656 without a mask
         x = xyz[s0:s0 + chunk]
         f = sample_map(pix, project(x, R_in, T_in, K_in), net.encoder, image_shape).permute(2, 0, 1)
         h = human_representation(net, pts_s[s0:s0 + chunk], centres, rot, tokens, int(cfg.KNN), float(cfg.KNN_DIST_ALPHA))
         raws.append(point_network(net, h, f, viewdir[s0:s0 + chunk]))
     raw = torch.cat(raws, 0).view(-1, S, 4)
-    rgb, acc, depth = composite(raw, z, ray_d, float(getattr(cfg, "raw_noise_std", 0.0)), bool(cfg.white_bkgd))
+    rgb, acc, depth = composite(raw, z, ray_d, noise_std, bool(cfg.white_bkgd))
     return {"rgb_map": rgb[None], "acc_map": acc[None], "depth_map": depth[None]}

@@ -1,0 +1,160 @@
+"""The three non-GEMM stages around the per-point network as autograd Functions on the device (K17).
+
+``cfg.train_kernels = "device"`` makes ``autograd_path.render`` run the token blend (K4), the pixel-aligned gather (K5) and
+the compositing (K7) through the HIP forwards that the inference paths use, with their adjoints as HIP kernels
+(k_dparf_bwd.hip, k_pixfeat_bwd.hip, k_composite.hip) instead of torch's index_add / grid_sample / cumprod backwards:
+
+    HumanRepresentationFn   tokens [V,N_c,192]   -> rows [P,V,256]     gradient: tokens
+    PixelGatherFn           map    [V,H,W,C]     -> rows [P,V,C]       gradient: map
+    CompositeFn             raw    [R,S,4]       -> rgb, acc, depth    gradient: raw
+
+K4 and K5 are linear in the tensor that gets the gradient, so nothing of the forward is kept for the backward but the
+geometry (points, centres, cameras): the [P,7,255] blend operands and the per-chunk map-sized gradients of the torch
+formulation do not exist here.  Points, centres, rotations, cameras, depths and ray directions come from the batch and get
+no gradient; an input of that kind that asks for one raises.
+
+Beside every kernel its float64 numpy restatement (``*_oracle``), tied to torch autograd through ``autograd_path`` by
+tests/test_train_ops_host.py.
+"""
+import numpy as np
+import torch
+
+from .. import hip
+
+
+def _no_grad_inputs(fn, **tensors):
+    for name, t in tensors.items():
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError(f"{fn}: '{name}' comes from the batch and has no gradient path (requires_grad=True)")
+
+
+def _on_device(fn, t):
+    if not t.is_cuda:
+        raise hip.HipError(f"{fn} needs its tensors on an MI355X (there is no CPU path)")
+
+
+class HumanRepresentationFn(torch.autograd.Function):
+    """get_human_representation (cross_transformer.py:158-205) -> [P,V,256] (255 features + one zero column).  The gradient
+    reaches the tokens only: columns 192.. (positional encoding of the point, pad) do not depend on them."""
+
+    @staticmethod
+    def forward(ctx, tokens, pts_smpl, centres, rot):
+        _no_grad_inputs("HumanRepresentationFn", pts_smpl=pts_smpl, centres=centres, rot=rot)
+        _on_device("HumanRepresentationFn", tokens)
+        ctx.save_for_backward(pts_smpl, centres, rot)
+        return hip.dparf_encode(pts_smpl, centres, rot, tokens)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pts_smpl, centres, rot = ctx.saved_tensors
+        return hip.dparf_encode_bwd(pts_smpl, centres, rot, grad_out), None, None, None
+
+
+class PixelGatherFn(torch.autograd.Function):
+    """get_pixel_aligned_feature (if_clight_renderer.py:210-269) on the channels-last map -> [P,V,C]"""
+
+    @staticmethod
+    def forward(ctx, map_nhwc, pts_world, cams, scale_xy):
+        _no_grad_inputs("PixelGatherFn", pts_world=pts_world, cams=cams, scale_xy=scale_xy)
+        _on_device("PixelGatherFn", map_nhwc)
+        if map_nhwc.dtype is not torch.float32 or not map_nhwc.is_contiguous():
+            raise ValueError("PixelGatherFn: the map must be a contiguous float32 [V,H,W,C] tensor")
+        ctx.save_for_backward(pts_world, cams, scale_xy)
+        ctx.map_shape = tuple(map_nhwc.shape)
+        return hip.pixel_gather(map_nhwc.detach(), pts_world, cams, scale_xy)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pts_world, cams, scale_xy = ctx.saved_tensors
+        return hip.pixel_gather_bwd(ctx.map_shape, pts_world, cams, scale_xy, grad_out), None, None, None
+
+
+class CompositeFn(torch.autograd.Function):
+    """raw2outputs (nerf_net_utils.py:14-59) -> rgb [R,3], acc [R], depth [R].  The density noise of training is added to
+    raw[..., 3] by the caller (a torch op), not here."""
+
+    @staticmethod
+    def forward(ctx, raw, z, ray_d, white_bkgd):
+        _no_grad_inputs("CompositeFn", z=z, ray_d=ray_d)
+        _on_device("CompositeFn", raw)
+        ctx.save_for_backward(raw, z, ray_d)
+        ctx.white = bool(white_bkgd)
+        return hip.composite(raw, z, ray_d, white_bkgd=ctx.white)
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_acc, g_depth):
+        raw, z, ray_d = ctx.saved_tensors
+        zero = lambda g, shape: g if g is not None else torch.zeros(shape, dtype=torch.float32, device=raw.device)
+        R = z.shape[0]
+        return hip.composite_bwd(raw, z, ray_d, zero(g_rgb, (R, 3)), zero(g_acc, (R,)), zero(g_depth, (R,)), ctx.white), \
+            None, None, None
+
+
+# ---- float64 restatements ---------------------------------------------------------------------------------------------------
+def _np64(x):
+    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
+
+
+def dparf_neighbours_oracle(pts_smpl, centres, K=7, alpha=0.5):
+    """get_dist_weight (cross_transformer.py:151-156, :170): the K nearest centres by squared distance (ties: lower index)
+    and softmax(-d / alpha) -> idx [P,K] int64, w [P,K] float64"""
+    p, c = _np64(pts_smpl), _np64(centres)
+    d2 = ((p[:, None, :] - c[None]) ** 2).sum(-1)
+    idx = np.argsort(d2, axis=1, kind="stable")[:, :K]
+    d = np.sqrt(np.take_along_axis(d2, idx, axis=1))
+    e = np.exp(-(d - d.min(1, keepdims=True)) / alpha)
+    return idx, e / e.sum(1, keepdims=True)
+
+
+def dparf_token_grad_oracle(pts_smpl, centres, n_views, grad_out, K=7, alpha=0.5):
+    """adjoint of the token blend: grad_out [P,V,>=192] -> grad_tokens [V,N_c,192] (float64)"""
+    g = _np64(grad_out)[..., :192]
+    idx, w = dparf_neighbours_oracle(pts_smpl, centres, K, alpha)
+    out = np.zeros((n_views, _np64(centres).shape[0], 192))
+    for v in range(n_views):
+        for k in range(idx.shape[1]):
+            np.add.at(out[v], idx[:, k], w[:, k, None] * g[:, v])
+    return out
+
+
+def pixel_map_grad_oracle(uv, scale_xy, H, W, grad_out):
+    """adjoint of sample_from_feature_map (if_clight_renderer.py:186-208: grid_sample, bilinear, align_corners, border) with
+    respect to the map: uv [V,N,2] pixel coordinates, scale_xy [2], grad_out [N,V,C] -> grad_map [V,H,W,C] (float64)"""
+    uv, s, g = _np64(uv), _np64(scale_xy), _np64(grad_out)
+    V, N = uv.shape[:2]
+    out = np.zeros((V, H, W, g.shape[-1]))
+    gx, gy = uv[..., 0] * s[0] - 1.0, uv[..., 1] * s[1] - 1.0
+    ix = np.clip(((gx + 1.0) / 2.0) * (W - 1), 0.0, W - 1.0)
+    iy = np.clip(((gy + 1.0) / 2.0) * (H - 1), 0.0, H - 1.0)
+    x0, y0 = np.floor(ix), np.floor(iy)
+    x1, y1 = x0 + 1.0, y0 + 1.0
+    for xs, ys, wt in ((x0, y0, (x1 - ix) * (y1 - iy)), (x1, y0, (ix - x0) * (y1 - iy)),
+                       (x0, y1, (x1 - ix) * (iy - y0)), (x1, y1, (ix - x0) * (iy - y0))):
+        ok = (xs <= W - 1) & (ys <= H - 1)                                   # (a corner outside the map adds nothing)
+        xi, yi = np.minimum(xs, W - 1).astype(np.int64), np.minimum(ys, H - 1).astype(np.int64)
+        for v in range(V):
+            np.add.at(out[v], (yi[v], xi[v]), (wt[v] * ok[v])[:, None] * g[:, v])
+    return out
+
+
+def composite_grad_oracle(raw, z, ray_d, white_bkgd, g_rgb, g_acc, g_depth):
+    """adjoint of raw2outputs (nerf_net_utils.py:14-59) with respect to raw [R,S,4] (float64); see k_composite.hip"""
+    raw, z, d = _np64(raw), _np64(z), _np64(ray_d)
+    g_rgb, g_acc, g_depth = _np64(g_rgb), _np64(g_acc), _np64(g_depth)
+    delta = np.concatenate([z[:, 1:] - z[:, :-1], np.full_like(z[:, :1], 1e10)], -1) * np.linalg.norm(d, axis=-1)[:, None]
+    sig = np.maximum(raw[..., 3], 0.0)
+    e = np.exp(-sig * delta)
+    a = 1.0 - e
+    t = 1.0 - a + 1e-10
+    T = np.concatenate([np.ones_like(t[:, :1]), np.cumprod(t, -1)[:, :-1]], -1)
+    w = a * T
+    c = 1.0 / (1.0 + np.exp(-raw[..., :3]))
+    ga = g_acc - g_rgb.sum(-1) if white_bkgd else g_acc
+    G = (c * g_rgb[:, None, :]).sum(-1) + ga[:, None] + g_depth[:, None] * z
+    x = G * w
+    after = np.concatenate([np.cumsum(x[:, ::-1], -1)[:, ::-1][:, 1:], np.zeros_like(x[:, :1])], -1)   # sum_{j>i} G_j w_j
+    g_a = G * T - after / t
+    out = np.empty_like(raw)
+    out[..., :3] = w[..., None] * g_rgb[:, None, :] * c * (1.0 - c)
+    out[..., 3] = np.where(raw[..., 3] > 0.0, g_a * e * delta, 0.0)
+    return out
