@@ -646,6 +646,61 @@ def test_prepass_equals_plain_render(hip, gpu, net):
     assert torch.equal(auto["rgb_map"][0], rgb0)          # (frame constants recomputed: deterministic kernels end to end)
 
 
+def test_frame_entry_points_refuse_and_recover(hip, gpu, net):
+    """the host-side refusals of the frame entry points (pool / workspace too small, no prepass pending) return before the
+    refused resource is touched, and the prepass state machine renders the same frame, bit for bit, after each of them"""
+    import ctypes as C
+    _cfg(32)
+    b = synth.batch_to(synth.make_batch(64, 64, 3, seed=0, focal=210.0), gpu)
+    frame = _renderer(net).prepare_frame(b)
+    lib, ctx, fc = hip.load_library(), hip.ctx(gpu), C.byref(frame.c)
+
+    def pts():
+        return hip.Points(b["ray_o"][0], b["ray_d"][0], b["near"][0], b["far"][0], n_samples=32)
+
+    def same_as_ref(out):
+        return all(torch.equal(a, r) for a, r in zip(out[:3], ref[:3])) and out[3] == ref[3]
+
+    def refused(rc, what):
+        return rc != 0 and what in lib.th_last_error().decode()
+
+    ref = hip.render_rays(net, frame, pts())
+    P0 = pts()
+    R, S = P0.R, P0.S
+    out = [torch.empty((R, 3), device=gpu), torch.empty(R, device=gpu), torch.empty(R, device=gpu)]
+    need = lib.th_render_workspace_bytes(fc, R, S)
+    ws = hip._cached_ws(need, gpu)
+    pool = hip._shade_pool(frame.c, R * S, True, gpu)
+    stats = (C.c_int64 * 4)()
+
+    def rays(ws_bytes, pool_bytes):
+        return lib.th_render_rays(ctx, fc, C.byref(P0.c), hip._p(out[0]), hip._p(out[1]), hip._p(out[2]), 0, hip._p(ws),
+                                  ws_bytes, hip._p(pool), pool_bytes, stats, hip._stream())
+
+    # 1. a pool of no bytes, no prepass pending
+    assert lib.th_render_prepass_drop(ctx, hip._p(ws)) == 0
+    assert refused(rays(ws.numel(), 0), "shading pool too small")
+    assert same_as_ref(hip.render_rays(net, frame, pts()))
+    # 2. the pre-gather stage refuses the pool: the token stays, nothing pre-gathered is assumed
+    P1 = pts()
+    hip.render_prepass(P1, b["tar_smpl_vertice"][0], 3, n_clusters=frame.c.n_clusters)
+    ws1 = P1._prepass_keep[1]
+    assert refused(lib.th_render_pregather(ctx, fc, C.byref(P1.c), hip._p(ws1), ws1.numel(), hip._p(pool), 0, hip._stream()),
+                   "shading pool too small")
+    assert same_as_ref(hip.render_rays(net, frame, P1))
+    # 3. a workspace one byte short
+    assert refused(rays(need - 1, pool.numel()), "workspace too small")
+    assert refused(lib.th_render_prepass(ctx, fc, C.byref(P0.c), hip._p(ws), need - 1, hip._stream()), "workspace too small")
+    # 4. no prepass pending for the workspace
+    assert lib.th_render_prepass_drop(ctx, hip._p(ws)) == 0
+    assert lib.th_render_prepass_wait(ctx, hip._p(ws), (C.c_int64 * 3)()) == 1
+    nb = lib.th_map_demand_bytes(frame.c.V, frame.c.H, frame.c.W)
+    demand = torch.empty(nb, dtype=torch.uint8, device=gpu)
+    assert lib.th_render_predemand(ctx, fc, C.byref(P0.c), hip._p(ws), ws.numel(), None, 0, hip._p(demand), nb, hip._stream()) == 1
+    assert lib.th_render_pregather(ctx, fc, C.byref(P0.c), hip._p(ws), ws.numel(), hip._p(pool), pool.numel(), hip._stream()) == 0
+    assert same_as_ref(hip.render_rays(net, frame, pts()))
+
+
 def test_weight_updates_are_picked_up(hip, gpu, net):
     """the per-frame weight check (version counters of a cached parameter list) sees in-place updates
     (optimiser step / load_state_dict) and re-uploads the packed images"""

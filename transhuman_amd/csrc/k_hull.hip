@@ -381,7 +381,7 @@ __global__ __launch_bounds__(256) void small_frame_apply_kernel(uint8_t* __restr
 }
 int th_small_frame_rule(uint8_t* mask, const int32_t* ray_hit, int R, int S, int thr, int32_t* dev_info,
                         hipStream_t s) {
-    // dev_info[0..1] must be zero on entry (shade_points clears the block)
+    // dev_info[0..1] must be zero on entry (hull_stage clears the block)
     hipLaunchKernelGGL(count_hits_kernel, dim3(R >= 65536 ? 256 : th_cdiv(R, 256)), dim3(256), 0, s, ray_hit, R, dev_info);
     long long P = (long long)R * S;
     const int nb = (int)(P >= (1LL << 20) ? 1024 : th_cdiv(P, 256));

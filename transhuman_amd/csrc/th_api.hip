@@ -118,7 +118,8 @@ void th_ctx_destroy(th_ctx* c) {
     for (auto& e : c->range_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& t : c->prepass)
-        if (t.ev) (void)hipEventDestroy(t.ev);
+        for (hipEvent_t e : {t.ev, t.ev2})
+            if (e) (void)hipEventDestroy(e);
     delete[] c->vit.blocks;
     if (c->prof) {
         ThProf* p = (ThProf*)c->prof;
@@ -1079,13 +1080,14 @@ static size_t shade_ws_bytes(const th_frame* f, long long P, int R) {
            th_align((size_t)P * 4) + th_align(64) + th_align((size_t)R * 27 * 4) + th_align((size_t)P * 16) +
            th_align(TPRIME_FLOATS(f->V) * 4) + th_dparf_grid_ws(f->n_clusters > 0 ? f->n_clusters : 1);
 }
-// (one carve for every entry point that works in a ray workspace)
+// (one prologue for every entry point that works in a ray workspace: size check, arena, carve)
 struct ShadeWs {
     uint8_t* mask; int32_t* ray_hit; void* hws; size_t hws_b; void* cws; size_t cws_b; int32_t* idx; int32_t* info;
     float* vd_all; float* raw; float* tprime; void* gws; size_t gws_b;
 };
-static ShadeWs carve_shade_ws(const th_frame* f, long long P, int R, ThArena& ar) {
-    ShadeWs w{};
+static int carve_shade_ws(const th_frame* f, long long P, int R, void* ws, size_t ws_bytes, ShadeWs& w) {
+    TH_REQUIRE(ws_bytes >= shade_ws_bytes(f, P, R), "workspace too small");
+    ThArena ar(ws, ws_bytes);
     w.mask = ar.take<uint8_t>((size_t)P);
     w.ray_hit = ar.take<int32_t>((size_t)R);
     w.hws_b = th_hull_ws(f->n_verts);
@@ -1099,209 +1101,222 @@ static ShadeWs carve_shade_ws(const th_frame* f, long long P, int R, ThArena& ar
     w.tprime = ar.take<float>(TPRIME_FLOATS(f->V));
     w.gws_b = th_dparf_grid_ws(f->n_clusters > 0 ? f->n_clusters : 1);
     w.gws = ar.take<char>(w.gws_b);
-    return w;
+    TH_REQUIRE(w.raw != nullptr && w.tprime != nullptr && w.gws != nullptr, "workspace too small");
+    return 0;
 }
 static int frame_f_ld(const th_frame* f) {
     return (f->map_channels == TH_MAP_COMPACT || f->map_channels == TH_MAP_SPLIT) ? 272 : 384;
 }
-
-// hull mask -> (small-frame rule) -> compaction -> chunked DPaRF + gather + MLP -> dense raw[P,4]
-// stage A (hull mask, small-frame rule, compaction, view embedding, cleared raw) may run ahead of time
-// (th_render_prepass): it needs only the rays, the posed vertices and the two thresholds.  `prepass` = 1: run
-// stage A only and leave the counts on their way to host_pinned[16..]; 2: stage A already ran into this workspace;
-// 3: stage A ran, queue the pre-gather stage (region A of the pool) and return.
-static int shade_points(th_ctx* c, const th_frame* f, const ThPointSrc& ps, long long P, bool ray_mode, ThArena& ar,
-                        void* pool, size_t pool_bytes, float** raw_out, const uint8_t** mask_out, int64_t* stats_host,
-                        hipStream_t s, int prepass = 0, int slot = 0, const int32_t** ray_hit_out = nullptr) {
-    const int R = ps.R, S = ps.S, V = f->V;
-    const bool compact = f->map_channels == TH_MAP_COMPACT || f->map_channels == TH_MAP_SPLIT;
-    const int f_ld = frame_f_ld(f);
-    const int fmt = mlp_row_format(c, V);
-    const bool tex = tex_rows(c, f);
-    const float* tex_map = tex ? f->map_fold : nullptr;                  // fold0, fold12 one map size behind it
-    const size_t tex_stride = (size_t)f->V * f->H * f->W * 256;
-    TH_REQUIRE(prepass == 1 || !compact || c->mlp.compact_ready,
+static int compact_ok(const th_ctx* c, const th_frame* f) {          // (asked by every entry point that goes past the hull stage)
+    TH_REQUIRE(f->map_channels == TH_MAP_FULL || c->mlp.compact_ready,
                "compact pixel map needs th_mlp_weights.upsample_color (colour-folded layers) to be uploaded");
-    const ShadeWs w = carve_shade_ws(f, P, R, ar);
-    uint8_t* mask = w.mask;
-    int32_t* ray_hit = w.ray_hit;
-    const size_t hws_b = w.hws_b, cws_b = w.cws_b, gws_b = w.gws_b;
-    void *hws = w.hws, *cws = w.cws, *gws = w.gws;
-    int32_t *idx = w.idx, *info = w.info;
-    float *vd_all = w.vd_all, *raw = w.raw, *tprime = w.tprime;
-    TH_REQUIRE(raw != nullptr && tprime != nullptr && gws != nullptr, "workspace too small");
-
-    ThProf* pf = prof_of(c);
-    int32_t* hp = c->host_pinned;
-    // Any per-sample stage that is handed a pool (th_render_rays, th_eval_sigma_grid) becomes the pool's last user: the
-    // "pool is free behind the previous th_render_rays" event th_render_pregather_early relies on is void from here on and
-    // is re-armed only by a th_render_rays that ran to its end (an error return leaves it void: the early path then falls
-    // back to ordering K4 behind everything queued on the stream).
-    if ((prepass == 0 || prepass == 2) && pool != nullptr) c->after_shade_valid = false;
-    if (prepass == 2 || prepass == 3) {
-        hp = c->host_pinned + 16 + 4 * slot;
-        TH_HIP(hipStreamWaitEvent(s, c->prepass[slot].ev, 0));      // the prepass may have run on another stream
-        ThWaitClock wc(c);
-        TH_HIP(hipEventSynchronize(c->prepass[slot].ev));
-    } else {
-    ProfScope sc_hull(pf, TH_PROF_HULL, s);          // (RAII: an early error return closes the span)
+    return 0;
+}
+// The slot of the valid th_render_prepass token for this workspace and these rays (same ray_o array, R and S), or -1.
+// th_render_pregather / _pregrid / _predemand look the token up and leave it; th_render_rays consumes it and, with it,
+// invalidates EVERY token of its workspace, matching or stale (th_render_prepass_drop): the workspace is overwritten.
+static int find_prepass(const th_ctx* c, const void* ws, const th_points* rays) {
+    int slot = -1;
+    for (int k = 0; k < th_ctx::kPrepassSlots; ++k) {
+        const th_ctx::Prepass& t = c->prepass[k];
+        if (t.valid && t.ws == ws && t.rays == (const void*)rays->ray_o && t.R == rays->R && t.S == rays->S) slot = k;
+    }
+    return slot;
+}
+// hull mask -> (small-frame rule) -> compaction -> chunked DPaRF + gather + MLP -> dense raw[P,4], in stages.
+// hull_stage (hull mask, small-frame rule, compaction, view embedding) may run ahead of time (th_render_prepass): it needs
+// only the rays, the posed vertices and the two thresholds.  Leaves {hit_rays, unmasked, n} in w.info; no host wait.
+static int hull_stage(th_ctx* c, const th_frame* f, const ThPointSrc& ps, long long P, bool ray_mode, const ShadeWs& w,
+                      hipStream_t s) {
+    const int R = ps.R, S = ps.S;
+    ProfScope sc_hull(prof_of(c), TH_PROF_HULL, s);          // (RAII: an early error return closes the span)
     const bool no_hull = f->hull_thresh < 0.f;   // Renderer.render (:486-498): every sample shaded, RGB everywhere
     if (no_hull) {
-        TH_HIP(hipMemsetAsync(info, 0, 16 * 4, s));
-        TH_HIP(hipMemsetAsync(mask, 1, (size_t)P, s));
-        if (ray_mode) TH_HIP(hipMemsetAsync(ray_hit, 1, (size_t)R * 4, s));   // any non-zero marks a hit
+        TH_HIP(hipMemsetAsync(w.info, 0, 16 * 4, s));
+        TH_HIP(hipMemsetAsync(w.mask, 1, (size_t)P, s));
+        if (ray_mode) TH_HIP(hipMemsetAsync(w.ray_hit, 1, (size_t)R * 4, s));   // any non-zero marks a hit
     } else {
         // (the grid build clears `info` and the per-ray hit flags: no memset launches)
-        TH_TRY(th_hull_mask_launch(ps, P, f->verts_world, f->n_verts, f->hull_thresh, mask,
-                                   ray_mode ? ray_hit : nullptr, hws, hws_b, s, info));
+        TH_TRY(th_hull_mask_launch(ps, P, f->verts_world, f->n_verts, f->hull_thresh, w.mask,
+                                   ray_mode ? w.ray_hit : nullptr, w.hws, w.hws_b, s, w.info));
     }
     if (ray_mode) {
         // hit-ray count, the R' <= 2400 rule (:551) and the compaction in one chain (no_hull: threshold R makes the
         // rule fire -> un-masked mode, rgb for all samples)
-        TH_TRY(th_view_embed_launch(ps.ray_d, R, 4, vd_all, s, ray_hit));      // (behind the hull test: hit rays only)
-        TH_TRY(th_compact_mask_rule(mask, P, ray_hit, R, S, no_hull ? R : f->small_frame_rays, info, idx, info + 2, cws,
-                                    cws_b, s));
+        TH_TRY(th_view_embed_launch(ps.ray_d, R, 4, w.vd_all, s, w.ray_hit));      // (behind the hull test: hit rays only)
+        TH_TRY(th_compact_mask_rule(w.mask, P, w.ray_hit, R, S, no_hull ? R : f->small_frame_rays, w.info, w.idx, w.info + 2,
+                                    w.cws, w.cws_b, s));
     } else {
-        TH_TRY(th_compact_mask(mask, P, idx, info + 2, cws, cws_b, s));
+        TH_TRY(th_compact_mask(w.mask, P, w.idx, w.info + 2, w.cws, w.cws_b, s));
     }
     // (raw is NOT cleared: its consumers read it through the mask -- 268 MB of memset + dense re-read saved per frame)
-    sc_hull.close();
-    if (prepass == 1) {
-        TH_HIP(hipMemcpyAsync(c->host_pinned + 16 + 4 * slot, info, 4 * 4, hipMemcpyDeviceToHost, s));
-        if (!c->prepass[slot].ev) TH_HIP(hipEventCreateWithFlags(&c->prepass[slot].ev, hipEventDisableTiming));
-        TH_HIP(hipEventRecord(c->prepass[slot].ev, s));
-        return 0;
+    return 0;
+}
+// {hit_rays, unmasked, n} of a hull stage on the host, two ways:
+struct HullCounts { int hit_rays, unmasked, n; };
+static int read_counts(const int32_t* hp, int64_t* stats_host, HullCounts* k) {
+    *k = HullCounts{hp[0], hp[1], hp[2]};
+    if (stats_host) { stats_host[0] = k->hit_rays; stats_host[1] = k->n; stats_host[2] = -1; stats_host[3] = k->unmasked; }
+    return 0;
+}
+// ... at once, behind a hull_stage this call queued on `s`
+static int counts_now(th_ctx* c, const ShadeWs& w, int64_t* stats_host, hipStream_t s, HullCounts* k) {
+    TH_HIP(hipMemcpyAsync(c->host_pinned, w.info, 4 * 4, hipMemcpyDeviceToHost, s));
+    {
+        ThWaitClock wc(c);
+        TH_HIP(hipStreamSynchronize(s));
     }
-    TH_HIP(hipMemcpyAsync(c->host_pinned, info, 4 * 4, hipMemcpyDeviceToHost, s));
-    ThWaitClock wc(c);
-    TH_HIP(hipStreamSynchronize(s));
+    return read_counts(c->host_pinned, stats_host, k);
+}
+// ... or from the slot's pinned words, where th_render_prepass sent them; `s` is ordered behind that hull stage as well
+static int counts_of_prepass(th_ctx* c, int slot, int64_t* stats_host, hipStream_t s, HullCounts* k) {
+    TH_HIP(hipStreamWaitEvent(s, c->prepass[slot].ev, 0));      // the prepass may have run on another stream
+    {
+        ThWaitClock wc(c);
+        TH_HIP(hipEventSynchronize(c->prepass[slot].ev));
     }
-    const int hit_rays = hp[0], unmasked = hp[1], n = hp[2];
-    if (stats_host) { stats_host[0] = hit_rays; stats_host[1] = n; stats_host[2] = -1; stats_host[3] = unmasked; }
-    th_ctx::Prepass* tk = (prepass == 2 || prepass == 3) ? &c->prepass[slot] : nullptr;
-    // A cropped map (th_frame.map_source) holds the texels within reach of the hull only.  The un-masked branch (:551,
-    // R' <= small_frame_rays: every sample of the hit rays is shaded), a frame without a hull test and a hull test wider
-    // than the crop's reach gather outside it: the rest of the map is written first (same values inside the box) -- once
-    // per frame (the pre-gather stage and the shading of one prepass share the completed map).
-    // A demand-driven map (th_map_source.demand, th_render_predemand) additionally holds only the texels of ONE prepass's sample
-    // list: any other caller of the frame (other rays, a sigma grid, a render without the prepass) gets the rest first too.
-    const bool demand_miss = f->map_source != nullptr && f->map_source->demand != nullptr &&
-                             !(tk && tk->demand == f->map_source->demand);
-    if (f->map_source != nullptr && n > 0 && !(tk && tk->map_done == f->pixel_map_nhwc) &&
-        !(f->map_source->demand != nullptr && c->map_completed != nullptr && c->map_completed == f->pixel_map_nhwc &&
-          c->map_completed_demand == (const void*)f->map_source->demand) &&       // (demand maps only, keyed on the PAIR: a freed
-                                                                                   // block handed to a later cropped map must not match)
-        (f->map_source->demand != nullptr ? demand_miss      // (a demand made from THIS sample list covers every branch)
-                                          : (unmasked || f->hull_thresh < 0.f || f->hull_thresh > f->map_source->reach))) {
-        const th_map_source* ms = f->map_source;
-        TH_REQUIRE(f->map_channels == TH_MAP_SPLIT && ms->img && ms->lat0 && ms->lat1 && ms->lat2, "map_source: split map only");
-        TH_TRY(th_upsample_concat_launch(ms->img, ms->lat0, ms->lat1, ms->lat2, ms->dims, V, f->H, f->W, nullptr, nullptr,
-                                         const_cast<float*>(f->pixel_map_nhwc), s, 1, nullptr));
-        // (the folded maps of the texel hand-over follow the map: alpha_res_0 / rgb_res_0 / rgb_res_1 of EVERY texel now)
-        if (tex) TH_TRY(th_map_fold_launch(c->fused, f->pixel_map_nhwc, V, f->H, f->W, nullptr, const_cast<float*>(f->map_fold),
-                                           c->range_dev, s));
-        if (tk) tk->map_done = f->pixel_map_nhwc;
-        if (f->map_source->demand != nullptr) {                                          // (until the next th_render_predemand / prepass)
-            c->map_completed = f->pixel_map_nhwc;
-            c->map_completed_demand = (const void*)f->map_source->demand;
-        }
+    return read_counts(c->host_pinned + 16 + 4 * slot, stats_host, k);
+}
+// A cropped map (th_frame.map_source) holds the texels within reach of the hull only.  The un-masked branch (:551,
+// R' <= small_frame_rays: every sample of the hit rays is shaded), a frame without a hull test and a hull test wider
+// than the crop's reach gather outside it: the rest of the map is written first (same values inside the box) -- once
+// per frame (the pre-gather stage and the shading of one prepass share the completed map).
+// A demand-driven map (th_map_source.demand, th_render_predemand) additionally holds only the texels of ONE prepass's sample
+// list: any other caller of the frame (other rays, a sigma grid, a render without the prepass) gets the rest first too.
+static bool map_incomplete(const th_ctx* c, const th_frame* f, const th_ctx::Prepass* tk, const HullCounts& k) {
+    const th_map_source* ms = f->map_source;
+    if (ms == nullptr || k.n <= 0) return false;
+    if (tk && tk->map_done == f->pixel_map_nhwc) return false;      // (this prepass's frame completed it already)
+    if (ms->demand == nullptr) return k.unmasked || f->hull_thresh < 0.f || f->hull_thresh > ms->reach;
+    // (demand maps only, keyed on the PAIR: a freed block handed to a later cropped map must not match)
+    if (c->map_completed != nullptr && c->map_completed == f->pixel_map_nhwc &&
+        c->map_completed_demand == (const void*)ms->demand) return false;
+    return !(tk && tk->demand == ms->demand);      // (a demand made from THIS sample list covers every branch)
+}
+// complete_map: needs the counts and the token `tk` of the prepass they came from, if any; leaves every texel written.
+static int complete_map(th_ctx* c, const th_frame* f, th_ctx::Prepass* tk, const HullCounts& k, hipStream_t s) {
+    if (!map_incomplete(c, f, tk, k)) return 0;
+    const th_map_source* ms = f->map_source;
+    TH_REQUIRE(f->map_channels == TH_MAP_SPLIT && ms->img && ms->lat0 && ms->lat1 && ms->lat2, "map_source: split map only");
+    TH_TRY(th_upsample_concat_launch(ms->img, ms->lat0, ms->lat1, ms->lat2, ms->dims, f->V, f->H, f->W, nullptr, nullptr,
+                                     const_cast<float*>(f->pixel_map_nhwc), s, 1, nullptr));
+    // (the folded maps of the texel hand-over follow the map: alpha_res_0 / rgb_res_0 / rgb_res_1 of EVERY texel now)
+    if (tex_rows(c, f)) TH_TRY(th_map_fold_launch(c->fused, f->pixel_map_nhwc, f->V, f->H, f->W, nullptr,
+                                                  const_cast<float*>(f->map_fold), c->range_dev, s));
+    if (tk) tk->map_done = f->pixel_map_nhwc;
+    if (ms->demand != nullptr) {                                          // (until the next th_render_predemand / prepass)
+        c->map_completed = f->pixel_map_nhwc;
+        c->map_completed_demand = (const void*)ms->demand;
     }
-    const bool can_pre = ray_mode && tok_gather(c, V) && fmt == TH_ROWS_SPLIT;
+    return 0;
+}
+
+// pregather_stage: K5 + K4 of the first pre_n valid samples, ONE launch each (needs the map, the cameras, the
+// token centres -- not the tokens).  Leaves their rows / records in region A of the pool and says so in the prepass's token `t`.
+static int pregather_stage(th_ctx* c, const th_frame* f, const ThPointSrc& ps, const ShadeWs& w, th_ctx::Prepass& t,
+                           const HullCounts& k, void* pool, size_t pool_bytes, bool early, hipStream_t s) {
+    const int V = f->V, f_ld = frame_f_ld(f), fmt = mlp_row_format(c, V);
+    const bool tex = tex_rows(c, f);
+    ThProf* pf = prof_of(c);
     char* pb = (char*)pool;
-    if (prepass == 3) {
-        // pre-gather stage: K5 + K4 of the first pre_n valid samples, ONE launch each (needs the map, the cameras, the
-        // token centres -- not the tokens)
-        th_ctx::Prepass& t = c->prepass[slot];
-        t.npre = 0;
-        if (!can_pre || n <= 0) return 0;
-        const PoolPlan pl = pool_plan(c, V, f_ld, n, true, tex);
-        TH_REQUIRE(pool != nullptr && pool_bytes >= pl.total, "shading pool too small (th_shade_pool_bytes)");
-        const int m = (int)pl.pre_n;
-        float* a_f = (float*)(pb + pl.a_f);
-        float* a_h = (float*)(pb + pl.a_h);
-        float* a_pe = (float*)(pb + pl.a_pe);
-        const bool grid = getenv("TH_DPARF_NOGRID") == nullptr && th_dparf_grid_ok(f->n_clusters);
-        // K4 on the context's second stream, K5 on `s`: the two producers share nothing but the sample list -- K5 sits on
-        // the texture path (TA busy 80-90 %, VALU 43 %), K4 since TH_ROWS_NBR is a 7-NN scan out of LDS (no row gather) --
-        // so their waves co-reside on the CUs instead of running back to back.
-        if (!c->aux) {
-            TH_HIP(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-            TH_HIP(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
-            TH_HIP(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
-            TH_HIP(hipStreamCreateWithFlags(&c->aux2, hipStreamNonBlocking));
-            TH_HIP(hipEventCreateWithFlags(&c->aux2_join, hipEventDisableTiming));
-        }
-        // th_render_pregather_early: K4 is ordered behind the per-sample stage of the previous th_render_rays on this
-        // stream and pool (the last user of the pool's record regions) instead of behind everything queued on `s` since
-        // -- that frame's compositing and whatever the caller queued after it run beside K4, not in front of it
-        const bool early = c->pregather_early && c->after_shade_valid && c->after_shade_stream == s &&
-                           c->after_shade_pool == pool;
-        c->after_shade_valid = false;
-        // K5t (the texel hand-over's producer: rays, cameras, sample list -- no map) gets a stream of its own under the same
-        // rule: in the early form it starts with K4 behind the previous frame's per-sample stage, beside that frame's
-        // compositing and the consumer's image assembly, instead of behind them on `s` (the window between two launches of
-        // the fused kernel of a rank of 8: 360 -> 240 us)
-        if (early) {
-            TH_HIP(hipStreamWaitEvent(c->aux, c->after_shade, 0));
-            if (tex) TH_HIP(hipStreamWaitEvent(c->aux2, c->after_shade, 0));
-        } else {
-            TH_HIP(hipEventRecord(c->aux_fork, s));      // sample list, candidate grid and every earlier user of the pool
-            TH_HIP(hipStreamWaitEvent(c->aux, c->aux_fork, 0));
-            if (tex) TH_HIP(hipStreamWaitEvent(c->aux2, c->aux_fork, 0));
-        }
-        hipStream_t s4 = c->aux, s5 = tex ? c->aux2 : s;
-        // From here on work may be in flight on the second stream: whatever happens, `s` waits for it before this call
-        // returns (a caller that frees or reuses the pool after an error must not race with K4).
-        int rc = 0;
-        {
-            // (the candidate grid of the 7-NN scan is K4's alone: built on K4's stream, not in front of the pixel gather)
-            if (grid && t.grid_centres != f->centres) rc = th_dparf_grid_build(f->centres, f->n_clusters, gws, gws_b, s4);
-            t.grid_centres = nullptr;                 // (th_render_pregrid's grid is consumed: chunks beyond the stage rebuild)
-            if (rc == 0) {
-                ProfScope ps1(pf, TH_PROF_DPARF, s4);
-                rc = th_dparf_launch(nullptr, &ps, f->Rh, f->Th, idx, m, f->centres, f->rot, nullptr, V, f->n_clusters, 0.5f, a_h,
-                                     a_pe, TH_ROWS_NBR, grid ? gws : nullptr, s4);
-            }
-            if (rc == 0) {
-                ProfScope ps2(pf, TH_PROF_GATHER, s5);
-                rc = tex ? th_pixtex_launch(V, f->H, f->W, &ps, idx, m, f->cams, f->scale_xy, a_f, s5)
-                         : th_pixgather_launch(f->pixel_map_nhwc, V, f->map_channels, f->H, f->W, nullptr, &ps, idx, m, f->cams,
-                                               f->scale_xy, a_f, f_ld, fmt, s, c->range_dev);
-            }
-        }
-        // th_render_pregather_early with the tokens already in the frame: the token table T' (one small GEMM + its split)
-        // is queued here, beside K4, instead of between K4's end and the fused MLP's start
-        t.pre_tokens = nullptr;
-        if (rc == 0 && c->pregather_early && f->tokens != nullptr) {
-            const float* table = nullptr;
-            rc = token_table(c, f->tokens, V, f->n_clusters, tprime, &table, s);
-            if (rc == 0) t.pre_tokens = f->tokens;
-        }
-        const hipError_t e1 = hipEventRecord(c->aux_join, c->aux);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s, c->aux_join, 0) : e1;
-        if (e2 != hipSuccess) (void)hipStreamSynchronize(c->aux);      // last resort: nothing left in flight
-        if (s5 != s) {
-            const hipError_t e3 = hipEventRecord(c->aux2_join, c->aux2);
-            const hipError_t e4 = e3 == hipSuccess ? hipStreamWaitEvent(s, c->aux2_join, 0) : e3;
-            if (e4 != hipSuccess) (void)hipStreamSynchronize(c->aux2);
-        }
-        if (rc != 0) return rc;
-        if (!t.ev2) TH_HIP(hipEventCreateWithFlags(&t.ev2, hipEventDisableTiming));
-        TH_HIP(hipEventRecord(t.ev2, s));
-        t.npre = m;
-        t.pre_map = f->pixel_map_nhwc;
-        t.pre_centres = f->centres;
-        t.pre_pool = pool;
-        return 0;
+    t.npre = 0;
+    if (!(tok_gather(c, V) && fmt == TH_ROWS_SPLIT) || k.n <= 0) return 0;
+    const PoolPlan pl = pool_plan(c, V, f_ld, k.n, true, tex);
+    TH_REQUIRE(pool != nullptr && pool_bytes >= pl.total, "shading pool too small (th_shade_pool_bytes)");
+    const int m = (int)pl.pre_n;
+    float* a_f = (float*)(pb + pl.a_f);
+    float* a_h = (float*)(pb + pl.a_h);
+    float* a_pe = (float*)(pb + pl.a_pe);
+    const bool grid = getenv("TH_DPARF_NOGRID") == nullptr && th_dparf_grid_ok(f->n_clusters);
+    // K4 on the context's second stream, K5 on `s`: the two producers share nothing but the sample list -- K5 sits on
+    // the texture path (TA busy 80-90 %, VALU 43 %), K4 since TH_ROWS_NBR is a 7-NN scan out of LDS (no row gather) --
+    // so their waves co-reside on the CUs instead of running back to back.
+    if (!c->aux) {
+        TH_HIP(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
+        TH_HIP(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
+        TH_HIP(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
+        TH_HIP(hipStreamCreateWithFlags(&c->aux2, hipStreamNonBlocking));
+        TH_HIP(hipEventCreateWithFlags(&c->aux2_join, hipEventDisableTiming));
     }
+    // th_render_pregather_early: K4 is ordered behind the per-sample stage of the previous th_render_rays on this
+    // stream and pool (the last user of the pool's record regions) instead of behind everything queued on `s` since
+    // -- that frame's compositing and whatever the caller queued after it run beside K4, not in front of it
+    const bool behind_shade = early && c->after_shade_valid && c->after_shade_stream == s && c->after_shade_pool == pool;
+    c->after_shade_valid = false;
+    // K5t (the texel hand-over's producer: rays, cameras, sample list -- no map) gets a stream of its own under the same
+    // rule: in the early form it starts with K4 behind the previous frame's per-sample stage, beside that frame's
+    // compositing and the consumer's image assembly, instead of behind them on `s` (the window between two launches of
+    // the fused kernel of a rank of 8: 360 -> 240 us)
+    if (behind_shade) {
+        TH_HIP(hipStreamWaitEvent(c->aux, c->after_shade, 0));
+        if (tex) TH_HIP(hipStreamWaitEvent(c->aux2, c->after_shade, 0));
+    } else {
+        TH_HIP(hipEventRecord(c->aux_fork, s));      // sample list, candidate grid and every earlier user of the pool
+        TH_HIP(hipStreamWaitEvent(c->aux, c->aux_fork, 0));
+        if (tex) TH_HIP(hipStreamWaitEvent(c->aux2, c->aux_fork, 0));
+    }
+    hipStream_t s4 = c->aux, s5 = tex ? c->aux2 : s;
+    // From here on work may be in flight on the second stream: whatever happens, `s` waits for it before this call
+    // returns (a caller that frees or reuses the pool after an error must not race with K4).
+    int rc = 0;
+    // (the candidate grid of the 7-NN scan is K4's alone: built on K4's stream, not in front of the pixel gather)
+    if (grid && t.grid_centres != f->centres) rc = th_dparf_grid_build(f->centres, f->n_clusters, w.gws, w.gws_b, s4);
+    t.grid_centres = nullptr;                 // (th_render_pregrid's grid is consumed: chunks beyond the stage rebuild)
+    if (rc == 0) {
+        ProfScope ps1(pf, TH_PROF_DPARF, s4);
+        rc = th_dparf_launch(nullptr, &ps, f->Rh, f->Th, w.idx, m, f->centres, f->rot, nullptr, V, f->n_clusters, 0.5f, a_h,
+                             a_pe, TH_ROWS_NBR, grid ? w.gws : nullptr, s4);
+    }
+    if (rc == 0) {
+        ProfScope ps2(pf, TH_PROF_GATHER, s5);
+        rc = tex ? th_pixtex_launch(V, f->H, f->W, &ps, w.idx, m, f->cams, f->scale_xy, a_f, s5)
+                 : th_pixgather_launch(f->pixel_map_nhwc, V, f->map_channels, f->H, f->W, nullptr, &ps, w.idx, m, f->cams,
+                                       f->scale_xy, a_f, f_ld, fmt, s, c->range_dev);
+    }
+    // th_render_pregather_early with the tokens already in the frame: the token table T' (one small GEMM + its split)
+    // is queued here, beside K4, instead of between K4's end and the fused MLP's start
+    t.pre_tokens = nullptr;
+    if (rc == 0 && early && f->tokens != nullptr) {
+        const float* table = nullptr;
+        rc = token_table(c, f->tokens, V, f->n_clusters, w.tprime, &table, s);
+        if (rc == 0) t.pre_tokens = f->tokens;
+    }
+    auto join = [s](hipEvent_t ev, hipStream_t side) {
+        const hipError_t e1 = hipEventRecord(ev, side);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s, ev, 0) : e1;
+        if (e2 != hipSuccess) (void)hipStreamSynchronize(side);      // last resort: nothing left in flight
+    };
+    join(c->aux_join, c->aux);
+    if (s5 != s) join(c->aux2_join, c->aux2);
+    if (rc != 0) return rc;
+    if (!t.ev2) TH_HIP(hipEventCreateWithFlags(&t.ev2, hipEventDisableTiming));
+    TH_HIP(hipEventRecord(t.ev2, s));
+    t.npre = m;
+    t.pre_map = f->pixel_map_nhwc;
+    t.pre_centres = f->centres;
+    t.pre_pool = pool;
+    return 0;
+}
+
+// shade_stage: token table, candidate grid, one fused launch over region A, the chunk loop, the scatter.  Needs the counts,
+// a complete map and (behind a prepass) its token `tk`, whose npre / pre_tokens it consumes.  Leaves raw[P,4] where masked.
+static int shade_stage(th_ctx* c, const th_frame* f, const ThPointSrc& ps, bool ray_mode, const ShadeWs& w, th_ctx::Prepass* tk,
+                       const HullCounts& k, void* pool, size_t pool_bytes, hipStream_t s) {
+    const int S = ps.S, V = f->V, n = k.n, unmasked = k.unmasked;
+    const int f_ld = frame_f_ld(f), fmt = mlp_row_format(c, V);
+    const bool tex = tex_rows(c, f);
+    const float* tex_map = tex ? f->map_fold : nullptr;                  // fold0, fold12 one map size behind it
+    const size_t tex_stride = (size_t)f->V * f->H * f->W * 256;
+    ThProf* pf = prof_of(c);
+    char* pb = (char*)pool;
     int npre = 0;                        // valid samples whose rows / records sit in region A of the pool
-    if (prepass == 2) {
-        th_ctx::Prepass& t = c->prepass[slot];
-        if (t.npre > 0 && can_pre && t.pre_map == f->pixel_map_nhwc && t.pre_centres == f->centres && t.pre_pool == pool) {
-            npre = t.npre;
-            TH_HIP(hipStreamWaitEvent(s, t.ev2, 0));
+    if (tk) {
+        const bool can_pre = ray_mode && tok_gather(c, V) && fmt == TH_ROWS_SPLIT;
+        if (tk->npre > 0 && can_pre && tk->pre_map == f->pixel_map_nhwc && tk->pre_centres == f->centres && tk->pre_pool == pool) {
+            npre = tk->npre;
+            TH_HIP(hipStreamWaitEvent(s, tk->ev2, 0));
         }
-        t.npre = 0;
+        tk->npre = 0;
     }
     const PoolPlan pl = pool_plan(c, V, f_ld, n, npre > 0, tex);
     TH_REQUIRE(n <= 0 || (pool != nullptr && pool_bytes >= pl.total), "shading pool too small (th_shade_pool_bytes)");
@@ -1317,27 +1332,27 @@ static int shade_points(th_ctx* c, const th_frame* f, const ThPointSrc& ps, long
     TH_REQUIRE(f->n_clusters <= TH_MAX_CLUSTERS, "too many token clusters");
     const float* table = nullptr;
     if (n > 0) {
-        if (npre > 0 && c->prepass[slot].pre_tokens == f->tokens && mlp_is_fused(c, V)) table = tprime;    // (queued by the pre-gather stage)
-        else TH_TRY(token_table(c, f->tokens, V, f->n_clusters, tprime, &table, s));
+        if (npre > 0 && tk->pre_tokens == f->tokens && mlp_is_fused(c, V)) table = w.tprime;    // (queued by the pre-gather stage)
+        else TH_TRY(token_table(c, f->tokens, V, f->n_clusters, w.tprime, &table, s));
     }
-    if (prepass == 2) c->prepass[slot].pre_tokens = nullptr;
+    if (tk) tk->pre_tokens = nullptr;
     // exact candidate grid for the 7-NN scan of K4 (TH_DPARF_NOGRID=1: full scan, same result)
     // (not needed when every sample's records were pre-gathered: K4 does not run again)
     const bool use_grid = n > npre && getenv("TH_DPARF_NOGRID") == nullptr && th_dparf_grid_ok(f->n_clusters);
-    if (use_grid) TH_TRY(th_dparf_grid_build(f->centres, f->n_clusters, gws, gws_b, s));
+    if (use_grid) TH_TRY(th_dparf_grid_build(f->centres, f->n_clusters, w.gws, w.gws_b, s));
     if (npre > 0) {          // rows and records of these samples were written by th_render_pregather: ONE fused launch
         ChunkBufs pc = cb;
         pc.f = (float*)(pb + pl.a_f); pc.h = (float*)(pb + pl.a_h); pc.pe = (float*)(pb + pl.a_pe);
         {
             ProfScope ps3(pf, TH_PROF_MLP, s);
-            TH_TRY(mlp_dispatch(c, V, npre, pc, f_ld, vd_all, idx, S, unmasked, s, tprime, f->n_clusters, tex_map, tex_stride));
+            TH_TRY(mlp_dispatch(c, V, npre, pc, f_ld, w.vd_all, w.idx, S, unmasked, s, w.tprime, f->n_clusters, tex_map, tex_stride));
         }
         ProfScope ps4(pf, TH_PROF_COMPOSITE, s);
-        TH_TRY(th_scatter_raw_launch(cb.raw_c, idx, npre, unmasked, raw, s));
+        TH_TRY(th_scatter_raw_launch(cb.raw_c, w.idx, npre, unmasked, w.raw, s));
     }
     for (int o = npre; o < n; o += CH) {
         int m = (n - o) < CH ? (n - o) : CH;
-        const int32_t* sel = idx + o;
+        const int32_t* sel = w.idx + o;
         // (K5 first: K4's small output -- records, tile headers, positional encodings, 0.3 KB per sample -- is then the
         // last thing written before the fused kernel reads it at the start of every tile: MALL instead of HBM)
         {
@@ -1349,22 +1364,19 @@ static int shade_points(th_ctx* c, const th_frame* f, const ThPointSrc& ps, long
         {
             ProfScope ps1(pf, TH_PROF_DPARF, s);
             TH_TRY(th_dparf_launch(nullptr, &ps, f->Rh, f->Th, sel, m, f->centres, f->rot, table, V,
-                                   f->n_clusters, 0.5f, cb.h, cb.pe, dparf_row_format(c, V), use_grid ? gws : nullptr, s));
+                                   f->n_clusters, 0.5f, cb.h, cb.pe, dparf_row_format(c, V), use_grid ? w.gws : nullptr, s));
         }
         {
             ProfScope ps3(pf, TH_PROF_MLP, s);
             // ray mode: the [R,27] embedding table is indexed sample -> ray (sel / S); mesh mode: zero rows (cb.vdc)
-            if (ray_mode) TH_TRY(mlp_dispatch(c, V, m, cb, f_ld, vd_all, sel, S, unmasked, s, tprime, f->n_clusters, tex_map, tex_stride));
+            if (ray_mode) TH_TRY(mlp_dispatch(c, V, m, cb, f_ld, w.vd_all, sel, S, unmasked, s, w.tprime, f->n_clusters, tex_map, tex_stride));
             // (the sigma grid never looks at colour: skip the RGB branch, which the reference evaluates and drops,
             // if_mesh_renderer.py:84-99)
-            else TH_TRY(mlp_dispatch(c, V, m, cb, f_ld, cb.vdc, nullptr, 1, 2, s, tprime, f->n_clusters, tex_map, tex_stride));
+            else TH_TRY(mlp_dispatch(c, V, m, cb, f_ld, cb.vdc, nullptr, 1, 2, s, w.tprime, f->n_clusters, tex_map, tex_stride));
         }
         ProfScope ps4(pf, TH_PROF_COMPOSITE, s);
-        TH_TRY(th_scatter_raw_launch(cb.raw_c, sel, m, unmasked, raw, s));
+        TH_TRY(th_scatter_raw_launch(cb.raw_c, sel, m, unmasked, w.raw, s));
     }
-    *raw_out = raw;
-    *mask_out = mask;
-    if (ray_hit_out) *ray_hit_out = ray_mode ? ray_hit : nullptr;
     return 0;
 }
 
@@ -1413,22 +1425,24 @@ int th_render_rays(th_ctx* c, const th_frame* f, const th_points* rays, float* r
     if (R <= 0) return 0;
     long long P = (long long)R * S;
     TH_REQUIRE(P < (1LL << 31), "R*S must fit in int32");
-    TH_REQUIRE(ws_bytes >= shade_ws_bytes(f, P, R), "workspace too small");
-    ThArena ar(ws, ws_bytes);
+    ShadeWs w;
+    TH_TRY(carve_shade_ws(f, P, R, ws, ws_bytes, w));
     ThPointSrc ps = th_src(rays);
-    float* raw = nullptr;
-    const uint8_t* mask = nullptr;
     // a matching th_render_prepass (same workspace, same ray arrays) already ran the hull / compaction stage
-    int slot = -1;
-    for (int k = 0; k < th_ctx::kPrepassSlots; ++k) {
-        th_ctx::Prepass& t = c->prepass[k];
-        if (!t.valid || t.ws != ws) continue;
-        t.valid = false;                              // consumed, or stale for this workspace
-        if (t.rays == (const void*)rays->ray_o && t.R == R && t.S == S) slot = k;
-    }
-    const int32_t* ray_hit = nullptr;
-    TH_TRY(shade_points(c, f, ps, P, true, ar, pool, pool_bytes, &raw, &mask, stats_host, s, slot >= 0 ? 2 : 0,
-                        slot >= 0 ? slot : 0, &ray_hit));
+    const int slot = find_prepass(c, ws, rays);
+    th_ctx::Prepass* tk = slot >= 0 ? &c->prepass[slot] : nullptr;
+    (void)th_render_prepass_drop(c, ws);              // consumed, or stale for this workspace
+    TH_TRY(compact_ok(c, f));
+    // Any per-sample stage that is handed a pool (th_render_rays, th_eval_sigma_grid) becomes the pool's last user: the
+    // "pool is free behind the previous th_render_rays" event th_render_pregather_early relies on is void from here on and
+    // is re-armed only by a th_render_rays that ran to its end (an error return leaves it void: the early path then falls
+    // back to ordering K4 behind everything queued on the stream).
+    if (pool != nullptr) c->after_shade_valid = false;
+    HullCounts k;
+    if (tk == nullptr) TH_TRY(hull_stage(c, f, ps, P, true, w, s));
+    TH_TRY(tk ? counts_of_prepass(c, slot, stats_host, s, &k) : counts_now(c, w, stats_host, s, &k));
+    TH_TRY(complete_map(c, f, tk, k, s));
+    TH_TRY(shade_stage(c, f, ps, true, w, tk, k, pool, pool_bytes, s));
     // (for th_render_pregather_early of the next frame: the pool's record regions are free from here on)
     if (!c->after_shade) TH_HIP(hipEventCreateWithFlags(&c->after_shade, hipEventDisableTiming));
     TH_HIP(hipEventRecord(c->after_shade, s));
@@ -1436,7 +1450,7 @@ int th_render_rays(th_ctx* c, const th_frame* f, const th_points* rays, float* r
     c->after_shade_pool = pool;
     c->after_shade_valid = true;
     ProfScope sc(prof_of(c), TH_PROF_COMPOSITE, s);
-    TH_TRY(th_composite_launch(raw, nullptr, ps, white_bkgd, rgb, acc, depth, nullptr, mask, s, ray_hit));
+    TH_TRY(th_composite_launch(w.raw, nullptr, ps, white_bkgd, rgb, acc, depth, nullptr, w.mask, s, w.ray_hit));
     const int snap = th_range_snapshot(c, stream);
     TH_REQUIRE(snap >= 0, "range snapshot failed");
     if (stats_host) stats_host[2] = snap;
@@ -1468,55 +1482,53 @@ int th_render_prepass(th_ctx* c, const th_frame* f, const th_points* rays, void*
     if (R <= 0) return 0;
     long long P = (long long)R * S;
     TH_REQUIRE(P < (1LL << 31), "R*S must fit in int32");
-    TH_REQUIRE(ws_bytes >= shade_ws_bytes(f, P, R), "workspace too small");
-    ThArena ar(ws, ws_bytes);
-    ThPointSrc ps = th_src(rays);
-    float* raw = nullptr;
-    const uint8_t* mask = nullptr;
-    TH_TRY(shade_points(c, f, ps, P, true, ar, nullptr, 0, &raw, &mask, nullptr, s, 1, slot));
+    ShadeWs w;
+    TH_TRY(carve_shade_ws(f, P, R, ws, ws_bytes, w));
+    TH_TRY(hull_stage(c, f, th_src(rays), P, true, w, s));
+    TH_HIP(hipMemcpyAsync(c->host_pinned + 16 + 4 * slot, w.info, 4 * 4, hipMemcpyDeviceToHost, s));
+    if (!t.ev) TH_HIP(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+    TH_HIP(hipEventRecord(t.ev, s));
     t.ws = ws; t.rays = rays->ray_o; t.R = R; t.S = S;
     t.valid = true;
     return 0;
 }
 
-int th_render_pregather(th_ctx* c, const th_frame* f, const th_points* rays, void* ws, size_t ws_bytes, void* pool,
-                        size_t pool_bytes, th_stream stream) {
+static int render_pregather(th_ctx* c, const th_frame* f, const th_points* rays, void* ws, size_t ws_bytes, void* pool,
+                            size_t pool_bytes, bool early, hipStream_t s) {
     TH_REQUIRE(c && f && rays && ws, "null argument");
     TH_REQUIRE(f->verts_world && f->Rh && f->Th && f->cams && f->scale_xy && f->pixel_map_nhwc && f->centres && f->rot &&
                    f->n_clusters >= 7 && f->V >= 1 && f->V <= 4,
                "th_render_pregather needs every th_frame field except the tokens");
     TH_REQUIRE(f->map_channels == TH_MAP_FULL || f->map_channels == TH_MAP_COMPACT || f->map_channels == TH_MAP_SPLIT,
                "th_frame.map_channels must be 384, 260 or 256");
-    int slot = -1;
-    for (int k = 0; k < th_ctx::kPrepassSlots; ++k) {
-        th_ctx::Prepass& t = c->prepass[k];
-        if (t.valid && t.ws == ws && t.rays == (const void*)rays->ray_o && t.R == rays->R && t.S == rays->S) slot = k;
-    }
+    const int slot = find_prepass(c, ws, rays);
     if (slot < 0) return 0;                      // no matching th_render_prepass: nothing to do (th_render_rays runs everything)
-    const int R = rays->R, S = rays->S;
-    long long P = (long long)R * S;
-    TH_REQUIRE(ws_bytes >= shade_ws_bytes(f, P, R), "workspace too small");
-    ThArena ar(ws, ws_bytes);
-    ThPointSrc ps = th_src(rays);
-    float* raw = nullptr;
-    const uint8_t* mask = nullptr;
-    return shade_points(c, f, ps, P, true, ar, pool, pool_bytes, &raw, &mask, nullptr, (hipStream_t)stream, 3, slot);
+    ShadeWs w;
+    TH_TRY(carve_shade_ws(f, (long long)rays->R * rays->S, rays->R, ws, ws_bytes, w));
+    TH_TRY(compact_ok(c, f));
+    HullCounts k;
+    TH_TRY(counts_of_prepass(c, slot, nullptr, s, &k));
+    TH_TRY(complete_map(c, f, &c->prepass[slot], k, s));
+    return pregather_stage(c, f, th_src(rays), w, c->prepass[slot], k, pool, pool_bytes, early, s);
+}
+
+int th_render_pregather(th_ctx* c, const th_frame* f, const th_points* rays, void* ws, size_t ws_bytes, void* pool,
+                        size_t pool_bytes, th_stream stream) {
+    return render_pregather(c, f, rays, ws, ws_bytes, pool, pool_bytes, false, (hipStream_t)stream);
+}
+
+int th_render_pregather_early(th_ctx* c, const th_frame* f, const th_points* rays, void* ws, size_t ws_bytes, void* pool,
+                              size_t pool_bytes, th_stream stream) {
+    return render_pregather(c, f, rays, ws, ws_bytes, pool, pool_bytes, true, (hipStream_t)stream);
 }
 
 int th_render_pregrid(th_ctx* c, const th_frame* f, const th_points* rays, void* ws, size_t ws_bytes, th_stream stream) {
     TH_REQUIRE(c && f && rays && ws && f->centres, "null argument");
     if (getenv("TH_DPARF_NOGRID") != nullptr || !th_dparf_grid_ok(f->n_clusters)) return 0;
-    int slot = -1;
-    for (int k = 0; k < th_ctx::kPrepassSlots; ++k) {
-        th_ctx::Prepass& t = c->prepass[k];
-        if (t.valid && t.ws == ws && t.rays == (const void*)rays->ray_o && t.R == rays->R && t.S == rays->S) slot = k;
-    }
+    const int slot = find_prepass(c, ws, rays);
     if (slot < 0) return 0;                      // no matching th_render_prepass: the pre-gather stage builds the grid itself
-    const long long P = (long long)rays->R * rays->S;
-    TH_REQUIRE(ws_bytes >= shade_ws_bytes(f, P, rays->R), "workspace too small");
-    ThArena ar(ws, ws_bytes);
-    const ShadeWs w = carve_shade_ws(f, P, rays->R, ar);
-    TH_REQUIRE(w.gws != nullptr, "workspace too small");
+    ShadeWs w;
+    TH_TRY(carve_shade_ws(f, (long long)rays->R * rays->S, rays->R, ws, ws_bytes, w));
     c->prepass[slot].grid_centres = nullptr;
     TH_TRY(th_dparf_grid_build(f->centres, f->n_clusters, w.gws, w.gws_b, (hipStream_t)stream));
     c->prepass[slot].grid_centres = f->centres;
@@ -1528,17 +1540,10 @@ int th_render_predemand(th_ctx* c, const th_frame* f, const th_points* rays, voi
     TH_REQUIRE(c && f && rays && ws && demand && f->cams && f->scale_xy, "null argument");
     TH_REQUIRE(f->V >= 1 && f->V <= 3 && f->H >= 1 && f->W >= 64, "th_render_predemand: 1..3 views and their map size");
     TH_REQUIRE(demand_bytes >= th_demand_bytes(f->V, f->H, f->W), "demand buffer too small (th_map_demand_bytes)");
-    int slot = -1;
-    for (int k = 0; k < th_ctx::kPrepassSlots; ++k) {
-        th_ctx::Prepass& t = c->prepass[k];
-        if (t.valid && t.ws == ws && t.rays == (const void*)rays->ray_o && t.R == rays->R && t.S == rays->S) slot = k;
-    }
+    const int slot = find_prepass(c, ws, rays);
     if (slot < 0) return 1;
-    const long long P = (long long)rays->R * rays->S;
-    TH_REQUIRE(ws_bytes >= shade_ws_bytes(f, P, rays->R), "workspace too small");
-    ThArena ar(ws, ws_bytes);
-    const ShadeWs w = carve_shade_ws(f, P, rays->R, ar);
-    TH_REQUIRE(w.gws != nullptr, "workspace too small");
+    ShadeWs w;
+    TH_TRY(carve_shade_ws(f, (long long)rays->R * rays->S, rays->R, ws, ws_bytes, w));
     hipStream_t s = (hipStream_t)stream;
     th_ctx::Prepass& t = c->prepass[slot];
     t.demand = nullptr;
@@ -1548,15 +1553,6 @@ int th_render_predemand(th_ctx* c, const th_frame* f, const th_points* rays, voi
     TH_TRY(th_demand_launch(th_src(rays), w.idx, w.info, f->cams, f->scale_xy, f->V, f->H, f->W, verts_paint, n_paint, demand, s));
     t.demand = demand;
     return 0;
-}
-
-int th_render_pregather_early(th_ctx* c, const th_frame* f, const th_points* rays, void* ws, size_t ws_bytes, void* pool,
-                              size_t pool_bytes, th_stream stream) {
-    TH_REQUIRE(c != nullptr, "null argument");
-    c->pregather_early = true;
-    const int rc = th_render_pregather(c, f, rays, ws, ws_bytes, pool, pool_bytes, stream);
-    c->pregather_early = false;
-    return rc;
 }
 
 int th_render_prepass_cancel(th_ctx* c) {
@@ -1586,14 +1582,18 @@ int th_eval_sigma_grid(th_ctx* c, const th_frame* f, const float* pts, int P, fl
     TH_TRY(frame_ok(f));
     hipStream_t s = (hipStream_t)stream;
     if (P <= 0) return 0;
-    TH_REQUIRE(ws_bytes >= shade_ws_bytes(f, P, P), "workspace too small");
-    ThArena ar(ws, ws_bytes);
+    ShadeWs w;
+    TH_TRY(carve_shade_ws(f, P, P, ws, ws_bytes, w));
     ThPointSrc ps{};
     ps.pts = pts; ps.R = P; ps.S = 1;
-    float* raw = nullptr;
-    const uint8_t* mask = nullptr;
-    TH_TRY(shade_points(c, f, ps, P, false, ar, pool, pool_bytes, &raw, &mask, stats_host, s));
-    hipLaunchKernelGGL(extract_sigma_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, (const float4*)raw, mask, (long long)P,
+    TH_TRY(compact_ok(c, f));
+    if (pool != nullptr) c->after_shade_valid = false;      // (the pool's last user from here on: see th_render_rays)
+    HullCounts k;
+    TH_TRY(hull_stage(c, f, ps, P, false, w, s));
+    TH_TRY(counts_now(c, w, stats_host, s, &k));
+    TH_TRY(complete_map(c, f, nullptr, k, s));
+    TH_TRY(shade_stage(c, f, ps, false, w, nullptr, k, pool, pool_bytes, s));
+    hipLaunchKernelGGL(extract_sigma_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, (const float4*)w.raw, w.mask, (long long)P,
                        sigma_out);
     TH_LAUNCH_CHECK();
     const int snap = th_range_snapshot(c, stream);

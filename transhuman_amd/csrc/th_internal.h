@@ -364,10 +364,10 @@ struct th_ctx {
     Prepass prepass[kPrepassSlots];
     int prepass_rr = 0;
     int n_cu = 256;
+    const void* map_completed = nullptr;    // a demand-driven map that a later call had to write in full (complete_map) ...
+    const void* map_completed_demand = nullptr;   // ... and the demand buffer it was made from (the pair identifies the frame)
     // second stream of the pre-gather stage: K4 (neighbour records: VALU / LDS work, no row gather since TH_ROWS_NBR)
     // runs beside K5 (pixel-feature gather: texture-path bound) instead of behind it
-    const void* map_completed = nullptr;    // a demand-driven map that a later call had to write in full (shade_points) ...
-    const void* map_completed_demand = nullptr;   // ... and the demand buffer it was made from (the pair identifies the frame)
     hipStream_t aux = nullptr, aux2 = nullptr;
     hipEvent_t aux_fork = nullptr, aux_join = nullptr, aux2_join = nullptr;
     // th_render_pregather_early: the point of the last th_render_rays' stream where its per-sample stage (fused MLP +
@@ -375,7 +375,7 @@ struct th_ctx {
     hipEvent_t after_shade = nullptr;
     hipStream_t after_shade_stream = nullptr;
     const void* after_shade_pool = nullptr;
-    bool after_shade_valid = false, pregather_early = false;
+    bool after_shade_valid = false;
     void* prof = nullptr;             // ThProf (th_api.hip)
     // range guard (th_range_*): device table the kernels merge their maxima into, pinned snapshots + events
     unsigned int* range_dev = nullptr;
