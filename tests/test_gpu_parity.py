@@ -355,6 +355,48 @@ def test_render_sequence_equals_per_frame_render(hip, gpu, net):
     assert list(r.render_sequence(iter([]))) == []
 
 
+def test_render_sequence_with_a_ray_slice_equals_per_frame_render(hip, gpu, net):
+    """``ray_slice`` through the frame pipeline (the multi-rank jobs' sharding, in process): for two interleaved index slices and
+    the empty slice, at look-ahead 1 and 2, render_sequence yields per frame exactly the maps and statistics of
+    render_fast(b, ray_slice=...) on that frame; an empty slice yields zero-length maps and leaves the pipeline usable -- an
+    unsliced sequence afterwards on the same renderer is still bit-identical to render_fast"""
+    _cfg(32)
+    r = _renderer(net)
+    frames = [synth.batch_to(synth.make_batch(64, 64, 3, seed=sd, focal=fc), gpu) for sd, fc in ((0, 210.0), (1, 190.0))]
+    idx = torch.arange(64 * 64, device=gpu)
+
+    def per_frame(sl):
+        ref = []
+        for b in frames:
+            o = r.render_fast(b, ray_slice=sl)
+            ref.append(({k: v.clone() for k, v in o.items()}, dict(r.last_stats)))
+        return ref
+
+    def check_sequence(sl, la, ref):
+        got = []
+        for i, o in enumerate(r.render_sequence(iter(frames), ray_slice=sl, lookahead=la)):
+            assert r.last_stats == ref[i][1], (la, i)
+            got.append({k: v.clone() for k, v in o.items()})
+        assert len(got) == len(frames)
+        torch.cuda.synchronize()
+        for i in range(len(frames)):
+            for k in ("rgb_map", "acc_map", "depth_map"):
+                assert torch.equal(got[i][k], ref[i][0][k]), (la, i, k)
+
+    full = per_frame(None)
+    for sl in (idx[0::2], idx[1::2]):
+        ref = per_frame(sl)
+        assert ref[0][0]["rgb_map"].shape == (1, 2048, 3) and ref[0][1]["hit_rays"] > 0
+        for la in (1, 2):
+            check_sequence(sl, la, ref)
+    empty = per_frame(slice(0, 0))
+    for la in (1, 2):
+        check_sequence(slice(0, 0), la, empty)
+    assert empty[0][0]["rgb_map"].shape == (1, 0, 3) and empty[0][0]["acc_map"].shape == (1, 0)
+    assert empty[0][0]["depth_map"].shape == (1, 0) and empty[0][1]["hit_rays"] == 0
+    check_sequence(None, 2, full)
+
+
 def test_render_ray_sharding_equals_full(hip, gpu, net):
     """rays are independent: rendering two interleaved shards == rendering the frame"""
     _cfg(32)

@@ -563,6 +563,9 @@ class Points:
     def __init__(self, ray_o=None, ray_d=None, near=None, far=None, n_samples=1, pts=None, z_vals=None, sigma_noise=None):
         """``z_vals`` [R,S]: explicit sample depths (the reference's stratified jitter, if_clight_renderer.py:276-283) instead of
         near (1 - t) + far t; ``sigma_noise`` [R,S]: added to sigma in front of raw2alpha's relu (nerf_net_utils.py:39-44)."""
+        # a pending render_prepass of these rays: (verts, workspace) it ran in and its cluster count (render_prepass), whether the
+        # producers of its first chunks have been queued (render_pregather); render_rays consumes all four
+        self._prepass_pending, self._prepass_keep, self._prepass_nc, self._pregathered = False, None, 0, False
         if pts is not None:
             self.pts = _f32(pts).reshape(-1, 3)
             self.R, self.S = self.pts.shape[0], 1
@@ -1371,6 +1374,9 @@ class Frame:
         self.map = pixel_map_nhwc
         self.centres, self.rot = _f32(centres).reshape(-1, 3), _f32(rot).reshape(-1, 9)
         self.tokens = _f32(tokens) if tokens is not None else None       # None: set_tokens() before the frame is rendered
+        # set by Renderer.prepare_frame: ``rebuild()`` -> the same constants again (range guard), ``stem_flag`` (device bool: the
+        # stem latents received from another rank were not finite), ``finish_tokens()`` (TransHE of a frame built without it)
+        self.rebuild = self.stem_flag = self.finish_tokens = None
         V, H, W, Cc = pixel_map_nhwc.shape
         assert Cc in (384, 260) or isinstance(pixel_map_nhwc, SplitMap), \
             "pixel map must be the full (384) or the compact (260 interleaved / SplitMap) channels-last map"
@@ -1474,7 +1480,7 @@ def render_predemand(points, cams, scale_xy, V, H, W, verts_paint=None):
     mark the map texels its valid samples -- and the ``verts_paint`` [n,3] vertices, if given -- read in the V views.  -> the demand
     buffer (device uint8 tensor) for upsample_concat_split(demand=...) / map_fold, or None (no pending prepass, or a map
     width that is not a multiple of 64)."""
-    if not getattr(points, "_prepass_pending", False) or int(W) % 64 != 0 or V > 3:
+    if not points._prepass_pending or int(W) % 64 != 0 or V > 3:
         return None
     lib = load_library()
     v, ws = points._prepass_keep
@@ -1498,7 +1504,7 @@ def render_predemand(points, cams, scale_xy, V, H, W, verts_paint=None):
 def render_pregrid(frame, points):
     """th_render_pregrid: the candidate grid of K4's 7-neighbour search for the frame's token centres, into the workspace of
     the pending render_prepass of ``points`` -- on the current stream (the one that produced the centres)."""
-    if not getattr(points, "_prepass_pending", False):
+    if not points._prepass_pending:
         return
     _, ws = points._prepass_keep
     _check(load_library().th_render_pregrid(ctx(frame.verts.device), C.byref(frame.c), C.byref(points.c), _p(ws), ws.numel(),
@@ -1511,7 +1517,7 @@ def render_pregather(net, frame, points, slot=0, early=False, pool_slot=None):
     so TransHE can run on another stream meanwhile.  ``early=True`` (th_render_pregather_early): the caller has made the
     current stream wait for this frame's front BEFORE it queued the previous frame's render_rays, so the neighbour
     records may start as soon as that frame's per-sample stage is done, beside its compositing."""
-    if not getattr(points, "_prepass_pending", False):
+    if not points._prepass_pending:
         return
     lib = load_library()
     _sync_weights(net, "mlp")
@@ -1550,24 +1556,25 @@ def render_rays(net, frame, points, white_bkgd=False, defer_guard=False, small_f
         fc.small_frame_rays = int(small_frame_rays)
     need = lib.th_render_workspace_bytes(C.byref(fc), R, points.S)
     n_bound, pre = R * points.S, False
-    if getattr(points, "_prepass_pending", False) and points._prepass_keep[1].numel() >= need:
+    if points._prepass_pending and points._prepass_keep[1].numel() >= need:
         points._prepass_pending = False
         ws = points._prepass_keep[1]                        # the workspace its prepass ran in
         cnt = _prepass_counts(ws, dev)                      # (on the host long ago in a frame pipeline)
         if cnt is not None:
-            n_bound, pre = cnt[2], bool(getattr(points, "_pregathered", False))
+            n_bound, pre = cnt[2], points._pregathered
     else:
         ws = _cached_ws(need, dev)
         _check(lib.th_render_prepass_drop(ctx(dev), _p(ws)))  # a token queued there for other (possibly freed) rays
     points._pregathered = False
     # the shading pool: sized from the valid-sample count when a prepass has put it on the host, else for the chunk
     # buffers only (the count bounds the chunk, not the pool)
-    pool = _shade_pool(fc, n_bound, pre, dev, pool_slot)
     stats = (C.c_int64 * 4)()
-    _check(lib.th_render_rays(ctx(dev), C.byref(fc), C.byref(points.c), _p(rgb), _p(acc), _p(dep), int(white_bkgd),
-                              _p(ws), ws.numel(), _p(pool), pool.numel(), stats, _stream()))
-    st = dict(hit_rays=stats[0], valid_samples=stats[1], unmasked=stats[3])
-    slot = int(stats[2])
+
+    def shade(pool):                             # (reads ``fc`` as it is when called) -> statistics, range-guard slot
+        _check(lib.th_render_rays(ctx(dev), C.byref(fc), C.byref(points.c), _p(rgb), _p(acc), _p(dep), int(white_bkgd),
+                                  _p(ws), ws.numel(), _p(pool), pool.numel(), stats, _stream()))
+        return dict(hit_rays=stats[0], valid_samples=stats[1], unmasked=stats[3]), int(stats[2])
+    st, slot = shade(_shade_pool(fc, n_bound, pre, dev, pool_slot))
     if defer_guard:
         return rgb, acc, dep, st, (lambda: _guard(dev, slot))
     # a snapshot that is not clean (or was overwritten before it could be read) -> the paths the guard switched are in
@@ -1576,17 +1583,13 @@ def render_rays(net, frame, points, white_bkgd=False, defer_guard=False, small_f
     for _ in range(3):
         if _guard(dev, slot):
             break
-        if (conv_fallback(dev) or vit_fallback(dev)) and getattr(frame, "rebuild", None) is not None:
+        if (conv_fallback(dev) or vit_fallback(dev)) and frame.rebuild is not None:
             frame = frame.rebuild()                  # frame constants again, through the stock convolutions
             keep_sfr = fc.small_frame_rays
             fc = ThFrame.from_buffer_copy(frame.c)
             fc.small_frame_rays = keep_sfr
         _check(lib.th_render_prepass_drop(ctx(dev), _p(ws)))
-        pool = _shade_pool(fc, st["valid_samples"], False, dev, pool_slot)   # (the guard may have changed the mode: other row formats)
-        _check(lib.th_render_rays(ctx(dev), C.byref(fc), C.byref(points.c), _p(rgb), _p(acc), _p(dep),
-                                  int(white_bkgd), _p(ws), ws.numel(), _p(pool), pool.numel(), stats, _stream()))
-        st = dict(hit_rays=stats[0], valid_samples=stats[1], unmasked=stats[3])
-        slot = int(stats[2])
+        st, slot = shade(_shade_pool(fc, st["valid_samples"], False, dev, pool_slot))   # (the guard may have changed the mode: other row formats)
     return rgb, acc, dep, st
 
 
@@ -1606,7 +1609,7 @@ def eval_sigma_grid(net, frame, pts):
                                       pool.numel(), stats, _stream()))
         if _guard(p.device, int(stats[2])):
             break
-        if (conv_fallback(p.device) or vit_fallback(p.device)) and getattr(frame, "rebuild", None) is not None:
+        if (conv_fallback(p.device) or vit_fallback(p.device)) and frame.rebuild is not None:
             frame = frame.rebuild()
     return out, dict(valid_samples=stats[1])
 

@@ -25,6 +25,7 @@ import sys
 _REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 if _REPO not in sys.path:
     sys.path.insert(0, _REPO)
+import collections                                                  # noqa: E402
 import pickle                                                       # noqa: E402
 
 import numpy as np                                                  # noqa: E402
@@ -38,6 +39,41 @@ class _PreparedBatch(dict):
     """a shallow copy of a batch whose ``input_imgs`` / ``input_K`` were made on the device (Renderer.frame_inputs);
     ``source`` is the caller's batch"""
     source = None
+
+
+class _Views:
+    """What the input views of a batch give a frame (time step ``t``): the images flattened to [V,3,H,W], ``image_shape``, V, H, W
+    and the device.  ``cams()`` and ``scale(enc)`` are computed by the stage that asks (the camera pack is a launch)."""
+    __slots__ = ("batch", "t", "images", "image_shape", "V", "H", "W", "dev")
+
+    def __init__(self, batch, t=0):
+        imgs = batch["input_imgs"][t]
+        self.batch, self.t, self.dev, self.image_shape = batch, t, imgs.device, imgs.shape[-2:]
+        self.images = imgs.reshape(-1, *imgs.shape[2:])                             # :397
+        self.V, self.H, self.W = (int(n) for n in (self.images.shape[0], *self.image_shape))
+
+    def cams(self):
+        R, T, K = (self.batch[k][self.t] for k in ("input_R", "input_T", "input_K"))
+        return hip.pack_cams(R.reshape(-1, 3, 3), T.reshape(-1, 3, 1), K.reshape(-1, 3, 3))
+
+    def scale(self, enc):
+        return hip.feat_scale(enc.feat_scale(self.H, self.W), self.image_shape, self.dev)
+
+    def takes_tex_rows(self):
+        """this frame takes the texel hand-over (hip.set_tex_rows) if its map is a split map"""
+        return hip.tex_rows_enabled(self.dev) and hip.mlp_is_fused(self.dev) and self.V <= 3 and self.V * self.H * self.W < (1 << 22)
+
+
+def _pregather_on():
+    return os.environ.get("TH_PREGATHER") != "0"
+
+
+def _pregather_early_on():
+    return os.environ.get("TH_PREGATHER_EARLY", "1") != "0"
+
+
+def _out(rgb, acc, depth):
+    return {"depth_map": depth[None], "rgb_map": rgb[None], "acc_map": acc[None]}
 
 
 class Renderer:
@@ -97,18 +133,22 @@ class Renderer:
         off, mem = self._csr(src.device)
         return hip.segment_mean(src, off, mem)
 
-    def _csr(self, device):
-        key = ("csr", str(device))
+    def _cached(self, key, make):
+        """``self._dev[key]``, made at its first use"""
         if key not in self._dev:
-            self._dev[key] = hip.csr_to_device(self.csr_offsets, self.csr_members, device)
+            self._dev[key] = make()
         return self._dev[key]
 
+    def _csr(self, device):
+        return self._cached(("csr", str(device)), lambda: hip.csr_to_device(self.csr_offsets, self.csr_members, device))
+
     def _pe_norm(self, V, device):
-        key = ("pe", V, str(device))
-        if key not in self._dev:
-            pe = self.voxel_PE_can.unsqueeze(0).repeat(V, 1, 1)                    # :536
-            self._dev[key] = self.normalize_PE(pe).to(device)
-        return self._dev[key]
+        return self._cached(("pe", V, str(device)),
+                            lambda: self.normalize_PE(self.voxel_PE_can.unsqueeze(0).repeat(V, 1, 1)).to(device))    # :536
+
+    def _stream(self, name, dev):
+        """the renderer's stream of that name on ``dev``"""
+        return self._cached((name, str(dev)), lambda: torch.cuda.Stream(dev))
 
     # ---- per-frame constants ---------------------------------------------------------
     def frame_inputs(self, batch):
@@ -179,140 +219,158 @@ class Renderer:
         # parameter set) is brought up to date BEFORE the stem runs and on the stream that runs it: a frame's own
         # convolutions are then never queued in front of the clear that new weights trigger
         hip._sync_weights(self.net, "mlp")
-        images = batch["input_imgs"][t]
-        images = images.reshape(-1, *images.shape[2:])                              # :397
-        dev = images.device
-        cams = hip.pack_cams(batch["input_R"][t].reshape(-1, 3, 3), batch["input_T"][t].reshape(-1, 3, 1),
-                             batch["input_K"][t].reshape(-1, 3, 3))
-        image_shape = batch["input_imgs"][t].shape[-2:]
-        off, mem = self._csr(dev)
+        v = _Views(batch, t)
+        cams = v.cams()
+        off, mem = self._csr(v.dev)
         if cfg.rasterize and cfg_get("vizmap_source", "batch") == "device":
             viz = self._device_vizmap(batch, t)              # (a callable: evaluated where the frame paints, once)
         else:
             viz = batch["input_vizmaps"][t][0] if cfg.rasterize else None           # :103-119
-        enc = self.net.encoder
-        fold_done = None
-        if fused_encoder_tail and hasattr(enc, "trunk"):
-            H, W = images.shape[2:]
-            V = images.shape[0]
-            # (a device whose stem has been switched to the stock convolutions -- range guard, or non-finite latents received
-            # from another rank -- computes its own latents from here on: the owner rank may not have switched yet)
-            # -- it still takes part in the exchange (a collective: the other ranks wait for its turn as owner) but drops what
-            # it receives
-            # (stem_graph: the stem's 31 launches replayed as one hipGraph -- the callers that render a stream of frames)
-            trunk = (lambda im: enc.trunk(im, graph=True)) if stem_graph else enc.trunk
-            lat = trunk(images) if stem_exchange is None else stem_exchange.latents(trunk, images)
-            stem_flag = None if stem_exchange is None else stem_exchange.last_flag
-            if stem_exchange is not None and hip.conv_fallback(dev) and not stem_exchange.last_mine:
-                lat, stem_flag = enc.trunk(images), None
-            cw, cb = enc.upsample_color.weight, enc.upsample_color.bias
-            scale = hip.feat_scale(enc.feat_scale(H, W), image_shape, dev)
-            thr = cfg_hull() if hull_thresh is None else hull_thresh
+        thr = cfg_hull() if hull_thresh is None else hull_thresh
+        if fused_encoder_tail and hasattr(self.net.encoder, "trunk"):
             if crop_map is None:
                 crop_map = os.environ.get("TH_MAP_CROP") != "0"
-            if compact_map == "interleaved":            # A/B: one [V,H,W,260] tensor (1040-byte texel rows)
-                map_nhwc = hip.upsample_concat_nhwc(images, lat[0], lat[1], lat[2])
-            elif compact_map and demand is not None:
-                torch.cuda.current_stream(dev).wait_event(demand[1])       # (the marks were made on the hull stage's stream)
-                map_nhwc = hip.upsample_concat_split(images, lat[0], lat[1], lat[2], demand=demand[0])
-            elif compact_map and crop_map and thr >= 0:
-                reach = float(thr) * 1.001 + 1e-6
-                box = hip.map_box(batch["tar_smpl_vertice"][0], batch["input_smpl_vertice"][t][0], cams, scale, H, W, reach)
-                map_nhwc = hip.upsample_concat_split(images, lat[0], lat[1], lat[2], box=box, reach=reach)
-            elif compact_map:
-                map_nhwc = hip.upsample_concat_split(images, lat[0], lat[1], lat[2])
-            else:
-                map_nhwc = hip.upsample_concat_nhwc(images, lat[0], lat[1], lat[2], cw, cb)
-            # texel hand-over (hip.set_tex_rows, default): the layers that read the pixel-aligned features (cross_transformer.py
-            # :316, :334, :346) are applied to the map's texels here, once per frame -- bilinear sampling commutes with them
-            if (isinstance(map_nhwc, hip.SplitMap) and hip.tex_rows_enabled(dev) and V <= 3 and V * H * W < (1 << 22)
-                    and hip.mlp_is_fused(dev)):
-                if pregather is not None:
-                    # a single frame (render_fast) is bound by its chain of dependent stages: stem -> map -> paint / group ->
-                    # TransHE -> fused MLP.  The fold (0.35 ms) is needed by the fused MLP only: beside that chain on a stream
-                    # of its own, not inside it.  (A stream of frames is bound by the chip's total work: render_sequence keeps
-                    # the fold on the side stream, measured -- no gain there, LOG.md.)
-                    cur = torch.cuda.current_stream(dev)
-                    fs = self._dev.get(("fold_stream", str(dev)))
-                    if fs is None:
-                        fs = self._dev[("fold_stream", str(dev))] = torch.cuda.Stream(dev)
-                    # (the packed MLP image is uploaded on the CURRENT stream if it is due -- first frame, new weights: uploaded on `fs`
-                    # by map_fold's own check, nothing would order a map completion that th_render_pregather queues on `cur`
-                    # behind it)
-                    hip._sync_weights(self.net, "mlp")
-                    fs.wait_stream(cur)
-                    with torch.cuda.stream(fs):
-                        fold = hip.map_fold(self.net, map_nhwc)
-                        fold_done = torch.cuda.Event()
-                        fold_done.record(fs)
-                    fold.record_stream(cur)
-                else:
-                    hip.map_fold(self.net, map_nhwc)
-
-            def group():
-                return hip.paint_group_nhwc(map_nhwc, batch["input_smpl_vertice"][t][0], cams, scale,
-                                            viz() if callable(viz) else viz,
-                                            enc.reduction_layer.weight, enc.reduction_layer.bias, off, mem,
-                                            color_w=cw if compact_map else None, color_b=cb if compact_map else None)
-            pix_scale = scale
+            map_nhwc, pix_scale, group, stem_flag = self._stem_and_map(v, cams, viz, thr, compact_map, crop_map, demand,
+                                                                       stem_exchange, stem_graph)
         else:
-            holder_map, holder_scale, pixel_map, pixel_scale = enc(images)          # :399
-            V, _, H, W = pixel_map.shape
-
-            def group():
-                return hip.paint_group(holder_map, batch["input_smpl_vertice"][t][0], cams,
-                                       hip.feat_scale(holder_scale, image_shape, dev), viz() if callable(viz) else viz,
-                                       off, mem)
-            map_nhwc = hip.nchw_to_nhwc(pixel_map)
-            pix_scale = hip.feat_scale(pixel_scale, image_shape, dev)
-
-        def make_tokens():
-            self.last_grouped = group()
-            return self.net.ViT(self.last_grouped, self._pe_norm(V, dev), mask=None, graph=stem_graph)    # :538
-
+            map_nhwc, pix_scale, group, stem_flag = self._reference_map(v, cams, viz)
+        fold_done = self._fold(map_nhwc, v, beside=pregather is not None)      # (None without a split map)
         centres = hip.segment_mean(batch["tar_smpl_vertice_smplcoord"][0], off, mem)   # :543
         rot = hip.segment_mean_rot(batch["blend_mtx"][0], off, mem)                 # :544 + cross_transformer.py:185
         mk_frame = lambda tok: hip.Frame(batch["tar_smpl_vertice"][0], batch["Rh"][0], batch["Th"][0], cams, pix_scale,
-                                         map_nhwc, tok, centres, rot,
-                                         hull_thresh=cfg_hull() if hull_thresh is None else hull_thresh,
-                                         small_frame_rays=2400)
+                                         map_nhwc, tok, centres, rot, hull_thresh=thr, small_frame_rays=2400)
         if token_exchange is not None:
-            frame = mk_frame(token_exchange(make_tokens, (V, self.num_clusters, get_cfg().embed_size), dev))
+            frame = self._tokens_exchanged(mk_frame, group, v, stem_graph, token_exchange)
         elif defer_tokens:
-            self.last_grouped = grouped = group()
-            pe_norm = self._pe_norm(V, dev)
-            frame = mk_frame(None)
-            frame.finish_tokens = lambda: frame.set_tokens(self.net.ViT(grouped, pe_norm, mask=None, graph=stem_graph))   # :538
-        elif pregather is None or os.environ.get("TH_PREGATHER") == "0":
-            frame = mk_frame(make_tokens())
+            frame = self._tokens_deferred(mk_frame, group, v, stem_graph)
+        elif pregather is None or not _pregather_on():
+            frame = self._tokens_at_once(mk_frame, group, v, stem_graph)
         else:
-            pts_pg, slot_pg = pregather
-            cur = torch.cuda.current_stream(dev)
-            self.last_grouped = grouped = group()
-            grouped_ready = torch.cuda.Event()
-            grouped_ready.record(cur)
-            frame = mk_frame(None)
-            vs = self._dev.get(("vit_stream", str(dev)))
-            if vs is None:
-                vs = self._dev[("vit_stream", str(dev))] = torch.cuda.Stream(dev)
-            # TransHE is ISSUED first (render_pregather waits on the host for the hull stage's sample count: the 63
-            # launches must not queue behind that wait); on the device it runs beside K5 + K4 of the first chunks
-            with torch.cuda.stream(vs):
-                vs.wait_event(grouped_ready)
-                tokens = self.net.ViT(grouped, self._pe_norm(V, dev), mask=None, graph=stem_graph)    # :538
-            hip.render_pregather(self.net, frame, pts_pg, slot_pg)
-            grouped.record_stream(vs)
-            tokens.record_stream(cur)
-            cur.wait_stream(vs)
-            frame.set_tokens(tokens)
+            frame = self._tokens_beside_pregather(mk_frame, group, v, stem_graph, *pregather)
         if fold_done is not None:
-            torch.cuda.current_stream(dev).wait_event(fold_done)
+            torch.cuda.current_stream(v.dev).wait_event(fold_done)
         # (range guard, hip.render_rays: the same constants again -- through the stock convolutions -- if the stem's
         # input left the fp16 range)
         # (a rebuilt frame computes its own tokens: the exchange's frame counter must not advance twice)
         frame.rebuild = lambda: self.prepare_frame(batch, hull_thresh, fused_encoder_tail, compact_map, crop_map=crop_map)
         # (device bool: the stem latents this frame was built from were not finite -- dist.StemExchange; read in finish())
-        frame.stem_flag = stem_flag if (fused_encoder_tail and hasattr(enc, "trunk")) else None
+        frame.stem_flag = stem_flag
+        return frame
+
+    def _stem_and_map(self, v, cams, viz, thr, compact_map, crop_map, demand, stem_exchange, stem_graph):
+        """Stem and map stage of prepare_frame with the fused encoder tail: the trunk (replayed as a graph or not, here or through
+        the stem exchange) and one of the five forms of the map.  -> map, pixel scale, ``group()`` (paint + cluster pooling of
+        the input vertices on that map), stem flag."""
+        batch, t, images, dev, H, W = v.batch, v.t, v.images, v.dev, v.H, v.W
+        enc = self.net.encoder
+        # (a device whose stem has been switched to the stock convolutions -- range guard, or non-finite latents received
+        # from another rank -- computes its own latents from here on: the owner rank may not have switched yet)
+        # -- it still takes part in the exchange (a collective: the other ranks wait for its turn as owner) but drops what
+        # it receives
+        # (stem_graph: the stem's 31 launches replayed as one hipGraph -- the callers that render a stream of frames)
+        trunk = (lambda im: enc.trunk(im, graph=True)) if stem_graph else enc.trunk
+        lat = trunk(images) if stem_exchange is None else stem_exchange.latents(trunk, images)
+        stem_flag = None if stem_exchange is None else stem_exchange.last_flag
+        if stem_exchange is not None and hip.conv_fallback(dev) and not stem_exchange.last_mine:
+            lat, stem_flag = enc.trunk(images), None
+        cw, cb = enc.upsample_color.weight, enc.upsample_color.bias
+        scale = v.scale(enc)
+        if compact_map == "interleaved":            # A/B: one [V,H,W,260] tensor (1040-byte texel rows)
+            map_nhwc = hip.upsample_concat_nhwc(images, lat[0], lat[1], lat[2])
+        elif compact_map and demand is not None:
+            torch.cuda.current_stream(dev).wait_event(demand[1])       # (the marks were made on the hull stage's stream)
+            map_nhwc = hip.upsample_concat_split(images, lat[0], lat[1], lat[2], demand=demand[0])
+        elif compact_map and crop_map and thr >= 0:
+            reach = float(thr) * 1.001 + 1e-6
+            box = hip.map_box(batch["tar_smpl_vertice"][0], batch["input_smpl_vertice"][t][0], cams, scale, H, W, reach)
+            map_nhwc = hip.upsample_concat_split(images, lat[0], lat[1], lat[2], box=box, reach=reach)
+        elif compact_map:
+            map_nhwc = hip.upsample_concat_split(images, lat[0], lat[1], lat[2])
+        else:
+            map_nhwc = hip.upsample_concat_nhwc(images, lat[0], lat[1], lat[2], cw, cb)
+        off, mem = self._csr(dev)
+
+        def group():
+            return hip.paint_group_nhwc(map_nhwc, batch["input_smpl_vertice"][t][0], cams, scale, viz() if callable(viz) else viz,
+                                        enc.reduction_layer.weight, enc.reduction_layer.bias, off, mem,
+                                        color_w=cw if compact_map else None, color_b=cb if compact_map else None)
+        return map_nhwc, scale, group, stem_flag
+
+    def _reference_map(self, v, cams, viz):
+        """The other producer of prepare_frame's map, pixel scale, ``group()`` and stem flag (None): the reference's op order
+        through ``net.encoder(images)``, without the fused tail."""
+        batch, t, dev = v.batch, v.t, v.dev
+        holder_map, holder_scale, pixel_map, pixel_scale = self.net.encoder(v.images)   # :399
+        off, mem = self._csr(dev)
+
+        def group():
+            return hip.paint_group(holder_map, batch["input_smpl_vertice"][t][0], cams,
+                                   hip.feat_scale(holder_scale, v.image_shape, dev), viz() if callable(viz) else viz, off, mem)
+        return hip.nchw_to_nhwc(pixel_map), hip.feat_scale(pixel_scale, v.image_shape, dev), group, None
+
+    def _fold(self, map_nhwc, v, beside):
+        """Fold stage of prepare_frame.  Texel hand-over (hip.set_tex_rows, default): the layers that read the pixel-aligned
+        features (cross_transformer.py :316, :334, :346) are applied to the map's texels here, once per frame -- bilinear sampling
+        commutes with them.  In line, or (``beside``) on the fold stream beside the chain.  -> the event to wait for, or None."""
+        if not (isinstance(map_nhwc, hip.SplitMap) and v.takes_tex_rows()):
+            return None
+        if not beside:
+            hip.map_fold(self.net, map_nhwc)
+            return None
+        # a single frame (render_fast) is bound by its chain of dependent stages: stem -> map -> paint / group ->
+        # TransHE -> fused MLP.  The fold (0.35 ms) is needed by the fused MLP only: beside that chain on a stream
+        # of its own, not inside it.  (A stream of frames is bound by the chip's total work: render_sequence keeps
+        # the fold on the side stream, measured -- no gain there, LOG.md.)
+        cur = torch.cuda.current_stream(v.dev)
+        fs = self._stream("fold_stream", v.dev)
+        # (the packed MLP image is uploaded on the CURRENT stream if it is due -- first frame, new weights: uploaded on `fs`
+        # by map_fold's own check, nothing would order a map completion that th_render_pregather queues on `cur`
+        # behind it)
+        hip._sync_weights(self.net, "mlp")
+        fs.wait_stream(cur)
+        with torch.cuda.stream(fs):
+            fold = hip.map_fold(self.net, map_nhwc)
+            fold_done = fs.record_event()
+        fold.record_stream(cur)
+        return fold_done
+
+    # ---- token stage of prepare_frame: one function per strategy, each builds the frame through ``mk_frame(tokens or None)`` ----
+    def _tokens_at_once(self, mk_frame, group, v, graph):
+        self.last_grouped = group()
+        return mk_frame(self.net.ViT(self.last_grouped, self._pe_norm(v.V, v.dev), mask=None, graph=graph))    # :538
+
+    def _tokens_exchanged(self, mk_frame, group, v, graph, token_exchange):
+        """paint -> group -> TransHE here, or the tokens received from the rank that ran them"""
+        def make_tokens():
+            self.last_grouped = group()
+            return self.net.ViT(self.last_grouped, self._pe_norm(v.V, v.dev), mask=None, graph=graph)    # :538
+        return mk_frame(token_exchange(make_tokens, (v.V, self.num_clusters, get_cfg().embed_size), v.dev))
+
+    def _tokens_deferred(self, mk_frame, group, v, graph):
+        """everything up to the grouped vertex features; ``frame.finish_tokens()`` runs TransHE later"""
+        self.last_grouped = grouped = group()
+        pe_norm = self._pe_norm(v.V, v.dev)
+        frame = mk_frame(None)
+        frame.finish_tokens = lambda: frame.set_tokens(self.net.ViT(grouped, pe_norm, mask=None, graph=graph))   # :538
+        return frame
+
+    def _tokens_beside_pregather(self, mk_frame, group, v, graph, pts_pg, slot_pg):
+        """TransHE on a stream of its own beside hip.render_pregather of (``pts_pg``, ``slot_pg``) on the current one"""
+        cur = torch.cuda.current_stream(v.dev)
+        self.last_grouped = grouped = group()
+        grouped_ready = cur.record_event()
+        frame = mk_frame(None)
+        vs = self._stream("vit_stream", v.dev)
+        # TransHE is ISSUED first (render_pregather waits on the host for the hull stage's sample count: the 63
+        # launches must not queue behind that wait); on the device it runs beside K5 + K4 of the first chunks
+        with torch.cuda.stream(vs):
+            vs.wait_event(grouped_ready)
+            tokens = self.net.ViT(grouped, self._pe_norm(v.V, v.dev), mask=None, graph=graph)    # :538
+        hip.render_pregather(self.net, frame, pts_pg, slot_pg)
+        grouped.record_stream(vs)
+        tokens.record_stream(cur)
+        cur.wait_stream(vs)
+        frame.set_tokens(tokens)
         return frame
 
     def _device_vizmap(self, batch, t):
@@ -329,10 +387,7 @@ class Renderer:
                              "(or the SMPL pickle's f, read when vertex_can is not injected)")
         verts = batch["input_smpl_vertice"][t][0]
         dev = verts.device
-        key = ("faces", str(dev))
-        if key not in self._dev:
-            self._dev[key] = visibility._faces_dev(self.faces, dev)
-        faces = self._dev[key]
+        faces = self._cached(("faces", str(dev)), lambda: visibility._faces_dev(self.faces, dev))
         R, T, K = batch["input_R"][t], batch["input_T"][t], batch["input_K"][t]
         H, W = batch["input_imgs"][t].shape[-2:]
         done = []
@@ -363,24 +418,38 @@ class Renderer:
         mode = os.environ.get("TH_MAP_DEMAND", "auto")
         if mode == "0" or (mode != "1" and not sharded) or not hasattr(self.net.encoder, "trunk"):
             return None
-        t = 0
-        batch = self.frame_inputs(batch)
-        imgs = batch["input_imgs"][t]
-        V, H, W = int(np.prod(imgs.shape[:-3])), int(imgs.shape[-2]), int(imgs.shape[-1])
-        dev = imgs.device
-        if not (hip.tex_rows_enabled(dev) and hip.mlp_is_fused(dev)) or V > 3 or V * H * W >= (1 << 22):
+        v = _Views(self.frame_inputs(batch))
+        if not v.takes_tex_rows():
             return None                     # (frames that take K5's rows read the latents of every corner: keep the box)
-        cams = hip.pack_cams(batch["input_R"][t].reshape(-1, 3, 3), batch["input_T"][t].reshape(-1, 3, 1),
-                             batch["input_K"][t].reshape(-1, 3, 3))
-        scale = hip.feat_scale(self.net.encoder.feat_scale(H, W), imgs.shape[-2:], dev)
         paints = token_exchange is None or token_exchange.will_compute()
-        buf = hip.render_predemand(pts, cams, scale, V, H, W,
-                                   verts_paint=batch["input_smpl_vertice"][t][0] if paints else None)
+        buf = hip.render_predemand(pts, v.cams(), v.scale(self.net.encoder), v.V, v.H, v.W,
+                                   verts_paint=v.batch["input_smpl_vertice"][v.t][0] if paints else None)
         if buf is None:
             return None
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-        return buf, ev
+        return buf, torch.cuda.current_stream(v.dev).record_event()
+
+    def _points(self, batch, ray_slice):
+        """the rays ``ray_slice`` (None: all) of a batch with the sampling randomisations the configuration asks for"""
+        cfg, sl = get_cfg(), slice(None) if ray_slice is None else ray_slice
+        return hip.Points(batch["ray_o"][0][sl], batch["ray_d"][0][sl], batch["near"][0][sl], batch["far"][0][sl],
+                          n_samples=cfg.N_samples, **self._sampling_randoms(batch, sl, cfg))
+
+    def _shade(self, frame, pts, **kw):
+        """hip.render_rays over the configuration's background"""
+        return hip.render_rays(self.net, frame, pts, white_bkgd=bool(get_cfg().white_bkgd), **kw)
+
+    def _hull_front(self, batch, pts, V, feed, hull, small_frame_rays, slot=0, **predemand_args):
+        """The hull front of a frame: behind everything queued on the stream ``feed``, the ray-only stage of ``pts`` (hip.render_prepass
+        into workspace ``slot``) and the demand marks of its valid samples (``self.predemand``) on the stream ``hull``.  -> the demand
+        for prepare_frame(demand=...), or None."""
+        hull.wait_stream(feed)
+        with torch.cuda.stream(hull):
+            hip.render_prepass(pts, batch["tar_smpl_vertice"][0], V, cfg_hull(), small_frame_rays, n_clusters=self.num_clusters,
+                               slot=slot)
+            dm = self.predemand(batch, pts, **predemand_args)
+        for t in (pts.ray_o, pts.ray_d, pts.near, pts.far):
+            t.record_stream(hull)
+        return dm
 
     # ---- reference API -------------------------------------------------------------------
     def _own_stream(self, dev):
@@ -392,14 +461,9 @@ class Renderer:
         17.85 -> 17.65 on another, profiles/r05_m).  render_sequence stays on the caller's stream: its steady state was 0.17 ms per
         frame SLOWER on a stream of its own (14.79 -> 14.96 ms, same profile).  None = stay on the caller's stream (it is not the
         default stream)."""
-        if not torch.cuda.is_available():
-            return None
         if torch.cuda.current_stream(dev) != torch.cuda.default_stream(dev):
             return None
-        m = self._dev.get(("main_stream", str(dev)))
-        if m is None:
-            m = self._dev[("main_stream", str(dev))] = torch.cuda.Stream(dev)
-        return m
+        return self._stream("main_stream", dev)
 
     def render_fast(self, batch, is_train=True, frame=None, ray_slice=None, small_frame_rays=2400):
         """:429-484.  ``frame`` lets callers reuse per-frame constants; ``ray_slice`` renders a sub-range of
@@ -423,36 +487,22 @@ class Renderer:
         return out
 
     def _render_fast(self, batch, frame, ray_slice, small_frame_rays):
-        cfg = get_cfg()
-        sl = slice(None) if ray_slice is None else ray_slice
-        pts = hip.Points(batch["ray_o"][0][sl], batch["ray_d"][0][sl], batch["near"][0][sl], batch["far"][0][sl],
-                         n_samples=cfg.N_samples, **self._sampling_randoms(batch, sl, cfg))
+        pts = self._points(batch, ray_slice)
         if frame is None:
             batch = self.frame_inputs(batch)
-            V = batch["input_imgs"][0].reshape(-1, *batch["input_imgs"][0].shape[2:]).shape[0]
+            V, dev = _Views(batch).V, pts.ray_o.device
             if V <= 4 and pts.R > 0:
                 # the ray-only stage (hull mask, compaction: ~10 launches, 0.85 ms) runs on a second stream beside the
                 # per-frame constants (encoder, paint, TransHE: ~110 latency-bound launches) instead of in front of them;
                 # th_render_rays waits for its event
-                dev = pts.ray_o.device
-                side = self._dev.get(("hull_stream", str(dev)))
-                if side is None:
-                    side = self._dev[("hull_stream", str(dev))] = torch.cuda.Stream(dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    hip.render_prepass(pts, batch["tar_smpl_vertice"][0], V, cfg_hull(), small_frame_rays,
-                                       n_clusters=len(self.csr_offsets) - 1)
-                    dm = self.predemand(batch, pts)
-                for t in (pts.ray_o, pts.ray_d, pts.near, pts.far):
-                    t.record_stream(side)
+                dm = self._hull_front(batch, pts, V, torch.cuda.current_stream(dev), self._stream("hull_stream", dev),
+                                      small_frame_rays)
                 frame = self.prepare_frame(batch, pregather=(pts, 0), demand=dm, stem_graph=True)
             else:
                 frame = self.prepare_frame(batch)
         # (the threshold applies to THIS call whether or not the frame constants were handed in)
-        rgb, acc, depth, stats = hip.render_rays(self.net, frame, pts, white_bkgd=bool(cfg.white_bkgd),
-                                                 small_frame_rays=small_frame_rays)
-        self.last_stats = stats
-        return {"depth_map": depth[None], "rgb_map": rgb[None], "acc_map": acc[None]}
+        *out, self.last_stats = self._shade(frame, pts, small_frame_rays=small_frame_rays)
+        return _out(*out)
 
     def _sampling_randoms(self, batch, sl, cfg):
         """The reference's two randomisations of the sampling, as keyword arguments of hip.Points (empty when both are off, which
@@ -529,160 +579,21 @@ class Renderer:
         The stem and TransHE of these frames are replayed hipGraphs (encoder.trunk(graph=True), hip.vit_forward(graph=True)):
         the latents and tokens of ``self.last_frame`` live in the graphs' rotating buffers and stay valid until three more
         frames have been yielded -- ``self.last_frame.rebuild()`` returns a frame that owns its memory."""
-        import collections
-        cfg = get_cfg()
-        sl = slice(None) if ray_slice is None else ray_slice
-        it = iter(batches)
-        lookahead = max(1, min(int(lookahead), 3))    # (th_render_prepass keeps at most 4 tokens)
-        if lookahead >= 3 and hip.graphs_enabled():
-            # the stem / TransHE graph rings hold 4 instances = pipeline depth 2 + the frame being shaded + the frame just handed
-            # out: at depth 3 the instance `last_frame` points at has been replayed for a later frame by the time it is yielded
-            lookahead = 2
-        # split front (single rank): the front of a frame is issued in two pieces -- A = hull stage, encoder, paint, group
-        # (chip-filling kernels) and B = TransHE (63 small dependent launches).  In the
-        # shading window of frame i the side stream runs B(i+1) FIRST and then A(i+2): the latency-bound launches of
-        # TransHE find free CUs beside the producers of frame i instead of queueing, one by one, behind MLP tiles.
-        split = token_exchange is None
-        if split:
-            lookahead = max(lookahead, 2)
-        elif os.environ.get("TH_PREGATHER_EARLY", "1") != "0":
-            # multi-rank job: two frames ahead as well, so that the front of frame i+1 is complete before the shading of
-            # frame i is queued and its neighbour records can start beside frame i's compositing and image gather
-            # (th_render_pregather_early below; emulated rank of 8: 2.835 -> 2.80 ms per frame)
-            lookahead = max(lookahead, 2)
-        nslots = lookahead + 1
-
-        def front(b, j, side):
-            """side stream: hull stage of b's rays into workspace 1 + j % nslots (0 is render_fast's), then b's frame
-            constants"""
-            # the range-guard epoch these constants are built under: a frame whose front was issued before the guard
-            # switched a path (fp32 MLP, stock convolutions, fp32 TransHE GEMMs) is rebuilt before it is handed out
-            ep = hip.range_epoch(b["ray_o"].device)
-            given = getattr(b, "source", None) or b        # (what the caller handed in: ``self.last_batch``)
-            with torch.cuda.stream(side):
-                b = self.frame_inputs(b)
-                pts = hip.Points(b["ray_o"][0][sl], b["ray_d"][0][sl], b["near"][0][sl], b["far"][0][sl],
-                                 n_samples=cfg.N_samples, **self._sampling_randoms(b, sl, cfg))
-                V = b["input_imgs"][0].reshape(-1, *b["input_imgs"][0].shape[2:]).shape[0]
-                if V <= 4 and pts.R > 0:
-                    # the ray-only hull stage (grid, hull test, compaction: ~10 dependent launches, 0.3 ms) shares nothing with
-                    # the frame constants: on a stream of its own beside them, not in front of them -- the side stream's chain of
-                    # ~55 dependent launches is what bounds a rank of 8 (2.7 ms against a 2.3 ms shard of the fused MLP)
-                    hull_side.wait_stream(side)
-                    with torch.cuda.stream(hull_side):
-                        hip.render_prepass(pts, b["tar_smpl_vertice"][0], V, cfg_hull(), small_frame_rays,
-                                           n_clusters=len(self.csr_offsets) - 1, slot=1 + j % nslots)
-                        dm = self.predemand(b, pts, token_exchange, sharded=token_exchange is not None or ray_slice is not None)
-                    for t in (pts.ray_o, pts.ray_d, pts.near, pts.far):
-                        t.record_stream(hull_side)
-                else:
-                    dm = None
-                frame = self.prepare_frame(b, token_exchange=token_exchange, defer_tokens=split, stem_exchange=stem_exchange,
-                                           demand=dm, stem_graph=True)
-                if V <= 4 and pts.R > 0:
-                    side.wait_stream(hull_side)
-                    hip.render_pregrid(frame, pts)         # K4's candidate grid: here, not in front of K4
-                ready = torch.cuda.Event()
-                ready.record(side)
-            return [given, pts, frame, ready, ep, ready, False]      # [5]: piece A's event (tokens() replaces [3]); [6]: see below
-
-        def tokens(ent, side):
-            """side stream: piece B of an entry whose piece A has been issued"""
-            fin = getattr(ent[2], "finish_tokens", None)
-            if fin is None:
-                return
-            with torch.cuda.stream(side):
-                fin()
-                ent[2].finish_tokens = None
-                ent[3] = torch.cuda.Event()
-                ent[3].record(side)
-
-        first = next(it, None)
-        if first is None:
-            return
-        dev = first["ray_o"].device
-        side = self._dev.get(("side_stream", str(dev)))
-        if side is None:
-            side = self._dev[("side_stream", str(dev))] = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        hull_side = self._dev.get(("hull_side_stream", str(dev)))
-        if hull_side is None:
-            hull_side = self._dev[("hull_side_stream", str(dev))] = torch.cuda.Stream(dev)
-        if token_exchange is not None:
-            # multi-rank job: a rank runs TransHE (and, with the stem exchange, the stem) only for the frames it owns, so the
-            # first-call capture of their graphs (a device synchronisation + a garbage collection per instance: tens of
-            # milliseconds) would land on its first OWNED frame -- frame r of rank r, inside a short run's timed frames.  One
-            # local set of frame constants up front (no exchange, result dropped) captures both rings on every rank at once.
-            # (Train-mode BatchNorm running statistics advance by this one extra frame; they do not enter the rendering.)
-            # (keyed on the shape AND the graph epoch: instances dropped for new weights are captured again the same way)
-            with torch.cuda.stream(side):
-                first = self.frame_inputs(first)           # (made once: front() below takes it as it is)
-            shape = (tuple(first["input_imgs"][0].shape), hip.graph_epoch())
-            primed = self._dev.setdefault(("graphs_primed", str(dev)), set())
-            if shape not in primed and hip.graphs_enabled():
-                primed.add(shape)
-                with torch.cuda.stream(side):
-                    # the extra frame must not show in the network's state: train-mode BatchNorm statistics are put back
-                    bns = [m for m in self.net.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
-                    keep = [(m, None if m.running_mean is None else m.running_mean.clone(),
-                             None if m.running_var is None else m.running_var.clone(),
-                             None if m.num_batches_tracked is None else m.num_batches_tracked.clone()) for m in bns]
-                    self.prepare_frame(first, stem_graph=True)
-                    for m, rm, rv, nb in keep:
-                        if rm is not None: m.running_mean.copy_(rm)
-                        if rv is not None: m.running_var.copy_(rv)
-                        if nb is not None: m.num_batches_tracked.copy_(nb)
-        queue = collections.deque([front(first, 0, side)])
-        tokens(queue[0], side)
-        queued, more = 1, True
-
-        def pull():
-            nonlocal queued, more
-            if not more:
-                return
-            with torch.cuda.stream(side):
-                b = next(it, None)
-            if b is None:
-                more = False
-                return
-            queue.append(front(b, queued, side))
-            queued += 1
-
-        for _ in range(lookahead - 1):
-            pull()
+        pipe = _FramePipeline(self, batches, ray_slice, small_frame_rays, lookahead, token_exchange, stem_exchange)
+        pipe.start()
         # A frame is handed out one step late: its range-guard snapshot (hip.render_rays, defer_guard) is read back
         # -- a host wait for that frame -- only after the shading of the NEXT frame has been queued, so the device
         # never waits for the host.  A frame whose snapshot is not clean (or that was queued before an earlier frame
         # switched the context to the fp32 path) is rendered again before it is yielded.
         shaded = collections.deque()
-
-        def finish(ent):
-            rgb, acc, depth, stats, frame, cur, pts, check, epoch = ent
-            ok = check()
-            bad_stem = getattr(frame, "stem_flag", None) is not None and bool(frame.stem_flag)
-            if bad_stem:
-                hip.force_conv_fallback(dev, "the stem latents received for this frame are not finite (fp16 overflow in "
-                                             "the owner rank's convolutions)")
-            # (bad_stem on its own is a reason to rebuild: once the device is in conv fallback the epoch does not move again)
-            if not ok or bad_stem or epoch != hip.range_epoch(dev):
-                # (look-ahead 3: five frames are alive when this one is finished, one more than the graphs' rings of four hold --
-                # its latents / tokens may have been handed to the frame three ahead: constants again in that case too)
-                if bad_stem or hip.conv_fallback(dev) or hip.vit_fallback(dev) or lookahead >= 3:
-                    frame = frame.rebuild()                 # constants again, through the paths the guard switched to
-                rgb, acc, depth, stats = hip.render_rays(self.net, frame, pts, white_bkgd=bool(cfg.white_bkgd),
-                                                         small_frame_rays=small_frame_rays)
-            self.last_stats, self.last_frame, self.last_batch = stats, frame, cur
-            return {"depth_map": depth[None], "rgb_map": rgb[None], "acc_map": acc[None]}
-
-        while queue:
-            cur, pts, frame, ready, epoch, _, early = queue.popleft()
-            main = torch.cuda.current_stream(dev)
-            main.wait_event(ready)
+        while pipe.queue:
+            ent = pipe.queue.popleft()
+            main = torch.cuda.current_stream(pipe.dev)
+            main.wait_event(ent.ready)
             # everything queued so far (inputs of coming batches, the shading of the previous frame -- the last user
             # of the workspace the next hull stage writes) is ordered before the side stream's next piece of work;
             # this frame's shading is not
-            fence = torch.cuda.Event()
-            fence.record(main)
+            fence = main.record_event()
             # two-phase shading: the texture-path-bound producers (pixel gather, neighbour records: ONE launch each over the
             # frame's valid samples, up to TH_PRE_SAMPLES = 2.6 M, into region A of the shading pool -- 3.6 KB per sample)
             # first, then the fused MLP over the same samples in one launch (what lies beyond: producers and MLP alternate
@@ -692,26 +603,26 @@ class Renderer:
             # (Built and removed in round 5: the NEXT frame's producers on a stream of their own BESIDE this frame's fused MLP,
             # every frame in flight with its own pool -- the window between two MLP launches closes, and the MLP slows down by
             # exactly what K4 / K5t take: they fill the chip, the window was never idle time.  profiles/r05_h.)
-            if os.environ.get("TH_PREGATHER") != "0":
-                hip.render_pregather(self.net, frame, pts, early=early)
+            if _pregather_on():
+                hip.render_pregather(self.net, ent.frame, ent.pts, early=ent.early)
             # The NEXT frame's neighbour records (K4, the long pole of its producers) may start the moment this frame's
             # per-sample stage is done, beside this frame's compositing and the consumer's image assembly instead of behind
             # them (th_render_pregather_early): for that, the current stream is ordered behind piece A of the next frame's
             # front BEFORE this frame's shading is queued -- it was issued a whole frame ago (split front: lookahead >= 2).
-            if queue and os.environ.get("TH_PREGATHER_EARLY", "1") != "0":
-                main.wait_event(queue[0][5])
-                queue[0][6] = True
-            rgb, acc, depth, stats, check = hip.render_rays(self.net, frame, pts, white_bkgd=bool(cfg.white_bkgd),
-                                                            defer_guard=True, small_frame_rays=small_frame_rays)
-            side.wait_event(fence)
-            if queue:
-                tokens(queue[0], side)        # B(i+1) first ...
-            pull()                            # ... then A(i+lookahead)
-            shaded.append((rgb, acc, depth, stats, frame, cur, pts, check, epoch))
+            nxt = pipe.queue[0] if pipe.queue else None
+            if nxt is not None and _pregather_early_on():
+                main.wait_event(nxt.front_done)
+                nxt.early = True
+            *out, stats, check = self._shade(ent.frame, ent.pts, defer_guard=True, small_frame_rays=small_frame_rays)
+            pipe.side.wait_event(fence)
+            if nxt is not None:
+                pipe.tokens(nxt)              # B(i+1) first ...
+            pipe.pull()                       # ... then A(i+lookahead)
+            shaded.append(_Shaded(ent, out, stats, check))
             if len(shaded) > 1:
-                yield finish(shaded.popleft())
+                yield pipe.finish(shaded.popleft())
         while shaded:
-            yield finish(shaded.popleft())
+            yield pipe.finish(shaded.popleft())
 
     def render(self, batch, is_train=True):
         """:486-498 -- no hull mask, every sample shaded, RGB everywhere.
@@ -741,14 +652,169 @@ class Renderer:
             self.last_stats = dict(hit_rays=int(batch["ray_o"].shape[1]), valid_samples=int(batch["ray_o"].shape[1]) * int(cfg.N_samples),
                                    unmasked=1)
             return out
-        frame = self.prepare_frame(batch, hull_thresh=-1.0)
-        pts = hip.Points(batch["ray_o"][0], batch["ray_d"][0], batch["near"][0], batch["far"][0],
-                         n_samples=cfg.N_samples)
-        rgb, acc, depth, stats = hip.render_rays(self.net, frame, pts, white_bkgd=bool(cfg.white_bkgd))
-        self.last_stats = stats
-        return {"rgb_map": rgb[None], "acc_map": acc[None], "depth_map": depth[None]}
+        # (no randomisation on this path, see above: the rays as they are)
+        *out, self.last_stats = self._shade(self.prepare_frame(batch, hull_thresh=-1.0), self._points(batch, None))
+        return _out(*out)
+
+
+class _InFlight:
+    """A frame of render_sequence whose front has been issued: the batch as the caller handed it in, its rays, its frame constants,
+    the event the shading waits for (piece A's until tokens() replaces it with piece B's), the range-guard epoch the constants
+    were built under, piece A's event, and whether the current stream was ordered behind piece A before the previous frame's
+    shading was queued (hip.render_pregather(early=...))."""
+    __slots__ = ("given", "pts", "frame", "ready", "epoch", "front_done", "early")
+
+    def __init__(self, given, pts, frame, ready, epoch):
+        self.given, self.pts, self.frame, self.ready, self.epoch = given, pts, frame, ready, epoch
+        self.front_done, self.early = ready, False
+
+
+class _Shaded:
+    """A frame of render_sequence whose shading has been queued: its entry, the outputs (rgb, acc, depth), the statistics and the deferred
+    range-guard check (hip.render_rays(defer_guard=True))."""
+    __slots__ = ("ent", "out", "stats", "check")
+
+    def __init__(self, ent, out, stats, check):
+        self.ent, self.out, self.stats, self.check = ent, out, stats, check
+
+
+class _FramePipeline:
+    """The state of one Renderer.render_sequence call: the iterator over the batches, the queue of frames whose front has been
+    issued, the side stream (fronts) and the hull side stream (hull stages), how many frames have been queued and whether the
+    iterator may have more."""
+
+    def __init__(self, renderer, batches, ray_slice, small_frame_rays, lookahead, token_exchange, stem_exchange):
+        self.r, self.it = renderer, iter(batches)
+        self.ray_slice, self.sharded = ray_slice, token_exchange is not None or ray_slice is not None
+        self.small_frame_rays, self.token_exchange, self.stem_exchange = small_frame_rays, token_exchange, stem_exchange
+        lookahead = max(1, min(int(lookahead), 3))    # (th_render_prepass keeps at most 4 tokens)
+        if lookahead >= 3 and hip.graphs_enabled():
+            # the stem / TransHE graph rings hold 4 instances = pipeline depth 2 + the frame being shaded + the frame just handed
+            # out: at depth 3 the instance `last_frame` points at has been replayed for a later frame by the time it is yielded
+            lookahead = 2
+        # split front (single rank): the front of a frame is issued in two pieces -- A = hull stage, encoder, paint, group
+        # (chip-filling kernels) and B = TransHE (63 small dependent launches).  In the
+        # shading window of frame i the side stream runs B(i+1) FIRST and then A(i+2): the latency-bound launches of
+        # TransHE find free CUs beside the producers of frame i instead of queueing, one by one, behind MLP tiles.
+        self.split = token_exchange is None
+        if self.split:
+            lookahead = max(lookahead, 2)
+        elif _pregather_early_on():
+            # multi-rank job: two frames ahead as well, so that the front of frame i+1 is complete before the shading of
+            # frame i is queued and its neighbour records can start beside frame i's compositing and image gather
+            # (th_render_pregather_early in render_sequence; emulated rank of 8: 2.835 -> 2.80 ms per frame)
+            lookahead = max(lookahead, 2)
+        self.lookahead, self.nslots = lookahead, lookahead + 1
+        self.queue, self.queued, self.more = collections.deque(), 0, True
+
+    def start(self):
+        """the streams, the graphs of a multi-rank job, the front of the first frame and piece A of the ``lookahead - 1`` frames
+        after it (nothing, and an empty queue, if there is no first frame)"""
+        first = next(self.it, None)
+        if first is None:
+            return
+        r = self.r
+        self.dev = dev = first["ray_o"].device
+        self.side = r._stream("side_stream", dev)
+        self.side.wait_stream(torch.cuda.current_stream(dev))
+        self.hull_side = r._stream("hull_side_stream", dev)
+        if self.token_exchange is not None:
+            first = self.prime_graphs(first)
+        self.queue.append(self.front(first, 0))
+        self.tokens(self.queue[0])
+        self.queued = 1
+        for _ in range(self.lookahead - 1):
+            self.pull()
+
+    def prime_graphs(self, first):
+        """-> ``first`` with its input views made (once: front() takes it as it is)"""
+        # multi-rank job: a rank runs TransHE (and, with the stem exchange, the stem) only for the frames it owns, so the
+        # first-call capture of their graphs (a device synchronisation + a garbage collection per instance: tens of
+        # milliseconds) would land on its first OWNED frame -- frame r of rank r, inside a short run's timed frames.  One
+        # local set of frame constants up front (no exchange, result dropped) captures both rings on every rank at once.
+        # (Train-mode BatchNorm running statistics advance by this one extra frame; they do not enter the rendering.)
+        # (keyed on the shape AND the graph epoch: instances dropped for new weights are captured again the same way)
+        r, side = self.r, self.side
+        with torch.cuda.stream(side):
+            first = r.frame_inputs(first)
+        shape = (tuple(first["input_imgs"][0].shape), hip.graph_epoch())
+        primed = r._dev.setdefault(("graphs_primed", str(self.dev)), set())
+        if shape not in primed and hip.graphs_enabled():
+            primed.add(shape)
+            with torch.cuda.stream(side):
+                # the extra frame must not show in the network's state: train-mode BatchNorm statistics are put back
+                bns = [m for m in r.net.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+                stats = [s for m in bns for s in (m.running_mean, m.running_var, m.num_batches_tracked) if s is not None]
+                keep = [s.clone() for s in stats]
+                r.prepare_frame(first, stem_graph=True)
+                for s, k in zip(stats, keep):
+                    s.copy_(k)
+        return first
+
+    def front(self, b, j):
+        """side stream: hull stage of b's rays into workspace 1 + j % nslots (0 is render_fast's), then b's frame
+        constants"""
+        r, side = self.r, self.side
+        # the range-guard epoch these constants are built under: a frame whose front was issued before the guard
+        # switched a path (fp32 MLP, stock convolutions, fp32 TransHE GEMMs) is rebuilt before it is handed out
+        ep = hip.range_epoch(b["ray_o"].device)
+        given = getattr(b, "source", None) or b        # (what the caller handed in: ``self.last_batch``)
+        with torch.cuda.stream(side):
+            b = r.frame_inputs(b)
+            pts = r._points(b, self.ray_slice)
+            V = _Views(b).V
+            hull = V <= 4 and pts.R > 0
+            dm = None
+            if hull:
+                # the ray-only hull stage (grid, hull test, compaction: ~10 dependent launches, 0.3 ms) shares nothing with
+                # the frame constants: on a stream of its own beside them, not in front of them -- the side stream's chain of
+                # ~55 dependent launches is what bounds a rank of 8 (2.7 ms against a 2.3 ms shard of the fused MLP)
+                dm = r._hull_front(b, pts, V, side, self.hull_side, self.small_frame_rays, 1 + j % self.nslots,
+                                   token_exchange=self.token_exchange, sharded=self.sharded)
+            frame = r.prepare_frame(b, token_exchange=self.token_exchange, defer_tokens=self.split,
+                                    stem_exchange=self.stem_exchange, demand=dm, stem_graph=True)
+            if hull:
+                side.wait_stream(self.hull_side)
+                hip.render_pregrid(frame, pts)         # K4's candidate grid: here, not in front of K4
+            ready = side.record_event()
+        return _InFlight(given, pts, frame, ready, ep)
+
+    def tokens(self, ent):
+        """side stream: piece B of an entry whose piece A has been issued"""
+        if ent.frame.finish_tokens is not None:
+            with torch.cuda.stream(self.side):
+                ent.frame.finish_tokens()
+                ent.frame.finish_tokens = None
+                ent.ready = self.side.record_event()
+
+    def pull(self):
+        """piece A of the next batch, taken from the iterator with the side stream current"""
+        if self.more:
+            with torch.cuda.stream(self.side):
+                b = next(self.it, None)
+            self.more = b is not None
+            if self.more:
+                self.queue.append(self.front(b, self.queued))
+                self.queued += 1
+
+    def finish(self, sh):
+        """the guard check of a shaded frame (a host wait for it), the frame again if it is not clean -> render_fast's dict"""
+        r, dev, ent, frame, out, stats = self.r, self.dev, sh.ent, sh.ent.frame, sh.out, sh.stats
+        ok = sh.check()
+        bad_stem = frame.stem_flag is not None and bool(frame.stem_flag)
+        if bad_stem:
+            hip.force_conv_fallback(dev, "the stem latents received for this frame are not finite (fp16 overflow in "
+                                         "the owner rank's convolutions)")
+        # (bad_stem on its own is a reason to rebuild: once the device is in conv fallback the epoch does not move again)
+        if not ok or bad_stem or ent.epoch != hip.range_epoch(dev):
+            # (look-ahead 3: five frames are alive when this one is finished, one more than the graphs' rings of four hold --
+            # its latents / tokens may have been handed to the frame three ahead: constants again in that case too)
+            if bad_stem or hip.conv_fallback(dev) or hip.vit_fallback(dev) or self.lookahead >= 3:
+                frame = frame.rebuild()                 # constants again, through the paths the guard switched to
+            *out, stats = r._shade(frame, ent.pts, small_frame_rays=self.small_frame_rays)
+        r.last_stats, r.last_frame, r.last_batch = stats, frame, ent.given
+        return _out(*out)
 
 
 def cfg_hull():
-    from transhuman_amd.config import cfg_get
     return float(cfg_get("hull_dist", 0.1))
