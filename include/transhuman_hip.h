@@ -596,6 +596,30 @@ int th_prep_views(th_ctx* ctx, const uint8_t* img_u8, const uint8_t* msk_u8, int
 int th_prep_mask(th_ctx* ctx, const uint8_t* a, const uint8_t* b_or_null, int V, int H0, int W0, int border, uint8_t* out,
                  th_stream stream);
 
+/* ---- K18: the training targets of a step -- patch ray sampling (additions, ABI 12) ---------------- */
+/* The train split of sample_ray_patch (lib/utils/if_nerf/if_nerf_data_utils.py:445-499 with :287-443), which the reference runs per
+ * step in numpy inside its dataset, on the dense per-pixel arrays of th_gen_rays.  All pointers are DEVICE pointers.
+ * Inputs: ray_o, ray_d fp32 [H W][3], near, far fp32 [H W], ray_mask uint8 [H W] as th_gen_rays writes them; msk uint8 [H][W] (any
+ * values, 100 = silhouette border); bound_mask uint8 [H][W] (th_bound_mask); img fp32, channel c of pixel p at
+ * img[p pix_stride + c chan_stride] (HWC: 3, 1; CHW: 1, H W); draws fp64 [N][2] in [0, 1); subject_ratio; N patches of P x P.
+ * m = msk * bound_mask in uint8, human = m > 0, background = ray_mask & ~human.  Patch i: candidate set = human if
+ * draws[i][0] < subject_ratio else background, n its pixel count, centre = its k-th pixel in row-major order,
+ * k = min(floor(draws[i][1] n), n - 1) with the product in fp64; x_min = clip(cx - P / 2, 0, W - P), y_min alike.
+ * Outputs: patch_masks / patch_masks_sub uint8 [N][P][P] = ray_mask / human on the window; target_patches fp32 [N][P][P][3];
+ * xy_min int32 [N][2] = (x_min, y_min); counts int32 [2][N] = n, then the window's ray count; and the ray list, patch after patch,
+ * each window's ray_mask pixels in row-major order (rows allocated at the bound N P P, the first sum(counts[1]) are written):
+ * out_rgb, out_ray_o, out_ray_d fp32 [.][3], out_near, out_far fp32 [.], out_sub_mask uint8 [.] (human), out_select_inds int64 [.]
+ * (cumsum(ray_mask) - 1 at the pixel).  A patch whose candidate set is empty writes nothing but counts[0][i] = counts[1][i] = 0
+ * (the reference raises there).  No atomics: bit-identical from run to run.  No host wait.
+ * Limits (argument errors otherwise): 1 <= H, W <= 4096, 1 <= P <= 64, P <= min(H, W), 1 <= N <= 64. */
+size_t th_patch_workspace_bytes(int H, int W);
+int th_patch_rays(th_ctx* ctx, const float* ray_o, const float* ray_d, const float* near, const float* far, const uint8_t* ray_mask,
+                  const uint8_t* msk, const uint8_t* bound_mask, const float* img, long long pix_stride, long long chan_stride, int H,
+                  int W, const double* draws, double subject_ratio, int N, int P, uint8_t* patch_masks, uint8_t* patch_masks_sub,
+                  float* target_patches, int32_t* xy_min, int32_t* counts, float* out_rgb, float* out_ray_o, float* out_ray_d,
+                  float* out_near, float* out_far, uint8_t* out_sub_mask, int64_t* out_select_inds, void* workspace,
+                  size_t workspace_bytes, th_stream stream);
+
 /* ---- K10: SMPL linear blend skinning ------------------------------------ */
 /* SMPL._call, lib/utils/SMPL.py:114-186, float64 like the reference.  Model arrays (DEVICE pointers, the fields
  * the reference reads from the SMPL pickle, :83-89): v_template [nv,3], shapedirs [nv,3,10], posedirs [nv,3,207],

@@ -65,6 +65,12 @@ def _defaults():
         # the training entry (autograd_path.render): "torch" composes every stage from torch operators; "device" runs the token
         # blend, the pixel-aligned gather and the compositing through the HIP forwards with HIP adjoints (networks/train_ops.py)
         train_kernels="torch",
+        # patch sampling of the training targets (train_or_eval.yaml:70-75)
+        patch=SimpleNamespace(use_patch_sampling=True, sample_subject_ratio=0.8, N_patches=6, size=20),
+        # where the training entry's rays and patch targets come from: "batch" (as the reference: its dataset samples them on the
+        # host) or "device" (made in Renderer.render from the target view, target_K / target_R / target_T and can_bounds, when the
+        # batch has no ray_o; transhuman_amd/train_targets.py, K18)
+        target_prep="batch",
     )
 
 

@@ -779,6 +779,25 @@ int th_prep_mask(th_ctx* c, const uint8_t* a, const uint8_t* b, int V, int H0, i
     return th_prep_mask_launch(a, b, V, H0, W0, border, out, (hipStream_t)stream);
 }
 
+size_t th_patch_workspace_bytes(int H, int W) { return th_patch_ws(H, W); }
+
+int th_patch_rays(th_ctx* c, const float* ray_o, const float* ray_d, const float* near_in, const float* far_in,
+                  const uint8_t* ray_mask, const uint8_t* msk, const uint8_t* bound_mask, const float* img, long long pix_stride,
+                  long long chan_stride, int H, int W, const double* draws, double subject_ratio, int N, int P,
+                  uint8_t* patch_masks, uint8_t* patch_masks_sub, float* target_patches, int32_t* xy_min, int32_t* counts,
+                  float* out_rgb, float* out_ray_o, float* out_ray_d, float* out_near, float* out_far, uint8_t* out_sub_mask,
+                  int64_t* out_select_inds, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c, "null argument");
+    TH_TRY(th_patch_check(H, W, N, P));
+    TH_REQUIRE(ray_o && ray_d && near_in && far_in && ray_mask && msk && bound_mask && img && draws, "null argument");
+    TH_REQUIRE(patch_masks && patch_masks_sub && target_patches && xy_min && counts && out_rgb && out_ray_o && out_ray_d &&
+                   out_near && out_far && out_sub_mask && out_select_inds && ws, "null argument");
+    return th_patch_rays_launch(ray_o, ray_d, near_in, far_in, ray_mask, msk, bound_mask, img, pix_stride, chan_stride, H, W, draws,
+                                subject_ratio, N, P, patch_masks, patch_masks_sub, target_patches, xy_min, counts, out_rgb,
+                                out_ray_o, out_ray_d, out_near, out_far, out_sub_mask, out_select_inds, ws, ws_bytes,
+                                (hipStream_t)stream);
+}
+
 size_t th_lpips_pack_bytes(void) { return th_lpips_pack_bytes_internal(); }
 
 int th_lpips_pack(th_ctx* c, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w,

@@ -561,5 +561,14 @@ int th_shade_mesh_launch(const float* verts, const float* normals, int nv, const
 int th_prep_views_launch(const uint8_t* img, const uint8_t* msk, int V, int H0, int W0, const float* K, const float* D, int n,
                          int mask_bkgd, int white_bkgd, const float* lut, float* out_img, uint8_t* out_msk, hipStream_t s);
 int th_prep_mask_launch(const uint8_t* a, const uint8_t* b, int V, int H0, int W0, int border, uint8_t* out, hipStream_t s);
+// k_patch.hip: the training targets of a step -- patch centres, windows and the gathered ray list of sample_ray_patch's train split
+size_t th_patch_ws(int H, int W);
+int th_patch_check(int H, int W, int N, int P);
+int th_patch_rays_launch(const float* ray_o, const float* ray_d, const float* near_in, const float* far_in, const uint8_t* ray_mask,
+                         const uint8_t* msk, const uint8_t* bound, const float* img, long long pix_stride, long long chan_stride,
+                         int H, int W, const double* draws, double subject_ratio, int N, int P, uint8_t* patch_masks,
+                         uint8_t* patch_masks_sub, float* target_patches, int32_t* xy_min, int32_t* counts, float* o_rgb,
+                         float* o_ray_o, float* o_ray_d, float* o_near, float* o_far, uint8_t* o_sub, int64_t* o_inds, void* ws,
+                         size_t ws_bytes, hipStream_t s);
 int th_segmean_masked_launch(const float* rows, int V, int width, const uint8_t* viz, int nv, const int32_t* off,
                              const int32_t* mem, int nc, float* out, hipStream_t s);

@@ -164,6 +164,9 @@ SYMBOLS = {
     "th_prep_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "th_prep_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "th_patch_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "th_patch_rays": (C.c_int, [C.c_void_p] * 9 + [C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int,
+                                C.c_int] + [C.c_void_p] * 13 + [C.c_size_t, C.c_void_p]),
     "th_lpips_pack_bytes": (C.c_size_t, []),
     "th_lpips_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "th_lpips_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
@@ -1215,6 +1218,48 @@ def bound_2d_mask(bounds, K, pose, H, W, device=None):
     mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
     _check(lib.th_bound_mask(ctx(dev), c2.ctypes.data_as(C.POINTER(C.c_int32)), H, W, _p(mask), _stream()))
     return mask
+
+
+def patch_rays(dense, msk, bound_mask, img, draws, subject_ratio, patch_size):
+    """th_patch_rays (K18): the train split of sample_ray_patch (if_nerf_data_utils.py:445-499) on the dense arrays of
+    ``gen_rays(..., compact=False)``.  ``dense``: {ray_o, ray_d [H*W,3], near, far [H*W], mask_at_box bool / uint8 [H*W]}; ``msk``,
+    ``bound_mask`` uint8 [H,W]; ``img`` float32 [H,W,3] or [3,H,W] (read in place through its strides); ``draws`` float64 [N,2] --
+    device tensors.  Returns the raw device outputs, the ray rows allocated at their bound N P^2: {patch_masks, patch_masks_sub
+    uint8 [N,P,P], target_patches [N,P,P,3], xy_min int32 [N,2], counts int32 [2,N] (candidate pixels, rays per patch), rgb, ray_o,
+    ray_d [N P^2,3], near, far [N P^2], sub_mask uint8 [N P^2], select_inds int64 [N P^2]}.  No host wait; sizes outside the
+    kernel's limits raise HipError before any launch."""
+    lib = load_library()
+    H, W = (int(n) for n in msk.shape)
+    dev = msk.device
+    N, P = int(draws.shape[0]), int(patch_size)
+    if img.dim() != 3 or img.dtype is not torch.float32:
+        raise ValueError(f"img must be float32 [H,W,3] or [3,H,W], got {img.dtype} {tuple(img.shape)}")
+    if tuple(img.shape) == (H, W, 3) and (img.stride(0) == W * img.stride(1) or H == 1):
+        pix, chan = img.stride(1), img.stride(2)
+    elif tuple(img.shape) == (3, H, W) and (img.stride(1) == W * img.stride(2) or H == 1):
+        pix, chan = img.stride(2), img.stride(0)
+    else:
+        raise ValueError(f"img {tuple(img.shape)} with strides {img.stride()}: [H,W,3] or [3,H,W] for H, W = {H}, {W}, its rows "
+                         "W pixels apart")
+    rm = dense["mask_at_box"]
+    rm = rm.view(torch.uint8) if rm.dtype is torch.bool else rm
+    ray_o, ray_d, near, far = (_f32(dense[k]) for k in ("ray_o", "ray_d", "near", "far"))
+    assert rm.numel() == H * W and ray_o.numel() == 3 * H * W and near.numel() == H * W and bound_mask.shape == msk.shape
+    assert msk.dtype is torch.uint8 and bound_mask.dtype is torch.uint8 and draws.dtype is torch.float64 and draws.shape[1] == 2
+    msk, bound_mask, rm, draws = msk.contiguous(), bound_mask.contiguous(), rm.contiguous(), draws.contiguous()
+    rows = max(N * P * P, 1)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    out = dict(patch_masks=e((N, P, P), torch.uint8), patch_masks_sub=e((N, P, P), torch.uint8),
+               target_patches=e((N, P, P, 3), torch.float32), xy_min=e((N, 2), torch.int32), counts=e((2, N), torch.int32),
+               rgb=e((rows, 3), torch.float32), ray_o=e((rows, 3), torch.float32), ray_d=e((rows, 3), torch.float32),
+               near=e((rows,), torch.float32), far=e((rows,), torch.float32), sub_mask=e((rows,), torch.uint8),
+               select_inds=e((rows,), torch.int64))
+    ws = _ws(lib.th_patch_workspace_bytes(H, W), dev)
+    _check(lib.th_patch_rays(ctx(dev), _p(ray_o), _p(ray_d), _p(near), _p(far), _p(rm), _p(msk), _p(bound_mask), _p(img), pix, chan,
+                             H, W, _p(draws), float(subject_ratio), N, P, *(_p(out[k]) for k in (
+                                 "patch_masks", "patch_masks_sub", "target_patches", "xy_min", "counts", "rgb", "ray_o", "ray_d",
+                                 "near", "far", "sub_mask", "select_inds")), _p(ws), ws.numel(), _stream()))
+    return out
 
 
 def ssim(a, b):

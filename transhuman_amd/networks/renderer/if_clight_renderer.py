@@ -13,7 +13,8 @@ What runs where
   * sampling, hull mask, compaction,
     DPaRF, pixel gather, MLP,
     compositing                        th_render_rays        (K1,K4,K5,K6,K7)
-Unlike the reference nothing here mutates ``batch`` (:459-462).
+Unlike the reference nothing here mutates ``batch`` (:459-462) -- with one documented exception: cfg.target_prep == "device"
+adds the training targets made on the device to it (``render``).
 """
 import os
 import sys
@@ -632,11 +633,21 @@ class Renderer:
         randomisations): the HIP kernels carry no autograd, so such a call is served by
         ``transhuman_amd.networks.autograd_path`` -- the same forward composed from differentiable torch operators on
         the batch's device.  It is a separate entry for training, not a fallback of the rendering hot path: without a GPU
-        this method raises like every other."""
+        this method raises like every other.
+        cfg.target_prep == "device": a training call whose batch has no ``ray_o`` gets its rays and patch targets made on the
+        device from the target view (transhuman_amd.train_targets.add_targets, K18); they are ADDED TO ``batch`` -- the one
+        exception to "nothing here mutates batch", because the trainer reads them from it after this returns."""
         cfg = get_cfg()
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.net.parameters())
         randomised = (float(getattr(cfg, "perturb", 0.0)) > 0.0 and self.net.training) or \
             float(getattr(cfg, "raw_noise_std", 0.0)) > 0.0
+        target_prep = cfg_get("target_prep", "batch")
+        if target_prep != "batch":
+            if target_prep != "device":
+                raise ValueError(f'cfg.target_prep is {target_prep!r}: "batch" or "device"')
+            if wants_grad or randomised:
+                from transhuman_amd import train_targets
+                train_targets.add_targets(batch)
         if wants_grad or randomised:
             if not batch["ray_o"].is_cuda:
                 raise hip.HipError("Renderer.render needs the batch on an MI355X (there is no CPU path)")
