@@ -341,6 +341,18 @@ size_t th_vit_workspace_bytes(int V, int N, int dim, int heads);
 int th_vit_forward(th_ctx* ctx, const float* x, const float* pe, int V, int N, float* out,
                    void* workspace, size_t workspace_bytes, th_stream stream);
 
+/* The attention of one TransHE layer on its own (addition, ABI 12; for tests: it feeds the two attention kernels chosen
+ * q, k, v).  qkv fp32 [V, N, 3 dim] with column = which dim + head 64 + d (the rows the qkv layer writes), dim = heads 64;
+ * out fp32 [V, N, dim] = softmax(q k^T 0.125) v per (view, head).  Runs the K / V^T operand split and then one attention
+ * kernel, through the launch code th_vit_forward runs: form 0 = the forward's own choice (N > 700: attn3_kernel, else
+ * attn2_kernel), 2 / 3 = attn2_kernel / attn3_kernel at any N; anything else is an argument error.  The result does not
+ * depend on what the workspace held.  Operand range: |q|, |k|, |v| < 65504; fp32-class (hi + lo to 2^-22) from 2^-3 up,
+ * an absolute 2^-25 per operand below.  Limits: 1 <= V <= 65535, 1 <= N <= 2^24, 1 <= heads <= 1024; qkv, out and the
+ * workspace 16-byte aligned.  th_attention_workspace_bytes is 0 for a shape outside them. */
+size_t th_attention_workspace_bytes(int V, int N, int heads);
+int th_attention(th_ctx* ctx, const float* qkv, int V, int N, int heads, int form, float* out, void* workspace,
+                 size_t workspace_bytes, th_stream stream);
+
 /* ---- K4: DPaRF encoding --------------------------------------------------- */
 /* Network.get_human_representation, cross_transformer.py:158-205.
  * pts_smpl [P,3]; centres [N_c,3]; rot [N_c,9]; tokens [V,N_c,192];

@@ -209,6 +209,19 @@ def segment_mean(src, offsets, members):
 # ---------------------------------------------------------------------------
 # a-6  TransHE  lib/networks/vision_transformer.py:257-383
 # ---------------------------------------------------------------------------
+def attention(qkv, heads):
+    """Attention.forward, :271-278, on the output of the fused qkv layer: qkv [V,N,3C] with column = which C + head hd + d
+    -> [V,N,C] (dtype kept: float64 in, float64 out)."""
+    V, N, C3 = qkv.shape
+    C = C3 // 3
+    hd = C // heads
+    qkv = qkv.reshape(V, N, 3, heads, hd).permute(2, 0, 3, 1, 4)
+    q, k, v = qkv[0], qkv[1], qkv[2]
+    a = (q @ k.transpose(-2, -1)) * (hd ** -0.5)                   # :274
+    a = a.softmax(dim=-1)
+    return (a @ v).transpose(1, 2).reshape(V, N, C)
+
+
 def vit_forward(x, pe_xyz, sd, depth, prefix="ViT.", heads=3):
     """x [V,N,192] tokens; pe_xyz [V,N,3] normalised canonical centres."""
     V, N, C = x.shape
@@ -218,16 +231,11 @@ def vit_forward(x, pe_xyz, sd, depth, prefix="ViT.", heads=3):
     # the goldens (the reference imported on the host) pin the host's table -- the oracle may run on a device (tools/dense_tail.py)
     pe = pe_encode(pe_xyz.float().cpu().reshape(-1, 3), C // 6, include_input=False).view(V, N, C).to(x)
     x = x + pe                                                     # :366-367
-    hd = C // heads
     for i in range(depth):
         p = f"{prefix}blocks.{i}."
         y = F.layer_norm(x, (C,), sd[p + "norm1.weight"], sd[p + "norm1.bias"], 1e-6)
         qkv = F.linear(y, sd[p + "attn.qkv.weight"], sd[p + "attn.qkv.bias"])
-        qkv = qkv.reshape(V, N, 3, heads, hd).permute(2, 0, 3, 1, 4)
-        q, k, v = qkv[0], qkv[1], qkv[2]
-        a = (q @ k.transpose(-2, -1)) * (hd ** -0.5)               # :274
-        a = a.softmax(dim=-1)
-        y = (a @ v).transpose(1, 2).reshape(V, N, C)
+        y = attention(qkv, heads)
         y = F.linear(y, sd[p + "attn.proj.weight"], sd[p + "attn.proj.bias"])
         x = x + y
         y = F.layer_norm(x, (C,), sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-6)

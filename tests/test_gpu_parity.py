@@ -41,10 +41,12 @@ def cams_of(b, dev):
 
 # ---------------------------------------------------------------------------
 def test_linear_mfma_vs_torch(hip, gpu):
-    """the fp32 MFMA GEMM, asymmetric operands, ragged M/N/K, all epilogues"""
+    """the fp32 MFMA GEMM, asymmetric operands, ragged M/N/K, all epilogues; M = 8192 / 8193 / 8200: both sides of the switch
+    from 16-row to 64-row workgroups (the form TransHE's dense layers take above 8192 tokens), ragged last row block"""
     rs = np.random.RandomState(0)
+    big = tuple((M, K, N) for M in (8192, 8193, 8200) for (K, N) in ((192, 576), (768, 192), (283, 128)))
     for (M, K, N) in ((1, 4, 1), (63, 255, 256), (200, 283, 128), (129, 384, 384), (70, 768, 192), (33, 192, 576),
-                      (5, 128, 3)):
+                      (5, 128, 3)) + big:
         x = torch.from_numpy(rs.normal(size=(M, K)).astype(np.float32))
         w = torch.from_numpy(rs.normal(size=(N, K)).astype(np.float32) / np.sqrt(K))
         b = torch.from_numpy(rs.normal(size=(N,)).astype(np.float32))

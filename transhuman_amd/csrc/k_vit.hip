@@ -68,6 +68,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 typedef _Float16 at_h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 at_h4 __attribute__((ext_vector_type(4)));
 
+// Supported operand range.  hi + lo reproduces x to 2^-22 relative while lo is a NORMAL fp16 number, i.e. for
+// 2^-3 <= |x| < 65504 (above: hi overflows to inf).  Below 2^-3 lo is subnormal and the error of the pair is absolute, at most
+// 2^-25 per operand -- harmless for the probabilities (in [0, 1], summed against an fp32 row sum) and for q, k, v of the
+// magnitude of the product's own rows (max |q| ~ 6).  tests/test_gpu_vit.py holds both kernels to 4 x the error of an fp32
+// evaluation for v scaled by 2^-10 .. 2^10 and q 2^-4 with k 2^4; a CPU emulation of the scheme leaves that class at v 2^-14
+// (16 x the fp32 error) and at q 2^-8: operands that small are outside the supported range (scale them up first).
 __device__ __forceinline__ void at_split(float x, _Float16& hi, _Float16& lo) {
     hi = (_Float16)x;
     lo = (_Float16)(x - (float)hi);
@@ -433,6 +439,54 @@ __global__ __launch_bounds__(256) void zero16_kernel(uint4* __restrict__ p, long
         p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
+// few tokens: the register-fed form (more, shorter workgroups); many: the LDS-staged form (64 queries share every K / V
+// tile: a quarter of the L2 traffic, which is what bounds the register-fed form from N ~ 1000 on).
+// Measured ViT forward, N_c = 300 / 500 / 1500: 0.80 / 0.99 / 2.15 ms register-fed, 0.86 / 1.07 / 2.06 ms LDS-staged.
+// (transposed register-fed form, late round 2: 0.77 / 0.95 / 1.19 / 2.06 ms at N_c = 500 / 800 / 1000 / 1500 against 0.93 / 1.16 /
+// 1.27 / 1.76 ms LDS-staged)
+// (round 6: from N ~ 700 on the third form -- attn2's arithmetic on K / V^T tiles shared through LDS, attn3_kernel)
+static bool vit_attn_tile(int N) { return N > 700; }
+
+// "split + attention" of one layer, shared by th_vit_launch and th_attention_launch: qkv [V, N, 3 dim] -> Y [V, N, dim].
+// split: write the K / V^T operand planes from qkv here (false when the qkv GEMM's epilogue already did); tile: attn3_kernel.
+static void vit_split_attention(const float* qkv, int V, int N, int Npad, int dim, int heads, bool split, bool tile,
+                                _Float16* Kp, _Float16* Vp, float* Y, hipStream_t s) {
+    const float scale = 0.125f;   // head_dim ** -0.5
+    if (split) hipLaunchKernelGGL(kv_split_kernel, dim3(Npad / 64, heads, V), dim3(256), 0, s, qkv, N, Npad, dim, Kp, Vp);
+    if (tile) hipLaunchKernelGGL(attn3_kernel, dim3(th_cdiv(N, 64), heads, V), dim3(256), 0, s, qkv, Kp, Vp, N, Npad, dim, scale, Y);
+    else hipLaunchKernelGGL(attn2_kernel, dim3(th_cdiv(N, 16), heads, V), dim3(64), 0, s, qkv, Kp, Vp, N, Npad, dim, scale, Y);
+}
+
+static bool attn_shape_ok(int V, int N, int heads) {
+    return V > 0 && V <= 65535 && N > 0 && N <= (1 << 24) && heads > 0 && heads <= 1024;
+}
+
+// the split K / V^T planes of one layer (2 x [V][heads][2][Npad][64] halves); 0 for a shape th_attention refuses
+size_t th_attn_ws(int V, int N, int heads) {
+    if (!attn_shape_ok(V, N, heads)) return 0;
+    return 2 * th_align((size_t)V * heads * 2 * vit_npad(N) * 64 * sizeof(_Float16));
+}
+
+// The attention of one layer on its own (tests): kv_split_kernel, then the kernel th_vit_launch would pick (form 0) or a forced
+// one (2: attn2_kernel, 3: attn3_kernel).  Every plane element the attention kernels read is written by kv_split_kernel first.
+int th_attention_launch(const float* qkv, int V, int N, int heads, int form, float* out, void* ws, size_t ws_bytes,
+                        hipStream_t s) {
+    TH_REQUIRE(attn_shape_ok(V, N, heads), "th_attention: need 1 <= V <= 65535, 1 <= N <= 2^24, 1 <= heads <= 1024");
+    TH_REQUIRE(form == 0 || form == 2 || form == 3,
+               "th_attention: form must be 0 (the forward's own choice), 2 (attn2_kernel) or 3 (attn3_kernel)");
+    TH_REQUIRE(ws_bytes >= th_attn_ws(V, N, heads), "workspace too small");
+    TH_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)out) & 15) == 0, "qkv and out must be 16-byte aligned");
+    TH_REQUIRE((((uintptr_t)ws) & 15) == 0, "workspace must be 16-byte aligned");
+    ThArena ar(ws, ws_bytes);
+    const int Npad = vit_npad(N), dim = heads * 64;
+    _Float16* Kp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
+    _Float16* Vp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
+    TH_REQUIRE(Kp != nullptr && Vp != nullptr, "workspace too small");
+    vit_split_attention(qkv, V, N, Npad, dim, heads, true, form == 0 ? vit_attn_tile(N) : form == 3, Kp, Vp, out, s);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
 size_t th_vit_ws(int V, int N, int dim, int heads) {
     size_t T = (size_t)V * N;
     // X, Y, qkv / hidden, and the split K / V^T planes of one layer (2 x [V][heads][2][Npad][64] halves)
@@ -456,17 +510,10 @@ int th_vit_launch(const ThVitPacked& W, const float* x, const float* pe, int V, 
     _Float16* Kp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
     _Float16* Vp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
     TH_REQUIRE(Vp != nullptr, "workspace too small");
-    // few tokens: the register-fed form (more, shorter workgroups); many: the LDS-staged form (64 queries share every K / V
-    // tile: a quarter of the L2 traffic, which is what bounds the register-fed form from N ~ 1000 on).
-    // Measured ViT forward, N_c = 300 / 500 / 1500: 0.80 / 0.99 / 2.15 ms register-fed, 0.86 / 1.07 / 2.06 ms LDS-staged.
-    // (transposed register-fed form, late round 2: 0.77 / 0.95 / 1.19 / 2.06 ms at N_c = 500 / 800 / 1000 / 1500 against 0.93 / 1.16 /
-    // 1.27 / 1.76 ms LDS-staged)
-    // (round 6: from N ~ 700 on the third form -- attn2's arithmetic on K / V^T tiles shared through LDS, attn3_kernel)
-    const bool attn_tile = N > 700;
+    const bool attn_tile = vit_attn_tile(N);
     TH_REQUIRE(Q != nullptr, "workspace carve failed");
     long long n = (long long)T * dim;
     hipLaunchKernelGGL(add_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, x, pe, n, X);
-    const float scale = 0.125f;   // head_dim ** -0.5
     // the two pre-LayerNorms of a block run inside the GEMM that consumes them
     const bool fuse_ln = th_gemm_ln_ok(T, W.blocks[0].qkv) && th_gemm_ln_ok(T, W.blocks[0].fc1);
     // dense layers on the fp16-split MFMA path (th_gemm_h3)
@@ -492,10 +539,7 @@ int th_vit_launch(const ThVitPacked& W, const float* x, const float* pe, int V, 
             hipLaunchKernelGGL(layernorm_kernel, dim3(th_cdiv(T, 4)), dim3(256), 0, s, X, T, dim, B.ln1_w, B.ln1_b, 1e-6f, Y);
             TH_TRY(th_gemm(Y, dim, T, B.qkv, TH_ACT_NONE, Q, 3 * dim, s));
         }
-        if (!fuse_split)
-            hipLaunchKernelGGL(kv_split_kernel, dim3(Npad / 64, heads, V), dim3(256), 0, s, Q, N, Npad, dim, Kp, Vp);
-        if (attn_tile) hipLaunchKernelGGL(attn3_kernel, dim3(th_cdiv(N, 64), heads, V), dim3(256), 0, s, Q, Kp, Vp, N, Npad, dim, scale, Y);
-        else hipLaunchKernelGGL(attn2_kernel, dim3(th_cdiv(N, 16), heads, V), dim3(64), 0, s, Q, Kp, Vp, N, Npad, dim, scale, Y);
+        vit_split_attention(Q, V, N, Npad, dim, heads, !fuse_split, attn_tile, Kp, Vp, Y, s);
         if (h3) {
             TH_TRY(th_gemm_h3(Y, dim, T, B.proj, nullptr, nullptr, 0.f, TH_ACT_NONE | TH_GEMM_ACCUM, X, dim, range, s));
             TH_TRY(th_gemm_h3(X, dim, T, B.fc1, B.ln2_w, B.ln2_b, 1e-6f, TH_ACT_GELU, Q, 4 * dim, range, s));

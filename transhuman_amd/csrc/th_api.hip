@@ -619,6 +619,14 @@ int th_vit_forward(th_ctx* c, const float* x, const float* pe, int V, int N, flo
                          c->vit_mode >= 1);
 }
 
+size_t th_attention_workspace_bytes(int V, int N, int heads) { return th_attn_ws(V, N, heads); }
+
+int th_attention(th_ctx* c, const float* qkv, int V, int N, int heads, int form, float* out, void* ws, size_t ws_bytes,
+                 th_stream stream) {
+    TH_REQUIRE(c && qkv && out && ws, "null argument");
+    return th_attention_launch(qkv, V, N, heads, form, out, ws, ws_bytes, (hipStream_t)stream);
+}
+
 int th_dparf_encode(th_ctx* c, const float* pts, const int32_t* sel, int P, const float* centres, const float* rot,
                     const float* tokens, int V, int nc, float* out, th_stream stream) {
     TH_REQUIRE(c && pts && centres && rot && tokens && out, "null argument");

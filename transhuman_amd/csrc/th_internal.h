@@ -488,6 +488,10 @@ int th_view_embed_launch(const float* d, int R, int res, float* out, hipStream_t
 size_t th_vit_ws(int V, int N, int dim, int heads);
 int th_vit_launch(const ThVitPacked& W, const float* x, const float* pe, int V, int N, float* out, void* ws,
                   size_t ws_bytes, hipStream_t s, unsigned int* range = nullptr, bool allow_h3 = true);
+// one layer's attention on its own: kv_split_kernel + attn2_kernel / attn3_kernel through the helper th_vit_launch uses
+size_t th_attn_ws(int V, int N, int heads);
+int th_attention_launch(const float* qkv, int V, int N, int heads, int form, float* out, void* ws, size_t ws_bytes,
+                        hipStream_t s);
 
 // k_smpl.hip
 size_t th_smpl_ws(int nv);

@@ -121,6 +121,9 @@ SYMBOLS = {
     "th_vit_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "th_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p]),
+    "th_attention_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                               C.c_void_p]),
     "th_dparf_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "th_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -1017,6 +1020,20 @@ def vit_forward(vit, x, pe, graph=False, _checked=False):
     out = torch.empty_like(x)
     ws = _ws(lib.th_vit_workspace_bytes(V, N, D, vit.num_heads), x.device)
     _check(lib.th_vit_forward(ctx(x.device), _p(x), _p(pe), V, N, _p(out), _p(ws), ws.numel(), _stream()))
+    return out
+
+
+def attention(qkv, heads=3, form=0):
+    """th_attention: one TransHE layer's softmax(q k^T / 8) v on its own.  qkv [V, N, 3 * heads * 64] as the qkv layer
+    writes it -> [V, N, heads * 64].  form 0: the kernel the forward picks at this N; 2 / 3: attn2_kernel / attn3_kernel."""
+    lib = load_library()
+    qkv = _f32(qkv)
+    V, N, C3 = qkv.shape
+    if C3 != 3 * heads * 64:
+        raise ValueError(f"qkv has {C3} columns, {heads} heads of 64 need {3 * heads * 64}")
+    out = torch.empty((V, N, heads * 64), dtype=torch.float32, device=qkv.device)
+    ws = _ws(lib.th_attention_workspace_bytes(V, N, heads), qkv.device)
+    _check(lib.th_attention(ctx(qkv.device), _p(qkv), V, N, heads, int(form), _p(out), _p(ws), ws.numel(), _stream()))
     return out
 
 
