@@ -353,6 +353,23 @@ size_t th_attention_workspace_bytes(int V, int N, int heads);
 int th_attention(th_ctx* ctx, const float* qkv, int V, int N, int heads, int form, float* out, void* workspace,
                  size_t workspace_bytes, th_stream stream);
 
+/* The training form of that attention (addition, ABI 12).  th_attention_train is th_attention -- the same kernels, the same
+ * `form`, bit for bit the same `out` -- which also writes lse fp32 [V][heads][N]: each row's log-sum-exp, natural log, of the
+ * scaled logits q.k / 8.  th_attention_bwd takes qkv, that out and lse, and g_out fp32 [V, N, dim] (the gradient of the loss
+ * with respect to out) and writes g_qkv fp32 [V, N, 3 dim] in qkv's column layout (it feeds the qkv layer's backward as it
+ * is).  The probabilities are recomputed tile by tile from lse on fp32-input MFMA (no operand range); nothing N x N is
+ * stored; there are no atomics: two runs agree bit for bit.  lse only centres the exponent: the rows are renormalised by
+ * their own recomputed sums, and D = rowsum(g_out * out) is formed from the recomputed probabilities as well (out is
+ * required and checked like the others but not read).  At N = 1 the q and k blocks of g_qkv are exactly 0 and the v
+ * block is g_out.  Limits and refusals as th_attention: every pointer non-null and 16-byte aligned; the workspace queries
+ * are 0 for a shape outside the limits.  Neither result depends on what the workspace held. */
+size_t th_attention_train_workspace_bytes(int V, int N, int heads);
+int th_attention_train(th_ctx* ctx, const float* qkv, int V, int N, int heads, int form, float* out, float* lse,
+                       void* workspace, size_t workspace_bytes, th_stream stream);
+size_t th_attention_bwd_workspace_bytes(int V, int N, int heads);
+int th_attention_bwd(th_ctx* ctx, const float* qkv, const float* out, const float* lse, const float* g_out, int V, int N,
+                     int heads, float* g_qkv, void* workspace, size_t workspace_bytes, th_stream stream);
+
 /* ---- K4: DPaRF encoding --------------------------------------------------- */
 /* Network.get_human_representation, cross_transformer.py:158-205.
  * pts_smpl [P,3]; centres [N_c,3]; rot [N_c,9]; tokens [V,N_c,192];

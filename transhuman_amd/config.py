@@ -65,6 +65,10 @@ def _defaults():
         # the training entry (autograd_path.render): "torch" composes every stage from torch operators; "device" runs the token
         # blend, the pixel-aligned gather and the compositing through the HIP forwards with HIP adjoints (networks/train_ops.py)
         train_kernels="torch",
+        # the attention of TransHE's blocks in the training entry: "torch" builds q k^T, softmax and the product with v from torch
+        # operators (autograd keeps the [V,heads,N,N] probabilities of every layer); "device" runs the inference path's attention
+        # kernels with the HIP backward that recomputes them tile by tile (train_ops.AttentionFn)
+        train_attention="torch",
         # patch sampling of the training targets (train_or_eval.yaml:70-75)
         patch=SimpleNamespace(use_patch_sampling=True, sample_subject_ratio=0.8, N_patches=6, size=20),
         # where the training entry's rays and patch targets come from: "batch" (as the reference: its dataset samples them on the

@@ -149,9 +149,10 @@ __global__ __launch_bounds__(256) void kv_split_kernel(const float* __restrict__
 // 21.4 us per layer at N = 500; this form 16.6 us.  Splitting the keys of a query block over 4 waves with an LDS merge
 // of the partial (m, l, O^T) triples was measured again on this form: 17.7 us -- the launch is not bound by the length of
 // the per-wave chain.)
+template <bool LSE>
 __global__ __launch_bounds__(64) void attn2_kernel(const float* __restrict__ qkv, const _Float16* __restrict__ Kp,
                                                    const _Float16* __restrict__ Vp, int N, int Npad, int dim,
-                                                   float scale, float* __restrict__ out) {
+                                                   float scale, float* __restrict__ out, float* __restrict__ lse) {
     const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
     const int kbeg = 0, kend = N;
     const int head = blockIdx.y, view = blockIdx.z, heads = gridDim.y;
@@ -278,6 +279,10 @@ __global__ __launch_bounds__(64) void attn2_kernel(const float* __restrict__ qkv
         for (int j = 0; j < 4; ++j)
             *reinterpret_cast<float4*>(out + ((long long)view * N + qi) * dim + head * 64 + j * 16 + 4 * g) =
                 make_float4(oacc[j][0] * inv, oacc[j][1] * inv, oacc[j][2] * inv, oacc[j][3] * inv);
+        // training form: the row's log-sum-exp of the scaled logits (the four lanes g of a query hold the same value)
+        if constexpr (LSE) {
+            if (g == 0) lse[((long long)view * heads + head) * N + qi] = mrun + logf(lrun);
+        }
     }
 }
 
@@ -292,9 +297,10 @@ __global__ __launch_bounds__(64) void attn2_kernel(const float* __restrict__ qkv
 // 16 lanes a ds_read_b128 services per cycle (16 rows, two slot columns) then hit 16 different positions of the bank row
 // (LDS-DMA writes lane-linear, so the swizzle is applied to the SOURCE address a lane fetches).
 #define AT3_PLANE (64 * 128)           // bytes of one tile plane
+template <bool LSE>
 __global__ __launch_bounds__(256) void attn3_kernel(const float* __restrict__ qkv, const _Float16* __restrict__ Kp,
                                                     const _Float16* __restrict__ Vp, int N, int Npad, int dim,
-                                                    float scale, float* __restrict__ out) {
+                                                    float scale, float* __restrict__ out, float* __restrict__ lse) {
     __shared__ __attribute__((aligned(16))) char tiles[2][4 * AT3_PLANE];      // [buffer][K hi | K lo | V^T hi | V^T lo]
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -424,6 +430,10 @@ __global__ __launch_bounds__(256) void attn3_kernel(const float* __restrict__ qk
         for (int j = 0; j < 4; ++j)
             *reinterpret_cast<float4*>(out + ((long long)view * N + qi) * dim + head * 64 + j * 16 + 4 * g) =
                 make_float4(oacc[j][0] * inv, oacc[j][1] * inv, oacc[j][2] * inv, oacc[j][3] * inv);
+        // training form: the row's log-sum-exp of the scaled logits (the four lanes g of a query hold the same value)
+        if constexpr (LSE) {
+            if (g == 0) lse[((long long)view * heads + head) * N + qi] = mrun + logf(lrun);
+        }
     }
 }
 
@@ -447,14 +457,21 @@ __global__ __launch_bounds__(256) void zero16_kernel(uint4* __restrict__ p, long
 // (round 6: from N ~ 700 on the third form -- attn2's arithmetic on K / V^T tiles shared through LDS, attn3_kernel)
 static bool vit_attn_tile(int N) { return N > 700; }
 
-// "split + attention" of one layer, shared by th_vit_launch and th_attention_launch: qkv [V, N, 3 dim] -> Y [V, N, dim].
+// "split + attention" of one layer, shared by th_vit_launch, th_attention_launch and th_attention_train_launch:
+// qkv [V, N, 3 dim] -> Y [V, N, dim].
 // split: write the K / V^T operand planes from qkv here (false when the qkv GEMM's epilogue already did); tile: attn3_kernel.
+// lse: nullptr (inference: the kernels as they always were) or [V][heads][N], each row's m + log(l) -- the LSE = true
+// instantiations differ from the others by that one store.
 static void vit_split_attention(const float* qkv, int V, int N, int Npad, int dim, int heads, bool split, bool tile,
-                                _Float16* Kp, _Float16* Vp, float* Y, hipStream_t s) {
+                                _Float16* Kp, _Float16* Vp, float* Y, hipStream_t s, float* lse = nullptr) {
     const float scale = 0.125f;   // head_dim ** -0.5
     if (split) hipLaunchKernelGGL(kv_split_kernel, dim3(Npad / 64, heads, V), dim3(256), 0, s, qkv, N, Npad, dim, Kp, Vp);
-    if (tile) hipLaunchKernelGGL(attn3_kernel, dim3(th_cdiv(N, 64), heads, V), dim3(256), 0, s, qkv, Kp, Vp, N, Npad, dim, scale, Y);
-    else hipLaunchKernelGGL(attn2_kernel, dim3(th_cdiv(N, 16), heads, V), dim3(64), 0, s, qkv, Kp, Vp, N, Npad, dim, scale, Y);
+    const dim3 g3(th_cdiv(N, 64), heads, V), g2(th_cdiv(N, 16), heads, V);
+    float* none = nullptr;
+    if (tile && lse) hipLaunchKernelGGL(attn3_kernel<true>, g3, dim3(256), 0, s, qkv, Kp, Vp, N, Npad, dim, scale, Y, lse);
+    else if (tile) hipLaunchKernelGGL(attn3_kernel<false>, g3, dim3(256), 0, s, qkv, Kp, Vp, N, Npad, dim, scale, Y, none);
+    else if (lse) hipLaunchKernelGGL(attn2_kernel<true>, g2, dim3(64), 0, s, qkv, Kp, Vp, N, Npad, dim, scale, Y, lse);
+    else hipLaunchKernelGGL(attn2_kernel<false>, g2, dim3(64), 0, s, qkv, Kp, Vp, N, Npad, dim, scale, Y, none);
 }
 
 static bool attn_shape_ok(int V, int N, int heads) {
@@ -483,6 +500,26 @@ int th_attention_launch(const float* qkv, int V, int N, int heads, int form, flo
     _Float16* Vp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
     TH_REQUIRE(Kp != nullptr && Vp != nullptr, "workspace too small");
     vit_split_attention(qkv, V, N, Npad, dim, heads, true, form == 0 ? vit_attn_tile(N) : form == 3, Kp, Vp, out, s);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+// The training form of the same launch: also writes lse [V][heads][N] (k_vit_bwd.hip recomputes the probabilities from it).
+int th_attention_train_launch(const float* qkv, int V, int N, int heads, int form, float* out, float* lse, void* ws,
+                              size_t ws_bytes, hipStream_t s) {
+    TH_REQUIRE(attn_shape_ok(V, N, heads), "th_attention_train: need 1 <= V <= 65535, 1 <= N <= 2^24, 1 <= heads <= 1024");
+    TH_REQUIRE(form == 0 || form == 2 || form == 3,
+               "th_attention_train: form must be 0 (the forward's own choice), 2 (attn2_kernel) or 3 (attn3_kernel)");
+    TH_REQUIRE(ws_bytes >= th_attn_ws(V, N, heads), "workspace too small");
+    TH_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)lse) & 15) == 0,
+               "qkv, out and lse must be 16-byte aligned");
+    TH_REQUIRE((((uintptr_t)ws) & 15) == 0, "workspace must be 16-byte aligned");
+    ThArena ar(ws, ws_bytes);
+    const int Npad = vit_npad(N), dim = heads * 64;
+    _Float16* Kp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
+    _Float16* Vp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
+    TH_REQUIRE(Kp != nullptr && Vp != nullptr, "workspace too small");
+    vit_split_attention(qkv, V, N, Npad, dim, heads, true, form == 0 ? vit_attn_tile(N) : form == 3, Kp, Vp, out, s, lse);
     TH_LAUNCH_CHECK();
     return 0;
 }

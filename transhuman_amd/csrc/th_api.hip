@@ -627,6 +627,22 @@ int th_attention(th_ctx* c, const float* qkv, int V, int N, int heads, int form,
     return th_attention_launch(qkv, V, N, heads, form, out, ws, ws_bytes, (hipStream_t)stream);
 }
 
+size_t th_attention_train_workspace_bytes(int V, int N, int heads) { return th_attn_ws(V, N, heads); }
+
+int th_attention_train(th_ctx* c, const float* qkv, int V, int N, int heads, int form, float* out, float* lse, void* ws,
+                       size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && qkv && out && lse && ws, "null argument");
+    return th_attention_train_launch(qkv, V, N, heads, form, out, lse, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t th_attention_bwd_workspace_bytes(int V, int N, int heads) { return th_attn_bwd_ws(V, N, heads); }
+
+int th_attention_bwd(th_ctx* c, const float* qkv, const float* out, const float* lse, const float* g_out, int V, int N,
+                     int heads, float* g_qkv, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && qkv && out && lse && g_out && g_qkv && ws, "null argument");
+    return th_attention_bwd_launch(qkv, out, lse, g_out, V, N, heads, g_qkv, ws, ws_bytes, (hipStream_t)stream);
+}
+
 int th_dparf_encode(th_ctx* c, const float* pts, const int32_t* sel, int P, const float* centres, const float* rot,
                     const float* tokens, int V, int nc, float* out, th_stream stream) {
     TH_REQUIRE(c && pts && centres && rot && tokens && out, "null argument");

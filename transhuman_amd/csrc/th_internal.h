@@ -492,6 +492,13 @@ int th_vit_launch(const ThVitPacked& W, const float* x, const float* pe, int V, 
 size_t th_attn_ws(int V, int N, int heads);
 int th_attention_launch(const float* qkv, int V, int N, int heads, int form, float* out, void* ws, size_t ws_bytes,
                         hipStream_t s);
+// the training form: the same launch, which also writes each row's log-sum-exp lse [V][heads][N] (workspace: th_attn_ws)
+int th_attention_train_launch(const float* qkv, int V, int N, int heads, int form, float* out, float* lse, void* ws,
+                              size_t ws_bytes, hipStream_t s);
+// k_vit_bwd.hip: g_qkv [V, N, 3 dim] from qkv, out, lse and g_out [V, N, dim]
+size_t th_attn_bwd_ws(int V, int N, int heads);
+int th_attention_bwd_launch(const float* qkv, const float* out, const float* lse, const float* g_out, int V, int N, int heads,
+                            float* g_qkv, void* ws, size_t ws_bytes, hipStream_t s);
 
 // k_smpl.hip
 size_t th_smpl_ws(int nv);

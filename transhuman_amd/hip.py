@@ -124,6 +124,12 @@ SYMBOLS = {
     "th_attention_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "th_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_void_p]),
+    "th_attention_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_attention_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_attention_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_attention_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "th_dparf_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "th_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -1035,6 +1041,42 @@ def attention(qkv, heads=3, form=0):
     ws = _ws(lib.th_attention_workspace_bytes(V, N, heads), qkv.device)
     _check(lib.th_attention(ctx(qkv.device), _p(qkv), V, N, heads, int(form), _p(out), _p(ws), ws.numel(), _stream()))
     return out
+
+
+def _attn_dims(qkv, heads):
+    V, N, C3 = qkv.shape
+    if C3 != 3 * heads * 64:
+        raise ValueError(f"qkv has {C3} columns, {heads} heads of 64 need {3 * heads * 64}")
+    return V, N
+
+
+def attention_train(qkv, heads=3, form=0):
+    """th_attention_train: attention() (the same kernels, the same bits) that also returns each row's log-sum-exp of the
+    scaled logits -> (out [V, N, heads * 64], lse [V, heads, N]); what attention_bwd needs beside qkv."""
+    lib = load_library()
+    qkv = _f32(qkv)
+    V, N = _attn_dims(qkv, heads)
+    out = torch.empty((V, N, heads * 64), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((V, heads, N), dtype=torch.float32, device=qkv.device)
+    ws = _ws(lib.th_attention_train_workspace_bytes(V, N, heads), qkv.device)
+    _check(lib.th_attention_train(ctx(qkv.device), _p(qkv), V, N, heads, int(form), _p(out), _p(lse), _p(ws), ws.numel(),
+                                  _stream()))
+    return out, lse
+
+
+def attention_bwd(qkv, out, lse, g_out, heads=3):
+    """th_attention_bwd: the gradient of attention() with respect to qkv, in qkv's layout, from the forward's out and lse and
+    the gradient g_out [V, N, heads * 64] of its output.  Nothing N x N is stored; bit-identical from run to run."""
+    lib = load_library()
+    qkv, out, lse, g_out = _f32(qkv), _f32(out), _f32(lse), _f32(g_out)
+    V, N = _attn_dims(qkv, heads)
+    if tuple(out.shape) != (V, N, heads * 64) or tuple(g_out.shape) != (V, N, heads * 64) or tuple(lse.shape) != (V, heads, N):
+        raise ValueError(f"attention_bwd: out / g_out must be [{V}, {N}, {heads * 64}] and lse [{V}, {heads}, {N}]")
+    g_qkv = torch.empty_like(qkv)
+    ws = _ws(lib.th_attention_bwd_workspace_bytes(V, N, heads), qkv.device)
+    _check(lib.th_attention_bwd(ctx(qkv.device), _p(qkv), _p(out), _p(lse), _p(g_out), V, N, heads, _p(g_qkv), _p(ws),
+                                ws.numel(), _stream()))
+    return g_qkv
 
 
 def dparf_encode(pts_smpl, centres, rot, tokens, sel=None):

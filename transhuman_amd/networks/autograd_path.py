@@ -13,6 +13,11 @@ them from torch operators like everything else; "device" runs the token blend (K
 compositing (K7) through the HIP forwards with HIP adjoints (``train_ops``), once over all samples before
 the chunk loop.  The encoder, TransHE and the per-point network stay on torch autograd in both modes.
 
+``cfg.train_attention`` selects, independently, how the attention inside TransHE's blocks runs: "torch" (default) as three
+torch operators whose autograd keeps a [V, heads, N, N] probability tensor per layer; "device" through the attention kernels
+of the inference path with a HIP backward that recomputes the probabilities tile by tile (``train_ops.AttentionFn``,
+DESIGN.md "K3 training form").  TransHE's dense layers, LayerNorm and GELU stay on torch autograd either way.
+
 Pinned by ``oracle/gen_golden_train.py`` (the real reference imported in the survey container: outputs and parameter
 gradients of one training step's forward/backward on a synthetic patch -> ``tests/golden/g18_train_step.npz``) and
 ``tests/test_train_path.py``.  Every function cites the reference lines it follows.
@@ -100,16 +105,34 @@ def pooling_matrix(offsets, members, n_verts, device, dtype):
 
 
 # ---- TransHE -------------------------------------------------------------------------------------------------------------
-def vit_forward(vit, x, pe_xyz):
-    """VisionTransformer.forward (vision_transformer.py:257-307, :362-383), mask = None."""
+def _attention_mode(value):
+    mode = str(value)
+    if mode not in ("torch", "device"):
+        raise ValueError(f"cfg.train_attention must be 'torch' or 'device', not {mode!r}")
+    return mode
+
+
+def vit_forward(vit, x, pe_xyz, attention="torch"):
+    """VisionTransformer.forward (vision_transformer.py:257-307, :362-383), mask = None.  attention = "device": every block's
+    softmax(q k^T / 8) v through train_ops.AttentionFn (HIP forward and backward, no N x N tensor) instead of torch operators."""
+    attention = _attention_mode(attention)
+    if attention == "device":
+        from .. import hip
+        from . import train_ops
+        if not x.is_cuda:
+            raise hip.HipError("cfg.train_attention = 'device' needs the tokens on an MI355X (the HIP kernels have no CPU "
+                               "form); use 'torch' for a CPU batch")
     x = x + vit.get_PE(pe_xyz).to(x.dtype)
     V, N, C = x.shape
     h = vit.num_heads
     for blk in vit.blocks:
         y = blk.norm1(x)
-        qkv = blk.attn.qkv(y).reshape(V, N, 3, h, C // h).permute(2, 0, 3, 1, 4)
-        a = (qkv[0] @ qkv[1].transpose(-2, -1)) * blk.attn.scale
-        y = (a.softmax(dim=-1) @ qkv[2]).transpose(1, 2).reshape(V, N, C)
+        if attention == "device":
+            y = train_ops.AttentionFn.apply(blk.attn.qkv(y).contiguous(), h)
+        else:
+            qkv = blk.attn.qkv(y).reshape(V, N, 3, h, C // h).permute(2, 0, 3, 1, 4)
+            a = (qkv[0] @ qkv[1].transpose(-2, -1)) * blk.attn.scale
+            y = (a.softmax(dim=-1) @ qkv[2]).transpose(1, 2).reshape(V, N, C)
         x = x + blk.attn.proj(y)
         x = x + blk.mlp.fc2(F.gelu(blk.mlp.fc1(blk.norm2(x))))
     return vit.norm(x)
@@ -181,6 +204,11 @@ def render(renderer, batch, chunk=32768):
         from .. import hip
         raise hip.HipError("cfg.train_kernels = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
                            "use 'torch' for a CPU batch")
+    attention = _attention_mode(getattr(cfg, "train_attention", "torch"))
+    if attention == "device" and not ray_o.is_cuda:
+        from .. import hip
+        raise hip.HipError("cfg.train_attention = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
+                           "use 'torch' for a CPU batch")
     near, far = batch["near"][0], batch["far"][0]
     dev = ray_o.device
     S = int(cfg.N_samples)
@@ -200,7 +228,8 @@ def render(renderer, batch, chunk=32768):
         painted = painted * batch["input_vizmaps"][0][0][..., None].to(painted.dtype)              # :181-182
     nv = verts_in.shape[0]
     M = pooling_matrix_cached(renderer, nv, dev, torch.float32)
-    tokens = vit_forward(net.ViT, torch.einsum("cn,vnd->vcd", M, painted), renderer._pe_norm(V, dev))
+    tokens = vit_forward(net.ViT, torch.einsum("cn,vnd->vcd", M, painted), renderer._pe_norm(V, dev),
+                         attention=attention)
     centres = M @ batch["tar_smpl_vertice_smplcoord"][0]
     blend = batch["blend_mtx"][0]
     M64 = pooling_matrix_cached(renderer, nv, dev, blend.dtype)        # (float64 mean, :544)

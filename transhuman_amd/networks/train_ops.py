@@ -1,4 +1,4 @@
-"""The three non-GEMM stages around the per-point network as autograd Functions on the device (K17).
+"""The three non-GEMM stages around the per-point network, and TransHE's attention, as autograd Functions on the device (K17).
 
 ``cfg.train_kernels = "device"`` makes ``autograd_path.render`` run the token blend (K4), the pixel-aligned gather (K5) and
 the compositing (K7) through the HIP forwards that the inference paths use, with their adjoints as HIP kernels
@@ -7,6 +7,10 @@ the compositing (K7) through the HIP forwards that the inference paths use, with
     HumanRepresentationFn   tokens [V,N_c,192]   -> rows [P,V,256]     gradient: tokens
     PixelGatherFn           map    [V,H,W,C]     -> rows [P,V,C]       gradient: map
     CompositeFn             raw    [R,S,4]       -> rgb, acc, depth    gradient: raw
+
+``cfg.train_attention = "device"`` does the same for the attention of every TransHE block:
+
+    AttentionFn             qkv    [V,N,3 C]     -> [V,N,C]            gradient: qkv         (k_vit.hip / k_vit_bwd.hip)
 
 K4 and K5 are linear in the tensor that gets the gradient, so nothing of the forward is kept for the backward but the
 geometry (points, centres, cameras): the [P,7,255] blend operands and the per-chunk map-sized gradients of the torch
@@ -90,6 +94,27 @@ class CompositeFn(torch.autograd.Function):
             None, None, None
 
 
+class AttentionFn(torch.autograd.Function):
+    """Attention.forward (vision_transformer.py:271-278) on the fused qkv layer's output: qkv [V,N,3 C] -> [V,N,C], through the
+    attention kernels of the inference path (K3) with the backward of k_vit_bwd.hip.  Kept for the backward: qkv, the output
+    and the rows' log-sum-exp [V,heads,N] -- nothing N x N, where torch autograd keeps the [V,heads,N,N] probabilities."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        _on_device("AttentionFn", qkv)
+        if qkv.dtype is not torch.float32 or not qkv.is_contiguous():
+            raise ValueError("AttentionFn: qkv must be a contiguous float32 [V,N,3 C] tensor")
+        out, lse = hip.attention_train(qkv.detach(), int(heads))
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.heads = int(heads)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qkv, out, lse = ctx.saved_tensors
+        return hip.attention_bwd(qkv, out, lse, grad_out.contiguous(), ctx.heads), None
+
+
 # ---- float64 restatements ---------------------------------------------------------------------------------------------------
 def _np64(x):
     return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
@@ -158,3 +183,27 @@ def composite_grad_oracle(raw, z, ray_d, white_bkgd, g_rgb, g_acc, g_depth):
     out[..., :3] = w[..., None] * g_rgb[:, None, :] * c * (1.0 - c)
     out[..., 3] = np.where(raw[..., 3] > 0.0, g_a * e * delta, 0.0)
     return out
+
+
+def attention_grad_oracle(qkv, g_out, heads):
+    """adjoint of Attention.forward (vision_transformer.py:271-278; head_dim 64, s = 1/8) with respect to the fused qkv rows:
+    qkv [V,N,3 C], g_out [V,N,C] -> (g_qkv [V,N,3 C], lse [V,heads,N]) in float64; the formulas of k_vit_bwd.hip"""
+    x, g = _np64(qkv), _np64(g_out)
+    V, N, C3 = x.shape
+    C = C3 // 3
+    hd = C // heads
+    s = hd ** -0.5
+    q, k, v = (x.reshape(V, N, 3, heads, hd).transpose(2, 0, 3, 1, 4)[i] for i in range(3))      # [V,heads,N,hd]
+    go = g.reshape(V, N, heads, hd).transpose(0, 2, 1, 3)
+    S = s * np.einsum("vhid,vhjd->vhij", q, k)
+    m = S.max(-1, keepdims=True)
+    lse = (m + np.log(np.exp(S - m).sum(-1, keepdims=True)))[..., 0]
+    P = np.exp(S - lse[..., None])
+    out = np.einsum("vhij,vhjd->vhid", P, v)
+    D = (go * out).sum(-1)
+    dV = np.einsum("vhij,vhid->vhjd", P, go)
+    dS = P * (np.einsum("vhid,vhjd->vhij", go, v) - D[..., None])
+    dQ = s * np.einsum("vhij,vhjd->vhid", dS, k)
+    dK = s * np.einsum("vhij,vhid->vhjd", dS, q)
+    g_qkv = np.stack([dQ, dK, dV], 0).transpose(1, 3, 0, 2, 4).reshape(V, N, C3)
+    return g_qkv, lse
