@@ -18,6 +18,7 @@ import torch
 from transhuman_amd import synth
 from transhuman_amd.config import get_cfg
 from transhuman_amd.networks import autograd_path, train_ops
+from dparf_cases import dparf_forward_weights
 from util import GOLD, can64, synth_assign, SIGMA_BIAS
 
 pytestmark = pytest.mark.gpu
@@ -64,23 +65,10 @@ def _dparf_case(P, nc, V, seed, near_one=False):
     return [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) for a in (pts, cen, rot, g)]
 
 
-def _dparf_forward_weights(hip, pts, cen, rot):
-    """W[p,c]: what the forward kernel selected and weighted, read with one-hot tokens in passes of 192 centres"""
-    P, nc = pts.shape[0], cen.shape[0]
-    Wm = torch.zeros((P, nc), dtype=torch.float64)
-    for c0 in range(0, nc, 192):
-        n = min(192, nc - c0)
-        tok = torch.zeros((1, nc, 192), device=pts.device)
-        tok[0, c0 + torch.arange(n), torch.arange(n)] = 1.0
-        Wm[:, c0:c0 + n] = hip.dparf_encode(pts, cen, rot, tok)[:, 0, :n].double().cpu()
-    assert ((Wm != 0).sum(1) == 7).all() and float((Wm.sum(1) - 1).abs().max()) < 1e-6
-    return Wm.numpy()
-
-
 @pytest.mark.parametrize("P,nc,V,near_one", [(1, 7, 1, False), (129, 7, 3, False), (3000, 300, 3, False), (3000, 300, 3, True)])
 def test_dparf_backward_is_the_adjoint_of_the_forward(hip, gpu, P, nc, V, near_one):
     pts, cen, rot, g = (t.to(gpu) for t in _dparf_case(P, nc, V, seed=P + nc, near_one=near_one))
-    Wm = _dparf_forward_weights(hip, pts, cen, rot)
+    Wm = dparf_forward_weights(hip, pts, cen, rot)
     if near_one:
         assert ((Wm != 0).sum(0) == P).sum() == 7                  # seven lists of length P: the chunk split
     out = torch.full((V, nc, 192), float("nan"), device=gpu)       # the kernel writes every element

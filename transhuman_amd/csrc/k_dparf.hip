@@ -54,7 +54,8 @@ typedef _Float16 dp_h4 __attribute__((ext_vector_type(4)));
 // sin(a) for |a| < 2^12 (the PE arguments are fma(x, pi*2^k, phase), k <= 9, |x| of the order of the body size).
 // Three-constant Cody-Waite reduction by 2*pi (every fma below is exact or rounds once at the 2^-22 level), then
 // the hardware sine of the reduced angle.  Absolute error measured against the fp64 sine of the same fp32
-// argument: < 1e-6 (tests/test_gpu_parity.py::test_dparf_vs_golden holds the channel tolerance 1e-4); about a
+// argument: < 1e-6 (tests/test_gpu_dparf_knn.py::test_full_scan_rows_match_the_float64_oracle holds every PE channel to
+// the rounding of its argument + 2e-6, its case `edge` with |a| just under 2^12 at octave 9); about a
 // fifth of the instructions of the full-range library sinf, which made the PE channels the largest VALU block
 // of this kernel.
 __device__ __forceinline__ float dp_sin(float a) {
