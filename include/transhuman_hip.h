@@ -370,6 +370,44 @@ size_t th_attention_bwd_workspace_bytes(int V, int N, int heads);
 int th_attention_bwd(th_ctx* ctx, const float* qkv, const float* out, const float* lse, const float* g_out, int V, int N,
                      int heads, float* g_qkv, void* workspace, size_t workspace_bytes, th_stream stream);
 
+/* The training form of TransHE's dense layers, LayerNorm and GELU (addition, ABI 12; k_vit_dense_bwd.hip).  Plain fp32 on the
+ * MFMA pipe (v_mfma_f32_16x16x4_f32: an fp32 fmaf chain), no fp16 split and so no operand range.  A layer is
+ * C[M, out_f] = op(A) W^T + b with W fp32 [out_f, in_f] row-major (th_linear; b may be NULL) and the operand form
+ *     form 0: op(A) = A                      A [M, in_f]
+ *     form 1: op(A) = LayerNorm(A; ln_w, ln_b, ln_eps) over the row (ln_w, ln_b fp32 [in_f]; in_f <= 256, M <= 8192)
+ *     form 2: op(A) = gelu(A), exact erf     (ln_w, ln_b ignored in forms 0 and 2)
+ * op(A) is never stored: the backward recomputes it from A on the operand's way into the matrix unit, for form 1 with the
+ * row statistics of the forward bit for bit.  Shapes: M >= 1, in_f and out_f multiples of 16, leading dimensions in floats,
+ * >= the row and multiples of 4, every pointer 16-byte aligned; anything else is refused with a message (th_last_error)
+ * and nothing is launched; the workspace queries return 0 for a refused shape.
+ *
+ * th_linear_train_forward writes C.  th_linear_bwd takes g_C [M, out_f] = dL/dC and writes
+ *     g_W [out_f, in_f] = sum_m g_C[m, :]^T op(A)[m, :]  and  g_b [out_f] = sum_m g_C[m, :]   (g_b may be NULL),
+ *     g_A [M, in_f] = dL/dA, THROUGH the operand form (form 1: the LayerNorm backward, form 2: * gelu'(A)); NULL skips it,
+ *     form 1 with g_A: g_ln_w [in_f] = sum_m g_op xhat and g_ln_b [in_f] = sum_m g_op, where g_op = g_C W.
+ * The sums over m are taken in th_wgrad_chunk_rows() (LayerNorm parameters: th_layernorm_bwd_chunk_rows()) row chunks whose
+ * partial results go to the workspace and are added in chunk order: no atomics, two runs agree bit for bit, and the result
+ * does not depend on what the workspace held.  g_A must not overlap A or g_C.
+ *
+ * th_layernorm_forward / th_layernorm_bwd are LayerNorm on its own (dim a multiple of 16 up to 256; the statistics rule of
+ * form 1): out = (x - mean) rstd w + b;  g_x = rstd (g w - mean(g w) - xhat mean(g w xhat)), g_w = sum_m g xhat,
+ * g_b = sum_m g.  g_x may be g itself (in place). */
+int    th_wgrad_chunk_rows(void);
+int    th_layernorm_bwd_chunk_rows(void);
+size_t th_linear_train_workspace_bytes(int M, int out_f, int in_f, int form);
+int th_linear_train_forward(th_ctx* ctx, const float* A, int lda, int M, int form, const float* ln_w, const float* ln_b,
+                            float ln_eps, const th_linear* lin, float* C, int ldc, void* workspace, size_t workspace_bytes,
+                            th_stream stream);
+size_t th_linear_bwd_workspace_bytes(int M, int out_f, int in_f, int form);
+int th_linear_bwd(th_ctx* ctx, const float* A, int lda, int M, int form, const float* ln_w, const float* ln_b, float ln_eps,
+                  const th_linear* lin, const float* g_C, int ldg, float* g_A, int ldga, float* g_W, float* g_b,
+                  float* g_ln_w, float* g_ln_b, void* workspace, size_t workspace_bytes, th_stream stream);
+int th_layernorm_forward(th_ctx* ctx, const float* x, int ldx, int M, int dim, const float* w, const float* b, float eps,
+                         float* out, int ldo, th_stream stream);
+size_t th_layernorm_bwd_workspace_bytes(int M, int dim);
+int th_layernorm_bwd(th_ctx* ctx, const float* x, int ldx, int M, int dim, const float* w, float eps, const float* g, int ldg,
+                     float* g_x, int ldgx, float* g_w, float* g_b, void* workspace, size_t workspace_bytes, th_stream stream);
+
 /* ---- K4: DPaRF encoding --------------------------------------------------- */
 /* Network.get_human_representation, cross_transformer.py:158-205.
  * pts_smpl [P,3]; centres [N_c,3]; rot [N_c,9]; tokens [V,N_c,192];

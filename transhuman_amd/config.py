@@ -69,6 +69,10 @@ def _defaults():
         # operators (autograd keeps the [V,heads,N,N] probabilities of every layer); "device" runs the inference path's attention
         # kernels with the HIP backward that recomputes them tile by tile (train_ops.AttentionFn)
         train_attention="torch",
+        # everything else inside TransHE's blocks in the training entry -- the dense layers, LayerNorm and GELU: "torch" runs the
+        # torch modules under torch autograd; "device" runs the fp32 MFMA GEMMs with HIP backwards that recompute LN(x) and gelu(u)
+        # and add their partial sums in a fixed order (train_ops.NormLinearFn / LinearFn / GeluLinearFn / LayerNormFn)
+        train_vit_dense="torch",
         # patch sampling of the training targets (train_or_eval.yaml:70-75)
         patch=SimpleNamespace(use_patch_sampling=True, sample_subject_ratio=0.8, N_patches=6, size=20),
         # where the training entry's rays and patch targets come from: "batch" (as the reference: its dataset samples them on the

@@ -130,6 +130,20 @@ SYMBOLS = {
     "th_attention_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "th_attention_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_wgrad_chunk_rows": (C.c_int, []),
+    "th_layernorm_bwd_chunk_rows": (C.c_int, []),
+    "th_linear_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "th_linear_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                          C.POINTER(ThLinear), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_linear_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "th_linear_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                C.POINTER(ThLinear), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_layernorm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                       C.c_void_p, C.c_int, C.c_void_p]),
+    "th_layernorm_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "th_layernorm_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
+                                   C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "th_dparf_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "th_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -1077,6 +1091,112 @@ def attention_bwd(qkv, out, lse, g_out, heads=3):
     _check(lib.th_attention_bwd(ctx(qkv.device), _p(qkv), _p(out), _p(lse), _p(g_out), V, N, heads, _p(g_qkv), _p(ws),
                                 ws.numel(), _stream()))
     return g_qkv
+
+
+OPERAND_PLAIN, OPERAND_LN, OPERAND_GELU = 0, 1, 2      # the operand forms of th_linear_train_forward / th_linear_bwd
+
+
+def wgrad_chunk_rows():
+    """rows per partial tile of the weight-gradient kernel (the chunks are added in order)"""
+    return int(load_library().th_wgrad_chunk_rows())
+
+
+def layernorm_bwd_chunk_rows():
+    return int(load_library().th_layernorm_bwd_chunk_rows())
+
+
+def _train_rows(fn, t, cols=None):
+    """a contiguous fp32 device tensor [..., cols] as rows [M, cols] (the training entries convert nothing silently)"""
+    if not t.is_cuda:
+        raise HipError(f"{fn} needs its tensors on an MI355X (there is no CPU path)")
+    if t.dtype is not torch.float32 or not t.is_contiguous() or t.dim() < 1:
+        raise ValueError(f"{fn}: tensors must be contiguous float32")
+    if cols is not None and t.shape[-1] != cols:
+        raise ValueError(f"{fn}: expected rows of {cols} values, got {t.shape[-1]}")
+    return t.detach().reshape(-1, t.shape[-1])
+
+
+def _train_vec(fn, t, n):
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise HipError(f"{fn} needs its tensors on an MI355X (there is no CPU path)")
+    if t.dtype is not torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n,):
+        raise ValueError(f"{fn}: expected a contiguous float32 vector of {n} values")
+    return t.detach()
+
+
+def linear_train_forward(a, weight, bias, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1e-6):
+    """th_linear_train_forward: op(a) W^T + b with op = identity / LayerNorm / gelu (form), a [..., in] -> [..., out]"""
+    lib = load_library()
+    fn = "linear_train_forward"
+    w = _train_rows(fn, weight)
+    out_f, in_f = w.shape
+    a2 = _train_rows(fn, a, in_f)
+    b = _train_vec(fn, bias, out_f)
+    lw, lb = _train_vec(fn, ln_w, in_f), _train_vec(fn, ln_b, in_f)
+    M = a2.shape[0]
+    lin = ThLinear(_p(w), _p(b), out_f, in_f)
+    out = torch.empty((*a.shape[:-1], out_f), dtype=torch.float32, device=a.device)
+    ws = _ws(lib.th_linear_train_workspace_bytes(M, out_f, in_f, int(form)), a.device)
+    _check(lib.th_linear_train_forward(ctx(a.device), _p(a2), in_f, M, int(form), _p(lw), _p(lb), float(eps), C.byref(lin),
+                                       _p(out), out_f, _p(ws), ws.numel(), _stream()))
+    return out
+
+
+def linear_bwd(a, weight, g_out, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1e-6, need_input=True, need_bias=True):
+    """th_linear_bwd: the gradients of linear_train_forward from g_out [..., out] -> (g_a or None, g_W, g_b or None, g_ln_w,
+    g_ln_b); the last two are None unless form = OPERAND_LN with need_input.  g_a is the gradient of `a` itself (through the
+    LayerNorm / the gelu).  Bit-identical from run to run."""
+    lib = load_library()
+    fn = "linear_bwd"
+    w = _train_rows(fn, weight)
+    out_f, in_f = w.shape
+    a2, g2 = _train_rows(fn, a, in_f), _train_rows(fn, g_out, out_f)
+    if a2.shape[0] != g2.shape[0]:
+        raise ValueError(f"{fn}: {a2.shape[0]} operand rows, {g2.shape[0]} gradient rows")
+    lw, lb = _train_vec(fn, ln_w, in_f), _train_vec(fn, ln_b, in_f)
+    M = a2.shape[0]
+    lin = ThLinear(_p(w), None, out_f, in_f)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=a.device)
+    g_a = new(*a.shape) if need_input else None
+    g_w = new(out_f, in_f)
+    g_b = new(out_f) if need_bias else None
+    ln = need_input and int(form) == OPERAND_LN
+    g_lw, g_lb = (new(in_f), new(in_f)) if ln else (None, None)
+    ws = _ws(lib.th_linear_bwd_workspace_bytes(M, out_f, in_f, int(form)), a.device)
+    _check(lib.th_linear_bwd(ctx(a.device), _p(a2), in_f, M, int(form), _p(lw), _p(lb), float(eps), C.byref(lin), _p(g2), out_f,
+                             _p(g_a), in_f, _p(g_w), _p(g_b), _p(g_lw), _p(g_lb), _p(ws), ws.numel(), _stream()))
+    return g_a, g_w, g_b, g_lw, g_lb
+
+
+def layernorm_train_forward(x, weight, bias, eps=1e-6):
+    """th_layernorm_forward: LayerNorm over the last dimension with the statistics rule of the LayerNorm-fused GEMM"""
+    lib = load_library()
+    fn = "layernorm_train_forward"
+    dim = x.shape[-1]
+    x2, w, b = _train_rows(fn, x), _train_vec(fn, weight, dim), _train_vec(fn, bias, dim)
+    out = torch.empty_like(x2)
+    _check(lib.th_layernorm_forward(ctx(x.device), _p(x2), dim, x2.shape[0], dim, _p(w), _p(b), float(eps), _p(out), dim,
+                                    _stream()))
+    return out.reshape(x.shape)
+
+
+def layernorm_bwd(x, weight, g_out, eps=1e-6):
+    """th_layernorm_bwd -> (g_x, g_w, g_b); bit-identical from run to run"""
+    lib = load_library()
+    fn = "layernorm_bwd"
+    dim = x.shape[-1]
+    x2, g2, w = _train_rows(fn, x), _train_rows(fn, g_out, dim), _train_vec(fn, weight, dim)
+    if x2.shape != g2.shape:
+        raise ValueError(f"{fn}: x and g_out differ in shape")
+    M = x2.shape[0]
+    g_x = torch.empty_like(x2)
+    g_w, g_b = (torch.empty((dim,), dtype=torch.float32, device=x.device) for _ in range(2))
+    ws = _ws(lib.th_layernorm_bwd_workspace_bytes(M, dim), x.device)
+    _check(lib.th_layernorm_bwd(ctx(x.device), _p(x2), dim, M, dim, _p(w), float(eps), _p(g2), dim, _p(g_x), dim, _p(g_w),
+                                _p(g_b), _p(ws), ws.numel(), _stream()))
+    return g_x.reshape(x.shape), g_w, g_b
 
 
 def dparf_encode(pts_smpl, centres, rot, tokens, sel=None):

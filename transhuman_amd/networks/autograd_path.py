@@ -11,12 +11,18 @@ rendering hot path and not a fallback of it -- inference calls (``render_fast``,
 ``cfg.train_kernels`` selects how the three non-GEMM stages around the per-point network run: "torch" (default) composes
 them from torch operators like everything else; "device" runs the token blend (K4), the pixel-aligned gather (K5) and the
 compositing (K7) through the HIP forwards with HIP adjoints (``train_ops``), once over all samples before
-the chunk loop.  The encoder, TransHE and the per-point network stay on torch autograd in both modes.
+the chunk loop.  The encoder and the per-point network stay on torch autograd in both modes.
 
 ``cfg.train_attention`` selects, independently, how the attention inside TransHE's blocks runs: "torch" (default) as three
 torch operators whose autograd keeps a [V, heads, N, N] probability tensor per layer; "device" through the attention kernels
 of the inference path with a HIP backward that recomputes the probabilities tile by tile (``train_ops.AttentionFn``,
-DESIGN.md "K3 training form").  TransHE's dense layers, LayerNorm and GELU stay on torch autograd either way.
+DESIGN.md "K3 training form").
+
+``cfg.train_vit_dense`` selects, independently again, how everything else inside TransHE runs -- the dense layers, LayerNorm
+and GELU: "torch" (default) as torch modules under torch autograd; "device" through the fp32 MFMA GEMMs of the inference
+path with HIP backwards that recompute LN(x) and gelu(u) instead of keeping them and add their partial sums in a fixed order
+(``train_ops.NormLinearFn`` / ``LinearFn`` / ``GeluLinearFn`` / ``LayerNormFn``): with both switches on "device" TransHE's
+gradient is bit-identical from run to run.  The residual adds and the positional table stay torch operators.
 
 Pinned by ``oracle/gen_golden_train.py`` (the real reference imported in the survey container: outputs and parameter
 gradients of one training step's forward/backward on a synthetic patch -> ``tests/golden/g18_train_step.npz``) and
@@ -112,10 +118,45 @@ def _attention_mode(value):
     return mode
 
 
-def vit_forward(vit, x, pe_xyz, attention="torch"):
+def _dense_mode(value):
+    mode = str(value)
+    if mode not in ("torch", "device"):
+        raise ValueError(f"cfg.train_vit_dense must be 'torch' or 'device', not {mode!r}")
+    return mode
+
+
+def _vit_forward_device_dense(vit, x, attention):
+    """the blocks of vit_forward with every dense layer, LayerNorm and GELU on the HIP Functions of train_ops"""
+    from . import train_ops as T
+    V, N, C = x.shape
+    h = vit.num_heads
+    x = x.contiguous()
+    for blk in vit.blocks:
+        a, m = blk.attn, blk.mlp
+        qkv = T.NormLinearFn.apply(x, blk.norm1.weight, blk.norm1.bias, a.qkv.weight, a.qkv.bias, blk.norm1.eps)
+        if attention == "device":
+            y = T.AttentionFn.apply(qkv, h)
+        else:
+            qkv = qkv.reshape(V, N, 3, h, C // h).permute(2, 0, 3, 1, 4)
+            s = (qkv[0] @ qkv[1].transpose(-2, -1)) * a.scale
+            y = (s.softmax(dim=-1) @ qkv[2]).transpose(1, 2).reshape(V, N, C).contiguous()
+        x = x + T.LinearFn.apply(y, a.proj.weight, a.proj.bias)
+        u = T.NormLinearFn.apply(x, blk.norm2.weight, blk.norm2.bias, m.fc1.weight, m.fc1.bias, blk.norm2.eps)
+        x = x + T.GeluLinearFn.apply(u, m.fc2.weight, m.fc2.bias)
+    return T.LayerNormFn.apply(x, vit.norm.weight, vit.norm.bias, vit.norm.eps)
+
+
+def vit_forward(vit, x, pe_xyz, attention="torch", dense="torch"):
     """VisionTransformer.forward (vision_transformer.py:257-307, :362-383), mask = None.  attention = "device": every block's
-    softmax(q k^T / 8) v through train_ops.AttentionFn (HIP forward and backward, no N x N tensor) instead of torch operators."""
+    softmax(q k^T / 8) v through train_ops.AttentionFn (HIP forward and backward, no N x N tensor) instead of torch operators.
+    dense = "device": every dense layer, LayerNorm and GELU through the HIP Functions of train_ops (k_vit_dense_bwd.hip)."""
     attention = _attention_mode(attention)
+    dense = _dense_mode(dense)
+    if dense == "device":
+        from .. import hip
+        if not x.is_cuda:
+            raise hip.HipError("cfg.train_vit_dense = 'device' needs the tokens on an MI355X (the HIP kernels have no CPU "
+                               "form); use 'torch' for a CPU batch")
     if attention == "device":
         from .. import hip
         from . import train_ops
@@ -123,6 +164,8 @@ def vit_forward(vit, x, pe_xyz, attention="torch"):
             raise hip.HipError("cfg.train_attention = 'device' needs the tokens on an MI355X (the HIP kernels have no CPU "
                                "form); use 'torch' for a CPU batch")
     x = x + vit.get_PE(pe_xyz).to(x.dtype)
+    if dense == "device":
+        return _vit_forward_device_dense(vit, x, attention)
     V, N, C = x.shape
     h = vit.num_heads
     for blk in vit.blocks:
@@ -209,6 +252,11 @@ def render(renderer, batch, chunk=32768):
         from .. import hip
         raise hip.HipError("cfg.train_attention = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
                            "use 'torch' for a CPU batch")
+    dense = _dense_mode(getattr(cfg, "train_vit_dense", "torch"))
+    if dense == "device" and not ray_o.is_cuda:
+        from .. import hip
+        raise hip.HipError("cfg.train_vit_dense = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
+                           "use 'torch' for a CPU batch")
     near, far = batch["near"][0], batch["far"][0]
     dev = ray_o.device
     S = int(cfg.N_samples)
@@ -229,7 +277,7 @@ def render(renderer, batch, chunk=32768):
     nv = verts_in.shape[0]
     M = pooling_matrix_cached(renderer, nv, dev, torch.float32)
     tokens = vit_forward(net.ViT, torch.einsum("cn,vnd->vcd", M, painted), renderer._pe_norm(V, dev),
-                         attention=attention)
+                         attention=attention, dense=dense)
     centres = M @ batch["tar_smpl_vertice_smplcoord"][0]
     blend = batch["blend_mtx"][0]
     M64 = pooling_matrix_cached(renderer, nv, dev, blend.dtype)        # (float64 mean, :544)

@@ -12,6 +12,15 @@ the compositing (K7) through the HIP forwards that the inference paths use, with
 
     AttentionFn             qkv    [V,N,3 C]     -> [V,N,C]            gradient: qkv         (k_vit.hip / k_vit_bwd.hip)
 
+``cfg.train_vit_dense = "device"`` does it for everything else inside TransHE: the dense layers, LayerNorm and GELU
+(k_vit_dense_bwd.hip).  Each Function keeps only what cannot be recomputed -- LN(x) and gelu(u) are rebuilt inside the
+weight-gradient kernel -- and returns the gradients of the Parameters themselves:
+
+    NormLinearFn            x, ln_w, ln_b, W, b  -> Linear(LN(x))      keeps x          qkv, fc1
+    GeluLinearFn            u, W, b              -> Linear(gelu(u))    keeps u          fc2
+    LinearFn                a, W, b              -> Linear(a)          keeps a          proj (a is AttentionFn's saved output)
+    LayerNormFn             x, w, b              -> LN(x)              keeps x          the final norm
+
 K4 and K5 are linear in the tensor that gets the gradient, so nothing of the forward is kept for the backward but the
 geometry (points, centres, cameras): the [P,7,255] blend operands and the per-chunk map-sized gradients of the torch
 formulation do not exist here.  Points, centres, rotations, cameras, depths and ray directions come from the batch and get
@@ -115,6 +124,91 @@ class AttentionFn(torch.autograd.Function):
         return hip.attention_bwd(qkv, out, lse, grad_out.contiguous(), ctx.heads), None
 
 
+def _dense_inputs(fn, **tensors):
+    for name, t in tensors.items():
+        _on_device(fn, t)
+        if t.dtype is not torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{fn}: '{name}' must be a contiguous float32 tensor")
+
+
+class _DenseFn(torch.autograd.Function):
+    """Linear(op(a)) of one TransHE layer: th_linear_train_forward / th_linear_bwd with the operand form of the subclass"""
+    FORM = 0
+
+    @classmethod
+    def _fwd(cls, ctx, a, W, b, ln_w=None, ln_b=None, eps=1e-6):
+        name = cls.__name__
+        _dense_inputs(name, a=a, W=W, b=b, **({"ln_w": ln_w, "ln_b": ln_b} if ln_w is not None else {}))
+        ctx.eps = float(eps)
+        ctx.save_for_backward(a, W, *((ln_w, ln_b) if ln_w is not None else ()))
+        return hip.linear_train_forward(a.detach(), W.detach(), b.detach(), cls.FORM, ln_w, ln_b, ctx.eps)
+
+    @classmethod
+    def _bwd(cls, ctx, grad_out):
+        a, W, *ln = ctx.saved_tensors
+        ln_w, ln_b = ln if ln else (None, None)
+        return hip.linear_bwd(a, W, grad_out.contiguous(), cls.FORM, ln_w, ln_b, ctx.eps)
+
+
+class LinearFn(_DenseFn):
+    """nn.Linear on rows: a [..., in] -> [..., out].  Kept: a (for TransHE's proj the tensor AttentionFn keeps anyway)."""
+    FORM = hip.OPERAND_PLAIN
+
+    @staticmethod
+    def forward(ctx, a, W, b):
+        return LinearFn._fwd(ctx, a, W, b)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_a, g_w, g_b, _, _ = LinearFn._bwd(ctx, grad_out)
+        return g_a, g_w, g_b
+
+
+class NormLinearFn(_DenseFn):
+    """Linear(LayerNorm(x)) (Block.norm1 -> attn.qkv, Block.norm2 -> mlp.fc1; vision_transformer.py:296-306).  Kept: x -- the
+    normalised rows are rebuilt, with the forward's statistics bit for bit, on their way into the weight-gradient kernel."""
+    FORM = hip.OPERAND_LN
+
+    @staticmethod
+    def forward(ctx, x, ln_w, ln_b, W, b, eps=1e-6):
+        return NormLinearFn._fwd(ctx, x, W, b, ln_w, ln_b, eps)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_x, g_w, g_b, g_lw, g_lb = NormLinearFn._bwd(ctx, grad_out)
+        return g_x, g_lw, g_lb, g_w, g_b, None
+
+
+class GeluLinearFn(_DenseFn):
+    """Linear(gelu(u)), exact erf (Mlp.act -> fc2).  Kept: u."""
+    FORM = hip.OPERAND_GELU
+
+    @staticmethod
+    def forward(ctx, u, W, b):
+        return GeluLinearFn._fwd(ctx, u, W, b)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_u, g_w, g_b, _, _ = GeluLinearFn._bwd(ctx, grad_out)
+        return g_u, g_w, g_b
+
+
+class LayerNormFn(torch.autograd.Function):
+    """nn.LayerNorm over the last dimension (VisionTransformer.norm).  Kept: x."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, eps=1e-6):
+        _dense_inputs("LayerNormFn", x=x, w=w, b=b)
+        ctx.eps = float(eps)
+        ctx.save_for_backward(x, w)
+        return hip.layernorm_train_forward(x.detach(), w.detach(), b.detach(), ctx.eps)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, w = ctx.saved_tensors
+        return (*hip.layernorm_bwd(x, w, grad_out.contiguous(), ctx.eps), None)
+
+
 # ---- float64 restatements ---------------------------------------------------------------------------------------------------
 def _np64(x):
     return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
@@ -207,3 +301,49 @@ def attention_grad_oracle(qkv, g_out, heads):
     dK = s * np.einsum("vhij,vhid->vhjd", dS, q)
     g_qkv = np.stack([dQ, dK, dV], 0).transpose(1, 3, 0, 2, 4).reshape(V, N, C3)
     return g_qkv, lse
+
+
+def _gelu64(u):
+    from math import erf
+    return u * 0.5 * (1.0 + np.vectorize(erf)(u / np.sqrt(2.0)))
+
+
+def _gelu_grad64(u):
+    from math import erf
+    return 0.5 * (1.0 + np.vectorize(erf)(u / np.sqrt(2.0))) + u * np.exp(-0.5 * u * u) / np.sqrt(2.0 * np.pi)
+
+
+def linear_grad_oracle(a, W, g_out):
+    """adjoint of y = a W^T + b on rows: a [M,in], W [out,in], g_out [M,out] -> (g_a, g_W, g_b) in float64"""
+    a, W, g = _np64(a), _np64(W), _np64(g_out)
+    a, g = a.reshape(-1, a.shape[-1]), g.reshape(-1, g.shape[-1])
+    return g @ W, g.T @ a, g.sum(0)
+
+
+def layernorm_grad_oracle(x, w, g_out, eps=1e-6):
+    """adjoint of nn.LayerNorm over the last dimension -> (g_x, g_w, g_b) in float64; the formulas of k_vit_dense_bwd.hip"""
+    x, w, g = _np64(x), _np64(w), _np64(g_out)
+    x, g = x.reshape(-1, x.shape[-1]), g.reshape(-1, g.shape[-1])
+    mean = x.mean(1, keepdims=True)
+    rstd = 1.0 / np.sqrt(((x - mean) ** 2).mean(1, keepdims=True) + eps)
+    xh = (x - mean) * rstd
+    gw = g * w
+    g_x = rstd * (gw - gw.mean(1, keepdims=True) - xh * (gw * xh).mean(1, keepdims=True))
+    return g_x, (g * xh).sum(0), g.sum(0)
+
+
+def norm_linear_grad_oracle(x, ln_w, ln_b, W, g_out, eps=1e-6):
+    """adjoint of Linear(LayerNorm(x)) -> (g_x, g_ln_w, g_ln_b, g_W, g_b) in float64"""
+    x2 = _np64(x).reshape(-1, _np64(x).shape[-1])
+    mean = x2.mean(1, keepdims=True)
+    y = (x2 - mean) / np.sqrt(((x2 - mean) ** 2).mean(1, keepdims=True) + eps) * _np64(ln_w) + _np64(ln_b)
+    g_y, g_W, g_b = linear_grad_oracle(y, W, g_out)
+    g_x, g_lw, g_lb = layernorm_grad_oracle(x2, ln_w, g_y, eps)
+    return g_x, g_lw, g_lb, g_W, g_b
+
+
+def gelu_linear_grad_oracle(u, W, g_out):
+    """adjoint of Linear(gelu(u)), exact erf -> (g_u, g_W, g_b) in float64"""
+    u2 = _np64(u).reshape(-1, _np64(u).shape[-1])
+    g_a, g_W, g_b = linear_grad_oracle(_gelu64(u2), W, g_out)
+    return g_a * _gelu_grad64(u2), g_W, g_b
