@@ -236,6 +236,20 @@ __device__ __forceinline__ void f8_mfma_dual(const uint4 (&r3)[2][2], const uint
     }
 }
 
+// one 1 KiB row global -> LDS (global_load_lds_dwordx4: lane l reads 16 bytes at gbase + voff_l and they land at ldst + 16 l),
+// issued from assembly so that the request stays outside the compiler's wait counts -- the caller orders the reads with its own
+// s_waitcnt vmcnt(n) + barrier.  gbase and ldst are wave-uniform; M0 (the LDS destination) is saved and restored around the request.
+// The s_nop 4 (5 wait states) in front of the load settles both hazards INSIDE the statement, where the compiler pads nothing:
+// gbase and ldst come straight out of v_readlane (a VALU write of an SGPR that a vector-memory instruction reads as its base: 5
+// wait states), and M0 is written by the s_mov in front of the LDS-DMA that reads it (1 wait state).
+__device__ __forceinline__ void f8_dma_row(const char* gbase, unsigned voff, unsigned ldst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(gbase), "s"(ldst)
+                 : "memory");
+}
+
 template <int V>
 __global__ __launch_bounds__(F8_THREADS, 2) void mlp_fused8_kernel(FusedParams P_arg) {
 #define PK P_arg
@@ -274,7 +288,7 @@ __global__ __launch_bounds__(F8_THREADS, 2) void mlp_fused8_kernel(FusedParams P
     unsigned seen_s = 0u, seen_p = 0u, seen_n = 0u, seen_i = 0u, seen_4 = 0u;
     char* a256_lo = abuf + ROWS * STR256;
 
-    // ---- texel hand-over (see mlp_fused_kernel: fill_tex); 8 waves: texel row i of the list is copied by wave i & 7, operand
+    // ---- texel hand-over (see mlp_fused_kernel: fill_tex); 8 waves: texel row i of the list is requested by wave i & 7, operand
     // row r is blended by wave r & 7 (12 rows per wave at V = 3)
     struct TexPre { unsigned h0, h1; fm_u4 rq; };
     auto tex_fetch = [&]() __attribute__((always_inline)) {
@@ -288,6 +302,18 @@ __global__ __launch_bounds__(F8_THREADS, 2) void mlp_fused8_kernel(FusedParams P
         if (tid < 64 * V) t.rq = *reinterpret_cast<const fm_u4*>(PK.tex_rec + (long long)tl * V * 32 * 8 + tid * 4);
         return t;
     };
+    // The listed rows go global -> LDS by LDS-DMA (no trip through registers, no ds_write pass): wave w requests rows w, w + 8, ...
+    // of the pass's list, ceil(U / 8) requests in every wave (the last group repeats the last row: the same bytes to the same place).
+    // Lane j of the wave works out request j (texel index out of the header words by ds_bpermute, source address, LDS address); the
+    // requests themselves are three v_readlane and one global_load_lds_dwordx4 each.
+    // V = 3, one-pass tiles, TWO STAGES: K5t numbers the rows view by view and operand row wv + 8 k belongs to view k >> 2, so the
+    // wave's four rows of view 0 need only the first rows of the list.  With F = 6, 4 or 2 requests per wave left in flight (the
+    // largest F for which view 0's rows all lie in front of them: s_waitcnt vmcnt(F) takes an immediate, so F comes from a short
+    // if-chain) the waves meet, blend view 0 while the tail lands, wait for the rest, meet again and blend views 1 and 2.
+    // The requests are issued from inline assembly (f8_dma_row): hipcc puts every ds_read behind ALL LDS-DMA requests it knows of
+    // (s_waitcnt vmcnt(0) in front of the first read), which would undo the overlap.  Nothing else of this wave may therefore be
+    // in flight when the first request is issued (a wait the compiler derives for an older load would also wait for every request
+    // behind it), and nothing is requested until the last has landed.
     auto fill_tex = [&](const TexPre& pre, auto rgb, auto&& under) __attribute__((always_inline)) {
         constexpr bool RGB = decltype(rgb)::value;
         constexpr int TSTR = 1040, TMAX = 103, NK = (TMAX + 7) / 8, NR = 4 * V;
@@ -298,133 +324,161 @@ __global__ __launch_bounds__(F8_THREADS, 2) void mlp_fused8_kernel(FusedParams P
         unsigned h0 = pre.h0, h1 = pre.h1;
         const int npass = __builtin_amdgcn_readfirstlane((int)(h0 >> 16));
         char* recl = reinterpret_cast<char*>(misc);
-        static_assert(32 * V * 32 <= (F8_PSTR * 32 + F8_PART_FLOATS) * 4, "row records must fit probs + part");
-        unsigned fv[NR][4] = {};
+        static_assert(32 * V * 32 + 1024 <= (F8_PSTR * 32 + F8_PART_FLOATS) * 4, "row records + the bias row must fit probs + part");
+        char* biasl = recl + 32 * V * 32;                    // the bias row of alpha_res_0 comes by LDS-DMA as well (first request of wave 0)
+        unsigned fv[NR][4];
         f32x2 bias_lo = {0.f, 0.f}, bias_hi = {0.f, 0.f};
-        if constexpr (!RGB) {
-            const float4 b4 = *reinterpret_cast<const float4*>(PK.ar0.bias + 4 * lane);
-            bias_lo = (f32x2){b4.x, b4.y};
-            bias_hi = (f32x2){b4.z, b4.w};
-        }
-        for (int p = 0; p < npass; ++p) {
+        const unsigned long long mbase = (unsigned long long)reinterpret_cast<size_t>(RGB ? PK.tex_map2 : PK.tex_map);
+        const unsigned loff = (unsigned)lane * 16u;
+        const unsigned lbase = (unsigned)(size_t)(fm_lptr)abuf;
+        const int cofs = lane * 16;
+        int p = 0, sh2 = 2;                                  // (pass; operand row wv + 8 k is sample wv + 8 (k & 3): its pass is (k & 3) >> sh2)
+        struct RowIn { float4 a, b, c, d; fm_u4 q0; };
+        auto issue = [&](int k, const fm_u4& o, RowIn& r) __attribute__((always_inline)) {
+            r.q0 = *reinterpret_cast<const fm_u4*>(recl + (wv + 8 * k) * 32);
+            r.a = *reinterpret_cast<const float4*>(abuf + (o[0] + cofs));
+            r.b = *reinterpret_cast<const float4*>(abuf + (o[1] + cofs));
+            r.c = *reinterpret_cast<const float4*>(abuf + (o[2] + cofs));
+            r.d = *reinterpret_cast<const float4*>(abuf + (o[3] + cofs));
+        };
+        auto offs = [&](int k) __attribute__((always_inline)) {
+            return *reinterpret_cast<const fm_u4*>(recl + (wv + 8 * k) * 32 + 16);
+        };
+        auto blend = [&](int k, const RowIn& r, auto sel) __attribute__((always_inline)) {
+            const unsigned u0 = r.q0[0], u1 = r.q0[1], u2 = r.q0[2], u3 = r.q0[3];
+            const float w00 = __builtin_bit_cast(float, u0), w01 = __builtin_bit_cast(float, u1),
+                        w10 = __builtin_bit_cast(float, u2), w11 = __builtin_bit_cast(float, u3);
+            // (pg_blend2 of k_pixfeat.hip: a w00, then fused multiply-adds in the order ne, sw, se)
+            const f32x2 W00 = {w00, w00}, W01 = {w01, w01}, W10 = {w10, w10}, W11 = {w11, w11};
+            f32x2 lo = (f32x2){r.a.x, r.a.y} * W00, hi = (f32x2){r.a.z, r.a.w} * W00;
+            lo = __builtin_elementwise_fma((f32x2){r.b.x, r.b.y}, W01, lo);
+            hi = __builtin_elementwise_fma((f32x2){r.b.z, r.b.w}, W01, hi);
+            lo = __builtin_elementwise_fma((f32x2){r.c.x, r.c.y}, W10, lo);
+            hi = __builtin_elementwise_fma((f32x2){r.c.z, r.c.w}, W10, hi);
+            lo = __builtin_elementwise_fma((f32x2){r.d.x, r.d.y}, W11, lo);
+            hi = __builtin_elementwise_fma((f32x2){r.d.z, r.d.w}, W11, hi);
+            unsigned n0, n1, n2, n3;
+            if constexpr (RGB) {
+                const float l0 = lo[0], l1 = lo[1], h0f = hi[0], h1f = hi[1];
+                n0 = __builtin_bit_cast(unsigned, l0); n1 = __builtin_bit_cast(unsigned, l1);
+                n2 = __builtin_bit_cast(unsigned, h0f); n3 = __builtin_bit_cast(unsigned, h1f);
+            } else {
+                lo = __builtin_elementwise_max(lo + bias_lo, (f32x2){0.f, 0.f});
+                hi = __builtin_elementwise_max(hi + bias_hi, (f32x2){0.f, 0.f});
+                split_pair(lo[0], lo[1], n0, n2);
+                split_pair(hi[0], hi[1], n1, n3);
+            }
+            if constexpr (decltype(sel)::value) {
+                const bool mine = ((k & 3) >> sh2) == p;
+                fv[k][0] = mine ? n0 : fv[k][0]; fv[k][1] = mine ? n1 : fv[k][1];
+                fv[k][2] = mine ? n2 : fv[k][2]; fv[k][3] = mine ? n3 : fv[k][3];
+            } else {
+                fv[k][0] = n0; fv[k][1] = n1; fv[k][2] = n2; fv[k][3] = n3;
+            }
+        };
+        // this wave's requests for the pass's U rows; returns their number (the same in every wave)
+        auto request_rows = [&](int U) __attribute__((always_inline)) {
+            const int c = (U + 7) >> 3;
+            const int il = min(wv + 8 * lane, U - 1);        // lane j: the row of request j (lanes >= c: never used)
+            const unsigned ida = (unsigned)__builtin_amdgcn_ds_bpermute((il + 8) << 2, (int)h0);      // (header word 8 + i: h0 up to entry 55,
+            const unsigned idb = (unsigned)__builtin_amdgcn_ds_bpermute((il - 56) << 2, (int)h1);     // word i - 56 of h1 from there)
+            const unsigned long long ga = mbase + ((unsigned long long)(il < 56 ? ida : idb) << 10);
+            const int alo = (int)(unsigned)ga, ahi = (int)(unsigned)(ga >> 32), ald = (int)(lbase + (unsigned)il * TSTR);
+            // everything this wave has requested is home (long since), and the compiler's wait counts know it from here on
+            __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0)
+            if constexpr (!RGB) {
+                if (p == 0 && wv == 0)
+                    f8_dma_row(reinterpret_cast<const char*>(PK.ar0.bias), loff,
+                               (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(fm_lptr)biasl));
+            }
+#pragma unroll
+            for (int j = 0; j < NK; ++j) {
+                if (j < c) {
+                    const unsigned lo = (unsigned)__builtin_amdgcn_readlane(alo, j), hi = (unsigned)__builtin_amdgcn_readlane(ahi, j);
+                    f8_dma_row(reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo), loff,
+                               (unsigned)__builtin_amdgcn_readlane(ald, j));
+                }
+            }
+            return c;
+        };
+        auto bias_read = [&]() __attribute__((always_inline)) {
+            if constexpr (!RGB) {
+                const float4 b4 = *reinterpret_cast<const float4*>(biasl + 16 * lane);
+                bias_lo = (f32x2){b4.x, b4.y};
+                bias_hi = (f32x2){b4.z, b4.w};
+            }
+        };
+        // one pass in one stage: requests, barrier, blend (multi-pass tiles: sel; V < 3)
+        auto pass_single = [&](auto sel) __attribute__((always_inline)) {
             if (p > 0) {
                 FM_SYNCL();
                 h0 = hb[p * 128 + lane];
                 h1 = hb[p * 128 + 64 + lane];
             }
+            request_rows(__builtin_amdgcn_readfirstlane((int)(h0 & 0xffffu)));
+            if (p == 0) {
+                under();
+                if (tid < 64 * V) *reinterpret_cast<fm_u4*>(recl + tid * 16) = pre.rq;
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            FM_SYNCL();                                      // the texel rows (and the records, the bias row) are in place
+            if (p == 0) bias_read();
+            RowIn in[2];
+            fm_u4 of[2];
+            of[0] = offs(0);
+            of[1] = offs(1);
+            issue(0, of[0], in[0]);
+#pragma unroll
+            for (int k = 0; k < NR; ++k) {
+                if (k + 1 < NR) issue(k + 1, of[(k + 1) & 1], in[(k + 1) & 1]);
+                if (k + 2 < NR) of[k & 1] = offs(k + 2);
+                FM_SB();
+                blend(k, in[k & 1], sel);
+                FM_SB();
+            }
+        };
+        if (npass > 1) {
+#pragma unroll
+            for (int k = 0; k < NR; ++k) fv[k][0] = fv[k][1] = fv[k][2] = fv[k][3] = 0u;
+            sh2 = npass == 2 ? 1 : 0;
+            for (p = 0; p < npass; ++p) pass_single(std::true_type{});
+        } else if constexpr (V != 3) {
+            pass_single(std::false_type{});
+        } else {
             const int U = __builtin_amdgcn_readfirstlane((int)(h0 & 0xffffu));
-            {
-                // rows wv, wv + 8, ...: the first 7 of a wave always (list entries 0 .. 55: header word 8 + i is in h0), 3 more for
-                // lists longer than 56, the last 3 for lists longer than 80 (entries 56 ..: word i - 56 of h1)
-                constexpr int NA = 7, NB = 10;
-                const char* mbase = reinterpret_cast<const char*>(RGB ? PK.tex_map2 : PK.tex_map);
-                const unsigned loff = (unsigned)lane * 16u;
-                const int last = U - 1;
-                fm_u4 ta[NA], tb[NB - NA], tc[NK - NB];
+            // rows of view 0 (texel index < H W) -> requests per wave that may stay in flight while view 0 is blended
+            const unsigned hw = PK.tex_hw;
+            const int vs0 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane >= 8 && lane - 8 < U && h0 < hw)) +
+                            __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane + 56 < U && h1 < hw));
+            const int c = request_rows(U);
+            const int spare = hw != 0u ? c - ((vs0 + 7) >> 3) : 0;      // requests of a wave behind the last one that carries a row of view 0
+            under();
+            if (tid < 64 * V) *reinterpret_cast<fm_u4*>(recl + tid * 16) = pre.rq;
+            if (spare >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            else if (spare >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            else if (spare >= 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            FM_SYNCL();                                      // view 0's rows, the records (and the bias row) are in place
+            bias_read();
+            RowIn in[2];
+            fm_u4 of[2];
+            of[0] = offs(0);
+            of[1] = offs(1);
+            issue(0, of[0], in[0]);
 #pragma unroll
-                for (int k = 0; k < NA; ++k) {
-                    const int i = min(wv + 8 * k, last);
-                    const unsigned id = (unsigned)__builtin_amdgcn_readlane((int)h0, 8 + i);
-                    ta[k] = *reinterpret_cast<const fm_u4*>(mbase + TX_ADDR(id));
-                }
-                const bool more = U > 8 * NA, most = U > 8 * NB;
-                if (more) {
-#pragma unroll
-                    for (int k = NA; k < NB; ++k) {
-                        const int i = min(wv + 8 * k, last);
-                        const unsigned id = (unsigned)__builtin_amdgcn_readlane((int)h1, i - 56);
-                        tb[k - NA] = *reinterpret_cast<const fm_u4*>(mbase + TX_ADDR(id));
-                    }
-                }
-                if (most) {
-#pragma unroll
-                    for (int k = NB; k < NK; ++k) {
-                        const int i = min(wv + 8 * k, last);
-                        const unsigned id = (unsigned)__builtin_amdgcn_readlane((int)h1, i - 56);
-                        tc[k - NB] = *reinterpret_cast<const fm_u4*>(mbase + TX_ADDR(id));
-                    }
-                }
-                if (p == 0) {
-                    under();
-                    if (tid < 64 * V) *reinterpret_cast<fm_u4*>(recl + tid * 16) = pre.rq;
-                }
-                int wv2 = wv;
-                asm volatile("" : "+s"(wv2));
-#pragma unroll
-                for (int k = 0; k < NA; ++k) *reinterpret_cast<fm_u4*>(abuf + min(wv2 + 8 * k, last) * TSTR + lane * 16) = ta[k];
-                if (more) {
-#pragma unroll
-                    for (int k = NA; k < NB; ++k) *reinterpret_cast<fm_u4*>(abuf + min(wv2 + 8 * k, last) * TSTR + lane * 16) = tb[k - NA];
-                }
-                if (most) {
-#pragma unroll
-                    for (int k = NB; k < NK; ++k) *reinterpret_cast<fm_u4*>(abuf + min(wv2 + 8 * k, last) * TSTR + lane * 16) = tc[k - NB];
+            for (int k = 0; k < NR; ++k) {
+                const bool edge = k + 1 == 4;                // row k + 1 is the first of view 1
+                if (k + 1 < NR && !edge) issue(k + 1, of[(k + 1) & 1], in[(k + 1) & 1]);
+                if (k + 2 < NR) of[k & 1] = offs(k + 2);
+                FM_SB();
+                blend(k, in[k & 1], std::false_type{});
+                FM_SB();
+                if (edge) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    FM_LDS_BARRIER();                        // every row is in place
+                    issue(k + 1, of[(k + 1) & 1], in[(k + 1) & 1]);
                 }
             }
-            FM_SYNCL();                                      // the texel rows (and the records) are in place
-            // operand row wv + 8 k is sample wv + 8 (k & 3): its pass is (k & 3) >> (sh - 1)
-            const int sh2 = npass == 1 ? 2 : npass == 2 ? 1 : 0;
-            const int cofs = lane * 16;
-            struct RowIn { float4 a, b, c, d; fm_u4 q0; };
-            auto issue = [&](int k, const fm_u4& o, RowIn& r) __attribute__((always_inline)) {
-                r.q0 = *reinterpret_cast<const fm_u4*>(recl + (wv + 8 * k) * 32);
-                r.a = *reinterpret_cast<const float4*>(abuf + (o[0] + cofs));
-                r.b = *reinterpret_cast<const float4*>(abuf + (o[1] + cofs));
-                r.c = *reinterpret_cast<const float4*>(abuf + (o[2] + cofs));
-                r.d = *reinterpret_cast<const float4*>(abuf + (o[3] + cofs));
-            };
-            auto offs = [&](int k) __attribute__((always_inline)) {
-                return *reinterpret_cast<const fm_u4*>(recl + (wv + 8 * k) * 32 + 16);
-            };
-            auto blend = [&](int k, const RowIn& r, auto sel) __attribute__((always_inline)) {
-                const unsigned u0 = r.q0[0], u1 = r.q0[1], u2 = r.q0[2], u3 = r.q0[3];
-                const float w00 = __builtin_bit_cast(float, u0), w01 = __builtin_bit_cast(float, u1),
-                            w10 = __builtin_bit_cast(float, u2), w11 = __builtin_bit_cast(float, u3);
-                // (pg_blend2 of k_pixfeat.hip: a w00, then fused multiply-adds in the order ne, sw, se)
-                const f32x2 W00 = {w00, w00}, W01 = {w01, w01}, W10 = {w10, w10}, W11 = {w11, w11};
-                f32x2 lo = (f32x2){r.a.x, r.a.y} * W00, hi = (f32x2){r.a.z, r.a.w} * W00;
-                lo = __builtin_elementwise_fma((f32x2){r.b.x, r.b.y}, W01, lo);
-                hi = __builtin_elementwise_fma((f32x2){r.b.z, r.b.w}, W01, hi);
-                lo = __builtin_elementwise_fma((f32x2){r.c.x, r.c.y}, W10, lo);
-                hi = __builtin_elementwise_fma((f32x2){r.c.z, r.c.w}, W10, hi);
-                lo = __builtin_elementwise_fma((f32x2){r.d.x, r.d.y}, W11, lo);
-                hi = __builtin_elementwise_fma((f32x2){r.d.z, r.d.w}, W11, hi);
-                unsigned n0, n1, n2, n3;
-                if constexpr (RGB) {
-                    const float l0 = lo[0], l1 = lo[1], h0f = hi[0], h1f = hi[1];
-                    n0 = __builtin_bit_cast(unsigned, l0); n1 = __builtin_bit_cast(unsigned, l1);
-                    n2 = __builtin_bit_cast(unsigned, h0f); n3 = __builtin_bit_cast(unsigned, h1f);
-                } else {
-                    lo = __builtin_elementwise_max(lo + bias_lo, (f32x2){0.f, 0.f});
-                    hi = __builtin_elementwise_max(hi + bias_hi, (f32x2){0.f, 0.f});
-                    split_pair(lo[0], lo[1], n0, n2);
-                    split_pair(hi[0], hi[1], n1, n3);
-                }
-                if constexpr (decltype(sel)::value) {
-                    const bool mine = ((k & 3) >> sh2) == p;
-                    fv[k][0] = mine ? n0 : fv[k][0]; fv[k][1] = mine ? n1 : fv[k][1];
-                    fv[k][2] = mine ? n2 : fv[k][2]; fv[k][3] = mine ? n3 : fv[k][3];
-                } else {
-                    fv[k][0] = n0; fv[k][1] = n1; fv[k][2] = n2; fv[k][3] = n3;
-                }
-            };
-            auto rows_loop = [&](auto sel) __attribute__((always_inline)) {
-                RowIn in[2];
-                fm_u4 of[2];
-                of[0] = offs(0);
-                of[1] = offs(1);
-                issue(0, of[0], in[0]);
-#pragma unroll
-                for (int k = 0; k < NR; ++k) {
-                    if (k + 1 < NR) issue(k + 1, of[(k + 1) & 1], in[(k + 1) & 1]);
-                    if (k + 2 < NR) of[k & 1] = offs(k + 2);
-                    FM_SB();
-                    blend(k, in[k & 1], sel);
-                    FM_SB();
-                }
-            };
-            if (npass == 1) rows_loop(std::false_type{});
-            else rows_loop(std::true_type{});
         }
         FM_SYNCL();                                          // every wave is done reading texel rows: ABUF takes the result
         if constexpr (RGB) {
@@ -800,6 +854,7 @@ __global__ __launch_bounds__(F8_THREADS, 2) void mlp_fused8_kernel(FusedParams P
     char* vd_lo = vd_hi + 32 * STRVD;
     tex_pre2 = tex_fetch();                              // (for the RGB branch's filling: the round trip runs under fc_3)
     f8_f4 va[1][RT];                                     // this wave's 16 of the 128 view_fc outputs, all rows
+    uint4 wvd[1][2];
     {
         f8_f4 a3[2][2];
         const float4 aw[2] = {f8_bias(PK.alpha_w, wave * 32, lane), f8_bias(PK.alpha_w, wave * 32 + 16, lane)};
@@ -869,6 +924,10 @@ __global__ __launch_bounds__(F8_THREADS, 2) void mlp_fused8_kernel(FusedParams P
         // stores; written as a select between s2[0] and s2[1] the array went to scratch memory and was indexed there)
         if (g4 == 0) part[wave * 32 + l15] = s2[0];
         if (g4 == 1) part[wave * 32 + 16 + l15] = s2[1];
+        // (the view-direction block of view_fc for the RGB branch: requested here, two barriers ahead, so that it is home before the
+        // filling's first row request -- that filling keeps nothing else in flight.  Requested by every tile: 2 KiB per wave and 8
+        // registers across two barriers are wasted on the tiles that skip the RGB branch -- rgb_all == 2, no sample with sigma > 0)
+        f8_load_w<1>(F8_WSLICE(PK.w16.vfD, wave, 1) + lane, 0, wvd);
         if (tid == 0) *flag = 0;
         FM_SYNCL();                                  // every wave is done reading the means (MBUF) and inter (ABUF)
         if (tid < 32) {
@@ -894,8 +953,6 @@ __global__ __launch_bounds__(F8_THREADS, 2) void mlp_fused8_kernel(FusedParams P
         // ================= RGB branch (cross_transformer.py:330-353) =================
         //   t = relu((Wa F) inter + Wd viewdir + blend(fold12[:, :128]) + b') ; u = t + blend(fold12[:, 128:]) + b_R1 ; mean over views ;
         //   fc_4 ; rgb_fc
-        uint4 wvd[1][2];
-        f8_load_w<1>(F8_WSLICE(PK.w16.vfD, wave, 1) + lane, 0, wvd);
         FM_SB();
         fill_tex(tex_pre2, std::true_type{}, [&]() __attribute__((always_inline)) {
             h8 xh[2], xl[2];

@@ -278,6 +278,7 @@ struct FusedParams {
     const unsigned* tex_rec;   // [tiles][V][32][8]  {w00 w01 w10 w11} {byte offsets of the four corner rows}
     const float* tex_map;      // fold0  [V][H*W][256]: alpha_res_0' of the map's texels (map_fold_kernel)
     const float* tex_map2;     // fold12 [V][H*W][256]: [Wa rgb_res_0' (128) | rgb_res_1' (128)] of the texels
+    unsigned tex_hw;           // H*W: texel index / tex_hw = view of a listed row (the 8-wave kernel stages the rows view by view)
     const float* vd;    // view-direction rows [.][27]: row of compacted sample p = vd_sel ? vd_sel[p] / vd_div : p
     const int32_t* vd_sel;
     int vd_div;
