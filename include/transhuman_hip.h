@@ -495,6 +495,25 @@ int th_pixel_gather_bwd(th_ctx* ctx, int V, int C, int H, int W, const float* pt
 int th_composite_bwd(th_ctx* ctx, const float* raw, const float* z, const th_points* rays, int white_bkgd,
                      const float* g_rgb, const float* g_acc, const float* g_depth, float* g_raw, th_stream stream);
 
+/* ---- K19: training -- the pixel-aligned gather read from the encoder's latents (additions, ABI 12) ---- */
+/* What th_upsample_concat_nhwc -> th_pixel_gather (sel = NULL, C = 384) compute, without the [V,H,W,384] map: a bilinear
+ * sample (grid_sample, align_corners, border; cams / scale_xy as in th_pixel_gather) of bilinearly upsampled latents
+ * (upsample_bilinear2d, align_corners) is a linear combination of at most 3 x 3 texels per latent level.
+ * lat0 [V,h0,w0,64], lat1 [V,h1,w1,64], lat2 [V,h2,w2,128]: CHANNELS-LAST fp32; dims = {h0,w0,h1,w1,h2,w2} (host), every
+ * level 1 <= h <= H, 1 <= w <= W; img [V,3,H,W]; lift_w [128][3], lift_b [128] (upsample_color); H * W < 2^31.
+ * out [P,V,ldo], ldo >= 384 and a multiple of 4: columns 0..63 lat0, 64..127 lat1, 128..255 lat2, 256..383 the lifted colour
+ * (columns 384.. are not written); rgb_s [P,V,4]: the blended raw colours (r, g, b, 0).  P = 0: nothing is written. */
+int th_latent_gather(th_ctx* ctx, const float* lat0, const float* lat1, const float* lat2, const int32_t* dims,
+                     const float* img, const float* lift_w, const float* lift_b, int V, int H, int W, const float* pts_world,
+                     int P, const float* cams, const float* scale_xy, float* out, int ldo, float* rgb_s, th_stream stream);
+/* Its adjoint with respect to the three latents: grad_out [P,V,ldo] (columns 0..255 are read) -> g_lat0 / g_lat1 / g_lat2 in
+ * the latents' channels-last layouts, every element written (the call clears them, then adds with float atomics: results
+ * can differ in the last bits from run to run; P = 0 writes zeros).  Points, cameras and the image get no gradient; the
+ * lift's own gradient is a reduction over grad_out[..., 256:384] and rgb_s (train_ops.LatentGatherFn). */
+int th_latent_gather_bwd(th_ctx* ctx, const int32_t* dims, int V, int H, int W, const float* pts_world, int P,
+                         const float* cams, const float* scale_xy, const float* grad_out, int ldo, float* g_lat0,
+                         float* g_lat1, float* g_lat2, th_stream stream);
+
 /* ---- K9: ray generation for a target camera --------------------------- */
 /* lib/utils/if_nerf/if_nerf_data_utils.py:11-30 (get_rays) + :65-97 (get_near_far) as the test split of
  * sample_ray_h36m uses them (:271-283): one ray per pixel of an H x W camera (K [3,3], R [3,3], T [3] float32,

@@ -1,0 +1,145 @@
+"""Time the encoder's part of a training step in both modes of cfg.train_maps on the same box in the same process, at the
+reference's training shape: V = 3 input views of 512 x 512, 6 890 input vertices (painting), 2 400 rays x 64 samples =
+153 600 points (pixel-aligned features).
+
+    timeout -k 10 600 python tools/encoder_tail_time.py [--rounds 5] [--warmup 2] [--size 512]
+
+One step = forward + backward of: trunk -> painting rows [V,6890,192] -> pixel rows [153600,V,384], with a seeded upstream
+gradient on both row tensors standing in for the rest of the network.
+  "full"     autograd_path.encode (upsample, concatenate, 1 x 1 reduction: the two full-size maps) + sample_map twice
+  "latents"  autograd_path.latent_features (K19, train_ops.LatentGatherFn on the three latents) + the reduction on the rows
+Prints one JSON line.  Per mode: the median of --rounds alternating rounds with the lowest and the highest (device events around
+the step, no host synchronisation inside; one synchronisation after the closing event), torch.cuda.max_memory_allocated of a
+step above what is allocated before it, and the largest difference of every encoder gradient between the modes.  The two
+kernels' own time: device events around th_latent_gather / th_latent_gather_bwd at the pixel shape, median of 20 calls.
+No threshold on any figure."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+RAYS, SAMPLES, VIEWS = 2400, 64, 3
+
+
+def setup(dev, size):
+    import torch
+    from transhuman_amd import hip, synth
+    from transhuman_amd.networks import autograd_path
+    from transhuman_amd.networks.encoder import SpatialEncoder
+    torch.manual_seed(0)
+    enc = SpatialEncoder().to(dev).train()
+    b = synth.make_batch(size, size, VIEWS, seed=0, all_rays=False)
+    n = b["ray_o"].shape[1]
+    pick = torch.from_numpy(np.sort(np.random.RandomState(0).choice(n, RAYS, replace=n < RAYS)))
+    for k in ("ray_o", "ray_d", "near", "far"):
+        b[k] = b[k][:, pick].contiguous()
+    b = synth.batch_to(b, dev)
+    z = autograd_path.sample_depths(b["near"][0], b["far"][0], SAMPLES, False)
+    xyz = (b["ray_o"][0][:, None] + b["ray_d"][0][:, None] * z[..., None]).reshape(-1, 3).contiguous()
+    images = b["input_imgs"][0].reshape(-1, *b["input_imgs"][0].shape[2:])
+    R, T, K = (b[k][0].reshape(VIEWS, *sh) for k, sh in (("input_R", (3, 3)), ("input_T", (3, 1)), ("input_K", (3, 3))))
+    verts = b["input_smpl_vertice"][0][0]
+    gen = torch.Generator().manual_seed(1)
+    g_paint = torch.randn((VIEWS, verts.shape[0], 192), generator=gen).to(dev)
+    g_pix = torch.randn((xyz.shape[0], VIEWS, 384), generator=gen).to(dev)
+    cams = hip.pack_cams(R, T, K)
+    scale = hip.feat_scale(enc.feat_scale(size, size), (size, size), dev)
+    return enc, images, verts, xyz, (R, T, K), cams, scale, g_paint, g_pix
+
+
+def step(maps, enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix):
+    from transhuman_amd.networks import autograd_path as A
+    enc.zero_grad(set_to_none=True)
+    image_shape = images.shape[-2:]
+    if maps == "latents":
+        gather = A.latent_features(enc, images, cams, scale)
+        painted, f = A._lin(enc.reduction_layer, gather(verts)).permute(1, 0, 2), gather(xyz)
+    else:
+        hol, pix = A.encode(enc, images)
+        painted = A.sample_map(hol, A.project(verts, *rtk), enc, image_shape).permute(0, 2, 1)
+        f = A.sample_map(pix, A.project(xyz, *rtk), enc, image_shape).permute(2, 0, 1)
+    ((painted * g_paint).sum() + (f * g_pix).sum()).backward()
+
+
+def kernel_times(enc, images, xyz, cams, scale, g_pix, reps=20):
+    """device time of th_latent_gather and th_latent_gather_bwd on their own at the pixel shape"""
+    import torch
+    from transhuman_amd import hip
+    with torch.no_grad():
+        lat = [l.permute(0, 2, 3, 1).contiguous() for l in enc.trunk(images, fused_bn=False)]
+        w, b = enc.upsample_color.weight.reshape(128, 3).contiguous(), enc.upsample_color.bias
+        shapes = [tuple(l.shape) for l in lat]
+        out = tuple(torch.empty_like(l) for l in lat)
+        fwd = lambda: hip.latent_gather(*lat, w, b, images, xyz, cams, scale)
+        bwd = lambda: hip.latent_gather_bwd(shapes, images.shape[2:], xyz, cams, scale, g_pix, out=out)
+        res = {}
+        for name, fn in (("th_latent_gather", fwd), ("th_latent_gather_bwd (with its three clears)", bwd)):
+            for _ in range(3):
+                fn()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+            for a, e in ev:
+                a.record()
+                fn()
+                e.record()
+            torch.cuda.synchronize()
+            ms = [a.elapsed_time(e) for a, e in ev]
+            res[name] = {"ms_median": round(float(np.median(ms)), 4), "ms_min": round(float(np.min(ms)), 4),
+                         "ms_max": round(float(np.max(ms)), 4), "calls": reps}
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--size", type=int, default=512)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("encoder_tail_time.py needs an MI355X: a time taken elsewhere says nothing")
+    dev = torch.device("cuda:0")
+    enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix = setup(dev, args.size)
+    a = (enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix)
+    res = {"device": torch.cuda.get_device_name(0),
+           "shape": {"views": VIEWS, "image": [args.size, args.size], "vertices": int(verts.shape[0]), "points": int(xyz.shape[0])}}
+    modes = ("full", "latents")
+    grads = {}
+    for m in modes:
+        for _ in range(args.warmup):
+            step(m, *a)
+        grads[m] = {k: p.grad.detach().clone() for k, p in enc.named_parameters() if p.grad is not None}
+    enc.zero_grad(set_to_none=True)
+    torch.cuda.synchronize()
+    ms, peak = {m: [] for m in modes}, {m: 0 for m in modes}
+    for r in range(args.rounds):
+        for m in (modes if r % 2 == 0 else modes[::-1]):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            step(m, *a)
+            t1.record()
+            torch.cuda.synchronize()
+            ms[m].append(t0.elapsed_time(t1))
+            peak[m] = max(peak[m], torch.cuda.max_memory_allocated() - base)
+            enc.zero_grad(set_to_none=True)
+    for m in modes:
+        res[m] = {"step_ms_median": round(float(np.median(ms[m])), 2), "step_ms_min": round(float(np.min(ms[m])), 2),
+                  "step_ms_max": round(float(np.max(ms[m])), 2), "rounds": args.rounds,
+                  "peak_allocated_MiB": round(peak[m] / 2 ** 20, 1)}
+    assert set(grads["full"]) == set(grads["latents"])
+    res["latents_vs_full"] = {"grads_max_rel_to_own_max": max(
+        float((grads["full"][k] - grads["latents"][k]).abs().max()) / max(float(grads["full"][k].abs().max()), 1e-30)
+        for k in grads["full"])}
+    res["kernels"] = kernel_times(enc, images, xyz, cams, scale, g_pix)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

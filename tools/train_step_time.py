@@ -5,7 +5,8 @@ the HIP adjoints of K17, transhuman_amd/networks/train_ops.py).
 
     timeout -k 10 900 python tools/train_step_time.py [--steps 10] [--warmup 2] [--rocprof DIR]
 
-Prints one JSON line.  Per mode: median and minimum wall time of a step over --steps steps after --warmup (host clock around
+--maps full,latents repeats every mode with cfg.train_maps = "latents" (K19: the encoder's latents sampled directly) in the same
+process.  Prints one JSON line.  Per mode: median and minimum wall time of a step over --steps steps after --warmup (host clock around
 forward + backward with a device synchronisation at both ends) and torch.cuda.max_memory_allocated of the timed steps; the
 largest difference of the outputs and of every parameter gradient between the two modes; and, with --rocprof DIR, the device
 time of the K17 kernels per step from `rocprofv3 --kernel-trace --stats` over a short run of the "device" mode in a fresh child
@@ -103,6 +104,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--modes", default="torch,device")
+    ap.add_argument("--maps", default="full", help="comma list of cfg.train_maps values; every mode runs once per value "
+                                                   "(results of a value other than 'full' are keyed '<mode>+<value>')")
     ap.add_argument("--rocprof", default=None, metavar="DIR", help="also trace a short 'device' run under rocprofv3 into DIR")
     args = ap.parse_args()
     res = {"shape": {"rays": RAYS, "samples": SAMPLES, "views": VIEWS, "n_clusters": NC, "image": [SIZE, SIZE]}}
@@ -121,14 +124,22 @@ def main():
     target = torch.rand((1, RAYS, 3), device=dev)
     seen = {}
     try:
-        for mode in args.modes.split(","):
-            res[mode], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
-            seen[mode] = (outs, grads)
+        for maps in args.maps.split(","):
+            cfg.train_maps = maps
+            for mode in args.modes.split(","):
+                key = mode if maps == "full" else f"{mode}+{maps}"
+                res[key], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
+                seen[key] = (outs, grads)
     finally:
-        cfg.train_kernels = "torch"
-    if len(seen) == 2:
+        cfg.train_kernels, cfg.train_maps = "torch", "full"
+    if "torch" in seen and "device" in seen:
         (o0, g0), (o1, g1) = seen["torch"], seen["device"]
         res["device_vs_torch"] = {
+            "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
+            "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0)}
+    for key in [k for k in seen if "+" in k and k.split("+")[0] in seen]:
+        (o0, g0), (o1, g1) = seen[key.split("+")[0]], seen[key]
+        res[key + "_vs_full"] = {
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
             "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0)}
     print(json.dumps(res))

@@ -73,6 +73,10 @@ def _defaults():
         # torch modules under torch autograd; "device" runs the fp32 MFMA GEMMs with HIP backwards that recompute LN(x) and gelu(u)
         # and add their partial sums in a fixed order (train_ops.NormLinearFn / LinearFn / GeluLinearFn / LayerNormFn)
         train_vit_dense="torch",
+        # what the training entry samples its image features from: "full" builds the reference's two full-size maps (pixel_feat_map
+        # [V,384,H,W], holder_feat_map [V,192,H,W]) and their gradients; "latents" samples the encoder's three latents and the
+        # images directly at the vertices and the ray samples (train_ops.LatentGatherFn, K19) -- neither map exists
+        train_maps="full",
         # patch sampling of the training targets (train_or_eval.yaml:70-75)
         patch=SimpleNamespace(use_patch_sampling=True, sample_subject_ratio=0.8, N_patches=6, size=20),
         # where the training entry's rays and patch targets come from: "batch" (as the reference: its dataset samples them on the

@@ -22,16 +22,7 @@ struct UpsSrc {
     int c0;            // first output channel
 };
 
-// torch upsample_bilinear2d(align_corners=True): src = dst * (in-1)/(out-1)
-__device__ __forceinline__ void ups_coord(int dst, int in, int out, int& i0, int& i1, float& l0, float& l1) {
-    float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
-    float src = scale * (float)dst;
-    i0 = (int)src;
-    i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-    l1 = src - (float)i0;
-    l0 = 1.0f - l1;
-}
-
+// (ups_coord, the upsample rule, lives in th_internal.h: K19 uses it too)
 // grid (W/64, H, V*NG): z%NG selects a 64-channel group: 0 lat0, 1 lat1, 2..3 lat2, then either 4..5 lifted
 // colour (NG = 6, CO = 384) or 4 = raw r,g,b,0 (NG = 5, CO = 260).
 // Phase 1: lane = x (coalesced source reads along x), waves stride over the group's 64 channels -> LDS tile.

@@ -730,6 +730,25 @@ int th_composite_bwd(th_ctx* c, const float* raw, const float* z, const th_point
     return th_composite_bwd_launch(raw, z, th_src(rays), white, g_rgb, g_acc, g_depth, g_raw, (hipStream_t)stream);
 }
 
+// ---- training: the pixel-aligned gather read from the latents, and its adjoint (K19, k_latgather.hip) ----
+int th_latent_gather(th_ctx* c, const float* lat0, const float* lat1, const float* lat2, const int32_t* dims, const float* img,
+                     const float* lift_w, const float* lift_b, int V, int H, int W, const float* pts, int P, const float* cams,
+                     const float* scale, float* out, int ldo, float* rgb_s, th_stream stream) {
+    TH_REQUIRE(c && lat0 && lat1 && lat2 && dims && img && lift_w && lift_b && cams && scale, "null argument");
+    TH_REQUIRE(P == 0 || (pts && out && rgb_s), "null argument");
+    return th_latgather_launch(lat0, lat1, lat2, dims, img, lift_w, lift_b, V, H, W, pts, P, cams, scale, out, ldo, rgb_s,
+                               (hipStream_t)stream);
+}
+
+int th_latent_gather_bwd(th_ctx* c, const int32_t* dims, int V, int H, int W, const float* pts, int P, const float* cams,
+                         const float* scale, const float* grad_out, int ldo, float* g_lat0, float* g_lat1, float* g_lat2,
+                         th_stream stream) {
+    TH_REQUIRE(c && dims && cams && scale && g_lat0 && g_lat1 && g_lat2, "null argument");
+    TH_REQUIRE(P == 0 || (pts && grad_out), "null argument");
+    return th_latgather_bwd_launch(dims, V, H, W, pts, P, cams, scale, grad_out, ldo, g_lat0, g_lat1, g_lat2,
+                                   (hipStream_t)stream);
+}
+
 int th_gen_rays(th_ctx* c, const float* K_host, const float* R_host, const float* T_host, const float* bounds_host, int H,
                 int W, float* ray_o, float* ray_d, float* near_out, float* far_out, uint8_t* mask_at_box,
                 th_stream stream) {

@@ -213,6 +213,17 @@ __device__ __forceinline__ void th_project(const float* __restrict__ cam, float 
     v = py / pz;
 }
 
+// ---- the upsample rule shared by K8 (dense map) and K19 (latent gather) ----
+// torch upsample_bilinear2d(align_corners=True): src = dst * (in-1)/(out-1)
+__device__ __forceinline__ void ups_coord(int dst, int in, int out, int& i0, int& i1, float& l0, float& l1) {
+    float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
+    float src = scale * (float)dst;
+    i0 = (int)src;
+    i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+    l1 = src - (float)i0;
+    l0 = 1.0f - l1;
+}
+
 #endif
 
 // ---- context ----------------------------------------------------------------------
@@ -463,6 +474,15 @@ int th_dparf_bwd_launch(const float* pts_smpl, int P, const float* centres, cons
 // k_pixfeat_bwd.hip: grad_map [V,H,W,C] = adjoint of the fp32-row gather applied to grad_out [P,V,ldo]; clears the map itself
 int th_pixgather_bwd_launch(int V, int C, int H, int W, const float* pts_world, int P, const float* cams, const float* scale,
                             const float* grad_out, int ldo, float* grad_map, hipStream_t s);
+// k_latgather.hip (K19): rows [P,V,ldo] = the 384-channel pixel feature sampled straight from the channels-last latents
+// (dims: h0,w0,h1,w1,h2,w2) and the image, + the blended raw colours rgb_s [P,V,4]; the adjoint clears the three latent
+// gradients itself
+int th_latgather_launch(const float* lat0, const float* lat1, const float* lat2, const int* dims, const float* img,
+                        const float* wc, const float* bc, int V, int H, int W, const float* pts_world, int P, const float* cams,
+                        const float* scale, float* out, int ldo, float* rgb_s, hipStream_t s);
+int th_latgather_bwd_launch(const int* dims, int V, int H, int W, const float* pts_world, int P, const float* cams,
+                            const float* scale, const float* grad_out, int ldo, float* g0, float* g1, float* g2,
+                            hipStream_t s);
 // k_pixfeat.hip
 int th_pixgather_launch(const float* map, int V, int C, int H, int W, const float* pts_world,
                         const ThPointSrc* ps, const int32_t* sel, int P, const float* cams, const float* scale,

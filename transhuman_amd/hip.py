@@ -161,6 +161,12 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "th_pixel_gather_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "th_latent_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "th_latent_gather_bwd": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "th_composite_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ThPoints), C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "th_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ThPoints), C.c_int, C.c_void_p,
@@ -1327,6 +1333,57 @@ def pixel_gather_bwd(map_shape, pts_world, cams, scale_xy, grad_out, out=None):
     assert out.shape == (V, H, W, Cc) and out.dtype is torch.float32 and out.is_contiguous()
     _check(lib.th_pixel_gather_bwd(ctx(g.device), V, Cc, H, W, _p(p), P, _p(cams), _p(scale_xy), _p(g), ldo, _p(out), _stream()))
     return out
+
+
+def _latent_dims(shapes):
+    """[(V,h,w,C)] x 3 -> the int32[6] {h0,w0,h1,w1,h2,w2} of th_latent_gather"""
+    (V, h0, w0, c0), (V1, h1, w1, c1), (V2, h2, w2, c2) = (tuple(int(x) for x in sh) for sh in shapes)
+    if (c0, c1, c2) != (64, 64, 128) or V1 != V or V2 != V:
+        raise ValueError(f"latent_gather: channels-last latents [V,h,w,64], [V,h,w,64], [V,h,w,128] expected, not {list(shapes)}")
+    return V, (C.c_int32 * 6)(h0, w0, h1, w1, h2, w2)
+
+
+def _channels_last_latent(t):
+    if t.dtype is not torch.float32 or not t.is_contiguous() or t.dim() != 4:
+        raise ValueError("latent_gather: every latent must be a contiguous float32 [V,h,w,C] tensor")
+    return _f32(t)
+
+
+def latent_gather(lat0, lat1, lat2, lift_w, lift_b, images, pts_world, cams, scale_xy, row_floats=384):
+    """th_latent_gather: the 384-channel pixel feature at the projected points, read from the channels-last latents
+    [V,h,w,64 | 64 | 128] and the images [V,3,H,W] -> (rows [P,V,row_floats], rgb_s [P,V,4])."""
+    lib = load_library()
+    l0, l1, l2 = (_channels_last_latent(t) for t in (lat0, lat1, lat2))
+    V, dims = _latent_dims((l0.shape, l1.shape, l2.shape))
+    img = _f32(images)
+    assert img.shape[0] == V and img.shape[1] == 3
+    H, W = int(img.shape[2]), int(img.shape[3])
+    p = _f32(pts_world).reshape(-1, 3)
+    P, ldo = p.shape[0], int(row_floats)
+    out = torch.empty((P, V, ldo), dtype=torch.float32, device=p.device)
+    rgb_s = torch.empty((P, V, 4), dtype=torch.float32, device=p.device)
+    _check(lib.th_latent_gather(ctx(p.device), _p(l0), _p(l1), _p(l2), dims, _p(img), _p(_f32(lift_w).reshape(128, 3)),
+                                _p(_f32(lift_b).reshape(128)), V, H, W, _p(p), P, _p(cams), _p(scale_xy), _p(out), ldo,
+                                _p(rgb_s), _stream()))
+    return out, rgb_s
+
+
+def latent_gather_bwd(latent_shapes, image_hw, pts_world, cams, scale_xy, grad_out, out=None):
+    """th_latent_gather_bwd: grad_out [P,V,ldo] -> the gradients of the three channels-last latents (latent_shapes), the adjoint
+    of latent_gather with respect to them.  ``out`` (optional, three tensors) is written in full."""
+    lib = load_library()
+    V, dims = _latent_dims(latent_shapes)
+    H, W = (int(x) for x in image_hw)
+    p, g = _f32(pts_world).reshape(-1, 3), _f32(grad_out)
+    P, ldo = p.shape[0], g.shape[-1]
+    assert g.shape == (P, V, ldo)
+    if out is None:
+        out = tuple(torch.empty(tuple(sh), dtype=torch.float32, device=g.device) for sh in latent_shapes)
+    for o, sh in zip(out, latent_shapes):
+        assert tuple(o.shape) == tuple(sh) and o.dtype is torch.float32 and o.is_contiguous()
+    _check(lib.th_latent_gather_bwd(ctx(g.device), dims, V, H, W, _p(p), P, _p(cams), _p(scale_xy), _p(g), ldo, _p(out[0]),
+                                    _p(out[1]), _p(out[2]), _stream()))
+    return tuple(out)
 
 
 def composite_bwd(raw, z, ray_d, g_rgb, g_acc, g_depth, white_bkgd=False):

@@ -13,6 +13,11 @@ them from torch operators like everything else; "device" runs the token blend (K
 compositing (K7) through the HIP forwards with HIP adjoints (``train_ops``), once over all samples before
 the chunk loop.  The encoder and the per-point network stay on torch autograd in both modes.
 
+``cfg.train_maps`` selects what the image features are sampled from: "full" (default) builds the reference's two full-size maps
+(``encode``); "latents" runs the trunk as before and samples its three latents and the images directly at the input vertices
+and at the ray samples (``train_ops.LatentGatherFn``) -- no [V,384,H,W] map, no [V,192,H,W] map, and no gradient
+of either.  It needs the batch on the device, whatever ``cfg.train_kernels`` says.
+
 ``cfg.train_attention`` selects, independently, how the attention inside TransHE's blocks runs: "torch" (default) as three
 torch operators whose autograd keeps a [V, heads, N, N] probability tensor per layer; "device" through the attention kernels
 of the inference path with a HIP backward that recomputes the probabilities tile by tile (``train_ops.AttentionFn``,
@@ -66,6 +71,22 @@ def encode(enc, images):
     lat = [F.interpolate(l, (H, W), mode="bilinear", align_corners=True) for l in lat]
     pix = torch.cat(lat + [enc.upsample_color(images)], dim=1)
     return enc.reduction_layer(pix), pix
+
+
+def _maps_mode(value):
+    mode = str(value)
+    if mode not in ("full", "latents"):
+        raise ValueError(f"cfg.train_maps must be 'full' or 'latents', not {mode!r}")
+    return mode
+
+
+def latent_features(enc, images, cams, scale):
+    """cfg.train_maps = "latents": the trunk as in ``encode`` (stock modules, torch autograd), each latent channels-last once;
+    returns ``gather(points [N,3]) -> [N,V,384]``, the rows ``sample_map(pix, ...)`` would give (K19)"""
+    from . import train_ops
+    lat = [l.permute(0, 2, 3, 1).contiguous() for l in enc.trunk(images, fused_bn=False)]
+    lift = enc.upsample_color
+    return lambda pts: train_ops.LatentGatherFn.apply(*lat, lift.weight, lift.bias, images, pts, cams, scale)
 
 
 def project(x, R, T, K):
@@ -257,6 +278,11 @@ def render(renderer, batch, chunk=32768):
         from .. import hip
         raise hip.HipError("cfg.train_vit_dense = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
                            "use 'torch' for a CPU batch")
+    maps = _maps_mode(getattr(cfg, "train_maps", "full"))
+    if maps == "latents" and not ray_o.is_cuda:
+        from .. import hip
+        raise hip.HipError("cfg.train_maps = 'latents' needs the batch on an MI355X (the HIP kernels have no CPU form); "
+                           "use 'full' for a CPU batch")
     near, far = batch["near"][0], batch["far"][0]
     dev = ray_o.device
     S = int(cfg.N_samples)
@@ -269,9 +295,17 @@ def render(renderer, batch, chunk=32768):
     V = images.shape[0]
     R_in, T_in, K_in = (batch[k][0].reshape(V, *sh) for k, sh in (("input_R", (3, 3)), ("input_T", (3, 1)), ("input_K", (3, 3))))
     image_shape = batch["input_imgs"][0].shape[-2:]
-    hol, pix = encode(net.encoder, images)
     verts_in = batch["input_smpl_vertice"][0][0]
-    painted = sample_map(hol, project(verts_in, R_in, T_in, K_in), net.encoder, image_shape).permute(0, 2, 1)
+    if maps == "latents":
+        from .. import hip
+        # a 1 x 1 convolution commutes with bilinear sampling: reduction_layer on the gathered rows (k_encoder.hip does the same)
+        gather = latent_features(net.encoder, images, hip.pack_cams(R_in, T_in, K_in),
+                                 hip.feat_scale(net.encoder.feat_scale(*images.shape[2:]), image_shape, dev))
+        painted = _lin(net.encoder.reduction_layer, gather(verts_in)).permute(1, 0, 2)
+        f_lat = gather(xyz)                                # once over all P samples, split per chunk below
+    else:
+        hol, pix = encode(net.encoder, images)
+        painted = sample_map(hol, project(verts_in, R_in, T_in, K_in), net.encoder, image_shape).permute(0, 2, 1)
     if cfg.rasterize:
         painted = painted * batch["input_vizmaps"][0][0][..., None].to(painted.dtype)              # :181-182
     nv = verts_in.shape[0]
@@ -291,8 +325,11 @@ def render(renderer, batch, chunk=32768):
         if int(cfg.KNN) != 7 or float(cfg.KNN_DIST_ALPHA) != 0.5:
             raise hip.HipError("cfg.train_kernels = 'device': K4 is built for KNN = 7, KNN_DIST_ALPHA = 0.5")
         # K5 and K4 once over all P samples: one map-sized gradient per step, nothing of the blends kept for backward
-        scale = hip.feat_scale(net.encoder.feat_scale(*pix.shape[2:]), image_shape, dev)
-        f_all = train_ops.PixelGatherFn.apply(pix.permute(0, 2, 3, 1).contiguous(), xyz, hip.pack_cams(R_in, T_in, K_in), scale)
+        if maps == "latents":
+            f_all = f_lat
+        else:
+            scale = hip.feat_scale(net.encoder.feat_scale(*pix.shape[2:]), image_shape, dev)
+            f_all = train_ops.PixelGatherFn.apply(pix.permute(0, 2, 3, 1).contiguous(), xyz, hip.pack_cams(R_in, T_in, K_in), scale)
         h_all = train_ops.HumanRepresentationFn.apply(tokens.contiguous(), pts_s, centres, rot)
         for f, h, vd in zip(f_all.split(chunk), h_all.split(chunk), viewdir.split(chunk)):
             raws.append(point_network(net, h[..., :255], f, vd))
@@ -304,7 +341,10 @@ def render(renderer, batch, chunk=32768):
         return {"rgb_map": rgb[None], "acc_map": acc[None], "depth_map": depth[None]}
     for s0 in range(0, xyz.shape[0], chunk):                       # batchify_rays :607-656 without a mask
         x = xyz[s0:s0 + chunk]
-        f = sample_map(pix, project(x, R_in, T_in, K_in), net.encoder, image_shape).permute(2, 0, 1)
+        if maps == "latents":
+            f = f_lat[s0:s0 + chunk]
+        else:
+            f = sample_map(pix, project(x, R_in, T_in, K_in), net.encoder, image_shape).permute(2, 0, 1)
         h = human_representation(net, pts_s[s0:s0 + chunk], centres, rot, tokens, int(cfg.KNN), float(cfg.KNN_DIST_ALPHA))
         raws.append(point_network(net, h, f, viewdir[s0:s0 + chunk]))
     raw = torch.cat(raws, 0).view(-1, S, 4)

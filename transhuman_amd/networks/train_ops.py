@@ -8,6 +8,12 @@ the compositing (K7) through the HIP forwards that the inference paths use, with
     PixelGatherFn           map    [V,H,W,C]     -> rows [P,V,C]       gradient: map
     CompositeFn             raw    [R,S,4]       -> rgb, acc, depth    gradient: raw
 
+``cfg.train_maps = "latents"`` replaces the encoder's tail -- upsample, concatenate, 1 x 1 reduction, sample -- by one gather
+that reads the three latents and the images at the projected points (K19, k_latgather.hip): a bilinear sample of a bilinearly
+upsampled latent is a linear combination of at most 3 x 3 of its texels, so neither full-size map nor its gradient exists:
+
+    LatentGatherFn          lat0..2 [V,h,w,C], lift -> rows [P,V,384]  gradient: the latents, the lift    keeps rgb_s [P,V,4]
+
 ``cfg.train_attention = "device"`` does the same for the attention of every TransHE block:
 
     AttentionFn             qkv    [V,N,3 C]     -> [V,N,C]            gradient: qkv         (k_vit.hip / k_vit_bwd.hip)
@@ -80,6 +86,35 @@ class PixelGatherFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         pts_world, cams, scale_xy = ctx.saved_tensors
         return hip.pixel_gather_bwd(ctx.map_shape, pts_world, cams, scale_xy, grad_out), None, None, None
+
+
+class LatentGatherFn(torch.autograd.Function):
+    """SpatialEncoder.forward's tail (encoder.py:133-146) + get_pixel_aligned_feature (if_clight_renderer.py:210-269) without the
+    map between them: the channels-last latents lat0 [V,h0,w0,64], lat1 [V,h1,w1,64], lat2 [V,h2,w2,128] and the colour lift
+    (upsample_color's weight [128,3(,1,1)] and bias) -> rows [P,V,384].  Kept for the backward: the geometry and the blended
+    raw colours rgb_s [P,V,4] (the lift's weight gradient)."""
+
+    @staticmethod
+    def forward(ctx, lat0, lat1, lat2, lift_w, lift_b, images, pts_world, cams, scale_xy):
+        _no_grad_inputs("LatentGatherFn", images=images, pts_world=pts_world, cams=cams, scale_xy=scale_xy)
+        _on_device("LatentGatherFn", lat0)
+        rows, rgb_s = hip.latent_gather(lat0.detach(), lat1.detach(), lat2.detach(), lift_w.detach(), lift_b.detach(), images,
+                                        pts_world, cams, scale_xy)
+        ctx.save_for_backward(pts_world, cams, scale_xy, rgb_s)
+        ctx.shapes = (tuple(lat0.shape), tuple(lat1.shape), tuple(lat2.shape))
+        ctx.image_hw = tuple(images.shape[2:])
+        ctx.lift_w_shape = tuple(lift_w.shape)
+        return rows
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pts_world, cams, scale_xy, rgb_s = ctx.saved_tensors
+        g = grad_out.contiguous()
+        g0, g1, g2 = hip.latent_gather_bwd(ctx.shapes, ctx.image_hw, pts_world, cams, scale_xy, g)
+        # the lift: 128 x 3 + 128 numbers, one small reduction over the rows (not the hot path)
+        gl = g[..., 256:384].reshape(-1, 128)
+        g_w = (gl.t() @ rgb_s.reshape(-1, 4)[:, :3]).reshape(ctx.lift_w_shape)
+        return g0, g1, g2, g_w, gl.sum(0), None, None, None, None
 
 
 class CompositeFn(torch.autograd.Function):
@@ -254,6 +289,88 @@ def pixel_map_grad_oracle(uv, scale_xy, H, W, grad_out):
         for v in range(V):
             np.add.at(out[v], (yi[v], xi[v]), (wt[v] * ok[v])[:, None] * g[:, v])
     return out
+
+
+def _upsample_taps64(n_out, n_in):
+    """upsample_bilinear2d(align_corners=True) along one axis: src = dst (in - 1) / (out - 1) -> i0, i1 [out] int64 and
+    l0, l1 [out] float64 (ups_coord of th_internal.h in float64)"""
+    scale = (n_in - 1) / (n_out - 1) if n_out > 1 else 0.0
+    src = scale * np.arange(n_out, dtype=np.float64)
+    i0 = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    l1 = src - i0
+    return i0, i1, 1.0 - l1, l1
+
+
+def _grid_corners64(uv, scale_xy, H, W):
+    """grid_sample (bilinear, align_corners, border) of an H x W map at pixel coordinates uv [V,N,2]: the four corners as
+    (y [V,N] int64, x [V,N] int64, weight [V,N] float64); a corner outside the map carries weight 0"""
+    uv, s = _np64(uv), _np64(scale_xy)
+    gx, gy = uv[..., 0] * s[0] - 1.0, uv[..., 1] * s[1] - 1.0
+    ix = np.clip(((gx + 1.0) / 2.0) * (W - 1), 0.0, W - 1.0)
+    iy = np.clip(((gy + 1.0) / 2.0) * (H - 1), 0.0, H - 1.0)
+    x0, y0 = np.floor(ix), np.floor(iy)
+    x1, y1 = x0 + 1.0, y0 + 1.0
+    out = []
+    for xs, ys, wt in ((x0, y0, (x1 - ix) * (y1 - iy)), (x1, y0, (ix - x0) * (y1 - iy)),
+                       (x0, y1, (x1 - ix) * (iy - y0)), (x1, y1, (ix - x0) * (iy - y0))):
+        ok = (xs <= W - 1) & (ys <= H - 1)
+        out.append((np.minimum(ys, H - 1).astype(np.int64), np.minimum(xs, W - 1).astype(np.int64), wt * ok))
+    return out
+
+
+def _latent_taps64(uv, scale_xy, H, W, h, w):
+    """the 16 composite taps of one latent level: (row [V,N], column [V,N], coefficient [V,N]) each"""
+    ry0, ry1, ly0, ly1 = _upsample_taps64(H, h)
+    rx0, rx1, lx0, lx1 = _upsample_taps64(W, w)
+    taps = []
+    for yi, xi, wt in _grid_corners64(uv, scale_xy, H, W):
+        for ry, ly in ((ry0, ly0), (ry1, ly1)):
+            for rx, lx in ((rx0, lx0), (rx1, lx1)):
+                taps.append((ry[yi], rx[xi], wt * ly[yi] * lx[xi]))
+    return taps
+
+
+def latent_gather_oracle(lat0, lat1, lat2, lift_w, lift_b, images, uv, scale_xy):
+    """LatentGatherFn's forward in float64: channels-last latents [V,h,w,C], the lift (weight [128,3], bias [128]), images
+    [V,3,H,W], uv [V,N,2] pixel coordinates (autograd_path.project), scale_xy [2] -> (rows [N,V,384], rgb_s [N,V,4])"""
+    lats = [_np64(l) for l in (lat0, lat1, lat2)]
+    img, wl, bl = _np64(images), _np64(lift_w).reshape(128, 3), _np64(lift_b).reshape(128)
+    V, _, H, W = img.shape
+    N = _np64(uv).shape[1]
+    rows, rgb_s = np.zeros((N, V, 384)), np.zeros((N, V, 4))
+    c0 = 0
+    for lat in lats:
+        Cl = lat.shape[-1]
+        for ry, rx, cf in _latent_taps64(uv, scale_xy, H, W, lat.shape[1], lat.shape[2]):
+            for v in range(V):
+                rows[:, v, c0:c0 + Cl] += cf[v][:, None] * lat[v][ry[v], rx[v]]
+        c0 += Cl
+    for yi, xi, wt in _grid_corners64(uv, scale_xy, H, W):
+        for v in range(V):
+            rgb = img[v][:, yi[v], xi[v]].T                                   # [N,3]
+            rows[:, v, 256:] += wt[v][:, None] * (rgb @ wl.T + bl)
+            rgb_s[:, v, :3] += wt[v][:, None] * rgb
+    return rows, rgb_s
+
+
+def latent_grad_oracle(uv, scale_xy, image_hw, latent_shapes, rgb_s, grad_out):
+    """LatentGatherFn's backward in float64: grad_out [N,V,>=384] -> (g_lat0, g_lat1, g_lat2 in the channels-last latent_shapes,
+    g_lift_w [128,3], g_lift_b [128]); rgb_s [N,V,4] as the forward returned it"""
+    g = _np64(grad_out)
+    H, W = (int(x) for x in image_hw)
+    outs = []
+    c0 = 0
+    for sh in latent_shapes:
+        V, h, w, Cl = (int(x) for x in sh)
+        out = np.zeros((V, h, w, Cl))
+        for ry, rx, cf in _latent_taps64(uv, scale_xy, H, W, h, w):
+            for v in range(V):
+                np.add.at(out[v], (ry[v], rx[v]), cf[v][:, None] * g[:, v, c0:c0 + Cl])
+        outs.append(out)
+        c0 += Cl
+    gl = g[..., 256:384].reshape(-1, 128)
+    return (*outs, gl.T @ _np64(rgb_s).reshape(-1, 4)[:, :3], gl.sum(0))
 
 
 def composite_grad_oracle(raw, z, ray_d, white_bkgd, g_rgb, g_acc, g_depth):
