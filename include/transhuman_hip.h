@@ -408,6 +408,35 @@ size_t th_layernorm_bwd_workspace_bytes(int M, int dim);
 int th_layernorm_bwd(th_ctx* ctx, const float* x, int ldx, int M, int dim, const float* w, float eps, const float* g, int ldg,
                      float* g_x, int ldgx, float* g_w, float* g_b, void* workspace, size_t workspace_bytes, th_stream stream);
 
+/* The training form of the per-point network's layers (addition, ABI 12; k_pointnet_bwd.hip).  Same arithmetic,
+ * conventions and refusals as th_linear_train_forward / th_linear_bwd form 0 above.
+ *
+ * th_linear_relu_forward: Y [M, out_f] = relu(A W^T + b), the ReLU in the GEMM's epilogue (no extra pass).
+ * th_linear_relu_bwd takes A, Y and g_Y = dL/dY and writes what th_linear_bwd form 0 writes for g_C = g_Y * [Y > 0] (the gradient
+ * at Y == 0 is 0): g_W, g_b (may be NULL) and g_A (NULL skips it).  The gate is applied on g_Y's way into the weight-gradient
+ * kernel; the input gradient costs one elementwise pass over g_Y into the workspace.  g_Y is not modified.  The same
+ * th_wgrad_chunk_rows() chunks added in chunk order: no atomics, two runs agree bit for bit, nothing depends on what the
+ * workspace held.  g_A must not overlap A, Y or g_Y.
+ *
+ * th_xview_attention: the cross-view attention of the network (cross_transformer.py:128-149) on its own.  kvp, kvs [P, V, 384]
+ * hold the rows [key(128) | value(256)] of the pixel and of the token branch; A[j][i] = kp_j . ks_i / sqrt(128), softmax over j,
+ * n_i = vs_i + sum_j A[j][i] vp_j -> n [P, V, 256].  P >= 1, V in 1..4, pointers 16-byte aligned.
+ * th_xview_attention_bwd: from g_n [P, V, 256] the gradients g_kvp, g_kvs [P, V, 384] in the layout of the inputs:
+ *     g_vs_i = g_n_i,  g_vp_j = sum_i A[j][i] g_n_i,  dA[j][i] = vp_j . g_n_i,  dS[j][i] = A[j][i] (dA[j][i] - sum_j' A[j'][i] dA[j'][i]),
+ *     g_kp_j = sum_i dS[j][i] ks_i / sqrt(128),  g_ks_i = sum_j dS[j][i] kp_j / sqrt(128).
+ * The probabilities are recomputed from the keys with the forward's statements (bit for bit the forward's); nothing P x V x V
+ * is stored; no atomics: two runs agree bit for bit.  At V = 1 both key blocks are exactly 0 and both value blocks are g_n. */
+size_t th_linear_relu_workspace_bytes(int M, int out_f, int in_f);
+int th_linear_relu_forward(th_ctx* ctx, const float* A, int lda, int M, const th_linear* lin, float* Y, int ldy, void* workspace,
+                           size_t workspace_bytes, th_stream stream);
+size_t th_linear_relu_bwd_workspace_bytes(int M, int out_f, int in_f);
+int th_linear_relu_bwd(th_ctx* ctx, const float* A, int lda, const float* Y, int ldy, int M, const th_linear* lin,
+                       const float* g_Y, int ldg, float* g_A, int ldga, float* g_W, float* g_b, void* workspace,
+                       size_t workspace_bytes, th_stream stream);
+int th_xview_attention(th_ctx* ctx, const float* kvp, const float* kvs, int P, int V, float* n, th_stream stream);
+int th_xview_attention_bwd(th_ctx* ctx, const float* kvp, const float* kvs, const float* g_n, int P, int V, float* g_kvp,
+                           float* g_kvs, th_stream stream);
+
 /* ---- K4: DPaRF encoding --------------------------------------------------- */
 /* Network.get_human_representation, cross_transformer.py:158-205.
  * pts_smpl [P,3]; centres [N_c,3]; rot [N_c,9]; tokens [V,N_c,192];

@@ -6,7 +6,8 @@ the HIP adjoints of K17, transhuman_amd/networks/train_ops.py).
     timeout -k 10 900 python tools/train_step_time.py [--steps 10] [--warmup 2] [--rocprof DIR]
 
 --maps full,latents repeats every mode with cfg.train_maps = "latents" (K19: the encoder's latents sampled directly) in the same
-process.  Prints one JSON line.  Per mode: median and minimum wall time of a step over --steps steps after --warmup (host clock around
+process; --point-net torch,device does the same with cfg.train_point_net = "device" (K20: the per-point network layer by layer
+on the device; keys gain '+pointnet').  Prints one JSON line.  Per mode: median and minimum wall time of a step over --steps steps after --warmup (host clock around
 forward + backward with a device synchronisation at both ends) and torch.cuda.max_memory_allocated of the timed steps; the
 largest difference of the outputs and of every parameter gradient between the two modes; and, with --rocprof DIR, the device
 time of the K17 kernels per step from `rocprofv3 --kernel-trace --stats` over a short run of the "device" mode in a fresh child
@@ -106,6 +107,8 @@ def main():
     ap.add_argument("--modes", default="torch,device")
     ap.add_argument("--maps", default="full", help="comma list of cfg.train_maps values; every mode runs once per value "
                                                    "(results of a value other than 'full' are keyed '<mode>+<value>')")
+    ap.add_argument("--point-net", default="torch", help="comma list of cfg.train_point_net values; every mode runs once per value "
+                                                         "(results of 'device' are keyed '<mode>[+<maps>]+pointnet')")
     ap.add_argument("--rocprof", default=None, metavar="DIR", help="also trace a short 'device' run under rocprofv3 into DIR")
     args = ap.parse_args()
     res = {"shape": {"rays": RAYS, "samples": SAMPLES, "views": VIEWS, "n_clusters": NC, "image": [SIZE, SIZE]}}
@@ -126,18 +129,26 @@ def main():
     try:
         for maps in args.maps.split(","):
             cfg.train_maps = maps
-            for mode in args.modes.split(","):
-                key = mode if maps == "full" else f"{mode}+{maps}"
-                res[key], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
-                seen[key] = (outs, grads)
+            for point_net in args.point_net.split(","):
+                cfg.train_point_net = point_net
+                for mode in args.modes.split(","):
+                    key = (mode if maps == "full" else f"{mode}+{maps}") + ("" if point_net == "torch" else "+pointnet")
+                    res[key], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
+                    seen[key] = (outs, grads)
     finally:
-        cfg.train_kernels, cfg.train_maps = "torch", "full"
+        cfg.train_kernels, cfg.train_maps, cfg.train_point_net = "torch", "full", "torch"
     if "torch" in seen and "device" in seen:
         (o0, g0), (o1, g1) = seen["torch"], seen["device"]
         res["device_vs_torch"] = {
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
             "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0)}
-    for key in [k for k in seen if "+" in k and k.split("+")[0] in seen]:
+    for key in [k for k in seen if k.endswith("+pointnet") and k[:-9] in seen]:
+        (o0, g0), (o1, g1) = seen[key[:-9]], seen[key]
+        res[key + "_vs_torch_point_net"] = {
+            "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
+            "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0
+                                            if not k.endswith("spatial_key_value_0.key_embed.bias"))}
+    for key in [k for k in seen if "+" in k and not k.endswith("+pointnet") and k.split("+")[0] in seen]:
         (o0, g0), (o1, g1) = seen[key.split("+")[0]], seen[key]
         res[key + "_vs_full"] = {
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),

@@ -77,6 +77,10 @@ def _defaults():
         # [V,384,H,W], holder_feat_map [V,192,H,W]) and their gradients; "latents" samples the encoder's three latents and the
         # images directly at the vertices and the ray samples (train_ops.LatentGatherFn, K19) -- neither map exists
         train_maps="full",
+        # the per-point network (MLP_forward_ori) in the training entry: "torch" composes it from torch operators under torch
+        # autograd; "device" runs it layer by layer on the fp32 MFMA GEMMs of the inference path with HIP backwards
+        # (autograd_path.point_network_device: train_ops.ReluLinearFn / LinearFn / CrossViewAttentionFn, K20)
+        train_point_net="torch",
         # patch sampling of the training targets (train_or_eval.yaml:70-75)
         patch=SimpleNamespace(use_patch_sampling=True, sample_subject_ratio=0.8, N_patches=6, size=20),
         # where the training entry's rays and patch targets come from: "batch" (as the reference: its dataset samples them on the

@@ -67,6 +67,19 @@ __global__ __launch_bounds__(256) void xattn_kernel(const float* __restrict__ kv
     }
 }
 
+// the same kernel on its own (th_xview_attention, k_pointnet_bwd.hip)
+int th_xattn_launch(const float* kvp, const float* kvs, int P, int V, float* n, hipStream_t s) {
+    dim3 g4(th_cdiv(P, 4));
+    switch (V) {
+        case 1: hipLaunchKernelGGL(xattn_kernel<1>, g4, dim3(256), 0, s, kvp, kvs, P, n); break;
+        case 2: hipLaunchKernelGGL(xattn_kernel<2>, g4, dim3(256), 0, s, kvp, kvs, P, n); break;
+        case 3: hipLaunchKernelGGL(xattn_kernel<3>, g4, dim3(256), 0, s, kvp, kvs, P, n); break;
+        default: hipLaunchKernelGGL(xattn_kernel<4>, g4, dim3(256), 0, s, kvp, kvs, P, n); break;
+    }
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
 // combine_interleaved(..., "average") (cross_transformer.py:61-72): mean over views
 __global__ void view_mean_kernel(const float* __restrict__ x, int P, int V, int C, float* __restrict__ out) {
     long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;

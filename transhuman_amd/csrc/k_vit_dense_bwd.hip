@@ -230,11 +230,12 @@ __global__ void gelu_fwd_kernel(const float* __restrict__ U, int ldu, float* __r
 }
 
 // grid (ceil(out / 64), ceil(in / 64), chunks); part[chunk][out in + out]
-template <int FORM>
+// GATE (k_pointnet_bwd.hip, the layers with a ReLU on their output): g_C = G * [Y > 0], applied on G's way into LDS
+template <int FORM, bool GATE = false>
 __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ A,
                                                     int lda, int M, int out_f, int in_f, const float* __restrict__ stats,
                                                     const float* __restrict__ ln_w, const float* __restrict__ ln_b,
-                                                    float* __restrict__ part) {
+                                                    float* __restrict__ part, const float* __restrict__ Y, int ldy) {
     __shared__ __attribute__((aligned(16))) float Gs[WG_ROWS * WG_STRIDE];
     __shared__ __attribute__((aligned(16))) float As[WG_ROWS * WG_STRIDE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -254,6 +255,11 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ G,
             float4 g = make_float4(0.f, 0.f, 0.f, 0.f), a = g;
             if (gm < m_hi) {
                 if (o0 + c < out_f) g = *reinterpret_cast<const float4*>(G + (long long)gm * ldg + o0 + c);
+                if (GATE && o0 + c < out_f) {
+                    const float4 y = *reinterpret_cast<const float4*>(Y + (long long)gm * ldy + o0 + c);
+                    g.x = y.x > 0.f ? g.x : 0.f; g.y = y.y > 0.f ? g.y : 0.f;
+                    g.z = y.z > 0.f ? g.z : 0.f; g.w = y.w > 0.f ? g.w : 0.f;
+                }
                 if (i0 + c < in_f) {
                     a = *reinterpret_cast<const float4*>(A + (long long)gm * lda + i0 + c);
                     if (FORM == OP_LN) {
@@ -344,6 +350,32 @@ static VdBwdWs vd_bwd_layout(int M, int out_f, int in_f, int form) {
     return w;
 }
 
+// ---- shared with k_pointnet_bwd.hip (th_internal.h) ----
+int th_wgrad_chunks(int M) { return vd_chunks(M); }
+
+int th_pack_linear_t(const float* W, int out_f, int in_f, void* storage, ThPacked* P, hipStream_t s) {
+    P->N = in_f; P->K = out_f; P->NB = in_f / 16; P->KB = out_f / 16;
+    P->w = (float*)storage;
+    P->b = (float*)((char*)storage + th_align((size_t)P->NB * P->KB * 256 * sizeof(float)));
+    const long long total = (long long)P->NB * P->KB * 256;
+    hipLaunchKernelGGL(pack_linear_t_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, s, W,
+                       out_f, in_f, P->NB, P->KB, P->w, P->b);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_wgrad_relu_launch(const float* g_Y, int ldg, const float* Y, int ldy, const float* A, int lda, int M, int out_f, int in_f,
+                         float* part, float* g_W, float* g_b, hipStream_t s) {
+    const int chunks = vd_chunks(M);
+    dim3 grid(th_cdiv(out_f, WG_TILE), th_cdiv(in_f, WG_TILE), chunks);
+    hipLaunchKernelGGL((wgrad_kernel<OP_PLAIN, true>), grid, dim3(256), 0, s, g_Y, ldg, A, lda, M, out_f, in_f, nullptr, nullptr,
+                       nullptr, part, Y, ldy);
+    const long long n1 = (long long)out_f * in_f, n = n1 + out_f;
+    hipLaunchKernelGGL(reduce_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, part, chunks, n, n1, n, g_W, g_b);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
 static int vd_ln_bwd_launch(const float* x, int ldx, int M, int dim, const float* w, float eps, const float* g, int ldg,
                             float* gx, int ldgx, float* g_w, float* g_b, float* part, hipStream_t s) {
     const int blocks = vd_ln_blocks(M);
@@ -425,13 +457,7 @@ int th_linear_bwd(th_ctx* c, const float* A, int lda, int M, int form, const flo
     }
     if (g_A != nullptr) {
         ThPacked P;
-        P.N = in_f; P.K = out_f; P.NB = in_f / 16; P.KB = out_f / 16;
-        P.w = (float*)(base + L.pack);
-        P.b = (float*)(base + L.pack + th_align((size_t)P.NB * P.KB * 256 * sizeof(float)));
-        const long long total = (long long)P.NB * P.KB * 256;
-        hipLaunchKernelGGL(pack_linear_t_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, s,
-                           lin->w, out_f, in_f, P.NB, P.KB, P.w, P.b);
-        TH_LAUNCH_CHECK();
+        TH_TRY(th_pack_linear_t(lin->w, out_f, in_f, base + L.pack, &P, s));
         TH_TRY(th_gemm(g_C, ldg, M, P, TH_ACT_NONE, g_A, ldga, s));
         if (form == OP_GELU) {
             const long long n4 = (long long)M * (in_f >> 2);
@@ -446,13 +472,14 @@ int th_linear_bwd(th_ctx* c, const float* A, int lda, int M, int form, const flo
     const int chunks = vd_chunks(M);
     dim3 grid(th_cdiv(out_f, WG_TILE), th_cdiv(in_f, WG_TILE), chunks);
     if (form == OP_LN)
-        hipLaunchKernelGGL(wgrad_kernel<OP_LN>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, stats, ln_w, ln_b, part);
+        hipLaunchKernelGGL(wgrad_kernel<OP_LN>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, stats, ln_w, ln_b, part,
+                           nullptr, 0);
     else if (form == OP_GELU)
         hipLaunchKernelGGL(wgrad_kernel<OP_GELU>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, nullptr, nullptr,
-                           nullptr, part);
+                           nullptr, part, nullptr, 0);
     else
         hipLaunchKernelGGL(wgrad_kernel<OP_PLAIN>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, nullptr, nullptr,
-                           nullptr, part);
+                           nullptr, part, nullptr, 0);
     const long long n1 = (long long)out_f * in_f, n = n1 + out_f;
     hipLaunchKernelGGL(reduce_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, part, chunks, n, n1, n, g_W, g_b);
     TH_LAUNCH_CHECK();

@@ -144,6 +144,16 @@ SYMBOLS = {
     "th_layernorm_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "th_layernorm_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
                                    C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_linear_relu_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_linear_relu_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ThLinear), C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_linear_relu_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_linear_relu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(ThLinear),
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
+    "th_xview_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "th_xview_attention_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     "th_dparf_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "th_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -1174,6 +1184,73 @@ def linear_bwd(a, weight, g_out, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1
     _check(lib.th_linear_bwd(ctx(a.device), _p(a2), in_f, M, int(form), _p(lw), _p(lb), float(eps), C.byref(lin), _p(g2), out_f,
                              _p(g_a), in_f, _p(g_w), _p(g_b), _p(g_lw), _p(g_lb), _p(ws), ws.numel(), _stream()))
     return g_a, g_w, g_b, g_lw, g_lb
+
+
+def linear_relu_forward(a, weight, bias):
+    """th_linear_relu_forward: relu(a W^T + b), a [..., in] -> [..., out] (the ReLU in the GEMM's epilogue)"""
+    lib = load_library()
+    fn = "linear_relu_forward"
+    w = _train_rows(fn, weight)
+    out_f, in_f = w.shape
+    a2 = _train_rows(fn, a, in_f)
+    b = _train_vec(fn, bias, out_f)
+    M = a2.shape[0]
+    lin = ThLinear(_p(w), _p(b), out_f, in_f)
+    out = torch.empty((*a.shape[:-1], out_f), dtype=torch.float32, device=a.device)
+    ws = _ws(lib.th_linear_relu_workspace_bytes(M, out_f, in_f), a.device)
+    _check(lib.th_linear_relu_forward(ctx(a.device), _p(a2), in_f, M, C.byref(lin), _p(out), out_f, _p(ws), ws.numel(), _stream()))
+    return out
+
+
+def linear_relu_bwd(a, y, weight, g_out, need_input=True, need_bias=True):
+    """th_linear_relu_bwd: the gradients of linear_relu_forward from its output y and g_out [..., out] -> (g_a or None, g_W,
+    g_b or None).  Bit-identical from run to run."""
+    lib = load_library()
+    fn = "linear_relu_bwd"
+    w = _train_rows(fn, weight)
+    out_f, in_f = w.shape
+    a2, y2, g2 = _train_rows(fn, a, in_f), _train_rows(fn, y, out_f), _train_rows(fn, g_out, out_f)
+    if not a2.shape[0] == y2.shape[0] == g2.shape[0]:
+        raise ValueError(f"{fn}: {a2.shape[0]} operand rows, {y2.shape[0]} output rows, {g2.shape[0]} gradient rows")
+    M = a2.shape[0]
+    lin = ThLinear(_p(w), None, out_f, in_f)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=a.device)
+    g_a = new(*a.shape) if need_input else None
+    g_w = new(out_f, in_f)
+    g_b = new(out_f) if need_bias else None
+    ws = _ws(lib.th_linear_relu_bwd_workspace_bytes(M, out_f, in_f), a.device)
+    _check(lib.th_linear_relu_bwd(ctx(a.device), _p(a2), in_f, _p(y2), out_f, M, C.byref(lin), _p(g2), out_f, _p(g_a), in_f,
+                                  _p(g_w), _p(g_b), _p(ws), ws.numel(), _stream()))
+    return g_a, g_w, g_b
+
+
+def _xview_rows(fn, kvp, kvs):
+    a, b = _train_rows(fn, kvp, 384), _train_rows(fn, kvs, 384)
+    if kvp.dim() != 3 or kvp.shape != kvs.shape or not 1 <= kvp.shape[1] <= 4 or kvp.shape[0] < 1:
+        raise ValueError(f"{fn}: kvp and kvs must both be [P, V, 384] with P >= 1 and V in 1..4")
+    return a, b, int(kvp.shape[0]), int(kvp.shape[1])
+
+
+def xview_attention(kvp, kvs):
+    """th_xview_attention: the rows [key(128) | value(256)] of the pixel and token branch, [P,V,384] each -> n [P,V,256]"""
+    lib = load_library()
+    a, b, P, V = _xview_rows("xview_attention", kvp, kvs)
+    n = torch.empty((P, V, 256), dtype=torch.float32, device=kvp.device)
+    _check(lib.th_xview_attention(ctx(kvp.device), _p(a), _p(b), P, V, _p(n), _stream()))
+    return n
+
+
+def xview_attention_bwd(kvp, kvs, g_n):
+    """th_xview_attention_bwd: g_n [P,V,256] -> (g_kvp, g_kvs) [P,V,384]; bit-identical from run to run"""
+    lib = load_library()
+    fn = "xview_attention_bwd"
+    a, b, P, V = _xview_rows(fn, kvp, kvs)
+    g = _train_rows(fn, g_n, 256)
+    if tuple(g_n.shape) != (P, V, 256):
+        raise ValueError(f"{fn}: g_n must be [{P}, {V}, 256]")
+    g_kvp, g_kvs = torch.empty_like(kvp), torch.empty_like(kvs)
+    _check(lib.th_xview_attention_bwd(ctx(kvp.device), _p(a), _p(b), _p(g), P, V, _p(g_kvp), _p(g_kvs), _stream()))
+    return g_kvp, g_kvs
 
 
 def layernorm_train_forward(x, weight, bias, eps=1e-6):

@@ -11,7 +11,7 @@ rendering hot path and not a fallback of it -- inference calls (``render_fast``,
 ``cfg.train_kernels`` selects how the three non-GEMM stages around the per-point network run: "torch" (default) composes
 them from torch operators like everything else; "device" runs the token blend (K4), the pixel-aligned gather (K5) and the
 compositing (K7) through the HIP forwards with HIP adjoints (``train_ops``), once over all samples before
-the chunk loop.  The encoder and the per-point network stay on torch autograd in both modes.
+the chunk loop.  The encoder stays on torch autograd in both modes; the per-point network follows ``cfg.train_point_net`` (below).
 
 ``cfg.train_maps`` selects what the image features are sampled from: "full" (default) builds the reference's two full-size maps
 (``encode``); "latents" runs the trunk as before and samples its three latents and the images directly at the input vertices
@@ -28,6 +28,11 @@ and GELU: "torch" (default) as torch modules under torch autograd; "device" thro
 path with HIP backwards that recompute LN(x) and gelu(u) instead of keeping them and add their partial sums in a fixed order
 (``train_ops.NormLinearFn`` / ``LinearFn`` / ``GeluLinearFn`` / ``LayerNormFn``): with both switches on "device" TransHE's
 gradient is bit-identical from run to run.  The residual adds and the positional table stay torch operators.
+
+``cfg.train_point_net`` selects, independently of the other four, how the per-point network runs: "torch" (default) is
+``point_network`` under torch autograd; "device" is ``point_network_device``: the layer-by-layer form of the inference path
+(th_mlp_forward) on the fp32 MFMA GEMMs, every ReLU in its layer's epilogue, with HIP backwards (``train_ops.ReluLinearFn`` /
+``LinearFn`` / ``CrossViewAttentionFn``).  View means and residual adds stay torch operators.
 
 Pinned by ``oracle/gen_golden_train.py`` (the real reference imported in the survey container: outputs and parameter
 gradients of one training step's forward/backward on a synthetic patch -> ``tests/golden/g18_train_step.npz``) and
@@ -238,6 +243,57 @@ def point_network(net, h, f, viewdir):
     return torch.cat([rgb, sigma], dim=1)
 
 
+def _point_net_mode(value):
+    mode = str(value)
+    if mode not in ("torch", "device"):
+        raise ValueError(f"cfg.train_point_net must be 'torch' or 'device', not {mode!r}")
+    return mode
+
+
+def _point_net_device_ops():
+    """the three operators point_network_device is composed from, on the HIP Functions of train_ops"""
+    from . import train_ops as T
+    return {"linear": T.LinearFn.apply, "relu_linear": T.ReluLinearFn.apply, "xattn": T.CrossViewAttentionFn.apply}
+
+
+def point_network_torch_ops():
+    """the same three operators as plain torch (any dtype, any device): what point_network_device computes, for the tests"""
+    def xattn(kvp, kvs):
+        A = F.softmax(torch.einsum("pjc,pic->pji", kvp[..., :128], kvs[..., :128]) / math.sqrt(128), dim=1)
+        return kvs[..., 128:] + torch.einsum("pjc,pji->pic", kvp[..., 128:], A)
+    return {"linear": F.linear, "relu_linear": lambda a, W, b: F.relu(F.linear(a, W, b)), "xattn": xattn}
+
+
+def point_network_device(net, h, f, viewdir, ops=None):
+    """point_network (same arguments, same result) as th_mlp_forward composes it (k_mlp.hip): one GEMM per layer with the ReLU
+    in its epilogue, the key and value embeddings of a branch as one 384-row layer, the cross-view attention as one kernel.
+    h may carry K4's zero pad column ([P,V,256]).  The GEMMs take multiples of 16: the odd layers are padded with zeros here,
+    by differentiable operators, so autograd slices the gradients of the Parameters back.  ``ops``: the three operators
+    (default: the HIP Functions of train_ops)."""
+    ops = ops or _point_net_device_ops()
+    lin, rlin = ops["linear"], ops["relu_linear"]
+    w = lambda m: m.weight.reshape(m.weight.shape[0], -1)
+    P, V = f.shape[:2]
+    if h.shape[-1] == 255:
+        h = F.pad(h, (0, 1))
+    h, f = h.contiguous(), f.contiguous()
+    kv0, kv1 = net.spatial_key_value_0, net.spatial_key_value_1
+    s = rlin(h, F.pad(w(net.fc_0), (0, 1)), net.fc_0.bias)                                      # 255 -> 256 columns
+    p = rlin(f, w(net.alpha_res_0), net.alpha_res_0.bias)
+    kvp = lin(p, torch.cat([w(kv0.key_embed), w(kv0.value_embed)]), torch.cat([kv0.key_embed.bias, kv0.value_embed.bias]))
+    kvs = lin(s, torch.cat([w(kv1.key_embed), w(kv1.value_embed)]), torch.cat([kv1.key_embed.bias, kv1.value_embed.bias]))
+    n = ops["xattn"](kvp, kvs)
+    inter = rlin(rlin(n, w(net.fc_1), net.fc_1.bias), w(net.fc_2), net.fc_2.bias)
+    a = rlin(inter.mean(dim=1), w(net.fc_3), net.fc_3.bias)
+    sigma = lin(a, F.pad(w(net.alpha_fc), (0, 0, 0, 15)), F.pad(net.alpha_fc.bias, (0, 15)))[:, :1]       # 1 -> 16 rows
+    feat = lin(inter, w(net.feature_fc), net.feature_fc.bias) + lin(f, w(net.rgb_res_0), net.rgb_res_0.bias)
+    feat = torch.cat([feat, viewdir[:, None, :].expand(-1, V, -1), feat.new_zeros((P, V, 5))], dim=-1)    # 283 -> 288 columns
+    c = rlin(feat, F.pad(w(net.view_fc), (0, 5)), net.view_fc.bias) + lin(f, w(net.rgb_res_1), net.rgb_res_1.bias)
+    c = rlin(c.mean(dim=1), w(net.fc_4), net.fc_4.bias)
+    rgb = lin(c, F.pad(w(net.rgb_fc), (0, 0, 0, 13)), F.pad(net.rgb_fc.bias, (0, 13)))[:, :3]              # 3 -> 16 rows
+    return torch.cat([rgb, sigma], dim=1)
+
+
 def composite(raw, z, ray_d, raw_noise_std, white_bkgd):
     """raw2outputs (nerf_net_utils.py:14-59)"""
     d = torch.cat([z[..., 1:] - z[..., :-1], torch.full_like(z[..., :1], 1e10)], -1)
@@ -283,6 +339,11 @@ def render(renderer, batch, chunk=32768):
         from .. import hip
         raise hip.HipError("cfg.train_maps = 'latents' needs the batch on an MI355X (the HIP kernels have no CPU form); "
                            "use 'full' for a CPU batch")
+    point_net = _point_net_mode(getattr(cfg, "train_point_net", "torch"))
+    if point_net == "device" and not ray_o.is_cuda:
+        from .. import hip
+        raise hip.HipError("cfg.train_point_net = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
+                           "use 'torch' for a CPU batch")
     near, far = batch["near"][0], batch["far"][0]
     dev = ray_o.device
     S = int(cfg.N_samples)
@@ -332,7 +393,10 @@ def render(renderer, batch, chunk=32768):
             f_all = train_ops.PixelGatherFn.apply(pix.permute(0, 2, 3, 1).contiguous(), xyz, hip.pack_cams(R_in, T_in, K_in), scale)
         h_all = train_ops.HumanRepresentationFn.apply(tokens.contiguous(), pts_s, centres, rot)
         for f, h, vd in zip(f_all.split(chunk), h_all.split(chunk), viewdir.split(chunk)):
-            raws.append(point_network(net, h[..., :255], f, vd))
+            if point_net == "device":
+                raws.append(point_network_device(net, h, f, vd))            # (K4's rows with their zero pad column)
+            else:
+                raws.append(point_network(net, h[..., :255], f, vd))
         raw = torch.cat(raws, 0).view(-1, S, 4)
         if noise_std > 0.0:                                        # nerf_net_utils.py:39-44, drawn by torch
             noise = torch.randn(raw[..., 3].shape).to(raw) * noise_std
@@ -346,7 +410,7 @@ def render(renderer, batch, chunk=32768):
         else:
             f = sample_map(pix, project(x, R_in, T_in, K_in), net.encoder, image_shape).permute(2, 0, 1)
         h = human_representation(net, pts_s[s0:s0 + chunk], centres, rot, tokens, int(cfg.KNN), float(cfg.KNN_DIST_ALPHA))
-        raws.append(point_network(net, h, f, viewdir[s0:s0 + chunk]))
+        raws.append((point_network_device if point_net == "device" else point_network)(net, h, f, viewdir[s0:s0 + chunk]))
     raw = torch.cat(raws, 0).view(-1, S, 4)
     rgb, acc, depth = composite(raw, z, ray_d, noise_std, bool(cfg.white_bkgd))
     return {"rgb_map": rgb[None], "acc_map": acc[None], "depth_map": depth[None]}

@@ -27,6 +27,12 @@ weight-gradient kernel -- and returns the gradients of the Parameters themselves
     LinearFn                a, W, b              -> Linear(a)          keeps a          proj (a is AttentionFn's saved output)
     LayerNormFn             x, w, b              -> LN(x)              keeps x          the final norm
 
+``cfg.train_point_net = "device"`` does it for the per-point network (MLP_forward_ori), layer by layer like th_mlp_forward
+(k_pointnet_bwd.hip; composed by ``autograd_path.point_network_device`` from these two and ``LinearFn``):
+
+    ReluLinearFn            a, W, b              -> relu(Linear(a))    keeps a, y       s, p, fc_1, fc_2, fc_3, view_fc, fc_4
+    CrossViewAttentionFn    kvp, kvs [P,V,384]   -> n [P,V,256]        keeps kvp, kvs   gradient: both; A is recomputed
+
 K4 and K5 are linear in the tensor that gets the gradient, so nothing of the forward is kept for the backward but the
 geometry (points, centres, cameras): the [P,7,255] blend operands and the per-chunk map-sized gradients of the torch
 formulation do not exist here.  Points, centres, rotations, cameras, depths and ray directions come from the batch and get
@@ -226,6 +232,39 @@ class GeluLinearFn(_DenseFn):
     def backward(ctx, grad_out):
         g_u, g_w, g_b, _, _ = GeluLinearFn._bwd(ctx, grad_out)
         return g_u, g_w, g_b
+
+
+class ReluLinearFn(torch.autograd.Function):
+    """relu(nn.Linear(a)) on rows: the ReLU is the GEMM's epilogue; the backward gates g_out by [y > 0] on its way into the
+    weight-gradient kernel (th_linear_relu_forward / th_linear_relu_bwd).  Kept: a and the output y, which autograd keeps anyway."""
+
+    @staticmethod
+    def forward(ctx, a, W, b):
+        _dense_inputs("ReluLinearFn", a=a, W=W, b=b)
+        y = hip.linear_relu_forward(a.detach(), W.detach(), b.detach())
+        ctx.save_for_backward(a, W, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a, W, y = ctx.saved_tensors
+        return hip.linear_relu_bwd(a, y, W, grad_out.contiguous(), need_input=ctx.needs_input_grad[0])
+
+
+class CrossViewAttentionFn(torch.autograd.Function):
+    """cross_attention (cross_transformer.py:128-149) on the fused [key(128) | value(256)] rows of the pixel branch (kvp) and the
+    token branch (kvs), [P,V,384] each -> n [P,V,256].  Kept: kvp and kvs; the V x V probabilities are recomputed."""
+
+    @staticmethod
+    def forward(ctx, kvp, kvs):
+        _dense_inputs("CrossViewAttentionFn", kvp=kvp, kvs=kvs)
+        ctx.save_for_backward(kvp, kvs)
+        return hip.xview_attention(kvp.detach(), kvs.detach())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        kvp, kvs = ctx.saved_tensors
+        return hip.xview_attention_bwd(kvp, kvs, grad_out.contiguous())
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -464,3 +503,39 @@ def gelu_linear_grad_oracle(u, W, g_out):
     u2 = _np64(u).reshape(-1, _np64(u).shape[-1])
     g_a, g_W, g_b = linear_grad_oracle(_gelu64(u2), W, g_out)
     return g_a * _gelu_grad64(u2), g_W, g_b
+
+
+def relu_linear_grad_oracle(a, W, b, g_out):
+    """y = relu(a W^T + b) and its adjoint, torch's rule (gradient 0 where y == 0) -> (y, g_a, g_W, g_b) in float64"""
+    a2 = _np64(a).reshape(-1, _np64(a).shape[-1])
+    y = np.maximum(a2 @ _np64(W).T + _np64(b), 0.0)
+    g = _np64(g_out).reshape(y.shape) * (y > 0.0)
+    return (y, *linear_grad_oracle(a2, W, g))
+
+
+def _xview_probs64(kvp, kvs):
+    p, s = _np64(kvp), _np64(kvs)
+    S = np.einsum("pjc,pic->pji", p[..., :128], s[..., :128]) / np.sqrt(128.0)
+    e = np.exp(S - S.max(1, keepdims=True))
+    return p, s, e / e.sum(1, keepdims=True)
+
+
+def xview_attention_oracle(kvp, kvs):
+    """cross_attention (cross_transformer.py:128-149) on [key(128) | value(256)] rows [P,V,384] -> n [P,V,256] in float64"""
+    p, s, A = _xview_probs64(kvp, kvs)
+    return s[..., 128:] + np.einsum("pjc,pji->pic", p[..., 128:], A)
+
+
+def xview_attention_grad_oracle(kvp, kvs, g_n):
+    """adjoint of xview_attention_oracle: g_n [P,V,256] -> (g_kvp, g_kvs) [P,V,384] in float64; the formulas of
+    k_pointnet_bwd.hip"""
+    p, s, A = _xview_probs64(kvp, kvs)
+    g = _np64(g_n)
+    dA = np.einsum("pjc,pic->pji", p[..., 128:], g)
+    dS = A * (dA - (A * dA).sum(1, keepdims=True))
+    g_kvp, g_kvs = np.empty_like(p), np.empty_like(s)
+    g_kvs[..., 128:] = g
+    g_kvp[..., 128:] = np.einsum("pji,pic->pjc", A, g)
+    g_kvp[..., :128] = np.einsum("pji,pic->pjc", dS, s[..., :128]) / np.sqrt(128.0)
+    g_kvs[..., :128] = np.einsum("pji,pjc->pic", dS, p[..., :128]) / np.sqrt(128.0)
+    return g_kvp, g_kvs
