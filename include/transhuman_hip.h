@@ -623,6 +623,46 @@ size_t th_lpips_workspace_bytes(int n, int h, int w);
 int th_lpips(th_ctx* ctx, const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out,
              void* workspace, size_t workspace_bytes, th_stream stream);
 
+/* ---- K21: LPIPS (VGG16) as the training loss -- its gradient with respect to in0 (additions, ABI 12) ------------ */
+/* lib/train/trainers/if_nerf_clight.py:68-72 back-propagates through the metric above into the rendered patches; in1 is the
+ * target and the VGG16 / lin weights are frozen, so only d total / d in0 exists.
+ * th_lpips_pack_bwd: a second packed image (th_lpips_bwd_pack_bytes() bytes) from the same conv_w as th_lpips_pack: the taps
+ * rotated by 180 degrees with the channel roles swapped, so that the input gradient of every 3x3 convolution runs through the
+ * forward's MFMA tile (per 8-channel chunk a fresh fp32 chain, the chunks summed in fp32).
+ * th_lpips_train: th_lpips -- the same launches, `out` bit-identical -- writing into `state` (th_lpips_train_state_bytes,
+ * caller-owned) instead of a workspace.  Kept for th_lpips_bwd: the post-ReLU output of all 13 layers of the in0 images and
+ * the five taps of the in1 images (NHWC); behind them scratch of the forward alone (in1's other layers, the pooled maps, the
+ * head's partials).  Every byte th_lpips_bwd reads is written here.
+ * th_lpips_bwd: g_out: doubles [n], the gradient of each image's total (out[i][5]); g_in0: fp32 NCHW [n][3][h][w], every
+ * element written.  From the deepest level to the first: the head's derivative in fp64 at the stored fp32 features, rounded
+ * to fp32 and added to the gradient from the deeper level; ReLU gates [y > 0] from the stored outputs; the max pools route to
+ * the first element of a window (row-major) that equals its maximum, as torch does, cropped rows / columns get 0; layer 0
+ * applies 1 / scale[c] of the ScalingLayer.  `in0` is the batch `state` was made from (not read: the state holds every
+ * activation).  No atomics: bit-identical from run to run.  No host wait.  h, w >= 16 as for th_lpips (size queries give 0).
+ * The stages on their own -- th_lpips_dgrad, th_lpips_pool_bwd, th_lpips_head_bwd: entries for the per-stage tests against
+ * float64, NOT part of the stable surface: their signatures may change or go without an ABI version step; callers use
+ * th_lpips_bwd.  Any H, W >= 1:
+ * th_lpips_dgrad: g fp32 NHWC [Z][H][W][COUT_layer] -> out NHWC [Z][H][W][CIN_layer], 0 where gate_or_null (same layout as
+ * out) is <= 0; layer 0: out NCHW [Z][3][H][W] times 1 / scale[c], no gate.
+ * th_lpips_pool_bwd: g [Z][H/2][W/2][C], y [Z][H][W][C] (the map that was pooled) -> out [Z][H][W][C]; C a multiple of 4.
+ * th_lpips_head_bwd: f0, f1 fp32 [N][hw][C], lin fp32 [C], g_out doubles [N] -> g [N][hw][C] = (accumulate ? g : 0) +
+ * fp32(g_out[n] / hw * d head / d f0), then 0 where gate != 0 and f0 <= 0; C a multiple of 32. */
+size_t th_lpips_bwd_pack_bytes(void);
+int th_lpips_pack_bwd(th_ctx* ctx, const float* const* conv_w /* [13] */, void* packed_bwd, size_t bytes, th_stream stream);
+size_t th_lpips_train_state_bytes(int n, int h, int w);
+int th_lpips_train(th_ctx* ctx, const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out,
+                   void* state, size_t state_bytes, th_stream stream);
+size_t th_lpips_bwd_workspace_bytes(int n, int h, int w);
+int th_lpips_bwd(th_ctx* ctx, const double* g_out, const float* in0, int n, int h, int w, const void* packed,
+                 const void* packed_bwd, const void* state, size_t state_bytes, float* g_in0, void* workspace,
+                 size_t workspace_bytes, th_stream stream);
+/* (test entries, may change:) */
+int th_lpips_dgrad(th_ctx* ctx, int layer, const float* g, const float* gate_or_null, int Z, int H, int W,
+                   const void* packed_bwd, float* out, th_stream stream);
+int th_lpips_pool_bwd(th_ctx* ctx, const float* g, const float* y, int Z, int H, int W, int C, float* out, th_stream stream);
+int th_lpips_head_bwd(th_ctx* ctx, const float* f0, const float* f1, int N, int hw, int C, const float* lin,
+                      const double* g_out, int accumulate, int gate, float* g, th_stream stream);
+
 /* ---- K14: mesh rasteriser, vertex visibility maps and SMPL depth maps -------------------------- */
 /* batch['input_vizmaps'] ([1, V, 6890], the mask paint_neural_human applies at if_clight_renderer.py:176-182) and
  * batch['input_depthmaps'] are LOADED by the reference from the .npy files of rasterize_root/<human>/{visibility,depth} (can_smpl.py:439-475);

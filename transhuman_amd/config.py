@@ -87,6 +87,10 @@ def _defaults():
         # host) or "device" (made in Renderer.render from the target view, target_K / target_R / target_T and can_bounds, when the
         # batch has no ray_o; transhuman_amd/train_targets.py, K18)
         target_prep="batch",
+        # the trainer's loss (lib/train/trainers/if_nerf_clight.py:34-38, train_or_eval.yaml): l2rec_weight * MSE +
+        # lpips_weight * mean(LPIPS_vgg) over the rendered patches (transhuman_amd/train_loss.py, K21)
+        l2rec_weight=1.0,
+        lpips_weight=0.1,
     )
 
 

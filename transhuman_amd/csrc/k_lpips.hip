@@ -19,6 +19,21 @@
 // accumulators, 36 k-steps of two MFMAs per chunk.  Each chunk's 72 products are a fresh MFMA chain added to a running fp32
 // sum: one 4608-long fma chain (CIN 512) was 5-10x less accurate at the deep taps than torch's fp32 CPU convolution.
 // The first layer (CIN 3) is one zero-padded chunk read from the NCHW input with the ScalingLayer applied in the staging.
+//
+// Training form (K21): th_lpips_train makes the same launches into a caller-owned state buffer that keeps what the backward reads:
+// the post-ReLU output of all 13 layers of the in0 images and the five taps of the in1 images (a tap is one [2N] array, in0's
+// images first).  The batch stays one grid.z: the convolutions' SPLIT form sends in1's other layers through two scratch
+// buffers behind the kept part, where the pooled maps and the head's partials pass through as well.  th_lpips_bwd walks from the deepest level to the first and gives d total / d in0:
+//   per level   lp_head_bwd_kernel   fp64 derivative of the tap's head at the stored fp32 features, rounded to fp32, added to
+//                                    the gradient arriving from the deeper level, gated by [y > 0] of the tap
+//   per layer   lp_conv_kernel<false, LP_EPI_DGRAD / LP_EPI_IMAGE>   the input gradient of a 3x3 / s1 / p1 convolution is the
+//                                    same convolution with the taps rotated by 180 degrees and the channel roles swapped: the
+//                                    forward's tile on a second packed image (lp_pack_bwd_kernel), the same per-chunk fresh MFMA
+//                                    chains summed in fp32; no bias, no ReLU, the gate [y > 0] of the layer below in the
+//                                    epilogue; layer 0: 3 channels, 1 / scale[c] of the ScalingLayer, NCHW
+//   per pool    lp_pool_bwd_kernel   the gradient goes to the first element of the window (row-major) that equals its maximum,
+//                                    torch's rule; rows / columns the floor cropped get 0
+// Gradients are NHWC fp32 in two ping-pong buffers of N x 64 x H x W.  No atomics: bit-identical from run to run.
 #include "th_internal.h"
 
 #include <math.h>
@@ -79,16 +94,27 @@ __global__ void lp_pack_kernel(const float* __restrict__ w, int CIN, int COUT, i
 // 3x3 / stride 1 / pad 1 convolution + bias + ReLU.  FIRST: the input is NCHW with 3 channels, images z < nsplit from `a`,
 // the others from `b` (image z - nsplit), with the ScalingLayer applied; otherwise the input is NHWC [z][H][W][CIN] at `a`.
 // Output NHWC [z][H][W][COUT].  grid: (tiles, COUT / 64, 2N).
-template <bool FIRST>
+// EPI (the input-gradient forms, on the image of lp_pack_bwd_kernel; CIN / COUT are then the forward layer's COUT / CIN):
+//   LP_EPI_DGRAD  no bias, no ReLU; `bias` is the gate source: the stored output y of the layer below, NHWC like `out`, the
+//                 result is 0 where y <= 0 (null: no gate, the layer below is a pool)
+//   LP_EPI_IMAGE  layer 0: channels 0..2 of the block times 1 / scale[c], written NCHW [z][3][H][W]
+// SPLIT (the training form of the forward, which keeps in0's layers and lets in1's pass through scratch): the images z >= nsplit
+//   live in arrays of their own, indexed from z - nsplit: the input at `b` (as the first layer's always does), the output at `out2`
+enum { LP_EPI_FORWARD = 0, LP_EPI_DGRAD = 1, LP_EPI_IMAGE = 2 };
+template <bool FIRST, int EPI = LP_EPI_FORWARD, bool SPLIT = false>
 __global__ __launch_bounds__(LP_THREADS) void lp_conv_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                              int nsplit, int H, int W, int CIN, int COUT,
                                                              const float* __restrict__ wpk, const float* __restrict__ bias,
-                                                             float* __restrict__ out, int tiles_x) {
+                                                             float* __restrict__ out, int tiles_x, float* __restrict__ out2) {
     __shared__ float sIn[LP_CK][LP_HH][LP_HW];
     __shared__ __attribute__((aligned(16))) float sW[LP_KC][LP_NB];
 
     const int tid = threadIdx.x, lane = tid % TH_WAVE, wave = tid / TH_WAVE;
     const int cob = blockIdx.y, z = blockIdx.z;
+    if (SPLIT && z >= nsplit) {                              // rebase, so that a + z * ... and out + z * ... below address them
+        if (!FIRST) a = b - (size_t)nsplit * H * W * CIN;
+        out = out2 - (size_t)nsplit * H * W * COUT;
+    }
     const int y0 = (blockIdx.x / tiles_x) * LP_TH, x0 = (blockIdx.x % tiles_x) * LP_TW;
     const int nch = FIRST ? 1 : CIN / LP_CK;
     const int i_pix = lane & 31, hk = lane >> 5;            // A row (pixel) and k half of this lane
@@ -146,6 +172,35 @@ __global__ __launch_bounds__(LP_THREADS) void lp_conv_kernel(const float* __rest
     // epilogue: lane holds output channels co0 = cob * 64 + (lane & 31) and co0 + 32 for 16 pixels
     // (C/D map of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5))
     const int co0 = cob * LP_NB + i_pix;
+    if (EPI == LP_EPI_DGRAD) {
+        float* dst = out + (size_t)z * H * W * COUT;
+        const float* gate = bias ? bias + (size_t)z * H * W * COUT : nullptr;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = (r & 3) + 8 * (r >> 2) + 4 * hk;
+            const int gy = y0 + 2 * wave + (i >> 4), gx = x0 + (i & 15);
+            if (gy < H && gx < W) {
+                const size_t o = ((size_t)gy * W + gx) * COUT + co0;
+                const bool on0 = gate ? gate[o] > 0.f : true, on1 = gate ? gate[o + 32] > 0.f : true;
+                dst[o] = on0 ? tot0[r] : 0.f;
+                dst[o + 32] = on1 ? tot1[r] : 0.f;
+            }
+        }
+        return;
+    }
+    if (EPI == LP_EPI_IMAGE) {
+        if (co0 < 3) {                                       // (cob == 0: the three image channels of the zero-padded block)
+            float* dst = out + ((size_t)z * 3 + co0) * H * W;
+            const float sc = lp_scale[co0];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int i = (r & 3) + 8 * (r >> 2) + 4 * hk;
+                const int gy = y0 + 2 * wave + (i >> 4), gx = x0 + (i & 15);
+                if (gy < H && gx < W) dst[(size_t)gy * W + gx] = tot0[r] / sc;
+            }
+        }
+        return;
+    }
     const float bb0 = bias[co0], bb1 = bias[co0 + 32];
     float* dst = out + (size_t)z * H * W * COUT;
 #pragma unroll
@@ -260,6 +315,116 @@ __global__ __launch_bounds__(LP_FIN_THREADS) void lp_finish_kernel(const double*
     }
 }
 
+// ---- training form: the adjoint --------------------------------------------------------------------------------------
+// packed input-gradient weights of one layer: [CIN_pad64 / 64][COUT / 8][k = tap * 8 + c][64] with the value
+// W[co = chunk * 8 + c][ci = block * 64 + j][2 - tap / 3][2 - tap % 3] (the taps rotated by 180 degrees), zero for ci >= CIN
+// (layer 0: 3 of 64).  w: torch layout [COUT][CIN][3][3].
+__global__ void lp_pack_bwd_kernel(const float* __restrict__ w, int CIN, int COUT, int nblk, float* __restrict__ out) {
+    const int nch = COUT / LP_CK;
+    const long long total = (long long)nblk * nch * LP_KC * LP_NB;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int j = (int)(idx % LP_NB);
+    const int k = (int)((idx / LP_NB) % LP_KC);
+    const int ch = (int)((idx / (LP_NB * LP_KC)) % nch);
+    const int blk = (int)(idx / ((long long)LP_NB * LP_KC * nch));
+    const int tap = k / LP_CK, co = ch * LP_CK + k % LP_CK, ci = blk * LP_NB + j;
+    out[idx] = ci < CIN ? w[((long long)co * CIN + ci) * 9 + (8 - tap)] : 0.f;
+}
+
+// backward of the 2 x 2 / stride 2 max pool (floor), NHWC, 4 channels per thread, one thread per element of the UNPOOLED map:
+// g [Z][H / 2][W / 2][C] (gradient of the pooled map), y [Z][H][W][C] (the map that was pooled) -> out [Z][H][W][C], every
+// element written: g where the element is the first of its window, in row-major window order, that equals the window's
+// maximum (torch's rule), 0 elsewhere and in the rows / columns the floor cropped.
+__global__ void lp_pool_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y, int Z, int H, int W, int C,
+                                   float* __restrict__ out) {
+    const int Ho = H / 2, Wo = W / 2, C4 = C / 4;
+    const long long total = (long long)Z * H * W * C4;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int c4 = (int)(idx % C4);
+    const long long p = idx / C4;
+    const int x = (int)(p % W), yy = (int)((p / W) % H), z = (int)(p / ((long long)W * H));
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int yo = yy / 2, xo = x / 2;
+    if (yo < Ho && xo < Wo) {
+        const float4* s = (const float4*)(y + (size_t)z * H * W * C) + c4;
+        const float4 v0 = s[((size_t)(2 * yo) * W + 2 * xo) * C4], v1 = s[((size_t)(2 * yo) * W + 2 * xo + 1) * C4];
+        const float4 v2 = s[((size_t)(2 * yo + 1) * W + 2 * xo) * C4], v3 = s[((size_t)(2 * yo + 1) * W + 2 * xo + 1) * C4];
+        const float4 gv = ((const float4*)(g + (size_t)z * Ho * Wo * C))[((size_t)yo * Wo + xo) * C4 + c4];
+        const int me = (yy & 1) * 2 + (x & 1);               // this element's place in the window
+        auto first = [](float a, float b, float c, float d) {
+            const float m = fmaxf(fmaxf(a, b), fmaxf(c, d));
+            return a == m ? 0 : b == m ? 1 : c == m ? 2 : 3;
+        };
+        r.x = first(v0.x, v1.x, v2.x, v3.x) == me ? gv.x : 0.f;
+        r.y = first(v0.y, v1.y, v2.y, v3.y) == me ? gv.y : 0.f;
+        r.z = first(v0.z, v1.z, v2.z, v3.z) == me ? gv.z : 0.f;
+        r.w = first(v0.w, v1.w, v2.w, v3.w) == me ? gv.w : 0.f;
+    }
+    ((float4*)out)[idx] = r;
+}
+
+// backward of one tap's head (lp_head_kernel) with respect to f0, in fp64 on the fp32 features.  With nk = sqrt(sk + 1e-10) +
+// 1e-10, rk = sqrt(sk + 1e-10), q[c] = f0[c] / n0 - f1[c] / n1 and T = sum_c 2 lin[c] q[c] f0[c]:
+//   d d / d f0[j] = (2 lin[j] q[j] - f0[j] T / (n0 r0)) / n0
+// times g_out[n] / hw (the spatial mean and the gradient of image n's total), rounded to fp32, added to g[n][p][j] when
+// `accumulate` (the gradient arriving from the deeper level) and, when `gate`, zeroed where f0[j] <= 0 (the ReLU that
+// produced the tap).
+// f0, f1: [N][hw][C].  8 lanes per pixel as in lp_head_kernel.  grid: (cdiv(hw, 32), N).
+__global__ __launch_bounds__(LP_HEAD_THREADS) void lp_head_bwd_kernel(const float* __restrict__ f0a,
+                                                                      const float* __restrict__ f1a, int hw, int C,
+                                                                      const float* __restrict__ lin,
+                                                                      const double* __restrict__ g_out, int accumulate,
+                                                                      int gate, float* __restrict__ g) {
+    const int n = blockIdx.y, sub = threadIdx.x % LP_HEAD_LANES;
+    const int p = blockIdx.x * LP_HEAD_PIX + threadIdx.x / LP_HEAD_LANES;
+    const bool live = p < hw;                                // (dead pixels still take part in the shuffles)
+    const size_t row = ((size_t)n * hw + (live ? p : 0)) * C;
+    const float* f0 = f0a + row;
+    const float* f1 = f1a + row;
+    double s0 = 0.0, s1 = 0.0;
+    if (live)
+        for (int c = 4 * sub; c < C; c += 4 * LP_HEAD_LANES) {
+            const float4 u = *(const float4*)(f0 + c), v = *(const float4*)(f1 + c);
+            s0 += (double)u.x * u.x + (double)u.y * u.y + (double)u.z * u.z + (double)u.w * u.w;
+            s1 += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+        }
+    s0 = lp_group_sum(s0);
+    s1 = lp_group_sum(s1);
+    const double r0 = sqrt(s0 + 1e-10), n0 = r0 + 1e-10, n1 = sqrt(s1 + 1e-10) + 1e-10;
+    double t = 0.0;
+    if (live)
+        for (int c = 4 * sub; c < C; c += 4 * LP_HEAD_LANES) {
+            const float4 u = *(const float4*)(f0 + c), v = *(const float4*)(f1 + c);
+            const float4 w = *(const float4*)(lin + c);
+            t += 2.0 * (double)w.x * ((double)u.x / n0 - (double)v.x / n1) * (double)u.x;
+            t += 2.0 * (double)w.y * ((double)u.y / n0 - (double)v.y / n1) * (double)u.y;
+            t += 2.0 * (double)w.z * ((double)u.z / n0 - (double)v.z / n1) * (double)u.z;
+            t += 2.0 * (double)w.w * ((double)u.w / n0 - (double)v.w / n1) * (double)u.w;
+        }
+    t = lp_group_sum(t);
+    if (!live) return;
+    const double tn = t / (n0 * r0), k = g_out[n] / (double)hw;
+    float* gr = g + row;
+    for (int c = 4 * sub; c < C; c += 4 * LP_HEAD_LANES) {
+        const float4 u = *(const float4*)(f0 + c), v = *(const float4*)(f1 + c);
+        const float4 w = *(const float4*)(lin + c);
+        float4 a = accumulate ? *(const float4*)(gr + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        a.x += (float)((2.0 * (double)w.x * ((double)u.x / n0 - (double)v.x / n1) - (double)u.x * tn) / n0 * k);
+        a.y += (float)((2.0 * (double)w.y * ((double)u.y / n0 - (double)v.y / n1) - (double)u.y * tn) / n0 * k);
+        a.z += (float)((2.0 * (double)w.z * ((double)u.z / n0 - (double)v.z / n1) - (double)u.z * tn) / n0 * k);
+        a.w += (float)((2.0 * (double)w.w * ((double)u.w / n0 - (double)v.w / n1) - (double)u.w * tn) / n0 * k);
+        if (gate) {
+            a.x = u.x > 0.f ? a.x : 0.f;
+            a.y = u.y > 0.f ? a.y : 0.f;
+            a.z = u.z > 0.f ? a.z : 0.f;
+            a.w = u.w > 0.f ? a.w : 0.f;
+        }
+        *(float4*)(gr + c) = a;
+    }
+}
+
 // spatial size of each level: H >> l with floor at every pool
 void lp_levels(int h, int w, int* hl, int* wl) {
     hl[0] = h;
@@ -290,6 +455,167 @@ size_t lp_partial_doubles(int n, int h, int w) {
     const LpTaps t = lp_taps(n, h, w);
     return (size_t)(t.off[4] + (long long)n * t.nblk[4]);
 }
+
+// packed input-gradient image: the 13 blocks of lp_pack_bwd_kernel (floats)
+int lp_bwd_blocks(int l) { return (LP_CIN[l] + LP_NB - 1) / LP_NB; }
+size_t lp_bwd_wfloats(int l) { return (size_t)lp_bwd_blocks(l) * LP_NB * LP_COUT[l] * 9; }
+size_t lp_bwd_woff(int l) {
+    size_t o = 0;
+    for (int i = 0; i < l; ++i) o += lp_bwd_wfloats(i);
+    return o;
+}
+
+int lp_level_of(int l) {
+    for (int k = 0; k < 5; ++k)
+        if (l <= LP_LEVEL_LAST[k]) return k;
+    return 4;
+}
+
+// where the forward writes: the output of each layer -- images 0..n-1 at layer[l], images n..2n-1 at layer1[l] (null: behind
+// the others in layer[l]; a tap is always one array, the pool and the head read it as such) --, the pooled map in front of
+// levels 1..4, the head's partials
+struct LpDest {
+    float* layer[LP_NL];
+    float* layer1[LP_NL];
+    float* pool[5];
+    double* partial;
+};
+
+bool lp_is_tap(int l) { return l == LP_LEVEL_LAST[lp_level_of(l)]; }
+
+// floats of ONE image's output of layer l
+size_t lp_layer_floats(int h, int w, int l) {
+    int hl[5], wl[5];
+    lp_levels(h, w, hl, wl);
+    const int k = lp_level_of(l);
+    return (size_t)hl[k] * wl[k] * LP_COUT[l];
+}
+
+// The training state.  Kept for the backward: in0's 13 layers and in1's five taps (a tap is [2N][H][W][C], in0's images first;
+// every other layer [N][H][W][C]).  Scratch of the forward alone, dead when it returns: in1's other layers pass through two
+// buffers (the first layer of a level writes sa, a middle layer sb), every pooled map through one, and the head's partials.
+struct LpStatePlan {
+    size_t layer[LP_NL], sa, sb, pool, partial;              // floats (partial: doubles)
+};
+LpStatePlan lp_state_plan(int n, int h, int w) {
+    LpStatePlan p{};
+    int hl[5], wl[5];
+    lp_levels(h, w, hl, wl);
+    for (int l = 0; l < LP_NL; ++l) {
+        const size_t one = (size_t)n * lp_layer_floats(h, w, l);
+        p.layer[l] = lp_is_tap(l) ? 2 * one : one;
+        if (!lp_is_tap(l)) {
+            const bool first = l == 0 || lp_is_tap(l - 1);
+            size_t& sc = first ? p.sa : p.sb;
+            if (one > sc) sc = one;
+        }
+    }
+    for (int lev = 1; lev < 5; ++lev) {
+        const size_t pf = (size_t)2 * n * hl[lev] * wl[lev] * LP_TAP_C[lev - 1];
+        if (pf > p.pool) p.pool = pf;
+    }
+    p.partial = lp_partial_doubles(n, h, w);
+    return p;
+}
+bool lp_state_carve(void* state, size_t bytes, int n, int h, int w, LpDest* d) {
+    const LpStatePlan p = lp_state_plan(n, h, w);
+    ThArena arena(state, bytes);
+    for (int l = 0; l < LP_NL; ++l) d->layer[l] = arena.take<float>(p.layer[l]);
+    float* sa = arena.take<float>(p.sa);
+    float* sb = arena.take<float>(p.sb);
+    float* pool = arena.take<float>(p.pool);
+    d->partial = arena.take<double>(p.partial);
+    for (int l = 0; l < LP_NL; ++l) d->layer1[l] = lp_is_tap(l) ? nullptr : (l == 0 || lp_is_tap(l - 1)) ? sa : sb;
+    d->pool[0] = nullptr;
+    for (int lev = 1; lev < 5; ++lev) d->pool[lev] = pool;
+    return d->partial != nullptr;
+}
+
+// the launches of the forward: 13 convolutions, 4 pools, 5 heads, the finish.  split: the destinations keep the two halves of
+// the batch in separate arrays (the training state); otherwise every layer1[] is null and the launches are th_lpips's own.
+int lp_forward(const float* in0, const float* in1, int n, int h, int w, const float* pk, double* out, const LpDest& d,
+               bool split, hipStream_t s) {
+    int hl[5], wl[5];
+    lp_levels(h, w, hl, wl);
+    const LpTaps taps = lp_taps(n, h, w);
+    const int Z = 2 * n;
+    int l = 0;
+    for (int lev = 0; lev < 5; ++lev) {
+        const int H = hl[lev], W = wl[lev];
+        const float *cur = nullptr, *cur1 = nullptr;         // the current activation: images 0..n-1, n..2n-1 (null: the input)
+        if (lev) {                                           // pool the previous tap
+            const int C = LP_COUT[l - 1];
+            const long long total = (long long)Z * (H) * (W) * (C / 4);
+            hipLaunchKernelGGL(lp_pool_kernel, dim3((unsigned)th_cdiv(total, 256)), dim3(256), 0, s, d.layer[l - 1], Z,
+                               hl[lev - 1], wl[lev - 1], C, d.pool[lev]);
+            TH_LAUNCH_CHECK();
+            cur = d.pool[lev];
+            cur1 = cur + (size_t)n * H * W * C;
+        }
+        const int tiles_x = th_cdiv(W, LP_TW), tiles = tiles_x * th_cdiv(H, LP_TH);
+        for (; l <= LP_LEVEL_LAST[lev]; ++l) {
+            const dim3 grid((unsigned)tiles, (unsigned)(LP_COUT[l] / LP_NB), (unsigned)Z);
+            const float* wl_pk = pk + lp_woff(l);
+            const float* bl = pk + lp_bias_off() + (size_t)l * LP_CMAX;
+            float* o1 = d.layer1[l] ? d.layer1[l] : d.layer[l] + (size_t)n * H * W * LP_COUT[l];
+            if (split) {
+                if (l == 0)
+                    hipLaunchKernelGGL((lp_conv_kernel<true, LP_EPI_FORWARD, true>), grid, dim3(LP_THREADS), 0, s, in0, in1, n,
+                                       H, W, LP_CIN[l], LP_COUT[l], wl_pk, bl, d.layer[l], tiles_x, o1);
+                else
+                    hipLaunchKernelGGL((lp_conv_kernel<false, LP_EPI_FORWARD, true>), grid, dim3(LP_THREADS), 0, s, cur, cur1, n,
+                                       H, W, LP_CIN[l], LP_COUT[l], wl_pk, bl, d.layer[l], tiles_x, o1);
+            } else if (l == 0) {
+                hipLaunchKernelGGL(lp_conv_kernel<true>, grid, dim3(LP_THREADS), 0, s, in0, in1, n, H, W, LP_CIN[l],
+                                   LP_COUT[l], wl_pk, bl, d.layer[l], tiles_x, (float*)nullptr);
+            } else {
+                hipLaunchKernelGGL(lp_conv_kernel<false>, grid, dim3(LP_THREADS), 0, s, cur, cur, Z, H, W, LP_CIN[l],
+                                   LP_COUT[l], wl_pk, bl, d.layer[l], tiles_x, (float*)nullptr);
+            }
+            TH_LAUNCH_CHECK();
+            cur = d.layer[l];
+            cur1 = o1;
+        }
+        hipLaunchKernelGGL(lp_head_kernel, dim3((unsigned)taps.nblk[lev], (unsigned)n), dim3(LP_HEAD_THREADS), 0, s, cur, n,
+                           H * W, LP_TAP_C[lev], pk + lp_lin_off() + (size_t)lev * LP_CMAX, d.partial + taps.off[lev]);
+        TH_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(lp_finish_kernel, dim3(1), dim3(LP_FIN_THREADS), 0, s, d.partial, taps, n, out);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int lp_dgrad_launch(int l, const float* g, const float* gate, int Z, int H, int W, const float* pkb, float* out,
+                    hipStream_t s) {
+    const int tiles_x = th_cdiv(W, LP_TW), tiles = tiles_x * th_cdiv(H, LP_TH);
+    const dim3 grid((unsigned)tiles, (unsigned)lp_bwd_blocks(l), (unsigned)Z);
+    // (the convolution's CIN / COUT are the forward layer's COUT / CIN; layer 0 writes 3 of its 64-channel block)
+    if (l == 0)
+        hipLaunchKernelGGL((lp_conv_kernel<false, LP_EPI_IMAGE>), grid, dim3(LP_THREADS), 0, s, g, g, Z, H, W, LP_COUT[l], 3,
+                           pkb + lp_bwd_woff(l), (const float*)nullptr, out, tiles_x, (float*)nullptr);
+    else
+        hipLaunchKernelGGL((lp_conv_kernel<false, LP_EPI_DGRAD>), grid, dim3(LP_THREADS), 0, s, g, g, Z, H, W, LP_COUT[l],
+                           LP_CIN[l], pkb + lp_bwd_woff(l), gate, out, tiles_x, (float*)nullptr);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int lp_pool_bwd_launch(const float* g, const float* y, int Z, int H, int W, int C, float* out, hipStream_t s) {
+    const long long total = (long long)Z * H * W * (C / 4);
+    hipLaunchKernelGGL(lp_pool_bwd_kernel, dim3((unsigned)th_cdiv(total, 256)), dim3(256), 0, s, g, y, Z, H, W, C, out);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int lp_head_bwd_launch(const float* f0, const float* f1, int N, int hw, int C, const float* lin, const double* g_out,
+                       int accumulate, int gate, float* g, hipStream_t s) {
+    hipLaunchKernelGGL(lp_head_bwd_kernel, dim3((unsigned)th_cdiv(hw, LP_HEAD_PIX), (unsigned)N), dim3(LP_HEAD_THREADS), 0, s,
+                       f0, f1, hw, C, lin, g_out, accumulate, gate, g);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t lp_grad_floats(int n, int h, int w) { return (size_t)n * 64 * h * w; }
 
 }  // namespace
 
@@ -327,50 +653,117 @@ int th_lpips_launch(const float* in0, const float* in1, int n, int h, int w, con
     TH_REQUIRE(h >= 16 && w >= 16, "image smaller than 16 x 16");
     TH_REQUIRE(n >= 1 && 2 * n <= 65535, "bad batch size");
     TH_REQUIRE(ws_bytes >= th_lpips_ws(n, h, w), "workspace too small");
-    const float* pk = (const float*)packed;
     ThArena arena(ws, ws_bytes);
     float* buf[2] = {arena.take<float>(lp_act_floats(n, h, w)), arena.take<float>(lp_act_floats(n, h, w))};
     double* partial = arena.take<double>(lp_partial_doubles(n, h, w));
     TH_REQUIRE(buf[0] && buf[1] && partial, "workspace too small");
-    int hl[5], wl[5];
-    lp_levels(h, w, hl, wl);
-    const LpTaps taps = lp_taps(n, h, w);
-    const int Z = 2 * n;
+    // two ping-pong buffers: every convolution and every pool writes the buffer its input is not in
+    LpDest d;
+    d.partial = partial;
+    int k = 0;
+    for (int l = 0, lev = 0; l < LP_NL; ++l) {
+        if (l > LP_LEVEL_LAST[lev]) d.pool[++lev] = buf[k++ & 1];
+        d.layer[l] = buf[k++ & 1];
+        d.layer1[l] = nullptr;
+    }
+    return lp_forward(in0, in1, n, h, w, (const float*)packed, out, d, false, s);
+}
 
-    int cur = -1;                                            // buffer holding the current activation (-1: the input)
-    int l = 0;
-    for (int lev = 0; lev < 5; ++lev) {
-        const int H = hl[lev], W = wl[lev];
-        if (lev) {                                           // pool the previous tap into the other buffer
-            const int C = LP_COUT[l - 1];
-            const long long total = (long long)Z * (H) * (W) * (C / 4);
-            hipLaunchKernelGGL(lp_pool_kernel, dim3((unsigned)th_cdiv(total, 256)), dim3(256), 0, s, buf[cur], Z,
-                               hl[lev - 1], wl[lev - 1], C, buf[cur ^ 1]);
-            TH_LAUNCH_CHECK();
-            cur ^= 1;
-        }
-        const int tiles_x = th_cdiv(W, LP_TW), tiles = tiles_x * th_cdiv(H, LP_TH);
-        for (; l <= LP_LEVEL_LAST[lev]; ++l) {
-            const dim3 grid((unsigned)tiles, (unsigned)(LP_COUT[l] / LP_NB), (unsigned)Z);
-            const float* wl_pk = pk + lp_woff(l);
-            const float* bl = pk + lp_bias_off() + (size_t)l * LP_CMAX;
-            if (l == 0) {
-                hipLaunchKernelGGL(lp_conv_kernel<true>, grid, dim3(LP_THREADS), 0, s, in0, in1, n, H, W, LP_CIN[l],
-                                   LP_COUT[l], wl_pk, bl, buf[0], tiles_x);
-                cur = 0;
-            } else {
-                hipLaunchKernelGGL(lp_conv_kernel<false>, grid, dim3(LP_THREADS), 0, s, buf[cur], buf[cur], Z, H, W,
-                                   LP_CIN[l], LP_COUT[l], wl_pk, bl, buf[cur ^ 1], tiles_x);
-                cur ^= 1;
-            }
-            TH_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(lp_head_kernel, dim3((unsigned)taps.nblk[lev], (unsigned)n), dim3(LP_HEAD_THREADS), 0, s,
-                           buf[cur], n, H * W, LP_TAP_C[lev], pk + lp_lin_off() + (size_t)lev * LP_CMAX,
-                           partial + taps.off[lev]);
+// ---- training form ----------------------------------------------------------------------------------------------------
+size_t th_lpips_bwd_pack_bytes_internal() { return lp_bwd_woff(LP_NL) * sizeof(float); }
+
+size_t th_lpips_state_bytes(int n, int h, int w) {
+    if (n < 1 || h < 16 || w < 16) return 0;
+    const LpStatePlan p = lp_state_plan(n, h, w);
+    size_t b = th_align(p.partial * sizeof(double)) + th_align(p.sa * sizeof(float)) + th_align(p.sb * sizeof(float)) +
+               th_align(p.pool * sizeof(float));
+    for (int l = 0; l < LP_NL; ++l) b += th_align(p.layer[l] * sizeof(float));
+    return b;
+}
+
+size_t th_lpips_bwd_ws(int n, int h, int w) {
+    if (n < 1 || h < 16 || w < 16) return 0;
+    return 2 * th_align(lp_grad_floats(n, h, w) * sizeof(float));
+}
+
+int th_lpips_pack_bwd_launch(const float* const* conv_w, void* packed_bwd, size_t bytes, hipStream_t s) {
+    TH_REQUIRE(bytes >= th_lpips_bwd_pack_bytes_internal(), "packed buffer too small");
+    float* pk = (float*)packed_bwd;
+    for (int l = 0; l < LP_NL; ++l) {
+        TH_REQUIRE(conv_w[l], "null conv weight of layer " + std::to_string(l));
+        const long long total = (long long)lp_bwd_wfloats(l);
+        hipLaunchKernelGGL(lp_pack_bwd_kernel, dim3((unsigned)th_cdiv(total, 256)), dim3(256), 0, s, conv_w[l], LP_CIN[l],
+                           LP_COUT[l], lp_bwd_blocks(l), pk + lp_bwd_woff(l));
         TH_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(lp_finish_kernel, dim3(1), dim3(LP_FIN_THREADS), 0, s, partial, taps, n, out);
-    TH_LAUNCH_CHECK();
     return 0;
+}
+
+int th_lpips_train_launch(const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out,
+                          void* state, size_t state_bytes, hipStream_t s) {
+    TH_REQUIRE(h >= 16 && w >= 16, "image smaller than 16 x 16");
+    TH_REQUIRE(n >= 1 && 2 * n <= 65535, "bad batch size");
+    TH_REQUIRE(state_bytes >= th_lpips_state_bytes(n, h, w), "state buffer too small");
+    LpDest d;
+    TH_REQUIRE(lp_state_carve(state, state_bytes, n, h, w, &d), "state buffer too small");
+    return lp_forward(in0, in1, n, h, w, (const float*)packed, out, d, true, s);
+}
+
+int th_lpips_bwd_launch(const double* g_out, int n, int h, int w, const void* packed, const void* packed_bwd,
+                        const void* state, size_t state_bytes, float* g_in0, void* ws, size_t ws_bytes, hipStream_t s) {
+    TH_REQUIRE(h >= 16 && w >= 16, "image smaller than 16 x 16");
+    TH_REQUIRE(n >= 1 && 2 * n <= 65535, "bad batch size");
+    TH_REQUIRE(state_bytes >= th_lpips_state_bytes(n, h, w), "state buffer too small");
+    TH_REQUIRE(ws_bytes >= th_lpips_bwd_ws(n, h, w), "workspace too small");
+    LpDest d;
+    TH_REQUIRE(lp_state_carve(const_cast<void*>(state), state_bytes, n, h, w, &d), "state buffer too small");
+    ThArena arena(ws, ws_bytes);
+    float* gb[2] = {arena.take<float>(lp_grad_floats(n, h, w)), arena.take<float>(lp_grad_floats(n, h, w))};
+    TH_REQUIRE(gb[0] && gb[1], "workspace too small");
+    const float* pk = (const float*)packed;
+    const float* pkb = (const float*)packed_bwd;
+    int hl[5], wl[5];
+    lp_levels(h, w, hl, wl);
+    int cur = 0;                                             // gb[cur]: the gradient of the current layer's output
+    for (int lev = 4; lev >= 0; --lev) {
+        const int H = hl[lev], W = wl[lev], L = LP_LEVEL_LAST[lev], first = lev ? LP_LEVEL_LAST[lev - 1] + 1 : 0;
+        const int C = LP_TAP_C[lev];
+        // the tap: images 0..n-1 of its layer are in0's features, n..2n-1 in1's
+        TH_TRY(lp_head_bwd_launch(d.layer[L], d.layer[L] + (size_t)n * H * W * C, n, H * W, C,
+                                  pk + lp_lin_off() + (size_t)lev * LP_CMAX, g_out, lev < 4, 1, gb[cur], s));
+        for (int l = L; l >= first; --l) {
+            if (l == 0) {
+                TH_TRY(lp_dgrad_launch(0, gb[cur], nullptr, n, H, W, pkb, g_in0, s));
+            } else {
+                TH_TRY(lp_dgrad_launch(l, gb[cur], l > first ? d.layer[l - 1] : nullptr, n, H, W, pkb, gb[cur ^ 1], s));
+                cur ^= 1;
+            }
+        }
+        if (lev) {                                           // through the pool into the previous level's tap
+            TH_TRY(lp_pool_bwd_launch(gb[cur], d.layer[first - 1], n, hl[lev - 1], wl[lev - 1], LP_TAP_C[lev - 1],
+                                      gb[cur ^ 1], s));
+            cur ^= 1;
+        }
+    }
+    return 0;
+}
+
+// the stages of th_lpips_bwd on their own (for the tests of each against float64)
+int th_lpips_dgrad_launch(int layer, const float* g, const float* gate, int Z, int H, int W, const void* packed_bwd, float* out,
+                          hipStream_t s) {
+    TH_REQUIRE(layer >= 0 && layer < LP_NL, "layer must be in 0..12");
+    TH_REQUIRE(Z >= 1 && Z <= 65535 && H >= 1 && W >= 1 && (long long)H * W < (1LL << 24), "bad shape");
+    TH_REQUIRE(layer > 0 || gate == nullptr, "layer 0 has no gate");
+    return lp_dgrad_launch(layer, g, gate, Z, H, W, (const float*)packed_bwd, out, s);
+}
+
+int th_lpips_pool_bwd_launch(const float* g, const float* y, int Z, int H, int W, int C, float* out, hipStream_t s) {
+    TH_REQUIRE(Z >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0, "bad shape (C must be a multiple of 4)");
+    return lp_pool_bwd_launch(g, y, Z, H, W, C, out, s);
+}
+
+int th_lpips_head_bwd_launch(const float* f0, const float* f1, int N, int hw, int C, const float* lin, const double* g_out,
+                             int accumulate, int gate, float* g, hipStream_t s) {
+    TH_REQUIRE(N >= 1 && N <= 65535 && hw >= 1 && C >= 32 && C % 32 == 0, "bad shape (C must be a multiple of 32)");
+    return lp_head_bwd_launch(f0, f1, N, hw, C, lin, g_out, accumulate, gate, g, s);
 }

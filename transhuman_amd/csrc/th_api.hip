@@ -859,6 +859,52 @@ int th_lpips(th_ctx* c, const float* in0, const float* in1, int n, int h, int w,
     return th_lpips_launch(in0, in1, n, h, w, packed, out, ws, ws_bytes, (hipStream_t)stream);
 }
 
+size_t th_lpips_bwd_pack_bytes(void) { return th_lpips_bwd_pack_bytes_internal(); }
+
+int th_lpips_pack_bwd(th_ctx* c, const float* const* conv_w, void* packed_bwd, size_t bytes, th_stream stream) {
+    TH_REQUIRE(c && conv_w && packed_bwd, "null argument");
+    return th_lpips_pack_bwd_launch(conv_w, packed_bwd, bytes, (hipStream_t)stream);
+}
+
+size_t th_lpips_train_state_bytes(int n, int h, int w) { return th_lpips_state_bytes(n, h, w); }
+
+int th_lpips_train(th_ctx* c, const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out,
+                   void* state, size_t state_bytes, th_stream stream) {
+    TH_REQUIRE(h >= 16 && w >= 16, "image is " + std::to_string(h) + " x " + std::to_string(w) +
+                                       ": LPIPS (VGG16) needs at least 16 x 16 pixels (the fifth tap would be empty)");
+    TH_REQUIRE(c && in0 && in1 && packed && out && state, "null argument");
+    return th_lpips_train_launch(in0, in1, n, h, w, packed, out, state, state_bytes, (hipStream_t)stream);
+}
+
+size_t th_lpips_bwd_workspace_bytes(int n, int h, int w) { return th_lpips_bwd_ws(n, h, w); }
+
+int th_lpips_bwd(th_ctx* c, const double* g_out, const float* in0, int n, int h, int w, const void* packed,
+                 const void* packed_bwd, const void* state, size_t state_bytes, float* g_in0, void* ws, size_t ws_bytes,
+                 th_stream stream) {
+    TH_REQUIRE(h >= 16 && w >= 16, "image is " + std::to_string(h) + " x " + std::to_string(w) +
+                                       ": LPIPS (VGG16) needs at least 16 x 16 pixels (the fifth tap would be empty)");
+    TH_REQUIRE(c && g_out && in0 && packed && packed_bwd && state && g_in0 && ws, "null argument");
+    return th_lpips_bwd_launch(g_out, n, h, w, packed, packed_bwd, state, state_bytes, g_in0, ws, ws_bytes,
+                               (hipStream_t)stream);
+}
+
+int th_lpips_dgrad(th_ctx* c, int layer, const float* g, const float* gate_or_null, int Z, int H, int W,
+                   const void* packed_bwd, float* out, th_stream stream) {
+    TH_REQUIRE(c && g && packed_bwd && out, "null argument");
+    return th_lpips_dgrad_launch(layer, g, gate_or_null, Z, H, W, packed_bwd, out, (hipStream_t)stream);
+}
+
+int th_lpips_pool_bwd(th_ctx* c, const float* g, const float* y, int Z, int H, int W, int C, float* out, th_stream stream) {
+    TH_REQUIRE(c && g && y && out, "null argument");
+    return th_lpips_pool_bwd_launch(g, y, Z, H, W, C, out, (hipStream_t)stream);
+}
+
+int th_lpips_head_bwd(th_ctx* c, const float* f0, const float* f1, int N, int hw, int C, const float* lin, const double* g_out,
+                      int accumulate, int gate, float* g, th_stream stream) {
+    TH_REQUIRE(c && f0 && f1 && lin && g_out && g, "null argument");
+    return th_lpips_head_bwd_launch(f0, f1, N, hw, C, lin, g_out, accumulate, gate, g, (hipStream_t)stream);
+}
+
 size_t th_marching_cubes_workspace_bytes(int X, int Y, int Z) { return th_mc_ws(X, Y, Z) + 256; }
 
 int th_marching_cubes_count(th_ctx* c, const float* cube, int X, int Y, int Z, float iso, void* ws, size_t ws_bytes,

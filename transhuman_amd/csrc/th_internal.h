@@ -583,6 +583,20 @@ int th_lpips_pack_launch(const float* const* conv_w, const float* const* conv_b,
                          size_t bytes, hipStream_t s);
 int th_lpips_launch(const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out, void* ws,
                     size_t ws_bytes, hipStream_t s);
+// ... its training form (K21): the forward into a state buffer, the gradient with respect to in0, and the backward's stages
+size_t th_lpips_bwd_pack_bytes_internal();
+size_t th_lpips_state_bytes(int n, int h, int w);
+size_t th_lpips_bwd_ws(int n, int h, int w);
+int th_lpips_pack_bwd_launch(const float* const* conv_w, void* packed_bwd, size_t bytes, hipStream_t s);
+int th_lpips_train_launch(const float* in0, const float* in1, int n, int h, int w, const void* packed, double* out,
+                          void* state, size_t state_bytes, hipStream_t s);
+int th_lpips_bwd_launch(const double* g_out, int n, int h, int w, const void* packed, const void* packed_bwd,
+                        const void* state, size_t state_bytes, float* g_in0, void* ws, size_t ws_bytes, hipStream_t s);
+int th_lpips_dgrad_launch(int layer, const float* g, const float* gate, int Z, int H, int W, const void* packed_bwd, float* out,
+                          hipStream_t s);
+int th_lpips_pool_bwd_launch(const float* g, const float* y, int Z, int H, int W, int C, float* out, hipStream_t s);
+int th_lpips_head_bwd_launch(const float* f0, const float* f1, int N, int hw, int C, const float* lin, const double* g_out,
+                             int accumulate, int gate, float* g, hipStream_t s);
 // k_raster.hip: z-buffer rasteriser of a triangle mesh into V views, and the two vertex-visibility rules on top of it
 size_t th_raster_ws(int V, int nv, int nf, int H, int W);
 int th_raster_launch(const float* verts, int nv, const int32_t* faces, int nf, const float* cams, int V, int H, int W,

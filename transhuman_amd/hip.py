@@ -211,6 +211,20 @@ SYMBOLS = {
     "th_lpips_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "th_lpips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_lpips_bwd_pack_bytes": (C.c_size_t, []),
+    "th_lpips_pack_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_lpips_train_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_lpips_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_lpips_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "th_lpips_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "th_lpips_dgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    "th_lpips_pool_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p]),
+    "th_lpips_head_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "th_marching_cubes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "th_marching_cubes_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                           C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),
@@ -1647,6 +1661,116 @@ def lpips(in0, in1, packed):
     out = torch.empty((N, 6), dtype=torch.float64, device=a.device)
     _check(lib.th_lpips(ctx(a.device), _p(a), _p(b), N, H, W, _p(packed), _p(out), _p(ws), ws.numel(), _stream()))
     return out
+
+
+def lpips_pack_bwd(conv_w, device=None):
+    """th_lpips_pack_bwd: the 13 VGG16 conv weights [COUT, CIN, 3, 3] (as lpips_pack takes them) -> the packed device image
+    of the input-gradient convolutions that th_lpips_bwd reads (a uint8 tensor, about the size of lpips_pack's)."""
+    assert len(conv_w) == 13
+    dev = torch.device(device) if device is not None else conv_w[0].device
+    ws = [w.detach().to(dev, torch.float32).contiguous() for w in conv_w]
+    for i, w in enumerate(ws):
+        co, ci = LPIPS_CONV_SHAPES[i]
+        if tuple(w.shape) != (co, ci, 3, 3):
+            raise ValueError(f"conv {i}: expected weight {(co, ci, 3, 3)}, got {tuple(w.shape)}")
+    lib = load_library()
+    packed = torch.empty(int(lib.th_lpips_bwd_pack_bytes()), dtype=torch.uint8, device=dev)
+    arr13 = C.c_void_p * 13
+    _check(lib.th_lpips_pack_bwd(ctx(dev), arr13(*[t.data_ptr() for t in ws]), _p(packed), packed.numel(), _stream()))
+    torch.cuda.current_stream(dev).synchronize()             # (the sources are temporaries)
+    return packed
+
+
+def _lpips_dims(fn, in0, in1=None):
+    if in0.dim() != 4 or in0.shape[1] != 3 or (in1 is not None and in0.shape != in1.shape):
+        raise ValueError(f"{fn} expects [N, 3, H, W] batches of one shape, got {tuple(in0.shape)}" +
+                         (f" and {tuple(in1.shape)}" if in1 is not None else ""))
+    N, _, H, W = (int(n) for n in in0.shape)
+    if H < 16 or W < 16:
+        raise ValueError(f"{fn}: a {H} x {W} image is smaller than 16 x 16 (VGG16's fifth tap would be empty)")
+    return N, H, W
+
+
+def lpips_train(in0, in1, packed, state=None):
+    """th_lpips_train: lpips() -- the same launches, a bit-identical [N, 6] float64 result -- that keeps what the backward
+    needs in `state` (a uint8 device tensor of th_lpips_train_state_bytes; allocated when None).  -> (out, state)"""
+    N, H, W = _lpips_dims("lpips_train", in0, in1)
+    if not (in0.is_cuda and in1.is_cuda):
+        raise HipError("lpips_train needs its tensors on an MI355X (there is no CPU path)")
+    assert in0.device == in1.device == packed.device, "expected tensors on one device"
+    a, b = _f32(in0), _f32(in1)
+    lib = load_library()
+    nbytes = int(lib.th_lpips_train_state_bytes(N, H, W))
+    if state is None:
+        state = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+    assert state.dtype is torch.uint8 and state.numel() >= nbytes and state.device == a.device
+    out = torch.empty((N, 6), dtype=torch.float64, device=a.device)
+    _check(lib.th_lpips_train(ctx(a.device), _p(a), _p(b), N, H, W, _p(packed), _p(out), _p(state), state.numel(), _stream()))
+    return out, state
+
+
+def lpips_bwd(g_out, in0, state, packed, packed_bwd, workspace=None):
+    """th_lpips_bwd: the gradient of sum_n g_out[n] * lpips_train(in0, in1)[n, 5] with respect to in0 -> float32 [N, 3, H, W].
+    g_out: [N] (any float dtype; float64 on the device); state: lpips_train's, of the same in0."""
+    N, H, W = _lpips_dims("lpips_bwd", in0)
+    assert in0.is_cuda and in0.device == state.device == packed.device == packed_bwd.device, "expected tensors on one device"
+    a = _f32(in0)
+    g = g_out.detach().reshape(-1).to(a.device, torch.float64).contiguous()
+    if g.numel() != N:
+        raise ValueError(f"lpips_bwd: g_out has {g.numel()} elements for a batch of {N}")
+    lib = load_library()
+    nbytes = int(lib.th_lpips_bwd_workspace_bytes(N, H, W))
+    ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+    assert ws.dtype is torch.uint8 and ws.numel() >= nbytes and ws.device == a.device
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=a.device)
+    _check(lib.th_lpips_bwd(ctx(a.device), _p(g), _p(a), N, H, W, _p(packed), _p(packed_bwd), _p(state), state.numel(), _p(out),
+                            _p(ws), ws.numel(), _stream()))
+    return out
+
+
+def lpips_dgrad(layer, g, packed_bwd, gate=None):
+    """th_lpips_dgrad: the input gradient of VGG16 conv `layer` (0..12) on its own.  g: float32 NHWC [Z, H, W, COUT] ->
+    NHWC [Z, H, W, CIN], zeroed where `gate` (same shape) is <= 0; layer 0: NCHW [Z, 3, H, W] times 1 / scale[c]."""
+    co, ci = LPIPS_CONV_SHAPES[layer]
+    g = _f32(g)
+    Z, H, W, Cg = (int(n) for n in g.shape)
+    if Cg != co:
+        raise ValueError(f"lpips_dgrad: layer {layer} takes {co} channels, got {Cg}")
+    out = torch.empty((Z, 3, H, W) if layer == 0 else (Z, H, W, ci), dtype=torch.float32, device=g.device)
+    if gate is not None:
+        gate = _f32(gate)
+        assert tuple(gate.shape) == tuple(out.shape)
+    _check(load_library().th_lpips_dgrad(ctx(g.device), layer, _p(g), _p(gate), Z, H, W, _p(packed_bwd), _p(out), _stream()))
+    return out
+
+
+def lpips_pool_bwd(g, y):
+    """th_lpips_pool_bwd: backward of the 2 x 2 / stride 2 max pool.  g: NHWC [Z, H // 2, W // 2, C], y: the pooled map's
+    source NHWC [Z, H, W, C] -> [Z, H, W, C]."""
+    g, y = _f32(g), _f32(y)
+    Z, H, W, Cc = (int(n) for n in y.shape)
+    assert tuple(g.shape) == (Z, H // 2, W // 2, Cc)
+    out = torch.empty_like(y)
+    _check(load_library().th_lpips_pool_bwd(ctx(y.device), _p(g), _p(y), Z, H, W, Cc, _p(out), _stream()))
+    return out
+
+
+def lpips_head_bwd(f0, f1, lin, g_out, g=None, gate=False):
+    """th_lpips_head_bwd: f0, f1 float32 [N, hw, C], lin [C], g_out float64 [N] -> [N, hw, C]: g (when given, in place) plus
+    the fp32-rounded derivative of the head with respect to f0; gate=True zeroes it where f0 <= 0."""
+    f0, f1, lin = _f32(f0), _f32(f1), _f32(lin).reshape(-1)
+    N, hw, Cc = (int(n) for n in f0.shape)
+    assert f1.shape == f0.shape and lin.numel() == Cc
+    go = g_out.detach().reshape(-1).to(f0.device, torch.float64).contiguous()
+    assert go.numel() == N
+    acc = g is not None
+    if acc:
+        assert g.dtype is torch.float32 and g.is_contiguous() and g.shape == f0.shape
+    else:
+        g = torch.empty_like(f0)
+    _check(load_library().th_lpips_head_bwd(ctx(f0.device), _p(f0), _p(f1), N, hw, Cc, _p(lin), _p(go), int(acc), int(gate),
+                                            _p(g), _stream()))
+    return g
 
 
 def marching_cubes(cube, iso, scale=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), x_range=None):

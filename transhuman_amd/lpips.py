@@ -12,6 +12,9 @@ evaluation of the formula (tests/test_lpips_host.py: lpips_oracle), not against 
 
 Weights: torchvision's pretrained VGG16 (`vgg16-397923af.pth`, keys features.{0,2,5,...,28}.{weight,bias}) and LPIPS's
 `weights/v0.1/vgg.pth` (keys lin{k}.model.1.weight).  Nothing is downloaded: both files are read from the given paths.
+
+As the training loss (lib/train/trainers/if_nerf_clight.py:68-72): called under enabled grad on an in0 that requires grad,
+``forward`` goes through ``train_ops.LpipsFn`` (th_lpips_train / th_lpips_bwd) and the value carries the gradient into in0.
 """
 import torch
 
@@ -81,6 +84,8 @@ class LPIPS:
         conv_w, conv_b, lin_w = load_lpips_weights(vgg16_path, model_path, dev)
         self.device = dev
         self.packed = hip.lpips_pack(conv_w, conv_b, lin_w, dev)
+        self._vgg16_path, self._model_path = vgg16_path, model_path     # the input-gradient image (as large again) is packed
+        self.packed_bwd = None                                          # from the files on first use
         if verbose:
             print(f"LPIPS (vgg, v0.1) from {vgg16_path} and {model_path}")
 
@@ -88,10 +93,23 @@ class LPIPS:
         if normalize:                                        # lpips.py:82-84
             in0 = 2 * in0 - 1
             in1 = 2 * in1 - 1
+        if torch.is_grad_enabled() and in0.requires_grad:
+            return self._forward_train(in0, in1, retPerLayer)
         out = hip.lpips(in0.to(self.device), in1.to(self.device), self.packed)
         val = out[:, 5].reshape(-1, 1, 1, 1)
         if retPerLayer:
             return val, [out[:, k].reshape(-1, 1, 1, 1) for k in range(5)]
         return val
+
+    def _forward_train(self, in0, in1, retPerLayer):
+        from .networks.train_ops import LpipsFn
+        if retPerLayer:
+            raise NotImplementedError("LPIPS: retPerLayer has no gradient path (only the total does)")
+        if self.packed_bwd is None:
+            conv_w, _, _ = load_lpips_weights(self._vgg16_path, self._model_path)
+            self.packed_bwd = hip.lpips_pack_bwd(conv_w, self.device)
+        if in0.dim() == 3:
+            in0, in1 = in0[None], in1[None]
+        return LpipsFn.apply(in0.to(self.device), in1.to(self.device), self.packed, self.packed_bwd).reshape(-1, 1, 1, 1)
 
     __call__ = forward

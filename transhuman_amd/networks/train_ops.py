@@ -33,6 +33,10 @@ weight-gradient kernel -- and returns the gradients of the Parameters themselves
     ReluLinearFn            a, W, b              -> relu(Linear(a))    keeps a, y       s, p, fc_1, fc_2, fc_3, view_fc, fc_4
     CrossViewAttentionFn    kvp, kvs [P,V,384]   -> n [P,V,256]        keeps kvp, kvs   gradient: both; A is recomputed
 
+The loss the trainer back-propagates through (lib/train/trainers/if_nerf_clight.py:68-72; k_lpips.hip):
+
+    LpipsFn                 in0, in1 [N,3,H,W]   -> LPIPS_vgg [N] float64  keeps in0 and the forward's state   gradient: in0
+
 K4 and K5 are linear in the tensor that gets the gradient, so nothing of the forward is kept for the backward but the
 geometry (points, centres, cameras): the [P,7,255] blend operands and the per-chunk map-sized gradients of the torch
 formulation do not exist here.  Points, centres, rotations, cameras, depths and ray directions come from the batch and get
@@ -281,6 +285,27 @@ class LayerNormFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, w = ctx.saved_tensors
         return (*hip.layernorm_bwd(x, w, grad_out.contiguous(), ctx.eps), None)
+
+
+class LpipsFn(torch.autograd.Function):
+    """LPIPS (VGG16, v0.1) of in0 against in1, [N,3,H,W] in [-1, 1] -> float64 [N], through th_lpips_train with the backward of
+    th_lpips_bwd.  ``packed`` / ``packed_bwd``: the images of hip.lpips_pack / hip.lpips_pack_bwd.  Kept for the backward: in0 and
+    the forward's state (every layer's output).  in1 is the target and the weights are frozen: only in0 gets a gradient, in its
+    own dtype; an in1 that asks for one raises."""
+
+    @staticmethod
+    def forward(ctx, in0, in1, packed, packed_bwd):
+        if in1.requires_grad:
+            raise NotImplementedError("LpipsFn: only in0 has a gradient path (in1 is the target; it requires grad)")
+        _on_device("LpipsFn", in0)
+        out, state = hip.lpips_train(in0.detach(), in1, packed)
+        ctx.save_for_backward(in0, state, packed, packed_bwd)
+        return out[:, 5].contiguous()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        in0, state, packed, packed_bwd = ctx.saved_tensors
+        return hip.lpips_bwd(grad_out, in0, state, packed, packed_bwd).to(in0.dtype), None, None, None
 
 
 # ---- float64 restatements ---------------------------------------------------------------------------------------------------
