@@ -929,6 +929,62 @@ int th_eval_sigma_grid(th_ctx* ctx, const th_frame* f, const float* pts, int P, 
                        void* workspace, size_t workspace_bytes, void* shade_pool, size_t shade_pool_bytes,
                        int64_t* stats_host, th_stream stream);
 
+/* ---- K22: the optimiser step -- value clipping + Adam / AdamW for every parameter tensor in one launch (additions, ABI 12) ---- */
+/* What the reference's loop does per step with clip_grad_value_(., 40) and torch.optim.Adam over one parameter group per tensor
+ * (lib/train/trainers/trainer.py:85-86, lib/train/optimizer.py:16-19), as ONE copy of a per-tensor table and ONE kernel.
+ * All fp32, every operation rounded once, in this order (no FMA contraction; division and square root correctly rounded;
+ * subnormals kept), per element of a tensor whose table entry is t:
+ *     g  = clamp(g, -clip, clip)              with TH_ADAM_CLIP; a NaN stays NaN
+ *     p  = p * t.decay_mul                    with TH_ADAM_T_DECOUPLED in t.flags (AdamW: decay_mul = fp32(1 - lr wd)), else
+ *     g  = g + t.weight_decay * p             when t.weight_decay != 0
+ *     m' = m + t.one_minus_beta1 * (g - m)
+ *     v' = t.beta2 * v + (t.one_minus_beta2 * g) * g
+ *     p' = p - t.step_size * (m' / (sqrt(v') / t.bc2_sqrt + t.eps))
+ * with step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) computed by the caller in double precision and
+ * rounded to fp32 once.  p, m, v are updated in place; TH_ADAM_ZERO_GRAD also writes 0 over g after reading it.  An entry whose
+ * p is NULL is skipped (a parameter without a gradient this step).  Elementwise, no float atomics: two runs agree bit for bit.
+ * TH_ADAM_COUNT_NONFINITE adds the number of NaN / +-inf gradient elements (before clipping) to a device word of the plan with
+ * an integer atomic; it is read -- behind a stream synchronisation -- only by a call that passes nonfinite_out (the running
+ * total since th_adam_plan), and such a call may pass n_tensors = 0 to read without stepping.
+ *
+ * th_adam_plan cuts the tensors (counts[i] fp32 elements each, contiguous) into chunks of th_adam_chunk_elems() elements, one
+ * workgroup each, and uploads that chunk table into `table` (th_adam_table_bytes(n_tensors, sum of counts) bytes of device
+ * memory, 16-byte aligned, owned by the caller and alive as long as the plan); `params` (optional) are checked to be device
+ * pointers.  The call drains `stream`.  th_adam_step copies `scalars` (host memory, n_tensors entries, free for reuse on return)
+ * through a ring of 16 pinned staging buffers of the plan into `table` and launches the kernel: two queue operations per step,
+ * plus one event record every 8th step that tells the ring when a staging buffer may be rewritten.  128-bit accesses are used
+ * for a tensor whose four pointers are 16-byte aligned, 32-bit ones otherwise.  TH_ADAM_CHECK_POINTERS asks the runtime about
+ * every pointer of the step (a host pointer is refused with an error, not dereferenced); it costs ~1 us per pointer, so a
+ * caller sets it when the pointers are new.  Data types and contiguity cannot be seen through a pointer: the Python binding
+ * (transhuman_amd.hip.adam_step) refuses tensors that are not contiguous fp32 device tensors. */
+#define TH_ADAM_CHUNK 4096
+enum { TH_ADAM_CLIP = 1, TH_ADAM_ZERO_GRAD = 2, TH_ADAM_COUNT_NONFINITE = 4, TH_ADAM_CHECK_POINTERS = 8 };
+enum { TH_ADAM_T_DECOUPLED = 1 };
+typedef struct th_adam_tensor {
+    void* p;               /* parameter, NULL: skip this tensor */
+    void* g;               /* gradient */
+    void* m;               /* exp_avg */
+    void* v;               /* exp_avg_sq */
+    float lr;              /* (informative: the kernel reads step_size and decay_mul) */
+    float step_size;       /* lr / (1 - beta1^step) */
+    float bc2_sqrt;        /* sqrt(1 - beta2^step) */
+    float one_minus_beta1;
+    float beta2;
+    float one_minus_beta2;
+    float eps;
+    float weight_decay;    /* coupled form; ignored with TH_ADAM_T_DECOUPLED */
+    float decay_mul;       /* decoupled form: 1 - lr weight_decay */
+    uint32_t flags;        /* TH_ADAM_T_* */
+} th_adam_tensor;
+typedef struct th_adam_plan_t th_adam_plan_t;
+int    th_adam_chunk_elems(void);
+size_t th_adam_table_bytes(int n_tensors, long long total_elems);      /* pure host call; 0 for sizes out of range */
+int th_adam_plan(th_ctx* ctx, int n_tensors, const long long* counts, const void* const* params /* or NULL */, void* table,
+                 size_t table_bytes, th_adam_plan_t** out, th_stream stream);
+void th_adam_plan_destroy(th_adam_plan_t* plan);                         /* drains the device; `table` stays the caller's */
+int th_adam_step(th_ctx* ctx, th_adam_plan_t* plan, const th_adam_tensor* scalars, int n_tensors, float clip, int flags,
+                 unsigned long long* nonfinite_out /* or NULL */, th_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

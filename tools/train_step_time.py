@@ -11,7 +11,8 @@ on the device; keys gain '+pointnet').  Prints one JSON line.  Per mode: median 
 forward + backward with a device synchronisation at both ends) and torch.cuda.max_memory_allocated of the timed steps; the
 largest difference of the outputs and of every parameter gradient between the two modes; and, with --rocprof DIR, the device
 time of the K17 kernels per step from `rocprofv3 --kernel-trace --stats` over a short run of the "device" mode in a fresh child
-process (DIR keeps the trace).  No threshold on any figure."""
+process (DIR keeps the trace).  --optim torch,device adds the optimiser step (the reference's torch.optim.Adam form with
+clip_grad_value_, or train_optim.DeviceAdam) to what is timed.  No threshold on any figure."""
 import argparse
 import csv
 import glob
@@ -87,6 +88,39 @@ def run_mode(mode, cfg, net, r, b, target, steps, warmup):
             "peak_allocated_MiB": round(peak / 2 ** 20, 1)}, outs, grads
 
 
+def run_optim(kind, net, r, b, target, steps, warmup):
+    """forward + backward + clip at 40 + optimiser step, in whatever mode cfg is left in; the weights are put back"""
+    import torch
+    from transhuman_amd.train_optim import DeviceAdam
+    saved = {k: v.detach().clone() for k, v in net.state_dict().items()}
+    params = [p for p in net.parameters() if p.requires_grad]
+    groups = [{"params": [p], "lr": 7e-4, "weight_decay": 0} for p in params]
+    if kind == "device":
+        opt = DeviceAdam(groups, 7e-4, clip_value=40.0)
+    elif kind == "torch":
+        opt = torch.optim.Adam(groups, 7e-4)
+    else:
+        raise SystemExit(f"--optim: {kind!r} is neither 'torch' nor 'device'")
+    ms, opt_ms = [], []
+    for i in range(warmup + steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step(net, r, b, target)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        if kind == "torch":
+            torch.nn.utils.clip_grad_value_(params, 40.0)
+        opt.step()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if i >= warmup:
+            ms.append((t2 - t0) * 1e3)
+            opt_ms.append((t2 - t1) * 1e3)
+    net.load_state_dict(saved)
+    return {"step_ms_median": round(float(np.median(ms)), 2), "step_ms_min": round(float(np.min(ms)), 2),
+            "optim_ms_median": round(float(np.median(opt_ms)), 3), "optim_ms_min": round(float(np.min(opt_ms)), 3), "steps": steps}
+
+
 def kernel_times(out_dir, steps):
     """per-step device time of the K17 kernels from the child's kernel trace"""
     agg = defaultdict(lambda: [0, 0])
@@ -110,6 +144,10 @@ def main():
     ap.add_argument("--point-net", default="torch", help="comma list of cfg.train_point_net values; every mode runs once per value "
                                                          "(results of 'device' are keyed '<mode>[+<maps>]+pointnet')")
     ap.add_argument("--rocprof", default=None, metavar="DIR", help="also trace a short 'device' run under rocprofv3 into DIR")
+    ap.add_argument("--optim", default="", help="comma list of 'torch' (the reference's form: torch.optim.Adam, one group per "
+                                                "parameter, + clip_grad_value_(., 40)) and 'device' (train_optim.DeviceAdam, "
+                                                "K22): adds the optimiser step to what is timed, in the last mode run "
+                                                "(results keyed 'step+optim:<value>'; the weights are restored afterwards)")
     args = ap.parse_args()
     res = {"shape": {"rays": RAYS, "samples": SAMPLES, "views": VIEWS, "n_clusters": NC, "image": [SIZE, SIZE]}}
     if args.rocprof:
@@ -135,6 +173,8 @@ def main():
                     key = (mode if maps == "full" else f"{mode}+{maps}") + ("" if point_net == "torch" else "+pointnet")
                     res[key], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
                     seen[key] = (outs, grads)
+        for kind in [k for k in args.optim.split(",") if k]:
+            res[f"step+optim:{kind}"] = run_optim(kind, net, r, b, target, args.steps, args.warmup)
     finally:
         cfg.train_kernels, cfg.train_maps, cfg.train_point_net = "torch", "full", "torch"
     if "torch" in seen and "device" in seen:

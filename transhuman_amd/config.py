@@ -91,6 +91,16 @@ def _defaults():
         # lpips_weight * mean(LPIPS_vgg) over the rendered patches (transhuman_amd/train_loss.py, K21)
         l2rec_weight=1.0,
         lpips_weight=0.1,
+        # the optimiser, its schedule and the epoch loop (train_or_eval.yaml:42-43, :88-108; lib/config/config.py:53-111):
+        # transhuman_amd/train_optim.py and trainer.py
+        train=SimpleNamespace(optim="adam", lr=7e-4, weight_decay=0.0, epoch=3000,
+                              scheduler=SimpleNamespace(type="cosine", warmup_epochs=300, decay_epochs=3000, end_lr=1e-6)),
+        ep_iter=500,
+        save_freq=5,
+        save_latest_ep=5,
+        log_interval=20,
+        resume=True,
+        trained_model_dir="data/trained_model",
     )
 
 

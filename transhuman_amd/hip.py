@@ -7,6 +7,7 @@ the shared library is missing or a call fails this module raises.
 """
 import ctypes as C
 import os
+import sys
 
 import torch
 
@@ -275,6 +276,13 @@ SYMBOLS = {
     "th_sigma_grid_workspace_bytes": (C.c_size_t, [C.POINTER(ThFrame), C.c_int]),
     "th_eval_sigma_grid": (C.c_int, [C.c_void_p, C.POINTER(ThFrame), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),
+    "th_adam_chunk_elems": (C.c_int, []),
+    "th_adam_table_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
+    "th_adam_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p),
+                               C.c_void_p]),
+    "th_adam_plan_destroy": (None, [C.c_void_p]),
+    "th_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint64),
+                               C.c_void_p]),
 }
 
 _lib = None
@@ -1133,6 +1141,94 @@ def wgrad_chunk_rows():
 
 def layernorm_bwd_chunk_rows():
     return int(load_library().th_layernorm_bwd_chunk_rows())
+
+
+# ---------------------------------------------------------------------------
+# K22: the optimiser step (th_adam_plan / th_adam_step)
+# ---------------------------------------------------------------------------
+ADAM_CLIP, ADAM_ZERO_GRAD, ADAM_COUNT_NONFINITE, ADAM_CHECK_POINTERS = 1, 2, 4, 8
+ADAM_T_DECOUPLED = 1
+# th_adam_tensor as a numpy record (72 bytes): the per-step table is filled column-wise, not entry by entry
+ADAM_TENSOR_FIELDS = [("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("lr", "<f4"), ("step_size", "<f4"),
+                      ("bc2_sqrt", "<f4"), ("one_minus_beta1", "<f4"), ("beta2", "<f4"), ("one_minus_beta2", "<f4"),
+                      ("eps", "<f4"), ("weight_decay", "<f4"), ("decay_mul", "<f4"), ("flags", "<u4")]
+
+
+def adam_chunk_elems():
+    """elements per workgroup of adam_step_kernel (a tensor's last chunk holds the rest)"""
+    return int(load_library().th_adam_chunk_elems())
+
+
+def adam_check_tensor(t, what):
+    """the refusals of the optimiser step that a raw pointer cannot show: HipError, nothing is converted silently"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise HipError(f"adam_step: {what} is not a device tensor (there is no CPU path)")
+    if t.dtype is not torch.float32:
+        raise HipError(f"adam_step: {what} is {t.dtype}, the kernel updates fp32 only")
+    if not t.is_contiguous():
+        raise HipError(f"adam_step: {what} is not contiguous")
+
+
+class AdamPlan:
+    """th_adam_plan for a fixed list of contiguous fp32 device tensors: owns the device tables and the pinned ring."""
+
+    def __init__(self, params):
+        import numpy as np
+        lib = load_library()
+        params = list(params)
+        if not params:
+            raise HipError("adam_plan: no tensors")
+        for i, p in enumerate(params):
+            adam_check_tensor(p, f"parameter {i}")
+            if p.numel() == 0:
+                raise HipError(f"adam_plan: parameter {i} has no elements")
+            if p.device != params[0].device:
+                raise HipError("adam_plan: the parameters live on different devices")
+        self.device = params[0].device
+        self.n = len(params)
+        counts = np.array([p.numel() for p in params], dtype=np.int64)
+        ptrs = np.array([p.data_ptr() for p in params], dtype=np.uint64)
+        nbytes = int(lib.th_adam_table_bytes(self.n, int(counts.sum())))
+        if nbytes == 0:
+            raise HipError("adam_plan: sizes out of range")
+        self.table = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.dtype = np.dtype(ADAM_TENSOR_FIELDS)
+        assert self.dtype.itemsize == 72
+        self.steps = 0
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(lib.th_adam_plan(ctx(self.device), self.n, counts.ctypes.data, ptrs.ctypes.data, _p(self.table),
+                                    nbytes, C.byref(h), _stream()))
+        self._h = h
+        self._destroy = lib.th_adam_plan_destroy
+
+    def step(self, table, clip=None, zero_grad=False, count_nonfinite=False, check_pointers=False):
+        """table: numpy records of ADAM_TENSOR_FIELDS, one per planned tensor (p = 0 skips a tensor)"""
+        assert table.dtype == self.dtype and table.shape == (self.n,) and table.flags.c_contiguous
+        flags = ((ADAM_CLIP if clip is not None else 0) | (ADAM_ZERO_GRAD if zero_grad else 0) |
+                 (ADAM_COUNT_NONFINITE if count_nonfinite else 0) | (ADAM_CHECK_POINTERS if check_pointers else 0))
+        clip = float(clip if clip is not None else 0.0)
+        if torch._C._cuda_getDevice() == self.device.index:              # (the usual case: no context manager on the hot path)
+            _check(_lib.th_adam_step(ctx(self.device), self._h, table.ctypes.data, self.n, clip, flags, None, _stream()))
+        else:
+            with torch.cuda.device(self.device):
+                _check(_lib.th_adam_step(ctx(self.device), self._h, table.ctypes.data, self.n, clip, flags, None, _stream()))
+        self.steps += 1
+
+    def nonfinite(self):
+        """gradient elements that were NaN or +-inf in the counted steps so far (synchronises the current stream)"""
+        out = C.c_uint64(0)
+        with torch.cuda.device(self.device):
+            _check(_lib.th_adam_step(ctx(self.device), self._h, None, 0, 0.0, 0, C.byref(out), _stream()))
+        return int(out.value)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and not sys.is_finalizing():          # (at interpreter exit the runtime may be gone already)
+            try:
+                self._destroy(h)
+            except Exception:
+                pass
 
 
 def _train_rows(fn, t, cols=None):
