@@ -87,9 +87,16 @@ def knn_points_exact(p, q, K, chunk=4096):
 
 def hull_mask(pts, verts, thresh=0.1):
     """if_clight_renderer.py:440-442 -- sqrt(min d2) < 0.1 per sample.
-    pts [P,3], verts [NV,3] (both world space) -> bool [P]."""
+    pts [P,3], verts [NV,3] (both world space) -> bool [P].
+    The square root is the CORRECTLY ROUNDED one of d2's own precision, as IEEE 754 and the reference's CUDA sqrt give it.  For
+    fp32 it is taken in float64 and rounded back (53 >= 2 * 24 + 2 bits: the double rounding is exact for a square root): the
+    fp32 sqrt of torch's CPU kernels is an ulp off on some hosts (one x86 server CPU: 14 % of the operands, 176 samples of
+    tests/hull_cases.py's thresh-0.3 shells decided the other way), and a sample an ulp from the threshold flips with it."""
     d2, _ = knn_points_exact(pts, verts, 1)
-    return d2[:, 0].sqrt() < thresh
+    d2 = d2[:, 0]
+    if d2.dtype == torch.float32:
+        return d2.double().sqrt().float() < thresh
+    return d2.sqrt() < thresh
 
 
 # ---------------------------------------------------------------------------

@@ -26,8 +26,13 @@ struct GridInfo {
 #define GRID_MAX_DIM 64
 #define GRID_MAX_CELLS (GRID_MAX_DIM * GRID_MAX_DIM * GRID_MAX_DIM)
 
+// Clamped in float to [-2, GRID_MAX_DIM + 1] in front of the conversion: every caller only asks "which cell of -1 .. dim"
+// (dim <= GRID_MAX_DIM), -2 and GRID_MAX_DIM + 1 are outside for all of them, and a float -> int conversion of a NaN, an
+// infinity or a value past 2^31 is undefined.  fmaxf returns its other operand for a NaN: -2, outside.  Results in
+// -1 .. GRID_MAX_DIM are unchanged.
 __device__ __forceinline__ int cell_coord(float x, float gmin, float inv_h) {
-    return (int)floorf((x - gmin) * inv_h);
+    const float c = floorf((x - gmin) * inv_h);
+    return (int)fminf(fmaxf(c, -2.0f), (float)(GRID_MAX_DIM + 1));
 }
 
 __device__ __forceinline__ int vert_cell(const GridInfo& g, float x, float y, float z) {
