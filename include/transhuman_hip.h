@@ -42,7 +42,7 @@ const char* th_last_error(void);
 int         th_ctx_create(int device, th_ctx** out);
 void        th_ctx_destroy(th_ctx* ctx);
 /* sizeof() of a struct of this header as the LIBRARY was compiled with it: "th_points", "th_frame", "th_map_source",
- * "th_linear", "th_mlp_weights", "th_vit_block", "th_smpl_model"; 0 for an unknown name.  A binding written in another language
+ * "th_linear", "th_mlp_weights", "th_vit_block", "th_smpl_model", "th_adam_tensor"; 0 for an unknown name.  A binding written in another language
  * (INTEGRATION.md's ctypes stub) checks its own struct definitions against it -- a struct that is short by one field
  * makes the library read garbage pointers (ABI 10 grew th_points by two). */
 size_t      th_sizeof(const char* type_name);

@@ -105,3 +105,118 @@ def test_integration_md_structs_match_the_library(lib):
     assert C.sizeof(hip.ThFrame) == lib.th_sizeof(b"th_frame")
     assert C.sizeof(hip.ThMapSource) == lib.th_sizeof(b"th_map_source")
     assert lib.th_sizeof(b"no_such_struct") == 0
+
+
+# ---- the binding is derived from the header (transhuman_amd/cheader.py) ----
+# every form the real header uses, once
+SMALL_HEADER = """\
+#ifndef SMALL_H
+#define SMALL_H
+#define TH_LIMIT 0x7B53u   /* 6.0e4 */
+enum { TH_A = 1, TH_B = 2 /* a note */, TH_C = 8 };
+typedef struct th_ctx th_ctx;
+typedef void* th_stream;
+typedef struct { const float* w; int out_f; } th_lin;
+typedef struct {
+    int a, b;                  /* two in one declaration */
+    const float *p, *q;
+    int32_t dims[6];
+    th_lin first, second;
+    const th_lin* next;
+} th_box;
+typedef struct th_rec { void* p; float lr; uint32_t flags; } th_rec;
+int         th_version(void);
+const char* th_error(void);
+void th_free(th_ctx* ctx);
+size_t th_bytes(const th_box* b, long long n, unsigned long long* count_out);
+int th_run(th_ctx* ctx, const float* x /* [3] */, float scale, double* out,
+           const void* const* tables, const th_lin* lin, th_rec* recs,
+           th_ctx** made, double ratio, th_stream stream);
+#endif
+"""
+
+
+def test_header_reader_on_every_declaration_form():
+    import ctypes as C
+    from transhuman_amd import cheader
+    h = cheader.parse(SMALL_HEADER, records=("th_rec",))
+    assert h.constants == {"TH_LIMIT": 0x7B53, "TH_A": 1, "TH_B": 2, "TH_C": 8}
+    assert list(h.structs) == ["th_lin", "th_box"]
+    lin, box = h.structs["th_lin"], h.structs["th_box"]
+    assert (lin.__name__, box.__name__) == ("ThLin", "ThBox") and issubclass(box, C.Structure)
+    assert lin._fields_ == [("w", C.c_void_p), ("out_f", C.c_int)]
+    assert box._fields_ == [("a", C.c_int), ("b", C.c_int), ("p", C.c_void_p), ("q", C.c_void_p), ("dims", C.c_int32 * 6),
+                            ("first", lin), ("second", lin), ("next", C.c_void_p)]
+    assert h.records == {"th_rec": [("p", "<u8"), ("lr", "<f4"), ("flags", "<u4")]}
+    vp = C.c_void_p
+    assert h.prototypes == {
+        "th_version": (C.c_int, []),
+        "th_error": (C.c_char_p, []),
+        "th_free": (None, [vp]),
+        "th_bytes": (C.c_size_t, [C.POINTER(box), C.c_longlong, vp]),
+        "th_run": (C.c_int, [vp, vp, C.c_float, vp, vp, C.POINTER(lin), vp, vp, C.c_double, vp]),
+    }
+
+
+@pytest.mark.parametrize("bad, line", [
+    ("int th_ok(void);\nint th_bad(unsigned x);\n", 2),                        # a scalar type outside the rules
+    ("int th_ok(void);\n\ntypedef struct { flaot x; } th_s;\n", 3),           # an unknown field type
+    ("/* two\n lines */\nint th_bad(int a) int th_more(int b);\n", 3),         # a lost semicolon
+    ("int th_ok(void);\nint th_ok(void);\n", 2),                               # declared twice
+    ("enum { TH_A = 1, TH_B };\n", 1),                                         # an enumerator without a value
+    ("#define TH_N twelve\n", 1),
+    ("int th_ok(void);\nint th_unfinished(int a\n", 2),
+    ("typedef struct th_rec { double d; } th_rec;\n", 1),                      # a record field numpy has no code for here
+])
+def test_header_reader_refuses_what_it_cannot_parse(bad, line):
+    from transhuman_amd import cheader
+    with pytest.raises(cheader.HeaderError, match=rf"^small\.h:{line}: "):
+        cheader.parse(bad, records=("th_rec",), where="small.h")
+
+
+def test_header_reader_is_complete_on_the_real_header(lib):
+    import ctypes as C
+    import numpy as np
+    from transhuman_amd import cheader, hip
+    h = cheader.load()
+    assert hip.SYMBOLS is h.prototypes and len(h.prototypes) == len(header_functions())
+    assert h.constants["TH_ABI_VERSION"] == lib.th_abi_version()
+    assert (hip.RANGE_FP16_LIMIT, hip.RANGE_FP16_FLOOR) == (0x7B53, 0x2400)
+    assert (hip.ADAM_CLIP, hip.ADAM_ZERO_GRAD, hip.ADAM_COUNT_NONFINITE, hip.ADAM_CHECK_POINTERS, hip.ADAM_T_DECOUPLED) == \
+        (1, 2, 4, 8, 1)
+    # every struct th_sizeof knows has a class or a record here, of the library's size
+    api = open(os.path.join(ROOT, "transhuman_amd", "csrc", "th_api.hip")).read()
+    sized = re.findall(r"TH_SZ\((th_\w+)\)", api)
+    assert len(sized) == 8 and set(sized) == set(h.structs) | set(h.records)
+    for name in sized:
+        want = lib.th_sizeof(name.encode())
+        have = C.sizeof(h.structs[name]) if name in h.structs else np.dtype(h.records[name]).itemsize
+        assert want > 0 and have == want, (name, have, want)
+    for name in ("ThLinear", "ThMlpWeights", "ThVitBlock", "ThPoints", "ThSmplModel", "ThMapSource", "ThFrame"):
+        assert getattr(hip, name) in h.structs.values() and getattr(hip, name).__name__ == name
+    assert hip.ADAM_TENSOR_FIELDS is h.records["th_adam_tensor"]
+
+
+def test_derived_signatures_against_hand_written_ones():
+    """The only signatures typed twice: five that between them use every rule of the reader."""
+    import ctypes as C
+    from transhuman_amd import hip
+    vp, i, f, sz, ll = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
+    frame, points, linear = C.POINTER(hip.ThFrame), C.POINTER(hip.ThPoints), C.POINTER(hip.ThLinear)
+    assert hip.SYMBOLS["th_render_rays"] == (i, [vp, frame, points, vp, vp, vp, i, vp, sz, vp, sz, vp, vp])
+    assert hip.SYMBOLS["th_patch_rays"] == (i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ll, ll, i, i, vp, C.c_double, i, i,
+                                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp])
+    assert hip.SYMBOLS["th_linear_bwd"] == (i, [vp, vp, i, i, i, vp, vp, f, linear, vp, i, vp, i, vp, vp, vp, vp, vp, sz, vp])
+    assert hip.SYMBOLS["th_adam_step"] == (i, [vp, vp, vp, i, f, i, vp, vp])
+    assert hip.SYMBOLS["th_shade_pool_bytes"] == (sz, [vp, frame, ll, i])
+
+
+def test_struct_field_offsets():
+    """th_sizeof cannot see two same-sized fields in the wrong order (H / W, centres / rot): offsets by hand from the header"""
+    import ctypes as C
+    from transhuman_amd import hip
+    F, P = hip.ThFrame, hip.ThPoints
+    assert [getattr(F, n).offset for n in ("verts_world", "H", "W", "centres", "rot", "map_fold")] == [0, 60, 64, 80, 88, 120]
+    assert C.sizeof(F) == 128
+    assert [getattr(P, n).offset for n in ("pts", "R", "S", "sigma_noise")] == [0, 56, 60, 72]
+    assert C.sizeof(P) == 80

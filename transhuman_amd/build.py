@@ -18,6 +18,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INC = os.path.join(os.path.dirname(HERE), "include")
+HEADER = os.path.join(INC, "transhuman_hip.h")       # the C ABI; cheader.py derives the ctypes binding from it
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libtranshuman_hip.so")
 ARCH = "gfx950"
@@ -39,7 +40,7 @@ def _sources():
 def _digest():
     h = hashlib.sha256()
     headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
-    for p in _sources() + headers + [os.path.join(INC, "transhuman_hip.h")]:
+    for p in _sources() + headers + [HEADER]:
         h.update(open(p, "rb").read())
     # (flags without the absolute -I paths: the same tree under another root -- the GPU box's snapshot -- is up to date)
     h.update(" ".join(f for f in FLAGS if not f.startswith("-I")).encode())

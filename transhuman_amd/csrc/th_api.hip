@@ -70,6 +70,7 @@ size_t th_sizeof(const char* type_name) {
     if (type_name == nullptr) return 0;
 #define TH_SZ(T) if (strcmp(type_name, #T) == 0) return sizeof(T)
     TH_SZ(th_points); TH_SZ(th_frame); TH_SZ(th_map_source); TH_SZ(th_linear); TH_SZ(th_mlp_weights); TH_SZ(th_vit_block); TH_SZ(th_smpl_model);
+    TH_SZ(th_adam_tensor);
 #undef TH_SZ
     return 0;
 }

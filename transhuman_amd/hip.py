@@ -11,279 +11,21 @@ import sys
 
 import torch
 
+from . import cheader
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TH_LIB_PATH: developer override to A/B an experimental build of the same ABI
 LIB_PATH = os.environ.get("TH_LIB_PATH") or os.path.join(_HERE, "libtranshuman_hip.so")
 
 c_float_p = C.POINTER(C.c_float)
 
-
-class ThLinear(C.Structure):
-    _fields_ = [("w", C.c_void_p), ("b", C.c_void_p), ("out_f", C.c_int), ("in_f", C.c_int)]
-
-
-class ThMlpWeights(C.Structure):
-    _names = ["fc_0", "alpha_res_0", "key0", "val0", "key1", "val1", "fc_1", "fc_2", "fc_3", "alpha_fc",
-              "feature_fc", "rgb_res_0", "view_fc", "rgb_res_1", "fc_4", "rgb_fc", "upsample_color"]
-    _fields_ = [(n, ThLinear) for n in _names]
-
-
-class ThSmplModel(C.Structure):
-    _fields_ = [("v_template", C.c_void_p), ("shapedirs", C.c_void_p), ("posedirs", C.c_void_p),
-                ("J_regressor", C.c_void_p), ("weights", C.c_void_p), ("parent", C.c_void_p), ("n_verts", C.c_int)]
-
-
-class ThVitBlock(C.Structure):
-    _fields_ = [("ln1_w", C.c_void_p), ("ln1_b", C.c_void_p), ("ln2_w", C.c_void_p), ("ln2_b", C.c_void_p),
-                ("qkv", ThLinear), ("proj", ThLinear), ("fc1", ThLinear), ("fc2", ThLinear)]
-
-
-class ThPoints(C.Structure):
-    _fields_ = [("pts", C.c_void_p), ("ray_o", C.c_void_p), ("ray_d", C.c_void_p), ("near", C.c_void_p),
-                ("far", C.c_void_p), ("t_vals", C.c_void_p), ("one_minus_t", C.c_void_p), ("R", C.c_int),
-                ("S", C.c_int), ("z_vals", C.c_void_p), ("sigma_noise", C.c_void_p)]
-
-
-class ThFrame(C.Structure):
-    _fields_ = [("verts_world", C.c_void_p), ("n_verts", C.c_int), ("Rh", C.c_void_p), ("Th", C.c_void_p),
-                ("cams", C.c_void_p), ("scale_xy", C.c_void_p), ("pixel_map_nhwc", C.c_void_p), ("V", C.c_int),
-                ("H", C.c_int), ("W", C.c_int), ("map_channels", C.c_int), ("tokens", C.c_void_p), ("centres", C.c_void_p),
-                ("rot", C.c_void_p), ("n_clusters", C.c_int), ("hull_thresh", C.c_float),
-                ("small_frame_rays", C.c_int), ("map_source", C.c_void_p), ("map_fold", C.c_void_p)]
-
-
-class ThMapSource(C.Structure):
-    _fields_ = [("box", C.c_void_p), ("reach", C.c_float), ("img", C.c_void_p), ("lat0", C.c_void_p),
-                ("lat1", C.c_void_p), ("lat2", C.c_void_p), ("dims", C.c_int32 * 6), ("demand", C.c_void_p)]
-
-
-# every symbol include/transhuman_hip.h declares (tests/test_cabi.py checks the export table)
-SYMBOLS = {
-    "th_abi_version": (C.c_int, []),
-    "th_last_error": (C.c_char_p, []),
-    "th_sizeof": (C.c_size_t, [C.c_char_p]),
-    "th_ctx_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
-    "th_ctx_destroy": (None, [C.c_void_p]),
-    "th_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
-    "th_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    "th_fused_cycles": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "th_host_wait_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
-    "th_clock_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "th_set_mlp_weights": (C.c_int, [C.c_void_p, C.POINTER(ThMlpWeights), C.c_void_p]),
-    "th_set_mlp_mode": (C.c_int, [C.c_void_p, C.c_int]),
-    "th_set_fused_waves": (C.c_int, [C.c_void_p, C.c_int]),
-    "th_set_vit_mode": (C.c_int, [C.c_void_p, C.c_int]),
-    "th_set_tok_gather": (C.c_int, [C.c_void_p, C.c_int]),
-    "th_set_tex_rows": (C.c_int, [C.c_void_p, C.c_int]),
-    "th_map_fold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "th_pixel_texlist_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "th_pixel_texlist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_range_snapshot": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "th_range_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]),
-    "th_range_last_slot": (C.c_int, [C.c_void_p]),
-    "th_set_chunk_samples": (C.c_int, [C.c_int]),
-    "th_set_vit_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ThVitBlock), C.c_void_p,
-                                     C.c_void_p, C.c_void_p]),
-    "th_linear_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "th_linear_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ThLinear), C.c_int,
-                                    C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_hull_workspace_bytes": (C.c_size_t, [C.c_int]),
-    "th_hull_mask": (C.c_int, [C.c_void_p, C.POINTER(ThPoints), C.c_void_p, C.c_int, C.c_float, C.c_void_p,
-                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_paint_group": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                 C.c_void_p, C.c_void_p]),
-    "th_segment_mean_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                      C.c_void_p]),
-    "th_segment_mean_rot_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                          C.c_void_p]),
-    "th_upsample_concat_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]),
-    "th_upsample_concat_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_upsample_concat_split_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                               C.c_void_p]),
-    "th_map_demand_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_upsample_concat_split_demand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                  C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p]),
-    "th_map_fold_demand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "th_render_predemand": (C.c_int, [C.c_void_p, C.POINTER(ThFrame), C.POINTER(ThPoints), C.c_void_p, C.c_size_t, C.c_void_p,
-                                      C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_map_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                             C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
-    "th_paint_group_nhwc_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "th_paint_group_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ThLinear), C.POINTER(ThLinear),
-                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_vit_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "th_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                 C.c_size_t, C.c_void_p]),
-    "th_attention_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
-                               C.c_void_p]),
-    "th_attention_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_attention_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_attention_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_attention_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_wgrad_chunk_rows": (C.c_int, []),
-    "th_layernorm_bwd_chunk_rows": (C.c_int, []),
-    "th_linear_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "th_linear_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
-                                          C.POINTER(ThLinear), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_linear_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "th_linear_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
-                                C.POINTER(ThLinear), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_layernorm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
-                                       C.c_void_p, C.c_int, C.c_void_p]),
-    "th_layernorm_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "th_layernorm_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
-                                   C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_linear_relu_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_linear_relu_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ThLinear), C.c_void_p, C.c_int,
-                                         C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_linear_relu_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_linear_relu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(ThLinear),
-                                     C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                     C.c_void_p]),
-    "th_xview_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_xview_attention_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_void_p]),
-    "th_dparf_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                  C.c_void_p]),
-    "th_pixel_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "th_pixel_gather_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "th_network_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "th_network_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
-                                     C.c_void_p]),
-    "th_dparf_encode_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_dparf_encode_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_pixel_gather_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_latent_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_latent_gather_bwd": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p]),
-    "th_composite_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ThPoints), C.c_int, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p]),
-    "th_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ThPoints), C.c_int, C.c_void_p,
-                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "th_gen_rays": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_int, C.c_int, C.c_void_p,
-                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "th_bound_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_ssim_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                          C.c_size_t, C.c_void_p]),
-    "th_rasterize_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
-    "th_rasterize_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_vertex_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                       C.c_void_p, C.c_void_p]),
-    "th_depth_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "th_vertex_normals_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "th_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_shade_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float,
-                                C.c_int, C.c_void_p, C.c_void_p]),
-    "th_prep_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "th_prep_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_patch_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "th_patch_rays": (C.c_int, [C.c_void_p] * 9 + [C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int,
-                                C.c_int] + [C.c_void_p] * 13 + [C.c_size_t, C.c_void_p]),
-    "th_lpips_pack_bytes": (C.c_size_t, []),
-    "th_lpips_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_lpips_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_lpips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                           C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_lpips_bwd_pack_bytes": (C.c_size_t, []),
-    "th_lpips_pack_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_lpips_train_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_lpips_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_lpips_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_lpips_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_lpips_dgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                 C.c_void_p, C.c_void_p]),
-    "th_lpips_pool_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                    C.c_void_p]),
-    "th_lpips_head_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_marching_cubes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_marching_cubes_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
-                                          C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),
-    "th_marching_cubes_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.POINTER(C.c_int64), C.c_void_p]),
-    "th_marching_cubes_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
-                                         C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
-                                         C.c_void_p, C.c_void_p]),
-    "th_smpl_workspace_bytes": (C.c_size_t, [C.c_int]),
-    "th_smpl_lbs": (C.c_int, [C.c_void_p, C.POINTER(ThSmplModel), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_view_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_render_workspace_bytes": (C.c_size_t, [C.POINTER(ThFrame), C.c_int, C.c_int]),
-    "th_shade_pool_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ThFrame), C.c_longlong, C.c_int]),
-    "th_render_prepass_wait": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
-    "th_render_rays": (C.c_int, [C.c_void_p, C.POINTER(ThFrame), C.POINTER(ThPoints), C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                 C.POINTER(C.c_int64), C.c_void_p]),
-    "th_render_prepass": (C.c_int, [C.c_void_p, C.POINTER(ThFrame), C.POINTER(ThPoints), C.c_void_p, C.c_size_t,
-                                    C.c_void_p]),
-    "th_render_pregrid": (C.c_int, [C.c_void_p, C.POINTER(ThFrame), C.POINTER(ThPoints), C.c_void_p, C.c_size_t,
-                                    C.c_void_p]),
-    "th_render_pregather": (C.c_int, [C.c_void_p, C.POINTER(ThFrame), C.POINTER(ThPoints), C.c_void_p, C.c_size_t,
-                                      C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_render_pregather_early": (C.c_int, [C.c_void_p, C.POINTER(ThFrame), C.POINTER(ThPoints), C.c_void_p, C.c_size_t,
-                                      C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_conv_pack_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_conv_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
-                               C.POINTER(C.c_float), C.c_void_p]),
-    "th_conv2d_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "th_conv2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int,
-                            C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_maxpool3x3s2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_bn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "th_bn_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                            C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
-                            C.c_void_p]),
-    "th_bn_act_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                 C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "th_conv2d_stats_partials": (C.c_int, [C.c_int] * 7),
-    "th_conv2d_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int,
-                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "th_bn_act_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                  C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                  C.c_void_p]),
-    "th_render_prepass_cancel": (C.c_int, [C.c_void_p]),
-    "th_render_prepass_drop": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "th_sigma_grid_workspace_bytes": (C.c_size_t, [C.POINTER(ThFrame), C.c_int]),
-    "th_eval_sigma_grid": (C.c_int, [C.c_void_p, C.POINTER(ThFrame), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                     C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),
-    "th_adam_chunk_elems": (C.c_int, []),
-    "th_adam_table_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
-    "th_adam_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p),
-                               C.c_void_p]),
-    "th_adam_plan_destroy": (None, [C.c_void_p]),
-    "th_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint64),
-                               C.c_void_p]),
-}
+# The binding follows include/transhuman_hip.h (cheader.py): prototypes, struct layouts and constants are written down there
+# only.  SYMBOLS: name -> (restype, [argtypes]) for every function the header declares.
+_H = cheader.load()
+SYMBOLS = _H.prototypes
+ThLinear, ThMlpWeights, ThVitBlock, ThPoints, ThSmplModel, ThMapSource, ThFrame = (
+    _H.structs[n] for n in ("th_linear", "th_mlp_weights", "th_vit_block", "th_points", "th_smpl_model", "th_map_source",
+                            "th_frame"))
 
 _lib = None
 _ctx = {}
@@ -306,8 +48,10 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if lib.th_abi_version() != 12:
-        raise HipError("ABI version mismatch")
+    have, want = lib.th_abi_version(), _H.constants["TH_ABI_VERSION"]
+    if have != want:
+        raise HipError(f"{LIB_PATH} has ABI version {have}, include/transhuman_hip.h declares {want}: rebuild it with "
+                       "`python -m transhuman_amd.build`")
     _lib = lib
     return lib
 
@@ -476,8 +220,8 @@ def _sync_weights(mod, kind):
 # range guard of the fp16 hi/lo split arithmetic (include/transhuman_hip.h: th_range_*)
 # ---------------------------------------------------------------------------
 RANGE_NAMES = ("f", "s", "p", "n", "inter", "fc4_in", "conv_in", "vit_in")
-RANGE_FP16_LIMIT = 0x7B53          # 6.0e4 as an fp16 bit pattern (inf / NaN are larger)
-RANGE_FP16_FLOOR = 0x2400          # 2^-6
+RANGE_FP16_LIMIT = _H.constants["TH_RANGE_FP16_LIMIT"]     # 6.0e4 as an fp16 bit pattern (inf / NaN are larger)
+RANGE_FP16_FLOOR = _H.constants["TH_RANGE_FP16_FLOOR"]     # 2^-6
 RANGE_FP32_LIMIT = 0x476A6000      # 6.0e4 as an fp32 bit pattern (slot conv_in)
 _user_mode = {}                    # device index -> mode requested through set_mlp_mode (default 1)
 _range_fallback = {}               # device index -> True while the guard forces mode 0 on this context
@@ -1146,12 +890,11 @@ def layernorm_bwd_chunk_rows():
 # ---------------------------------------------------------------------------
 # K22: the optimiser step (th_adam_plan / th_adam_step)
 # ---------------------------------------------------------------------------
-ADAM_CLIP, ADAM_ZERO_GRAD, ADAM_COUNT_NONFINITE, ADAM_CHECK_POINTERS = 1, 2, 4, 8
-ADAM_T_DECOUPLED = 1
-# th_adam_tensor as a numpy record (72 bytes): the per-step table is filled column-wise, not entry by entry
-ADAM_TENSOR_FIELDS = [("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("lr", "<f4"), ("step_size", "<f4"),
-                      ("bc2_sqrt", "<f4"), ("one_minus_beta1", "<f4"), ("beta2", "<f4"), ("one_minus_beta2", "<f4"),
-                      ("eps", "<f4"), ("weight_decay", "<f4"), ("decay_mul", "<f4"), ("flags", "<u4")]
+ADAM_CLIP, ADAM_ZERO_GRAD, ADAM_COUNT_NONFINITE, ADAM_CHECK_POINTERS, ADAM_T_DECOUPLED = (
+    _H.constants["TH_" + n] for n in ("ADAM_CLIP", "ADAM_ZERO_GRAD", "ADAM_COUNT_NONFINITE", "ADAM_CHECK_POINTERS",
+                                      "ADAM_T_DECOUPLED"))
+# th_adam_tensor as a numpy record: the per-step table is filled column-wise, not entry by entry
+ADAM_TENSOR_FIELDS = _H.records["th_adam_tensor"]
 
 
 def adam_chunk_elems():
@@ -1193,7 +936,7 @@ class AdamPlan:
             raise HipError("adam_plan: sizes out of range")
         self.table = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.dtype = np.dtype(ADAM_TENSOR_FIELDS)
-        assert self.dtype.itemsize == 72
+        assert self.dtype.itemsize == lib.th_sizeof(b"th_adam_tensor")
         self.steps = 0
         h = C.c_void_p()
         with torch.cuda.device(self.device):
