@@ -985,6 +985,48 @@ void th_adam_plan_destroy(th_adam_plan_t* plan);                         /* drai
 int th_adam_step(th_ctx* ctx, th_adam_plan_t* plan, const th_adam_tensor* scalars, int n_tensors, float clip, int flags,
                  unsigned long long* nonfinite_out /* or NULL */, th_stream stream);
 
+/* ---- K23: the backward of the encoder trunk in training (additions, ABI 12) ---- */
+/* The sites of SpatialEncoder.trunk (encoder.py:114-126: conv1 / bn1 / relu, the 3x3 / 2 max pool, layer1, layer2), backward only: the
+ * forward stays the stock torch modules.  All tensors NCHW fp32, contiguous; H and W are the INPUT size of the convolution or the
+ * pool, its output is Ho = (H + 2 (ks / 2) - ks) / stride + 1 rows.  No atomics, every sum in a fixed order: two runs agree bit
+ * for bit.  Matrix work runs on the fp32-input MFMA, no reduced-precision operand and no range guard.  DESIGN.md 4, K23.
+ *
+ * th_conv2d_bwd_supported: 0, or bit 0 (1): th_conv2d_wgrad is built for this convolution, bit 1 (2): th_conv2d_dgrad as well.
+ * Built: 3x3/1 64->64, 3x3/1 128->128, 3x3/2 64->128, 1x1/2 64->128 (both), 7x7/2 3->64 (weight gradient only).
+ *
+ * th_bn_act_bwd: train-mode BatchNorm (batch statistics, biased variance) followed by an optional residual add and an optional
+ * ReLU.  y: the BatchNorm's input; out: the site's output, read for the gate [out > 0] (NULL: no ReLU); g: the gradient of the
+ * site's output; gamma NULL: 1.  g_y: the gradient of y; g_res (optional): the gated gradient, which is the residual's; g_gamma /
+ * g_beta [C] (optional).  Statistics and sums are fp64 (th_bn_act_bwd_slice_elems: the least slice of a channel one workgroup sums).
+ *
+ * th_conv2d_dgrad: g_y [N, cout, Ho, Wo] -> g_x [N, cin, H, W], every element written, from an image of the weights that
+ * th_conv2d_dgrad_pack writes into caller-owned memory (th_conv2d_dgrad_pack_bytes, 16-byte aligned; pack again when the weights
+ * change).  A workgroup owns th_conv2d_dgrad_tile_rows x th_conv2d_dgrad_tile_cols input pixels of one parity class.
+ *
+ * th_conv2d_wgrad: x [N, cin, H, W], g_y -> g_w [cout, cin, ks, ks].  The output pixels are cut into chunks of
+ * th_conv2d_wgrad_chunk_pixels; each chunk's partial is a fresh MFMA chain, the chunks are added in chunk order (fp64, one rounding).
+ *
+ * th_maxpool3x3s2_bwd: x [planes, H, W] (the pool's input), g [planes, Ho, Wo] -> g_x; a window's gradient goes to the element
+ * torch's forward records (the last one, kh outer / kw inner, with val > max || isnan(val)); the padding never wins. */
+int    th_conv2d_bwd_supported(int cin, int cout, int ks, int stride);
+int    th_conv2d_wgrad_chunk_pixels(void);
+int    th_conv2d_dgrad_tile_rows(void);
+int    th_conv2d_dgrad_tile_cols(void);
+int    th_bn_act_bwd_slice_elems(void);
+size_t th_bn_act_bwd_workspace_bytes(int N, int C, int HW);                                    /* pure host call; 0: unsupported */
+int th_bn_act_bwd(th_ctx* ctx, const float* y, const float* out_or_null, const float* g, int N, int C, int HW,
+                  const float* gamma_or_null, double eps, float* g_y, float* g_res_or_null, float* g_gamma_or_null,
+                  float* g_beta_or_null, void* workspace, size_t workspace_bytes, th_stream stream);
+int th_maxpool3x3s2_bwd(th_ctx* ctx, const float* x, const float* g, int planes, int H, int W, float* g_x, th_stream stream);
+size_t th_conv2d_dgrad_pack_bytes(int cin, int cout, int ks, int stride);                     /* pure host call; 0: unsupported */
+int th_conv2d_dgrad_pack(th_ctx* ctx, const float* w, int cin, int cout, int ks, int stride, void* packed, size_t packed_bytes,
+                         th_stream stream);
+int th_conv2d_dgrad(th_ctx* ctx, const float* g_y, int N, int cin, int cout, int ks, int stride, int H, int W, const void* packed,
+                    size_t packed_bytes, float* g_x, th_stream stream);
+size_t th_conv2d_wgrad_workspace_bytes(int N, int cin, int cout, int ks, int stride, int H, int W);   /* pure host call */
+int th_conv2d_wgrad(th_ctx* ctx, const float* x, const float* g_y, int N, int cin, int cout, int ks, int stride, int H, int W,
+                    float* g_w, void* workspace, size_t workspace_bytes, th_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

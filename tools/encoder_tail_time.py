@@ -8,6 +8,10 @@ One step = forward + backward of: trunk -> painting rows [V,6890,192] -> pixel r
 gradient on both row tensors standing in for the rest of the network.
   "full"     autograd_path.encode (upsample, concatenate, 1 x 1 reduction: the two full-size maps) + sample_map twice
   "latents"  autograd_path.latent_features (K19, train_ops.LatentGatherFn on the three latents) + the reduction on the rows
+--encoder torch,device repeats every mode with cfg.train_encoder's "device" form of the trunk (K23: autograd_path.trunk_device, the
+same forward, HIP backwards; keys gain '+encoder'); --maps picks the modes.  --rocprof DIR first runs a fresh child process under
+`rocprofv3 --kernel-trace` (last --maps value, last --encoder value) and reports, per step, the number of kernel launches of the
+stage and the device time of its ten slowest kernel names (DIR keeps the trace).
 Prints one JSON line.  Per mode: the median of --rounds alternating rounds with the lowest and the highest (device events around
 the step, no host synchronisation inside; one synchronisation after the closing event), torch.cuda.max_memory_allocated of a
 step above what is allocated before it, and the largest difference of every encoder gradient between the modes.  The two
@@ -52,15 +56,16 @@ def setup(dev, size):
     return enc, images, verts, xyz, (R, T, K), cams, scale, g_paint, g_pix
 
 
-def step(maps, enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix):
+def step(mode, enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix):
     from transhuman_amd.networks import autograd_path as A
+    maps, encoder = mode.split("+")[0], "device" if mode.endswith("+encoder") else "torch"
     enc.zero_grad(set_to_none=True)
     image_shape = images.shape[-2:]
     if maps == "latents":
-        gather = A.latent_features(enc, images, cams, scale)
+        gather = A.latent_features(enc, images, cams, scale, encoder=encoder)
         painted, f = A._lin(enc.reduction_layer, gather(verts)).permute(1, 0, 2), gather(xyz)
     else:
-        hol, pix = A.encode(enc, images)
+        hol, pix = A.encode(enc, images, encoder=encoder)
         painted = A.sample_map(hol, A.project(verts, *rtk), enc, image_shape).permute(0, 2, 1)
         f = A.sample_map(pix, A.project(xyz, *rtk), enc, image_shape).permute(2, 0, 1)
     ((painted * g_paint).sum() + (f * g_pix).sum()).backward()
@@ -93,12 +98,72 @@ def kernel_times(enc, images, xyz, cams, scale, g_pix, reps=20):
     return res
 
 
+MARKER = "maxpool3x3s2_kernel"      # the inference path's pooling kernel: no training stage launches it
+
+
+def traced_child(mode, size, steps):
+    """the body of the child that --rocprof traces: `steps` steps of `mode`, each between two launches of the marker kernel"""
+    import torch
+    from transhuman_amd import hip
+    dev = torch.device("cuda:0")
+    a = setup(dev, size)
+    mark = torch.zeros((1, 1, 2, 2), device=dev)
+    step(mode, *a)
+    for _ in range(steps):
+        hip.maxpool3x3s2(mark)
+        step(mode, *a)
+    hip.maxpool3x3s2(mark)
+    torch.cuda.synchronize()
+
+
+def trace_summary(out_dir):
+    """launches per step and device time per kernel name between the marker launches of the child's kernel trace"""
+    import csv
+    import glob
+    from collections import defaultdict
+    rows = []
+    for path in glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True):
+        rows += [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(path))]
+    rows.sort()
+    marks = [i for i, r in enumerate(rows) if MARKER in r[2]]
+    if len(marks) < 2:
+        return {"error": f"{len(marks)} marker launches in the trace"}
+    steps = len(marks) - 1
+    agg = defaultdict(lambda: [0, 0])
+    for i in range(marks[0], marks[-1]):
+        if i not in marks:
+            key = rows[i][2].replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0][:70]
+            agg[key][0] += 1
+            agg[key][1] += rows[i][1] - rows[i][0]
+    top = sorted(agg.items(), key=lambda kv: -kv[1][1])[:10]
+    return {"steps": steps, "launches_per_step": round(sum(c for c, _ in agg.values()) / steps, 1),
+            "kernel_us_per_step": round(sum(t for _, t in agg.values()) / 1e3 / steps, 1),
+            "slowest": {k: {"calls_per_step": round(c / steps, 2), "us_per_step": round(t / 1e3 / steps, 1)} for k, (c, t) in top}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--maps", default="full,latents", help="comma list of cfg.train_maps values")
+    ap.add_argument("--encoder", default="torch", help="comma list of cfg.train_encoder values (results of 'device' are keyed "
+                                                       "'<maps>+encoder')")
+    ap.add_argument("--rocprof", default=None, metavar="DIR", help="also trace a short run of the last mode under rocprofv3 into DIR")
+    ap.add_argument("--traced-child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    modes = tuple(m + ("" if e == "torch" else "+encoder") for m in args.maps.split(",") for e in args.encoder.split(","))
+    if args.traced_child:
+        return traced_child(args.traced_child, args.size, 3)
+    traced = None
+    if args.rocprof:
+        # (first, before this process opens the GPU; the traced program is a fresh child behind `--`)
+        import subprocess
+        os.makedirs(args.rocprof, exist_ok=True)
+        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", args.rocprof, "-o", "encoder_tail", "--",
+               sys.executable, os.path.abspath(__file__), "--traced-child", modes[-1], "--size", str(args.size)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        traced = dict(trace_summary(args.rocprof), mode=modes[-1]) if p.returncode == 0 else {"error": p.stderr[-400:]}
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("encoder_tail_time.py needs an MI355X: a time taken elsewhere says nothing")
@@ -107,7 +172,8 @@ def main():
     a = (enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix)
     res = {"device": torch.cuda.get_device_name(0),
            "shape": {"views": VIEWS, "image": [args.size, args.size], "vertices": int(verts.shape[0]), "points": int(xyz.shape[0])}}
-    modes = ("full", "latents")
+    if traced is not None:
+        res["traced"] = traced
     grads = {}
     for m in modes:
         for _ in range(args.warmup):
@@ -133,11 +199,17 @@ def main():
         res[m] = {"step_ms_median": round(float(np.median(ms[m])), 2), "step_ms_min": round(float(np.min(ms[m])), 2),
                   "step_ms_max": round(float(np.max(ms[m])), 2), "rounds": args.rounds,
                   "peak_allocated_MiB": round(peak[m] / 2 ** 20, 1)}
-    assert set(grads["full"]) == set(grads["latents"])
-    res["latents_vs_full"] = {"grads_max_rel_to_own_max": max(
-        float((grads["full"][k] - grads["latents"][k]).abs().max()) / max(float(grads["full"][k].abs().max()), 1e-30)
-        for k in grads["full"])}
-    res["kernels"] = kernel_times(enc, images, xyz, cams, scale, g_pix)
+    rel = lambda p, q: max(float((grads[p][k] - grads[q][k]).abs().max()) / max(float(grads[p][k].abs().max()), 1e-30)
+                           for k in grads[p])
+    if "full" in grads and "latents" in grads:
+        assert set(grads["full"]) == set(grads["latents"])
+        res["latents_vs_full"] = {"grads_max_rel_to_own_max": rel("full", "latents")}
+    for m in modes:
+        if m.endswith("+encoder") and m[:-8] in grads:
+            assert set(grads[m]) == set(grads[m[:-8]])
+            res[m + "_vs_torch_encoder"] = {"grads_max_rel_to_own_max": rel(m[:-8], m)}
+    if any(m.startswith("latents") for m in modes):
+        res["kernels"] = kernel_times(enc, images, xyz, cams, scale, g_pix)
     print(json.dumps(res))
 
 

@@ -7,7 +7,9 @@ the HIP adjoints of K17, transhuman_amd/networks/train_ops.py).
 
 --maps full,latents repeats every mode with cfg.train_maps = "latents" (K19: the encoder's latents sampled directly) in the same
 process; --point-net torch,device does the same with cfg.train_point_net = "device" (K20: the per-point network layer by layer
-on the device; keys gain '+pointnet').  Prints one JSON line.  Per mode: median and minimum wall time of a step over --steps steps after --warmup (host clock around
+on the device; keys gain '+pointnet'); --encoder torch,device with cfg.train_encoder = "device" (K23: the encoder trunk's backward as
+HIP kernels; keys gain '+encoder'); --attention / --vit-dense set cfg.train_attention / cfg.train_vit_dense for the whole run.
+Prints one JSON line.  Per mode: median and minimum wall time of a step over --steps steps after --warmup (host clock around
 forward + backward with a device synchronisation at both ends) and torch.cuda.max_memory_allocated of the timed steps; the
 largest difference of the outputs and of every parameter gradient between the two modes; and, with --rocprof DIR, the device
 time of the K17 kernels per step from `rocprofv3 --kernel-trace --stats` over a short run of the "device" mode in a fresh child
@@ -143,6 +145,10 @@ def main():
                                                    "(results of a value other than 'full' are keyed '<mode>+<value>')")
     ap.add_argument("--point-net", default="torch", help="comma list of cfg.train_point_net values; every mode runs once per value "
                                                          "(results of 'device' are keyed '<mode>[+<maps>]+pointnet')")
+    ap.add_argument("--encoder", default="torch", help="comma list of cfg.train_encoder values; every mode runs once per value "
+                                                       "(results of 'device' are keyed '<mode>[+<maps>][+pointnet]+encoder')")
+    ap.add_argument("--attention", default="torch", help="cfg.train_attention of every run")
+    ap.add_argument("--vit-dense", default="torch", help="cfg.train_vit_dense of every run")
     ap.add_argument("--rocprof", default=None, metavar="DIR", help="also trace a short 'device' run under rocprofv3 into DIR")
     ap.add_argument("--optim", default="", help="comma list of 'torch' (the reference's form: torch.optim.Adam, one group per "
                                                 "parameter, + clip_grad_value_(., 40)) and 'device' (train_optim.DeviceAdam, "
@@ -165,30 +171,41 @@ def main():
     target = torch.rand((1, RAYS, 3), device=dev)
     seen = {}
     try:
+        cfg.train_attention, cfg.train_vit_dense = args.attention, args.vit_dense
         for maps in args.maps.split(","):
             cfg.train_maps = maps
             for point_net in args.point_net.split(","):
                 cfg.train_point_net = point_net
-                for mode in args.modes.split(","):
-                    key = (mode if maps == "full" else f"{mode}+{maps}") + ("" if point_net == "torch" else "+pointnet")
-                    res[key], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
-                    seen[key] = (outs, grads)
+                for encoder in args.encoder.split(","):
+                    cfg.train_encoder = encoder
+                    for mode in args.modes.split(","):
+                        key = (mode if maps == "full" else f"{mode}+{maps}") + ("" if point_net == "torch" else "+pointnet") + \
+                            ("" if encoder == "torch" else "+encoder")
+                        res[key], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
+                        seen[key] = (outs, grads)
         for kind in [k for k in args.optim.split(",") if k]:
             res[f"step+optim:{kind}"] = run_optim(kind, net, r, b, target, args.steps, args.warmup)
     finally:
-        cfg.train_kernels, cfg.train_maps, cfg.train_point_net = "torch", "full", "torch"
+        cfg.train_kernels, cfg.train_maps, cfg.train_point_net, cfg.train_encoder = "torch", "full", "torch", "torch"
+        cfg.train_attention, cfg.train_vit_dense = "torch", "torch"
     if "torch" in seen and "device" in seen:
         (o0, g0), (o1, g1) = seen["torch"], seen["device"]
         res["device_vs_torch"] = {
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
             "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0)}
+    for key in [k for k in seen if k.endswith("+encoder") and k[:-8] in seen]:
+        (o0, g0), (o1, g1) = seen[key[:-8]], seen[key]
+        res[key + "_vs_torch_encoder"] = {
+            "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
+            "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0
+                                            if not k.endswith("spatial_key_value_0.key_embed.bias"))}
     for key in [k for k in seen if k.endswith("+pointnet") and k[:-9] in seen]:
         (o0, g0), (o1, g1) = seen[key[:-9]], seen[key]
         res[key + "_vs_torch_point_net"] = {
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
             "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0
                                             if not k.endswith("spatial_key_value_0.key_embed.bias"))}
-    for key in [k for k in seen if "+" in k and not k.endswith("+pointnet") and k.split("+")[0] in seen]:
+    for key in [k for k in seen if "+" in k and not k.endswith(("+pointnet", "+encoder")) and k.split("+")[0] in seen]:
         (o0, g0), (o1, g1) = seen[key.split("+")[0]], seen[key]
         res[key + "_vs_full"] = {
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),

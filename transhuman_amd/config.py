@@ -81,6 +81,12 @@ def _defaults():
         # autograd; "device" runs it layer by layer on the fp32 MFMA GEMMs of the inference path with HIP backwards
         # (autograd_path.point_network_device: train_ops.ReluLinearFn / LinearFn / CrossViewAttentionFn, K20)
         train_point_net="torch",
+        # the ResNet18 trunk of the encoder (conv1 / bn1, the max pool, layer1, layer2) in the training entry: "torch" runs the stock
+        # modules under torch autograd; "device" runs the same torch operators in the forward, site by site without a graph, and
+        # HIP backwards with fixed-order sums (autograd_path.trunk_device: train_ops.ConvFn / BnActFn / MaxPoolFn, K23).  The
+        # device backward is that of batch statistics: a trunk with a BatchNorm site in eval mode, or converted to SyncBatchNorm,
+        # runs under torch autograd whatever this says
+        train_encoder="torch",
         # patch sampling of the training targets (train_or_eval.yaml:70-75)
         patch=SimpleNamespace(use_patch_sampling=True, sample_subject_ratio=0.8, N_patches=6, size=20),
         # where the training entry's rays and patch targets come from: "batch" (as the reference: its dataset samples them on the

@@ -1711,6 +1711,60 @@ int th_eval_sigma_grid(th_ctx* c, const th_frame* f, const float* pts, int P, fl
     return 0;
 }
 
+// ---- K23: the backward of the encoder trunk (k_encoder_bwd.hip) ----
+int th_conv2d_bwd_supported(int cin, int cout, int ks, int stride) { return th_conv2d_bwd_supported_internal(cin, cout, ks, stride); }
+int th_conv2d_wgrad_chunk_pixels(void) { return th_conv2d_wgrad_chunk_internal(); }
+int th_conv2d_dgrad_tile_rows(void) {
+    int r, c;
+    th_conv2d_dgrad_tile_internal(&r, &c);
+    return r;
+}
+int th_conv2d_dgrad_tile_cols(void) {
+    int r, c;
+    th_conv2d_dgrad_tile_internal(&r, &c);
+    return c;
+}
+int th_bn_act_bwd_slice_elems(void) { return th_bn_act_bwd_slice_internal(); }
+
+size_t th_bn_act_bwd_workspace_bytes(int N, int C, int HW) { return th_bn_act_bwd_ws(N, C, HW); }
+
+int th_bn_act_bwd(th_ctx* c, const float* y, const float* out_or_null, const float* g, int N, int C, int HW,
+                  const float* gamma_or_null, double eps, float* g_y, float* g_res_or_null, float* g_gamma_or_null,
+                  float* g_beta_or_null, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && y && g && g_y && ws, "null argument");
+    return th_bn_act_bwd_launch(y, out_or_null, g, N, C, HW, gamma_or_null, eps, g_y, g_res_or_null, g_gamma_or_null,
+                                g_beta_or_null, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int th_maxpool3x3s2_bwd(th_ctx* c, const float* x, const float* g, int planes, int H, int W, float* g_x, th_stream stream) {
+    TH_REQUIRE(c && x && g && g_x, "null argument");
+    return th_maxpool3x3s2_bwd_launch(x, g, planes, H, W, g_x, (hipStream_t)stream);
+}
+
+size_t th_conv2d_dgrad_pack_bytes(int cin, int cout, int ks, int stride) { return th_conv2d_dgrad_pack_size(cin, cout, ks, stride); }
+
+int th_conv2d_dgrad_pack(th_ctx* c, const float* w, int cin, int cout, int ks, int stride, void* packed, size_t packed_bytes,
+                         th_stream stream) {
+    TH_REQUIRE(c && w && packed, "null argument");
+    return th_conv2d_dgrad_pack_launch(w, cin, cout, ks, stride, packed, packed_bytes, (hipStream_t)stream);
+}
+
+int th_conv2d_dgrad(th_ctx* c, const float* g_y, int N, int cin, int cout, int ks, int stride, int H, int W, const void* packed,
+                    size_t packed_bytes, float* g_x, th_stream stream) {
+    TH_REQUIRE(c && g_y && packed && g_x, "null argument");
+    return th_conv2d_dgrad_launch(g_y, N, cin, cout, ks, stride, H, W, packed, packed_bytes, g_x, (hipStream_t)stream);
+}
+
+size_t th_conv2d_wgrad_workspace_bytes(int N, int cin, int cout, int ks, int stride, int H, int W) {
+    return th_conv2d_wgrad_ws(N, cin, cout, ks, stride, H, W);
+}
+
+int th_conv2d_wgrad(th_ctx* c, const float* x, const float* g_y, int N, int cin, int cout, int ks, int stride, int H, int W,
+                    float* g_w, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && x && g_y && g_w && ws, "null argument");
+    return th_conv2d_wgrad_launch(x, g_y, N, cin, cout, ks, stride, H, W, g_w, ws, ws_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 static ThProf* prof_of(th_ctx* c) {

@@ -597,6 +597,23 @@ int th_lpips_dgrad_launch(int layer, const float* g, const float* gate, int Z, i
 int th_lpips_pool_bwd_launch(const float* g, const float* y, int Z, int H, int W, int C, float* out, hipStream_t s);
 int th_lpips_head_bwd_launch(const float* f0, const float* f1, int N, int hw, int C, const float* lin, const double* g_out,
                              int accumulate, int gate, float* g, hipStream_t s);
+// k_encoder_bwd.hip (K23): the backward of the encoder trunk's sites -- BatchNorm (+ residual) (+ ReLU), the convolutions' input and
+// weight gradients, the 3x3 / 2 max pool; NCHW fp32, H / W are the convolution's or the pool's INPUT size
+int th_conv2d_bwd_supported_internal(int cin, int cout, int ks, int stride);      // bit 0: weight gradient, bit 1: input gradient
+int th_conv2d_wgrad_chunk_internal();
+void th_conv2d_dgrad_tile_internal(int* rows, int* cols);
+int th_bn_act_bwd_slice_internal();
+size_t th_bn_act_bwd_ws(int N, int C, int HW);
+int th_bn_act_bwd_launch(const float* y, const float* out, const float* g, int N, int C, int HW, const float* gamma, double eps,
+                         float* g_y, float* g_res, float* g_gamma, float* g_beta, void* ws, size_t ws_bytes, hipStream_t s);
+int th_maxpool3x3s2_bwd_launch(const float* x, const float* g, int planes, int H, int W, float* gx, hipStream_t s);
+size_t th_conv2d_dgrad_pack_size(int cin, int cout, int ks, int stride);
+int th_conv2d_dgrad_pack_launch(const float* w, int cin, int cout, int ks, int stride, void* packed, size_t bytes, hipStream_t s);
+int th_conv2d_dgrad_launch(const float* gy, int N, int cin, int cout, int ks, int stride, int H, int W, const void* packed,
+                           size_t packed_bytes, float* gx, hipStream_t s);
+size_t th_conv2d_wgrad_ws(int N, int cin, int cout, int ks, int stride, int H, int W);
+int th_conv2d_wgrad_launch(const float* x, const float* gy, int N, int cin, int cout, int ks, int stride, int H, int W, float* gw,
+                           void* ws, size_t ws_bytes, hipStream_t s);
 // k_raster.hip: z-buffer rasteriser of a triangle mesh into V views, and the two vertex-visibility rules on top of it
 size_t th_raster_ws(int V, int nv, int nf, int H, int W);
 int th_raster_launch(const float* verts, int nv, const int32_t* faces, int nf, const float* cams, int V, int H, int W,

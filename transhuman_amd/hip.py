@@ -888,6 +888,141 @@ def layernorm_bwd_chunk_rows():
 
 
 # ---------------------------------------------------------------------------
+# K23: the backward of the encoder trunk (k_encoder_bwd.hip); NCHW fp32
+# ---------------------------------------------------------------------------
+def conv2d_bwd_supported(cin, cout, ks, stride):
+    """th_conv2d_bwd_supported: 0, or bit 0: conv2d_wgrad is built for this convolution, bit 1: conv2d_dgrad as well"""
+    return int(load_library().th_conv2d_bwd_supported(int(cin), int(cout), int(ks), int(stride)))
+
+
+def conv2d_wgrad_chunk_pixels():
+    return int(load_library().th_conv2d_wgrad_chunk_pixels())
+
+
+def conv2d_dgrad_tile():
+    """(rows, columns) of input pixels of one parity class that a workgroup of conv2d_dgrad owns"""
+    lib = load_library()
+    return int(lib.th_conv2d_dgrad_tile_rows()), int(lib.th_conv2d_dgrad_tile_cols())
+
+
+def bn_act_bwd_slice_elems():
+    return int(load_library().th_bn_act_bwd_slice_elems())
+
+
+def _nchw(fn, name, t, channels=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype is torch.float32 and t.dim() == 4 and t.is_contiguous()):
+        raise ValueError(f"{fn}: '{name}' must be a contiguous float32 [N,C,H,W] device tensor")
+    if channels is not None and t.shape[1] != channels:
+        raise ValueError(f"{fn}: '{name}' has {t.shape[1]} channels, expected {channels}")
+    return t.detach()
+
+
+def _conv_out(n, ks, stride):
+    return (n + 2 * (ks // 2) - ks) // stride + 1
+
+
+def _conv_weight(fn, weight):
+    if not (weight.is_cuda and weight.dtype is torch.float32 and weight.dim() == 4 and weight.is_contiguous()
+            and weight.shape[2] == weight.shape[3]):
+        raise ValueError(f"{fn}: the weight must be a contiguous float32 [cout, cin, ks, ks] device tensor")
+    return weight.detach(), int(weight.shape[1]), int(weight.shape[0]), int(weight.shape[2])
+
+
+def conv2d_dgrad_pack(weight, stride):
+    """th_conv2d_dgrad_pack: the image of `weight` [cout, cin, ks, ks] that conv2d_dgrad reads (one block per input-parity class)"""
+    lib = load_library()
+    w, cin, cout, ks = _conv_weight("conv2d_dgrad_pack", weight)
+    n = int(lib.th_conv2d_dgrad_pack_bytes(cin, cout, ks, int(stride)))
+    if n == 0:
+        raise HipError(f"conv2d_dgrad_pack: no input gradient is built for a {ks}x{ks}/{stride} convolution {cin}->{cout}")
+    packed = torch.empty(n, dtype=torch.uint8, device=w.device)
+    _check(lib.th_conv2d_dgrad_pack(ctx(w.device), _p(w), cin, cout, ks, int(stride), _p(packed), n, _stream()))
+    return packed
+
+
+_dgrad_images = {}      # id(weight) -> (weakref, version, data_ptr, stride, packed)
+
+
+def conv2d_dgrad_image(weight, stride):
+    """the packed image of a Parameter, made once per weight version (an optimiser step bumps it)"""
+    import weakref
+    ent = _dgrad_images.get(id(weight))
+    if ent is not None and ent[0]() is weight and ent[1:4] == (weight._version, weight.data_ptr(), int(stride)):
+        return ent[4]
+    if len(_dgrad_images) > 64:
+        _dgrad_images.clear()
+    packed = conv2d_dgrad_pack(weight, stride)
+    _dgrad_images[id(weight)] = (weakref.ref(weight), weight._version, weight.data_ptr(), int(stride), packed)
+    return packed
+
+
+def conv2d_dgrad(g_y, weight_shape, stride, in_hw, packed):
+    """th_conv2d_dgrad: g_y [N,cout,Ho,Wo] -> g_x [N,cin,H,W] for the convolution whose weight has `weight_shape` and whose input
+    was H x W = `in_hw`; `packed` = conv2d_dgrad_pack(weight, stride).  Bit-identical from run to run."""
+    lib = load_library()
+    cout, cin, ks = int(weight_shape[0]), int(weight_shape[1]), int(weight_shape[2])
+    H, W = int(in_hw[0]), int(in_hw[1])
+    g = _nchw("conv2d_dgrad", "g_y", g_y, cout)
+    if tuple(g.shape[2:]) != (_conv_out(H, ks, stride), _conv_out(W, ks, stride)):
+        raise ValueError(f"conv2d_dgrad: g_y is {tuple(g.shape[2:])}, a {ks}x{ks}/{stride} convolution of {H}x{W} gives "
+                         f"{(_conv_out(H, ks, stride), _conv_out(W, ks, stride))}")
+    N = int(g.shape[0])
+    g_x = torch.empty((N, cin, H, W), dtype=torch.float32, device=g.device)
+    _check(lib.th_conv2d_dgrad(ctx(g.device), _p(g), N, cin, cout, ks, int(stride), H, W, _p(packed), packed.numel(), _p(g_x),
+                               _stream()))
+    return g_x
+
+
+def conv2d_wgrad(x, g_y, ks, stride):
+    """th_conv2d_wgrad: x [N,cin,H,W], g_y [N,cout,Ho,Wo] -> g_W [cout,cin,ks,ks].  Bit-identical from run to run."""
+    lib = load_library()
+    x2, g = _nchw("conv2d_wgrad", "x", x), _nchw("conv2d_wgrad", "g_y", g_y)
+    N, cin, H, W = (int(n) for n in x2.shape)
+    cout = int(g.shape[1])
+    if tuple(g.shape) != (N, cout, _conv_out(H, ks, stride), _conv_out(W, ks, stride)):
+        raise ValueError(f"conv2d_wgrad: g_y is {tuple(g.shape)}, expected "
+                         f"{(N, cout, _conv_out(H, ks, stride), _conv_out(W, ks, stride))}")
+    g_w = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=x2.device)
+    ws = _ws(lib.th_conv2d_wgrad_workspace_bytes(N, cin, cout, int(ks), int(stride), H, W), x2.device)
+    _check(lib.th_conv2d_wgrad(ctx(x2.device), _p(x2), _p(g), N, cin, cout, int(ks), int(stride), H, W, _p(g_w), _p(ws), ws.numel(),
+                               _stream()))
+    return g_w
+
+
+def bn_act_bwd(y, out, g, gamma, eps, need_residual=False, need_affine=True):
+    """th_bn_act_bwd: the backward of train-mode BatchNorm (+ residual) (+ ReLU).  y: the BatchNorm's input, out: the site's
+    output (None: the site has no ReLU), g: the gradient of the site's output, gamma: [C] or None (1) ->
+    (g_y, g_residual or None, g_gamma or None, g_beta or None).  Bit-identical from run to run."""
+    lib = load_library()
+    fn = "bn_act_bwd"
+    y2, g2 = _nchw(fn, "y", y), _nchw(fn, "g", g)
+    o2 = None if out is None else _nchw(fn, "out", out)
+    if g2.shape != y2.shape or (o2 is not None and o2.shape != y2.shape):
+        raise ValueError(f"{fn}: y, out and g must have one shape")
+    N, Cc, H, W = (int(n) for n in y2.shape)
+    gm = None if gamma is None else _train_vec(fn, gamma, Cc)
+    g_y = torch.empty_like(y2)
+    g_res = torch.empty_like(y2) if need_residual else None
+    g_gamma = torch.empty(Cc, dtype=torch.float32, device=y2.device) if need_affine else None
+    g_beta = torch.empty(Cc, dtype=torch.float32, device=y2.device) if need_affine else None
+    ws = _ws(lib.th_bn_act_bwd_workspace_bytes(N, Cc, H * W), y2.device)
+    _check(lib.th_bn_act_bwd(ctx(y2.device), _p(y2), _p(o2), _p(g2), N, Cc, H * W, _p(gm), float(eps), _p(g_y), _p(g_res),
+                             _p(g_gamma), _p(g_beta), _p(ws), ws.numel(), _stream()))
+    return g_y, g_res, g_gamma, g_beta
+
+
+def maxpool3x3s2_bwd(x, g):
+    """th_maxpool3x3s2_bwd: x [N,C,H,W] (the input of nn.MaxPool2d(3, 2, 1)), g [N,C,Ho,Wo] -> g_x; torch's routing rule"""
+    x2, g2 = _nchw("maxpool3x3s2_bwd", "x", x), _nchw("maxpool3x3s2_bwd", "g", g)
+    N, Cc, H, W = (int(n) for n in x2.shape)
+    if tuple(g2.shape) != (N, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise ValueError(f"maxpool3x3s2_bwd: g is {tuple(g2.shape)}, expected {(N, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1)}")
+    g_x = torch.empty_like(x2)
+    _check(load_library().th_maxpool3x3s2_bwd(ctx(x2.device), _p(x2), _p(g2), N * Cc, H, W, _p(g_x), _stream()))
+    return g_x
+
+
+# ---------------------------------------------------------------------------
 # K22: the optimiser step (th_adam_plan / th_adam_step)
 # ---------------------------------------------------------------------------
 ADAM_CLIP, ADAM_ZERO_GRAD, ADAM_COUNT_NONFINITE, ADAM_CHECK_POINTERS, ADAM_T_DECOUPLED = (

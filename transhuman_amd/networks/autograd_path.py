@@ -11,7 +11,7 @@ rendering hot path and not a fallback of it -- inference calls (``render_fast``,
 ``cfg.train_kernels`` selects how the three non-GEMM stages around the per-point network run: "torch" (default) composes
 them from torch operators like everything else; "device" runs the token blend (K4), the pixel-aligned gather (K5) and the
 compositing (K7) through the HIP forwards with HIP adjoints (``train_ops``), once over all samples before
-the chunk loop.  The encoder stays on torch autograd in both modes; the per-point network follows ``cfg.train_point_net`` (below).
+the chunk loop.  The encoder trunk follows ``cfg.train_encoder`` and the per-point network ``cfg.train_point_net`` (both below).
 
 ``cfg.train_maps`` selects what the image features are sampled from: "full" (default) builds the reference's two full-size maps
 (``encode``); "latents" runs the trunk as before and samples its three latents and the images directly at the input vertices
@@ -33,6 +33,12 @@ gradient is bit-identical from run to run.  The residual adds and the positional
 ``point_network`` under torch autograd; "device" is ``point_network_device``: the layer-by-layer form of the inference path
 (th_mlp_forward) on the fp32 MFMA GEMMs, every ReLU in its layer's epilogue, with HIP backwards (``train_ops.ReluLinearFn`` /
 ``LinearFn`` / ``CrossViewAttentionFn``).  View means and residual adds stay torch operators.
+
+``cfg.train_encoder`` selects, independently of the other five, how the ResNet18 trunk of the encoder is differentiated: "torch"
+(default) is ``SpatialEncoder.trunk(fused_bn=False)`` under torch autograd; "device" is ``trunk_device``: the same torch
+operators in the forward, site by site without a graph -- latents, running statistics and num_batches_tracked are the "torch"
+mode's bit for bit --, and HIP backwards with fixed-order sums (``train_ops.ConvFn`` / ``BnActFn`` / ``MaxPoolFn``, DESIGN.md
+K23).  The upsamples, ``upsample_color`` and ``reduction_layer`` stay what ``cfg.train_maps`` makes them.
 
 Pinned by ``oracle/gen_golden_train.py`` (the real reference imported in the survey container: outputs and parameter
 gradients of one training step's forward/backward on a synthetic patch -> ``tests/golden/g18_train_step.npz``) and
@@ -69,10 +75,59 @@ def embed_view(ray_d, view_res):
 
 
 # ---- encoder, painting, grouping ----------------------------------------------------------------------------------------
-def encode(enc, images):
-    """SpatialEncoder.forward (encoder.py:97-155) through torch's own modules (autograd)."""
+def _encoder_mode(value):
+    mode = str(value)
+    if mode not in ("torch", "device"):
+        raise ValueError(f"cfg.train_encoder must be 'torch' or 'device', not {mode!r}")
+    return mode
+
+
+def _trunk_sites_have_batch_statistics(enc):
+    """every BatchNorm site of the trunk is a train-mode nn.BatchNorm2d with a momentum: what th_bn_act_bwd is the backward of
+    (eval mode normalises with the running statistics; SyncBatchNorm, after the reference trainer's conversion, with the
+    statistics of all ranks)"""
+    return all(isinstance(b, torch.nn.BatchNorm2d) and b.training and b.momentum is not None for b in enc._bn_sites())
+
+
+def trunk_device(enc, images):
+    """SpatialEncoder.trunk(images, fused_bn=False) and BasicBlock.forward (encoder.py:114-126) restated on the per-site Functions
+    of train_ops: the same torch operators in the forward, called without recording a graph, and k_encoder_bwd.hip in the backward
+    (K23).  A trunk whose BatchNorm sites do not all use batch statistics runs under torch autograd as a whole."""
+    from .. import hip
+    from . import train_ops as T
+    if not images.is_cuda:
+        raise hip.HipError("cfg.train_encoder = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
+                           "use 'torch' for a CPU batch")
+    if not _trunk_sites_have_batch_statistics(enc):
+        return enc.trunk(images, fused_bn=False)
+    m = enc.model
+
+    def conv_bn(conv, bn, t, residual=None, relu=True):
+        if conv.bias is not None:
+            raise hip.HipError("cfg.train_encoder = 'device': the trunk's convolutions have no bias in the HIP backward")
+        return T.BnActFn.apply(T.ConvFn.apply(t, conv.weight, conv.stride[0]), bn, residual, relu, bn.weight, bn.bias)
+
+    x = conv_bn(m.conv1, m.bn1, images)
+    lat = [x]
+    x = T.MaxPoolFn.apply(x)
+    for layer in (m.layer1, m.layer2):
+        for blk in layer:
+            idt = x if blk.downsample is None else conv_bn(blk.downsample[0], blk.downsample[1], x, relu=False)
+            y = conv_bn(blk.conv1, blk.bn1, x)
+            x = conv_bn(blk.conv2, blk.bn2, y, residual=idt)
+        lat.append(x)
+    return lat
+
+
+def _trunk(enc, images, encoder):
+    return trunk_device(enc, images) if _encoder_mode(encoder) == "device" else enc.trunk(images, fused_bn=False)
+
+
+def encode(enc, images, encoder="torch"):
+    """SpatialEncoder.forward (encoder.py:97-155) through torch's own modules (autograd); encoder = "device": the trunk through
+    ``trunk_device``."""
     H, W = images.shape[2:]
-    lat = enc.trunk(images, fused_bn=False)
+    lat = _trunk(enc, images, encoder)
     lat = [F.interpolate(l, (H, W), mode="bilinear", align_corners=True) for l in lat]
     pix = torch.cat(lat + [enc.upsample_color(images)], dim=1)
     return enc.reduction_layer(pix), pix
@@ -85,11 +140,11 @@ def _maps_mode(value):
     return mode
 
 
-def latent_features(enc, images, cams, scale):
-    """cfg.train_maps = "latents": the trunk as in ``encode`` (stock modules, torch autograd), each latent channels-last once;
-    returns ``gather(points [N,3]) -> [N,V,384]``, the rows ``sample_map(pix, ...)`` would give (K19)"""
+def latent_features(enc, images, cams, scale, encoder="torch"):
+    """cfg.train_maps = "latents": the trunk as in ``encode`` (stock modules; torch autograd, or ``trunk_device``), each latent
+    channels-last once; returns ``gather(points [N,3]) -> [N,V,384]``, the rows ``sample_map(pix, ...)`` would give (K19)"""
     from . import train_ops
-    lat = [l.permute(0, 2, 3, 1).contiguous() for l in enc.trunk(images, fused_bn=False)]
+    lat = [l.permute(0, 2, 3, 1).contiguous() for l in _trunk(enc, images, encoder)]
     lift = enc.upsample_color
     return lambda pts: train_ops.LatentGatherFn.apply(*lat, lift.weight, lift.bias, images, pts, cams, scale)
 
@@ -344,6 +399,11 @@ def render(renderer, batch, chunk=32768):
         from .. import hip
         raise hip.HipError("cfg.train_point_net = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
                            "use 'torch' for a CPU batch")
+    encoder = _encoder_mode(getattr(cfg, "train_encoder", "torch"))
+    if encoder == "device" and not ray_o.is_cuda:
+        from .. import hip
+        raise hip.HipError("cfg.train_encoder = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
+                           "use 'torch' for a CPU batch")
     near, far = batch["near"][0], batch["far"][0]
     dev = ray_o.device
     S = int(cfg.N_samples)
@@ -361,11 +421,11 @@ def render(renderer, batch, chunk=32768):
         from .. import hip
         # a 1 x 1 convolution commutes with bilinear sampling: reduction_layer on the gathered rows (k_encoder.hip does the same)
         gather = latent_features(net.encoder, images, hip.pack_cams(R_in, T_in, K_in),
-                                 hip.feat_scale(net.encoder.feat_scale(*images.shape[2:]), image_shape, dev))
+                                 hip.feat_scale(net.encoder.feat_scale(*images.shape[2:]), image_shape, dev), encoder=encoder)
         painted = _lin(net.encoder.reduction_layer, gather(verts_in)).permute(1, 0, 2)
         f_lat = gather(xyz)                                # once over all P samples, split per chunk below
     else:
-        hol, pix = encode(net.encoder, images)
+        hol, pix = encode(net.encoder, images, encoder=encoder)
         painted = sample_map(hol, project(verts_in, R_in, T_in, K_in), net.encoder, image_shape).permute(0, 2, 1)
     if cfg.rasterize:
         painted = painted * batch["input_vizmaps"][0][0][..., None].to(painted.dtype)              # :181-182

@@ -37,6 +37,14 @@ The loss the trainer back-propagates through (lib/train/trainers/if_nerf_clight.
 
     LpipsFn                 in0, in1 [N,3,H,W]   -> LPIPS_vgg [N] float64  keeps in0 and the forward's state   gradient: in0
 
+``cfg.train_encoder = "device"`` does it for the encoder trunk (SpatialEncoder.trunk, encoder.py:114-126): the forward of every
+site is the stock torch operator, called without recording a graph, so the latents and the BatchNorm statistics are those of
+the "torch" mode bit for bit; the backward is k_encoder_bwd.hip (composed by ``autograd_path.trunk_device``):
+
+    ConvFn                  x, W, stride         -> conv2d(x, W)       keeps x, W       gradient: x (not conv1's images), W
+    BnActFn                 y, bn, residual, relu, gamma, beta -> relu(bn(y) + residual)   keeps y, the output (with a ReLU), gamma
+    MaxPoolFn               x                    -> max_pool2d(x, 3, 2, 1)   keeps x
+
 K4 and K5 are linear in the tensor that gets the gradient, so nothing of the forward is kept for the backward but the
 geometry (points, centres, cameras): the [P,7,255] blend operands and the per-chunk map-sized gradients of the torch
 formulation do not exist here.  Points, centres, rotations, cameras, depths and ray directions come from the batch and get
@@ -269,6 +277,92 @@ class CrossViewAttentionFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         kvp, kvs = ctx.saved_tensors
         return hip.xview_attention_bwd(kvp, kvs, grad_out.contiguous())
+
+
+def _trunk_input(fn, name, t):
+    _on_device(fn, t)
+    if t.dtype is not torch.float32 or t.dim() != 4:
+        raise ValueError(f"{fn}: '{name}' must be a float32 [N,C,H,W] tensor")
+
+
+class ConvFn(torch.autograd.Function):
+    """nn.Conv2d(cin, cout, ks, stride, ks // 2, bias=False) of the encoder trunk.  Forward: torch's own convolution (the call the
+    module makes).  Backward: th_conv2d_dgrad / th_conv2d_wgrad (fp32-input MFMA, fixed-order sums).  conv1 (7x7/2 on the images)
+    has no input gradient: images that require one raise."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride):
+        _trunk_input("ConvFn", "x", x)
+        cout, cin, ks = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
+        have = hip.conv2d_bwd_supported(cin, cout, ks, stride)
+        if not have & 1:
+            raise hip.HipError(f"ConvFn: no HIP backward is built for a {ks}x{ks}/{stride} convolution {cin}->{cout}")
+        if x.requires_grad and not have & 2:
+            raise ValueError(f"ConvFn: 'x' requires a gradient, and a {ks}x{ks}/{stride} convolution {cin}->{cout} has no input "
+                             "gradient here (the images come from the batch)")
+        ctx.stride = int(stride)
+        ctx.save_for_backward(x, weight)
+        return torch.nn.functional.conv2d(x.detach(), weight.detach(), None, int(stride), ks // 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight = ctx.saved_tensors
+        g = grad_out.contiguous()
+        xc = x.contiguous()
+        ks = int(weight.shape[2])
+        g_x = None
+        if ctx.needs_input_grad[0]:
+            g_x = hip.conv2d_dgrad(g, weight.shape, ctx.stride, xc.shape[2:], hip.conv2d_dgrad_image(weight, ctx.stride))
+        g_w = hip.conv2d_wgrad(xc, g, ks, ctx.stride) if ctx.needs_input_grad[1] else None
+        return g_x, g_w, None
+
+
+class BnActFn(torch.autograd.Function):
+    """The tail of a ``conv -> bn [-> += identity] [-> relu]`` site: relu(bn(y) + residual) with `bn` a train-mode
+    nn.BatchNorm2d.  Forward: the stock module call (it updates the running statistics and num_batches_tracked as always), torch's
+    add and ReLU.  Backward: th_bn_act_bwd from y, the output (the gate) and gamma.  ``gamma`` / ``beta`` are bn.weight / bn.bias
+    (None without affine), passed so that autograd sees them."""
+
+    @staticmethod
+    def forward(ctx, y, bn, residual, relu, gamma, beta):
+        _trunk_input("BnActFn", "y", y)
+        if not (isinstance(bn, torch.nn.BatchNorm2d) and bn.training and bn.momentum is not None):
+            raise ValueError("BnActFn: the backward is defined for a train-mode nn.BatchNorm2d with a momentum (batch statistics)")
+        out = bn(y.detach())
+        if residual is not None:
+            out = out + residual.detach()
+        if relu:
+            out = torch.relu_(out)
+        ctx.relu, ctx.eps, ctx.has_res = bool(relu), float(bn.eps), residual is not None
+        ctx.save_for_backward(y, out if relu else None, gamma)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        y, out, gamma = ctx.saved_tensors
+        g = grad_out.contiguous()
+        need_res = ctx.has_res and ctx.needs_input_grad[2]
+        g_y, g_res, g_gamma, g_beta = hip.bn_act_bwd(y.contiguous(), out, g, gamma, ctx.eps, need_residual=need_res and ctx.relu,
+                                                     need_affine=gamma is not None)
+        if need_res and not ctx.relu:
+            g_res = g                                          # (no gate: the residual's gradient is the arriving one)
+        return g_y, None, g_res, None, g_gamma, g_beta
+
+
+class MaxPoolFn(torch.autograd.Function):
+    """nn.MaxPool2d(3, 2, 1).  Forward: torch's.  Backward: th_maxpool3x3s2_bwd, which finds the element torch recorded again from
+    the input (nothing but the input is kept)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _trunk_input("MaxPoolFn", "x", x)
+        ctx.save_for_backward(x)
+        return torch.nn.functional.max_pool2d(x.detach(), 3, 2, 1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (x,) = ctx.saved_tensors
+        return hip.maxpool3x3s2_bwd(x.contiguous(), grad_out.contiguous())
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -564,3 +658,44 @@ def xview_attention_grad_oracle(kvp, kvs, g_n):
     g_kvp[..., :128] = np.einsum("pji,pic->pjc", dS, s[..., :128]) / np.sqrt(128.0)
     g_kvs[..., :128] = np.einsum("pji,pjc->pic", dS, p[..., :128]) / np.sqrt(128.0)
     return g_kvp, g_kvs
+
+
+def bn_act_grad_oracle(y, out, g, gamma, eps):
+    """adjoint of out = [relu](bn(y) [+ residual]) with train-mode BatchNorm (batch statistics, biased variance), NCHW.
+    ``out``: the site's output, read for the gate [out > 0] (None: no ReLU); gamma [C] or None (1) ->
+    (g_y, g_residual, g_gamma, g_beta) in float64; the formulas of k_encoder_bwd.hip"""
+    y, g = _np64(y), _np64(g)
+    gp = g if out is None else g * (_np64(out) > 0.0)
+    ax = (0, 2, 3)
+    mean = y.mean(ax, keepdims=True)
+    invstd = 1.0 / np.sqrt(((y - mean) ** 2).mean(ax, keepdims=True) + eps)
+    xh = (y - mean) * invstd
+    gam = np.ones(y.shape[1]) if gamma is None else _np64(gamma)
+    g_y = gam.reshape(1, -1, 1, 1) * invstd * (gp - gp.mean(ax, keepdims=True) - xh * (gp * xh).mean(ax, keepdims=True))
+    return g_y, gp, (gp * xh).sum(ax), gp.sum(ax)
+
+
+def maxpool3x3s2_grad_oracle(x, g):
+    """adjoint of nn.MaxPool2d(3, 2, 1) on x [N,C,H,W] with torch's routing rule: a window's gradient goes to the last element,
+    scanning kh outer / kw inner, for which val > max || isnan(val), starting from -inf -- the FIRST maximum of the window; the
+    padding never wins (a window of nothing but -inf is not handled here) -> g_x in float64"""
+    x, g = _np64(x), _np64(g)
+    N, C, H, W = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    xp = np.full((N, C, 2 * Ho + 1, 2 * Wo + 1), -np.inf)
+    xp[:, :, 1:H + 1, 1:W + 1] = x
+    best = np.full((N, C, Ho, Wo), -np.inf)
+    bi = np.zeros((N, C, Ho, Wo), dtype=np.int64)
+    bj = np.zeros((N, C, Ho, Wo), dtype=np.int64)
+    oy, ox = np.meshgrid(np.arange(Ho), np.arange(Wo), indexing="ij")
+    for kh in range(3):
+        for kw in range(3):
+            v = xp[:, :, kh:kh + 2 * Ho:2, kw:kw + 2 * Wo:2]
+            take = (v > best) | np.isnan(v)
+            best = np.where(take, v, best)
+            bi = np.where(take, 2 * oy - 1 + kh, bi)
+            bj = np.where(take, 2 * ox - 1 + kw, bj)
+    g_x = np.zeros_like(x)
+    n, c = np.meshgrid(np.arange(N), np.arange(C), indexing="ij")
+    np.add.at(g_x, (n[:, :, None, None], c[:, :, None, None], bi, bj), g)
+    return g_x
