@@ -542,6 +542,20 @@ int th_latent_gather(th_ctx* ctx, const float* lat0, const float* lat1, const fl
 int th_latent_gather_bwd(th_ctx* ctx, const int32_t* dims, int V, int H, int W, const float* pts_world, int P,
                          const float* cams, const float* scale_xy, const float* grad_out, int ldo, float* g_lat0,
                          float* g_lat1, float* g_lat2, th_stream stream);
+/* The same adjoint with no float atomic (the ordered form): the (sample, view) pairs are sorted by the map pixel of their
+ * north-west corner (a stable radix sort: equal pixels keep ascending sample order), and every latent texel sums the pairs that
+ * reach it in ascending (map row, map column, sample, slot) order on one fp32 accumulator per channel, with the coefficients
+ * of th_latent_gather itself.  Every element of g_lat0 / g_lat1 / g_lat2 is stored exactly once (zeros where nothing
+ * arrives; P = 0 writes zeros): nothing is cleared, and neither the outputs' nor the workspace's earlier contents matter.
+ * Bit-identical from run to run.  g_lift_w [128,3] and g_lift_b [128] (both or both NULL): the lift's gradient, sums over
+ * the P V rows of grad_out[..., 256:384] rgb_s[..., j] and of grad_out[..., 256:384] as fixed-order partial sums; they need
+ * rgb_s [P,V,4] of the forward.  V H W < 2^31 - 1.  workspace: th_latent_gather_bwd_ordered_ws(V, H, W, P) bytes (a host
+ * computation: no device is touched; 0 for arguments out of range). */
+size_t th_latent_gather_bwd_ordered_ws(int V, int H, int W, int P);
+int th_latent_gather_bwd_ordered(th_ctx* ctx, const int32_t* dims, int V, int H, int W, const float* pts_world, int P,
+                                 const float* cams, const float* scale_xy, const float* grad_out, int ldo,
+                                 const float* rgb_s, float* g_lat0, float* g_lat1, float* g_lat2, float* g_lift_w,
+                                 float* g_lift_b, void* workspace, size_t workspace_bytes, th_stream stream);
 
 /* ---- K9: ray generation for a target camera --------------------------- */
 /* lib/utils/if_nerf/if_nerf_data_utils.py:11-30 (get_rays) + :65-97 (get_near_far) as the test split of

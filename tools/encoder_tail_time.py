@@ -9,13 +9,16 @@ gradient on both row tensors standing in for the rest of the network.
   "full"     autograd_path.encode (upsample, concatenate, 1 x 1 reduction: the two full-size maps) + sample_map twice
   "latents"  autograd_path.latent_features (K19, train_ops.LatentGatherFn on the three latents) + the reduction on the rows
 --encoder torch,device repeats every mode with cfg.train_encoder's "device" form of the trunk (K23: autograd_path.trunk_device, the
-same forward, HIP backwards; keys gain '+encoder'); --maps picks the modes.  --rocprof DIR first runs a fresh child process under
+same forward, HIP backwards; keys gain '+encoder'); --gather-bwd atomic,ordered repeats the "latents" modes with cfg.train_gather_bwd's
+"ordered" form of K19's backward (k_latgather_ord.hip: no float atomic; keys gain '+ordered', before '+encoder'); --maps picks the
+modes.  --rocprof DIR first runs a fresh child process under
 `rocprofv3 --kernel-trace` (last --maps value, last --encoder value) and reports, per step, the number of kernel launches of the
 stage and the device time of its ten slowest kernel names (DIR keeps the trace).
 Prints one JSON line.  Per mode: the median of --rounds alternating rounds with the lowest and the highest (device events around
 the step, no host synchronisation inside; one synchronisation after the closing event), torch.cuda.max_memory_allocated of a
 step above what is allocated before it, and the largest difference of every encoder gradient between the modes.  The two
-kernels' own time: device events around th_latent_gather / th_latent_gather_bwd at the pixel shape, median of 20 calls.
+kernels' own time: device events around th_latent_gather / th_latent_gather_bwd (and, with --gather-bwd ordered, all the kernels of
+th_latent_gather_bwd_ordered, with its workspace size and the peak allocation of a call) at the pixel shape, median of 20 calls.
 No threshold on any figure."""
 import argparse
 import json
@@ -58,11 +61,12 @@ def setup(dev, size):
 
 def step(mode, enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix):
     from transhuman_amd.networks import autograd_path as A
-    maps, encoder = mode.split("+")[0], "device" if mode.endswith("+encoder") else "torch"
+    parts = mode.split("+")
+    maps, encoder, gather_bwd = parts[0], "device" if "encoder" in parts else "torch", "ordered" if "ordered" in parts else "atomic"
     enc.zero_grad(set_to_none=True)
     image_shape = images.shape[-2:]
     if maps == "latents":
-        gather = A.latent_features(enc, images, cams, scale, encoder=encoder)
+        gather = A.latent_features(enc, images, cams, scale, encoder=encoder, gather_bwd=gather_bwd)
         painted, f = A._lin(enc.reduction_layer, gather(verts)).permute(1, 0, 2), gather(xyz)
     else:
         hol, pix = A.encode(enc, images, encoder=encoder)
@@ -71,8 +75,9 @@ def step(mode, enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix):
     ((painted * g_paint).sum() + (f * g_pix).sum()).backward()
 
 
-def kernel_times(enc, images, xyz, cams, scale, g_pix, reps=20):
-    """device time of th_latent_gather and th_latent_gather_bwd on their own at the pixel shape"""
+def kernel_times(enc, images, xyz, cams, scale, g_pix, reps=20, ordered=False):
+    """device time of th_latent_gather and th_latent_gather_bwd on their own at the pixel shape; ordered: also of
+    th_latent_gather_bwd_ordered (latents and lift), with its workspace and the peak allocation of one call"""
     import torch
     from transhuman_amd import hip
     with torch.no_grad():
@@ -83,7 +88,18 @@ def kernel_times(enc, images, xyz, cams, scale, g_pix, reps=20):
         fwd = lambda: hip.latent_gather(*lat, w, b, images, xyz, cams, scale)
         bwd = lambda: hip.latent_gather_bwd(shapes, images.shape[2:], xyz, cams, scale, g_pix, out=out)
         res = {}
-        for name, fn in (("th_latent_gather", fwd), ("th_latent_gather_bwd (with its three clears)", bwd)):
+        calls = [("th_latent_gather", fwd), ("th_latent_gather_bwd (with its three clears)", bwd)]
+        if ordered:
+            rgb_s = fwd()[1]
+            V, (H, W) = images.shape[0], images.shape[2:]
+            ws = torch.empty(hip.load_library().th_latent_gather_bwd_ordered_ws(V, H, W, xyz.shape[0]), dtype=torch.uint8,
+                             device=xyz.device)
+            calls.append(("th_latent_gather_bwd_ordered (all its kernels, latents only)",
+                          lambda: hip.latent_gather_bwd_ordered(shapes, (H, W), xyz, cams, scale, g_pix, out=out, workspace=ws)))
+            calls.append(("th_latent_gather_bwd_ordered (all its kernels, latents and lift)",
+                          lambda: hip.latent_gather_bwd_ordered(shapes, (H, W), xyz, cams, scale, g_pix, rgb_s=rgb_s, out=out,
+                                                                workspace=ws)))
+        for name, fn in calls:
             for _ in range(3):
                 fn()
             ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
@@ -95,6 +111,16 @@ def kernel_times(enc, images, xyz, cams, scale, g_pix, reps=20):
             ms = [a.elapsed_time(e) for a, e in ev]
             res[name] = {"ms_median": round(float(np.median(ms)), 4), "ms_min": round(float(np.min(ms)), 4),
                          "ms_max": round(float(np.max(ms)), 4), "calls": reps}
+        if ordered:
+            del ws
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            hip.latent_gather_bwd_ordered(shapes, (H, W), xyz, cams, scale, g_pix, rgb_s=rgb_s, out=out)
+            torch.cuda.synchronize()
+            res["th_latent_gather_bwd_ordered memory"] = {
+                "workspace_MiB": round(hip.load_library().th_latent_gather_bwd_ordered_ws(V, H, W, xyz.shape[0]) / 2 ** 20, 2),
+                "peak_allocated_MiB_of_a_call": round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 2)}
     return res
 
 
@@ -149,10 +175,14 @@ def main():
     ap.add_argument("--maps", default="full,latents", help="comma list of cfg.train_maps values")
     ap.add_argument("--encoder", default="torch", help="comma list of cfg.train_encoder values (results of 'device' are keyed "
                                                        "'<maps>+encoder')")
+    ap.add_argument("--gather-bwd", default="atomic", help="comma list of cfg.train_gather_bwd values, for the 'latents' modes "
+                                                           "(results of 'ordered' are keyed '<maps>+ordered')")
     ap.add_argument("--rocprof", default=None, metavar="DIR", help="also trace a short run of the last mode under rocprofv3 into DIR")
     ap.add_argument("--traced-child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
-    modes = tuple(m + ("" if e == "torch" else "+encoder") for m in args.maps.split(",") for e in args.encoder.split(","))
+    modes = tuple(m + ("" if g == "atomic" else "+ordered") + ("" if e == "torch" else "+encoder")
+                  for m in args.maps.split(",") for g in (args.gather_bwd.split(",") if m == "latents" else ["atomic"])
+                  for e in args.encoder.split(","))
     if args.traced_child:
         return traced_child(args.traced_child, args.size, 3)
     traced = None
@@ -208,8 +238,13 @@ def main():
         if m.endswith("+encoder") and m[:-8] in grads:
             assert set(grads[m]) == set(grads[m[:-8]])
             res[m + "_vs_torch_encoder"] = {"grads_max_rel_to_own_max": rel(m[:-8], m)}
+    for m in modes:
+        q = m.replace("+ordered", "")
+        if q != m and q in grads:
+            assert set(grads[m]) == set(grads[q])
+            res[m + "_vs_atomic"] = {"grads_max_rel_to_own_max": rel(q, m)}
     if any(m.startswith("latents") for m in modes):
-        res["kernels"] = kernel_times(enc, images, xyz, cams, scale, g_pix)
+        res["kernels"] = kernel_times(enc, images, xyz, cams, scale, g_pix, ordered=any("+ordered" in m for m in modes))
     print(json.dumps(res))
 
 

@@ -8,7 +8,10 @@ the HIP adjoints of K17, transhuman_amd/networks/train_ops.py).
 --maps full,latents repeats every mode with cfg.train_maps = "latents" (K19: the encoder's latents sampled directly) in the same
 process; --point-net torch,device does the same with cfg.train_point_net = "device" (K20: the per-point network layer by layer
 on the device; keys gain '+pointnet'); --encoder torch,device with cfg.train_encoder = "device" (K23: the encoder trunk's backward as
-HIP kernels; keys gain '+encoder'); --attention / --vit-dense set cfg.train_attention / cfg.train_vit_dense for the whole run.
+HIP kernels; keys gain '+encoder'); --gather-bwd atomic,ordered with cfg.train_gather_bwd = "ordered" for the "latents" runs (K19's
+backward without float atomics, k_latgather_ord.hip; keys gain '+ordered' after '+latents'); --rounds N repeats the whole sweep N
+times in alternating order, so the forms are timed in turn in one process (per key then: the median of the rounds' medians with
+the lowest and the highest); --attention / --vit-dense set cfg.train_attention / cfg.train_vit_dense for the whole run.
 Prints one JSON line.  Per mode: median and minimum wall time of a step over --steps steps after --warmup (host clock around
 forward + backward with a device synchronisation at both ends) and torch.cuda.max_memory_allocated of the timed steps; the
 largest difference of the outputs and of every parameter gradient between the two modes; and, with --rocprof DIR, the device
@@ -147,6 +150,9 @@ def main():
                                                          "(results of 'device' are keyed '<mode>[+<maps>]+pointnet')")
     ap.add_argument("--encoder", default="torch", help="comma list of cfg.train_encoder values; every mode runs once per value "
                                                        "(results of 'device' are keyed '<mode>[+<maps>][+pointnet]+encoder')")
+    ap.add_argument("--gather-bwd", default="atomic", help="comma list of cfg.train_gather_bwd values; every 'latents' mode runs once "
+                                                           "per value (results of 'ordered' are keyed '<mode>+latents+ordered...')")
+    ap.add_argument("--rounds", type=int, default=1, help="repeat the sweep this many times, in alternating order")
     ap.add_argument("--attention", default="torch", help="cfg.train_attention of every run")
     ap.add_argument("--vit-dense", default="torch", help="cfg.train_vit_dense of every run")
     ap.add_argument("--rocprof", default=None, metavar="DIR", help="also trace a short 'device' run under rocprofv3 into DIR")
@@ -172,21 +178,34 @@ def main():
     seen = {}
     try:
         cfg.train_attention, cfg.train_vit_dense = args.attention, args.vit_dense
+        sweep = []
         for maps in args.maps.split(","):
-            cfg.train_maps = maps
-            for point_net in args.point_net.split(","):
-                cfg.train_point_net = point_net
-                for encoder in args.encoder.split(","):
-                    cfg.train_encoder = encoder
-                    for mode in args.modes.split(","):
-                        key = (mode if maps == "full" else f"{mode}+{maps}") + ("" if point_net == "torch" else "+pointnet") + \
-                            ("" if encoder == "torch" else "+encoder")
-                        res[key], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
-                        seen[key] = (outs, grads)
+            for gather_bwd in (args.gather_bwd.split(",") if maps == "latents" else ["atomic"]):
+                for point_net in args.point_net.split(","):
+                    for encoder in args.encoder.split(","):
+                        for mode in args.modes.split(","):
+                            key = (mode if maps == "full" else f"{mode}+{maps}") + ("" if gather_bwd == "atomic" else "+ordered") + \
+                                ("" if point_net == "torch" else "+pointnet") + ("" if encoder == "torch" else "+encoder")
+                            sweep.append((key, mode, maps, gather_bwd, point_net, encoder))
+        rounds = {}
+        for rnd in range(max(args.rounds, 1)):
+            for key, mode, maps, gather_bwd, point_net, encoder in (sweep if rnd % 2 == 0 else sweep[::-1]):
+                cfg.train_maps, cfg.train_gather_bwd, cfg.train_point_net, cfg.train_encoder = maps, gather_bwd, point_net, encoder
+                res[key], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
+                rounds.setdefault(key, []).append(res[key])
+                seen[key] = (outs, grads)
+        if args.rounds > 1:
+            for key, rr in rounds.items():
+                med = [x["step_ms_median"] for x in rr]
+                res[key] = {"step_ms_median": round(float(np.median(med)), 2), "step_ms_lowest_round": min(med),
+                            "step_ms_highest_round": max(med), "step_ms_min": min(x["step_ms_min"] for x in rr),
+                            "rounds": len(rr), "steps": args.steps,
+                            "peak_allocated_MiB": max(x["peak_allocated_MiB"] for x in rr)}
         for kind in [k for k in args.optim.split(",") if k]:
             res[f"step+optim:{kind}"] = run_optim(kind, net, r, b, target, args.steps, args.warmup)
     finally:
         cfg.train_kernels, cfg.train_maps, cfg.train_point_net, cfg.train_encoder = "torch", "full", "torch", "torch"
+        cfg.train_gather_bwd = "atomic"
         cfg.train_attention, cfg.train_vit_dense = "torch", "torch"
     if "torch" in seen and "device" in seen:
         (o0, g0), (o1, g1) = seen["torch"], seen["device"]
@@ -205,7 +224,12 @@ def main():
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
             "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0
                                             if not k.endswith("spatial_key_value_0.key_embed.bias"))}
-    for key in [k for k in seen if "+" in k and not k.endswith(("+pointnet", "+encoder")) and k.split("+")[0] in seen]:
+    for key in [k for k in seen if "+ordered" in k and k.replace("+ordered", "") in seen]:
+        (o0, g0), (o1, g1) = seen[key.replace("+ordered", "")], seen[key]
+        res[key + "_vs_atomic"] = {
+            "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
+            "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0)}
+    for key in [k for k in seen if "+" in k and not k.endswith(("+pointnet", "+encoder", "+ordered")) and k.split("+")[0] in seen]:
         (o0, g0), (o1, g1) = seen[key.split("+")[0]], seen[key]
         res[key + "_vs_full"] = {
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),

@@ -77,6 +77,12 @@ def _defaults():
         # [V,384,H,W], holder_feat_map [V,192,H,W]) and their gradients; "latents" samples the encoder's three latents and the
         # images directly at the vertices and the ray samples (train_ops.LatentGatherFn, K19) -- neither map exists
         train_maps="full",
+        # the adjoint of that gather, read only with train_maps = "latents": "atomic" clears the three latent gradients and adds
+        # onto them with float atomics (last bits differ from run to run; the lift's gradient through torch's GEMM); "ordered"
+        # sorts the (sample, view) pairs by map pixel and sums per latent texel in ascending (row, column, sample, slot) order,
+        # the lift's gradient by fixed-order partial sums -- all five gradients bit-identical from run to run
+        # (th_latent_gather_bwd_ordered, k_latgather_ord.hip)
+        train_gather_bwd="atomic",
         # the per-point network (MLP_forward_ori) in the training entry: "torch" composes it from torch operators under torch
         # autograd; "device" runs it layer by layer on the fp32 MFMA GEMMs of the inference path with HIP backwards
         # (autograd_path.point_network_device: train_ops.ReluLinearFn / LinearFn / CrossViewAttentionFn, K20)

@@ -750,6 +750,20 @@ int th_latent_gather_bwd(th_ctx* c, const int32_t* dims, int V, int H, int W, co
                                    (hipStream_t)stream);
 }
 
+size_t th_latent_gather_bwd_ordered_ws(int V, int H, int W, int P) { return th_latgather_bwd_ord_ws(V, H, W, P); }
+
+int th_latent_gather_bwd_ordered(th_ctx* c, const int32_t* dims, int V, int H, int W, const float* pts, int P, const float* cams,
+                                 const float* scale, const float* grad_out, int ldo, const float* rgb_s, float* g_lat0,
+                                 float* g_lat1, float* g_lat2, float* g_lift_w, float* g_lift_b, void* ws, size_t ws_bytes,
+                                 th_stream stream) {
+    TH_REQUIRE(c && dims && cams && scale && g_lat0 && g_lat1 && g_lat2 && ws, "null argument");
+    TH_REQUIRE(P == 0 || (pts && grad_out), "null argument");
+    TH_REQUIRE((g_lift_w != nullptr) == (g_lift_b != nullptr), "g_lift_w and g_lift_b come together");
+    TH_REQUIRE(!g_lift_w || P == 0 || rgb_s, "the lift's gradient needs rgb_s");
+    return th_latgather_bwd_ord_launch(dims, V, H, W, pts, P, cams, scale, grad_out, ldo, rgb_s, g_lat0, g_lat1, g_lat2,
+                                       g_lift_w, g_lift_b, ws, ws_bytes, (hipStream_t)stream);
+}
+
 int th_gen_rays(th_ctx* c, const float* K_host, const float* R_host, const float* T_host, const float* bounds_host, int H,
                 int W, float* ray_o, float* ray_d, float* near_out, float* far_out, uint8_t* mask_at_box,
                 th_stream stream) {

@@ -483,6 +483,14 @@ int th_latgather_launch(const float* lat0, const float* lat1, const float* lat2,
 int th_latgather_bwd_launch(const int* dims, int V, int H, int W, const float* pts_world, int P, const float* cams,
                             const float* scale, const float* grad_out, int ldo, float* g0, float* g1, float* g2,
                             hipStream_t s);
+// k_latgather_ord.hip (K19, ordered form): the same adjoint with no float atomic -- a stable sort of the (sample, view) pairs
+// by map pixel, then one wave per latent texel summing in ascending (y0, x0, sample, slot) order; every element of the three
+// gradients is stored once (nothing is cleared), bit-identical from run to run.  g_w [128,3] / g_b [128] (both or neither;
+// they need rgb_s [P,V,4]): the lift's gradient by fixed-order partial sums
+size_t th_latgather_bwd_ord_ws(int V, int H, int W, int P);
+int th_latgather_bwd_ord_launch(const int* dims, int V, int H, int W, const float* pts_world, int P, const float* cams,
+                                const float* scale, const float* grad_out, int ldo, const float* rgb_s, float* g0, float* g1,
+                                float* g2, float* g_w, float* g_b, void* ws, size_t ws_bytes, hipStream_t s);
 // k_pixfeat.hip
 int th_pixgather_launch(const float* map, int V, int C, int H, int W, const float* pts_world,
                         const ThPointSrc* ps, const int32_t* sel, int P, const float* cams, const float* scale,

@@ -1451,6 +1451,41 @@ def latent_gather_bwd(latent_shapes, image_hw, pts_world, cams, scale_xy, grad_o
     return tuple(out)
 
 
+# the sizes at which k_latgather_ord.hip takes another path (its LGO_B, LGO_ROUND, LGO_TILE, LGO_LIFT_ROWS): pairs = P * V
+LATENT_GATHER_ORDERED_SIZES = dict(batch=64, sort_round=256, sort_tile=2048, lift_rows=256)
+
+
+def latent_gather_bwd_ordered(latent_shapes, image_hw, pts_world, cams, scale_xy, grad_out, rgb_s=None, out=None,
+                              workspace=None):
+    """th_latent_gather_bwd_ordered: what latent_gather_bwd computes, with no float atomic and every sum in a fixed order
+    (bit-identical from run to run) -> the three latent gradients; with ``rgb_s`` [P,V,4] (latent_gather's second result) also
+    the lift's gradients: (g0, g1, g2, g_w [128,3], g_b [128]).  ``out`` (optional, three tensors) is written in full;
+    ``workspace`` (optional, uint8) replaces the one allocated here and may hold anything."""
+    lib = load_library()
+    V, dims = _latent_dims(latent_shapes)
+    H, W = (int(x) for x in image_hw)
+    p, g = _f32(pts_world).reshape(-1, 3), _f32(grad_out)
+    P, ldo = p.shape[0], g.shape[-1]
+    assert g.shape == (P, V, ldo)
+    if out is None:
+        out = tuple(torch.empty(tuple(sh), dtype=torch.float32, device=g.device) for sh in latent_shapes)
+    for o, sh in zip(out, latent_shapes):
+        assert tuple(o.shape) == tuple(sh) and o.dtype is torch.float32 and o.is_contiguous()
+    lift = ()
+    if rgb_s is not None:
+        rgb_s = _f32(rgb_s)
+        assert rgb_s.shape == (P, V, 4)
+        lift = (torch.empty((128, 3), dtype=torch.float32, device=g.device),
+                torch.empty(128, dtype=torch.float32, device=g.device))
+    need = lib.th_latent_gather_bwd_ordered_ws(V, H, W, P)
+    ws = _ws(need, g.device) if workspace is None else workspace
+    assert ws.dtype is torch.uint8 and ws.is_contiguous() and ws.device == g.device
+    _check(lib.th_latent_gather_bwd_ordered(ctx(g.device), dims, V, H, W, _p(p), P, _p(cams), _p(scale_xy), _p(g), ldo,
+                                            _p(rgb_s), _p(out[0]), _p(out[1]), _p(out[2]), _p(lift[0] if lift else None),
+                                            _p(lift[1] if lift else None), _p(ws), ws.numel(), _stream()))
+    return tuple(out) + lift
+
+
 def composite_bwd(raw, z, ray_d, g_rgb, g_acc, g_depth, white_bkgd=False):
     """th_composite_bwd: the gradients of composite's three outputs -> g_raw [R,S,4]"""
     lib = load_library()

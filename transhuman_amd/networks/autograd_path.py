@@ -140,13 +140,21 @@ def _maps_mode(value):
     return mode
 
 
-def latent_features(enc, images, cams, scale, encoder="torch"):
+def _gather_bwd_mode(value):
+    mode = str(value)
+    if mode not in ("atomic", "ordered"):
+        raise ValueError(f"cfg.train_gather_bwd must be 'atomic' or 'ordered', not {mode!r}")
+    return mode
+
+
+def latent_features(enc, images, cams, scale, encoder="torch", gather_bwd="atomic"):
     """cfg.train_maps = "latents": the trunk as in ``encode`` (stock modules; torch autograd, or ``trunk_device``), each latent
-    channels-last once; returns ``gather(points [N,3]) -> [N,V,384]``, the rows ``sample_map(pix, ...)`` would give (K19)"""
+    channels-last once; returns ``gather(points [N,3]) -> [N,V,384]``, the rows ``sample_map(pix, ...)`` would give (K19);
+    ``gather_bwd``: the form of its adjoint (cfg.train_gather_bwd)"""
     from . import train_ops
     lat = [l.permute(0, 2, 3, 1).contiguous() for l in _trunk(enc, images, encoder)]
     lift = enc.upsample_color
-    return lambda pts: train_ops.LatentGatherFn.apply(*lat, lift.weight, lift.bias, images, pts, cams, scale)
+    return lambda pts: train_ops.LatentGatherFn.apply(*lat, lift.weight, lift.bias, images, pts, cams, scale, gather_bwd)
 
 
 def project(x, R, T, K):
@@ -390,6 +398,7 @@ def render(renderer, batch, chunk=32768):
         raise hip.HipError("cfg.train_vit_dense = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
                            "use 'torch' for a CPU batch")
     maps = _maps_mode(getattr(cfg, "train_maps", "full"))
+    gather_bwd = _gather_bwd_mode(getattr(cfg, "train_gather_bwd", "atomic")) if maps == "latents" else "atomic"
     if maps == "latents" and not ray_o.is_cuda:
         from .. import hip
         raise hip.HipError("cfg.train_maps = 'latents' needs the batch on an MI355X (the HIP kernels have no CPU form); "
@@ -421,7 +430,8 @@ def render(renderer, batch, chunk=32768):
         from .. import hip
         # a 1 x 1 convolution commutes with bilinear sampling: reduction_layer on the gathered rows (k_encoder.hip does the same)
         gather = latent_features(net.encoder, images, hip.pack_cams(R_in, T_in, K_in),
-                                 hip.feat_scale(net.encoder.feat_scale(*images.shape[2:]), image_shape, dev), encoder=encoder)
+                                 hip.feat_scale(net.encoder.feat_scale(*images.shape[2:]), image_shape, dev), encoder=encoder,
+                                 gather_bwd=gather_bwd)
         painted = _lin(net.encoder.reduction_layer, gather(verts_in)).permute(1, 0, 2)
         f_lat = gather(xyz)                                # once over all P samples, split per chunk below
     else:

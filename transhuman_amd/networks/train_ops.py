@@ -14,6 +14,9 @@ upsampled latent is a linear combination of at most 3 x 3 of its texels, so neit
 
     LatentGatherFn          lat0..2 [V,h,w,C], lift -> rows [P,V,384]  gradient: the latents, the lift    keeps rgb_s [P,V,4]
 
+``cfg.train_gather_bwd = "ordered"`` gives that Function's backward without float atomics (k_latgather_ord.hip): a sort of the
+(sample, view) pairs by map pixel, then every latent texel sums what reaches it in a fixed order; "atomic" is the default.
+
 ``cfg.train_attention = "device"`` does the same for the attention of every TransHE block:
 
     AttentionFn             qkv    [V,N,3 C]     -> [V,N,C]            gradient: qkv         (k_vit.hip / k_vit_bwd.hip)
@@ -110,10 +113,15 @@ class LatentGatherFn(torch.autograd.Function):
     """SpatialEncoder.forward's tail (encoder.py:133-146) + get_pixel_aligned_feature (if_clight_renderer.py:210-269) without the
     map between them: the channels-last latents lat0 [V,h0,w0,64], lat1 [V,h1,w1,64], lat2 [V,h2,w2,128] and the colour lift
     (upsample_color's weight [128,3(,1,1)] and bias) -> rows [P,V,384].  Kept for the backward: the geometry and the blended
-    raw colours rgb_s [P,V,4] (the lift's weight gradient)."""
+    raw colours rgb_s [P,V,4] (the lift's weight gradient).  ``gather_bwd`` (cfg.train_gather_bwd): "atomic" (the default) adds
+    onto the latent gradients with float atomics and reduces the lift's through torch; "ordered" computes all five with
+    fixed-order sums (hip.latent_gather_bwd_ordered): bit-identical from run to run."""
 
     @staticmethod
-    def forward(ctx, lat0, lat1, lat2, lift_w, lift_b, images, pts_world, cams, scale_xy):
+    def forward(ctx, lat0, lat1, lat2, lift_w, lift_b, images, pts_world, cams, scale_xy, gather_bwd="atomic"):
+        if gather_bwd not in ("atomic", "ordered"):
+            raise ValueError(f"LatentGatherFn: gather_bwd must be 'atomic' or 'ordered', not {gather_bwd!r}")
+        ctx.gather_bwd = gather_bwd
         _no_grad_inputs("LatentGatherFn", images=images, pts_world=pts_world, cams=cams, scale_xy=scale_xy)
         _on_device("LatentGatherFn", lat0)
         rows, rgb_s = hip.latent_gather(lat0.detach(), lat1.detach(), lat2.detach(), lift_w.detach(), lift_b.detach(), images,
@@ -128,11 +136,15 @@ class LatentGatherFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         pts_world, cams, scale_xy, rgb_s = ctx.saved_tensors
         g = grad_out.contiguous()
+        if ctx.gather_bwd == "ordered":
+            g0, g1, g2, g_w, g_b = hip.latent_gather_bwd_ordered(ctx.shapes, ctx.image_hw, pts_world, cams, scale_xy, g,
+                                                                 rgb_s=rgb_s)
+            return g0, g1, g2, g_w.reshape(ctx.lift_w_shape), g_b, None, None, None, None, None
         g0, g1, g2 = hip.latent_gather_bwd(ctx.shapes, ctx.image_hw, pts_world, cams, scale_xy, g)
         # the lift: 128 x 3 + 128 numbers, one small reduction over the rows (not the hot path)
         gl = g[..., 256:384].reshape(-1, 128)
         g_w = (gl.t() @ rgb_s.reshape(-1, 4)[:, :3]).reshape(ctx.lift_w_shape)
-        return g0, g1, g2, g_w, gl.sum(0), None, None, None, None
+        return g0, g1, g2, g_w, gl.sum(0), None, None, None, None, None
 
 
 class CompositeFn(torch.autograd.Function):
