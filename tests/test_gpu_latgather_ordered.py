@@ -8,15 +8,14 @@ filled with NaN bytes before every call: the kernels clear nothing and must not 
 The lift: (rows + 2) 2^-24 sum |terms|, the bound of test_function_gradients_of_the_latents_and_the_lift.
 Reproducibility: torch.equal between calls whose outputs and workspace held different garbage; the whole synthetic training step
 twice, every output and every parameter gradient torch.equal."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from transhuman_amd import config
 from transhuman_amd.networks import autograd_path, train_ops
 from test_gpu_train_maps import SHAPES, CH, EPS, _check_adjoint, _coefficients, _geometry, _grid_weights, _inputs, _points
-from util import GOLD
+from train_step_case import STEP_CFG, check_step, golden, setup
 
 pytestmark = pytest.mark.gpu
 
@@ -245,37 +244,8 @@ def test_function_in_the_ordered_mode(hip, gpu, P, V):
 def test_training_step_with_the_ordered_gather_matches_the_reference(hip, gpu, kernels):
     """tests/test_gpu_train_maps.py::test_training_step_on_the_latents_matches_the_reference with cfg.train_gather_bwd =
     "ordered": the same golden step of the real reference, the same bars"""
-    from test_gpu_train_maps import _reset, _setup
-    g = np.load(os.path.join(GOLD, "g18_train_step.npz"))
-    cfg, net, r, b = _setup(gpu)
-    try:
-        cfg.train_maps, cfg.train_kernels, cfg.train_gather_bwd = "latents", kernels, "ordered"
-        assert b["ray_o"].shape[1] == int(g["rays"])
-        ret = autograd_path.render(r, b)
-        for k, name in (("rgb_map", "rgb"), ("acc_map", "acc"), ("depth_map", "depth")):
-            d = float((ret[k][0].detach().cpu() - torch.from_numpy(g[name])).abs().max())
-            print(k, d)
-            assert d < 2e-5, (k, d)
-        target = torch.from_numpy(g["target"])[None].to(gpu)
-        loss = torch.mean((ret["rgb_map"] - target) ** 2) + 0.1 * ret["acc_map"].mean() + 0.01 * ret["depth_map"].mean()
-        assert abs(float(loss) - float(g["loss"])) < 1e-6
-        loss.backward()
-        params = dict(net.named_parameters())
-        keys = [k[5:] for k in g.files if k.startswith("grad:")]
-        assert len(keys) == 20
-        for k in keys:
-            ref = torch.from_numpy(g["grad:" + k])
-            got = params[k].grad
-            assert got is not None and got.shape == ref.shape, k
-            err = float((got.cpu() - ref).abs().max()) / float(ref.abs().max())
-            print(k, err)
-            assert err < 2e-3, (k, err)
-        missing = [k for k, p in params.items() if p.grad is None and not k.endswith(("cls_token", "mask_token"))
-                   and ".layer3." not in k and ".layer4." not in k and "PE" not in k]
-        assert not missing, missing
-    finally:
-        cfg.train_gather_bwd = "atomic"
-        _reset(cfg)
+    with config.override(**STEP_CFG, train_maps="latents", train_kernels=kernels, train_gather_bwd="ordered"):
+        check_step(golden(), *setup(gpu))
 
 
 # ---- 6: the whole step, twice ----------------------------------------------------------------------------------------------------
@@ -283,23 +253,17 @@ def test_the_whole_step_twice_gives_the_same_bits(hip, gpu):
     """the synthetic step of tests/test_gpu_train_encoder.py, rebuilt from its seeds for each run, every training switch on its
     device value and the ordered gather backward, MIOpen on its deterministic kernels: the three outputs and every parameter
     gradient are torch.equal between two runs"""
-    from test_gpu_train_encoder import ALL_DEVICE, _reproducible_torch, _restore, _setup
+    from test_gpu_train_encoder import ALL_DEVICE, _reproducible_torch
     runs = []
     for _ in range(2):
-        cfg, net, r, b = _setup(gpu)
-        try:
-            for k, v in ALL_DEVICE.items():
-                setattr(cfg, k, v)
-            cfg.train_encoder, cfg.train_gather_bwd = "device", "ordered"
+        with config.override(**STEP_CFG, **ALL_DEVICE, train_encoder="device", train_gather_bwd="ordered"):
+            net, r, b = setup(gpu)
             with _reproducible_torch():
                 ret = autograd_path.render(r, b)
                 (ret["rgb_map"].mean() + 0.1 * ret["acc_map"].mean() + 0.01 * ret["depth_map"].mean()).backward()
             out = {k: ret[k].detach().clone() for k in ("rgb_map", "acc_map", "depth_map")}
             out.update({"grad:" + k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None})
             runs.append(out)
-        finally:
-            cfg.train_gather_bwd = "atomic"
-            _restore(cfg)
     a, b2 = runs
     assert set(a) == set(b2)
     trunk = [k for k in a if k.startswith(("grad:encoder.model.conv1.", "grad:encoder.model.bn1.", "grad:encoder.model.layer1.",

@@ -373,10 +373,11 @@ def test_network_wrapper_on_six_patches_of_20(hip, gpu, net, lp_mod, monkeypatch
 def test_training_step_through_the_loss(hip, gpu, net, lp_mod, monkeypatch):
     """Renderer.render under autograd at tests/test_gpu_train_ops.py's shapes, NetworkWrapper's loss, backward(): every
     parameter that gets a gradient from the stand-in loss (MSE + acc + depth terms) gets a finite one from the reference's"""
-    from test_gpu_train_ops import _setup
+    from train_step_case import STEP_CFG, setup
+    from transhuman_amd import config
     from transhuman_amd.train_loss import NetworkWrapper
-    cfg, model, r, b = _setup(gpu)
-    try:
+    with config.override(**STEP_CFG) as cfg:
+        model, r, b = setup(gpu)
         monkeypatch.setattr(cfg, "l2rec_weight", 1.0, raising=False)
         monkeypatch.setattr(cfg, "lpips_weight", 0.1, raising=False)
         n = int(b["ray_o"].shape[1])
@@ -402,5 +403,3 @@ def test_training_step_through_the_loss(hip, gpu, net, lp_mod, monkeypatch):
         bad = [k for k in had if params[k].grad is None or not bool(torch.isfinite(params[k].grad).all())]
         assert not bad, bad
         assert any(float(params[k].grad.abs().max()) > 0 for k in had)
-    finally:
-        cfg.vit_depth, cfg.N_samples = 12, 64

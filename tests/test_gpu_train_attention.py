@@ -13,17 +13,16 @@ the worst ratios).
 Figures measured on an MI355X are in DESIGN.md section 4."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import th_oracle as O
-from transhuman_amd import synth
-from transhuman_amd.config import get_cfg
+from transhuman_amd import config, synth
 from transhuman_amd.networks import autograd_path, train_ops
-from util import GOLD, SIGMA_BIAS, can64, make_net, maxdiff, synth_assign
+from train_step_case import STEP_CFG, check_step, golden, setup
+from util import make_net, maxdiff
 
 pytestmark = pytest.mark.gpu
 
@@ -356,55 +355,12 @@ def test_vit_forward_with_device_attention_vs_float64(hip, gpu, V, N):
 # ---------------------------------------------------------------------------
 # 7: the golden training step
 # ---------------------------------------------------------------------------
-def _setup(device):
-    """the step of tests/test_gpu_train_ops.py::_setup (g18_train_step)"""
-    from transhuman_amd.networks.cross_transformer import Network
-    from transhuman_amd.networks.renderer.if_clight_renderer import Renderer
-    cfg = get_cfg()
-    cfg.vit_depth, cfg.N_samples, cfg.num_class, cfg.perturb, cfg.raw_noise_std = 2, 16, 300, 0.0, 0.0
-    torch.manual_seed(0)
-    net = Network()
-    net.load_state_dict(synth.det_state_dict(net.state_dict(), seed=0, sigma_bias=SIGMA_BIAS))
-    net.train()
-    net = net.to(device)
-    r = Renderer(net, vertex_can=can64().numpy(), pc2voxel_ind=synth_assign(300))
-    b = synth.batch_to(synth.make_batch(20, 20, 3, seed=0, all_rays=False, focal=62.5), device)
-    return cfg, net, r, b
-
-
 @pytest.mark.parametrize("kernels", ("torch", "device"))
 def test_training_step_with_device_attention_matches_the_reference(hip, gpu, kernels):
     """tests/test_train_path.py::test_training_step_matches_the_reference with cfg.train_attention = "device": the same golden
     step of the real reference, the same bars, under both values of cfg.train_kernels"""
-    g = np.load(os.path.join(GOLD, "g18_train_step.npz"))
-    cfg, net, r, b = _setup(gpu)
-    try:
-        cfg.train_kernels, cfg.train_attention = kernels, "device"
-        assert b["ray_o"].shape[1] == int(g["rays"])
-        ret = autograd_path.render(r, b)
-        for k, name in (("rgb_map", "rgb"), ("acc_map", "acc"), ("depth_map", "depth")):
-            d = float((ret[k][0].detach().cpu() - torch.from_numpy(g[name])).abs().max())
-            print(k, d)
-            assert d < 2e-5, (k, d)
-        target = torch.from_numpy(g["target"])[None].to(gpu)
-        loss = torch.mean((ret["rgb_map"] - target) ** 2) + 0.1 * ret["acc_map"].mean() + 0.01 * ret["depth_map"].mean()
-        assert abs(float(loss) - float(g["loss"])) < 1e-6
-        loss.backward()
-        params = dict(net.named_parameters())
-        keys = [k[5:] for k in g.files if k.startswith("grad:")]
-        assert len(keys) == 20
-        for k in keys:
-            ref = torch.from_numpy(g["grad:" + k])
-            got = params[k].grad
-            assert got is not None and got.shape == ref.shape, k
-            err = float((got.cpu() - ref).abs().max()) / float(ref.abs().max())
-            print(k, err)
-            assert err < 2e-3, (k, err)
-        missing = [k for k, p in params.items() if p.grad is None and not k.endswith(("cls_token", "mask_token"))
-                   and ".layer3." not in k and ".layer4." not in k and "PE" not in k]
-        assert not missing, missing
-    finally:
-        cfg.train_kernels, cfg.train_attention, cfg.vit_depth, cfg.N_samples = "torch", "torch", 12, 64
+    with config.override(**STEP_CFG, train_kernels=kernels, train_attention="device"):
+        check_step(golden(), *setup(gpu))
 
 
 # ---------------------------------------------------------------------------

@@ -18,17 +18,16 @@ forward is torch's bit for bit, so both fp32 runs gate and route alike.
 Convolution reference data are computed once per (shape, N, H, W) and shared by the dgrad and wgrad tests."""
 import contextlib
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from transhuman_amd import synth
-from transhuman_amd.config import get_cfg
+from transhuman_amd import config
 from transhuman_amd.networks import autograd_path, train_ops
-from util import GOLD, SIGMA_BIAS, can64, maxdiff, synth_assign
+from train_step_case import STEP_CFG, check_step, golden, setup
+from util import maxdiff
 
 pytestmark = pytest.mark.gpu
 
@@ -447,32 +446,8 @@ def test_trunk_without_batch_statistics_is_torch_autograds(hip, gpu):
 # ---------------------------------------------------------------------------
 # 5: the golden training step
 # ---------------------------------------------------------------------------
-SWITCHES = {"train_kernels": "torch", "train_attention": "torch", "train_vit_dense": "torch", "train_maps": "full",
-            "target_prep": "batch", "train_point_net": "torch", "train_encoder": "torch"}
 ALL_DEVICE = {"train_kernels": "device", "train_attention": "device", "train_vit_dense": "device", "train_maps": "latents",
               "target_prep": "device", "train_point_net": "device"}
-
-
-def _setup(device):
-    """the step of tests/test_gpu_train_ops.py::_setup (g18_train_step)"""
-    from transhuman_amd.networks.cross_transformer import Network
-    from transhuman_amd.networks.renderer.if_clight_renderer import Renderer
-    cfg = get_cfg()
-    cfg.vit_depth, cfg.N_samples, cfg.num_class, cfg.perturb, cfg.raw_noise_std = 2, 16, 300, 0.0, 0.0
-    torch.manual_seed(0)
-    net = Network()
-    net.load_state_dict(synth.det_state_dict(net.state_dict(), seed=0, sigma_bias=SIGMA_BIAS))
-    net.train()
-    net = net.to(device)
-    r = Renderer(net, vertex_can=can64().numpy(), pc2voxel_ind=synth_assign(300))
-    b = synth.batch_to(synth.make_batch(20, 20, 3, seed=0, all_rays=False, focal=62.5), device)
-    return cfg, net, r, b
-
-
-def _restore(cfg):
-    for k, v in SWITCHES.items():
-        setattr(cfg, k, v)
-    cfg.vit_depth, cfg.N_samples = 12, 64
 
 
 @pytest.mark.parametrize("others", ({"train_kernels": "torch"}, {"train_kernels": "device"}, {"train_maps": "latents"}, ALL_DEVICE),
@@ -481,37 +456,8 @@ def test_training_step_with_the_encoder_on_the_device_matches_the_reference(hip,
     """tests/test_gpu_train_ops.py::test_training_step_on_the_device_kernels_matches_the_reference with cfg.train_encoder = "device":
     the same golden step of the real reference, the same bars, under both values of cfg.train_kernels, under cfg.train_maps =
     "latents" (the default "full" is in the first two) and with all six training switches on their device values"""
-    g = np.load(os.path.join(GOLD, "g18_train_step.npz"))
-    cfg, net, r, b = _setup(gpu)
-    try:
-        cfg.train_encoder = "device"
-        for k, v in others.items():
-            setattr(cfg, k, v)
-        assert b["ray_o"].shape[1] == int(g["rays"])
-        ret = autograd_path.render(r, b)
-        for k, name in (("rgb_map", "rgb"), ("acc_map", "acc"), ("depth_map", "depth")):
-            d = float((ret[k][0].detach().cpu() - torch.from_numpy(g[name])).abs().max())
-            print(k, d)
-            assert d < 2e-5, (k, d)
-        target = torch.from_numpy(g["target"])[None].to(gpu)
-        loss = torch.mean((ret["rgb_map"] - target) ** 2) + 0.1 * ret["acc_map"].mean() + 0.01 * ret["depth_map"].mean()
-        assert abs(float(loss) - float(g["loss"])) < 1e-6
-        loss.backward()
-        params = dict(net.named_parameters())
-        keys = [k[5:] for k in g.files if k.startswith("grad:")]
-        assert len(keys) == 20
-        for k in keys:
-            ref = torch.from_numpy(g["grad:" + k])
-            got = params[k].grad
-            assert got is not None and got.shape == ref.shape, k
-            err = float((got.cpu() - ref).abs().max()) / float(ref.abs().max())
-            print(k, err)
-            assert err < 2e-3, (k, err)
-        missing = [k for k, p in params.items() if p.grad is None and not k.endswith(("cls_token", "mask_token"))
-                   and ".layer3." not in k and ".layer4." not in k and "PE" not in k]
-        assert not missing, missing
-    finally:
-        _restore(cfg)
+    with config.override(**STEP_CFG, train_encoder="device", **others):
+        check_step(golden(), *setup(gpu))
 
 
 @pytest.mark.parametrize("maps", ("full", "latents"))
@@ -520,17 +466,14 @@ def test_only_the_encoder_switch_changed_gives_the_same_outputs(hip, gpu, maps):
     gradient close to torch autograd's"""
     outs, grads = {}, {}
     for mode in ("torch", "device"):
-        cfg, net, r, b = _setup(gpu)
-        try:
-            cfg.train_encoder, cfg.train_maps = mode, maps
+        with config.override(**STEP_CFG, train_encoder=mode, train_maps=maps):
+            net, r, b = setup(gpu)
             with _reproducible_torch():
                 ret = autograd_path.render(r, b)
             (ret["rgb_map"].mean() + 0.1 * ret["acc_map"].mean() + 0.01 * ret["depth_map"].mean()).backward()
             outs[mode] = {k: ret[k].detach().clone() for k in ("rgb_map", "acc_map", "depth_map")}
             grads[mode] = {k: p.grad.clone() for k, p in net.encoder.named_parameters() if p.grad is not None}
             stats = _stats(net.encoder)
-        finally:
-            _restore(cfg)
         outs[mode]["stats"] = stats
     for k in ("rgb_map", "acc_map", "depth_map"):
         assert torch.equal(outs["torch"][k], outs["device"][k]), k
@@ -548,16 +491,13 @@ def test_a_trunk_without_batch_statistics_trains_as_in_the_torch_mode(hip, gpu):
     the trunk), the step's outputs are torch.equal"""
     outs = {}
     for mode in ("torch", "device"):
-        cfg, net, r, b = _setup(gpu)
-        try:
-            cfg.train_encoder = mode
+        with config.override(**STEP_CFG, train_encoder=mode):
+            net, r, b = setup(gpu)
             net.encoder.eval()
             with _reproducible_torch():
                 ret = autograd_path.render(r, b)
             outs[mode] = {k: ret[k].detach().clone() for k in ("rgb_map", "acc_map", "depth_map")}
             ret["rgb_map"].mean().backward()
             assert net.encoder.model.conv1.weight.grad is not None
-        finally:
-            _restore(cfg)
     for k, v in outs["torch"].items():
         assert torch.equal(v, outs["device"][k]), k

@@ -15,17 +15,14 @@ contributes.
 The training entry: the golden step of tests/test_train_path.py with the same bars; every executed encoder parameter against a
 float64 run of the "full" torch path, bar 4 x the error of the fp32 "full" torch path (at least 2^-22 of the tensor's maximum);
 peak memory."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from transhuman_amd import synth
-from transhuman_amd.config import get_cfg
+from transhuman_amd import config, synth
 from transhuman_amd.networks import autograd_path, train_ops
 from transhuman_amd.networks.encoder import SpatialEncoder
-from util import GOLD, can64, synth_assign, SIGMA_BIAS
+from train_step_case import STEP_CFG, check_step, golden, setup
 
 pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -24
@@ -323,58 +320,12 @@ def test_entry_points_refuse_bad_arguments(hip, gpu):
 
 
 # ---- the training entry -----------------------------------------------------------------------------------------------------------
-def _setup(device):
-    from transhuman_amd.networks.cross_transformer import Network
-    from transhuman_amd.networks.renderer.if_clight_renderer import Renderer
-    cfg = get_cfg()
-    cfg.vit_depth, cfg.N_samples, cfg.num_class, cfg.perturb, cfg.raw_noise_std = 2, 16, 300, 0.0, 0.0
-    torch.manual_seed(0)
-    net = Network()
-    net.load_state_dict(synth.det_state_dict(net.state_dict(), seed=0, sigma_bias=SIGMA_BIAS))
-    net.train()
-    net = net.to(device)
-    r = Renderer(net, vertex_can=can64().numpy(), pc2voxel_ind=synth_assign(300))
-    b = synth.batch_to(synth.make_batch(20, 20, 3, seed=0, all_rays=False, focal=62.5), device)
-    return cfg, net, r, b
-
-
-def _reset(cfg):
-    cfg.train_maps, cfg.train_kernels, cfg.vit_depth, cfg.N_samples = "full", "torch", 12, 64
-
-
 @pytest.mark.parametrize("kernels", ["torch", "device"])
 def test_training_step_on_the_latents_matches_the_reference(hip, gpu, kernels):
     """tests/test_train_path.py::test_training_step_matches_the_reference with cfg.train_maps = "latents": the same golden step
     of the real reference, the same bars"""
-    g = np.load(os.path.join(GOLD, "g18_train_step.npz"))
-    cfg, net, r, b = _setup(gpu)
-    try:
-        cfg.train_maps, cfg.train_kernels = "latents", kernels
-        assert b["ray_o"].shape[1] == int(g["rays"])
-        ret = autograd_path.render(r, b)
-        for k, name in (("rgb_map", "rgb"), ("acc_map", "acc"), ("depth_map", "depth")):
-            d = float((ret[k][0].detach().cpu() - torch.from_numpy(g[name])).abs().max())
-            print(k, d)
-            assert d < 2e-5, (k, d)
-        target = torch.from_numpy(g["target"])[None].to(gpu)
-        loss = torch.mean((ret["rgb_map"] - target) ** 2) + 0.1 * ret["acc_map"].mean() + 0.01 * ret["depth_map"].mean()
-        assert abs(float(loss) - float(g["loss"])) < 1e-6
-        loss.backward()
-        params = dict(net.named_parameters())
-        keys = [k[5:] for k in g.files if k.startswith("grad:")]
-        assert len(keys) == 20
-        for k in keys:
-            ref = torch.from_numpy(g["grad:" + k])
-            got = params[k].grad
-            assert got is not None and got.shape == ref.shape, k
-            err = float((got.cpu() - ref).abs().max()) / float(ref.abs().max())
-            print(k, err)
-            assert err < 2e-3, (k, err)
-        missing = [k for k, p in params.items() if p.grad is None and not k.endswith(("cls_token", "mask_token"))
-                   and ".layer3." not in k and ".layer4." not in k and "PE" not in k]
-        assert not missing, missing
-    finally:
-        _reset(cfg)
+    with config.override(**STEP_CFG, train_maps="latents", train_kernels=kernels):
+        check_step(golden(), *setup(gpu))
 
 
 def _tail_rows(enc, images, verts, xyz, R, T, K, maps):
@@ -405,8 +356,8 @@ def test_every_encoder_parameter_vs_float64(hip, gpu):
     bar: 4 x the error of the fp32 "full" torch path on the same device against the same float64, at least 2^-22 of the
     tensor's maximum."""
     import copy
-    cfg, net, r, b = _setup(gpu)
-    try:
+    with config.override(**STEP_CFG) as cfg:
+        net, r, b = setup(gpu)
         S = int(cfg.N_samples)
         ray_o, ray_d, near, far = b["ray_o"][0], b["ray_d"][0], b["near"][0], b["far"][0]
         z = autograd_path.sample_depths(near, far, S, False)
@@ -440,8 +391,6 @@ def test_every_encoder_parameter_vs_float64(hip, gpu):
             if not err <= bar:
                 misses.append((k, err / bar))
         assert not misses, misses
-    finally:
-        _reset(cfg)
 
 
 def test_peak_memory_is_lower_by_at_least_one_pixel_map(hip, gpu):

@@ -9,17 +9,14 @@ tolerance per element is derived, not chosen:  (n + 2) 2^-24 sum_p |W[p,d] g[p,.
 
 K7 is non-linear: the reference is composite_grad_oracle (float64), the bar 4 x the error of torch's own fp32 backward of
 autograd_path.composite on the same inputs (at least 2^-22 of the largest reference value)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from transhuman_amd import synth
-from transhuman_amd.config import get_cfg
+from transhuman_amd import config, synth
 from transhuman_amd.networks import autograd_path, train_ops
 from dparf_cases import dparf_forward_weights
-from util import GOLD, can64, synth_assign, SIGMA_BIAS
+from train_step_case import STEP_CFG, check_step, golden, setup
 
 pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -24
@@ -209,63 +206,17 @@ def test_composite_backward_vs_float64(hip, gpu, S, white):
 
 
 # ---- the training entry -----------------------------------------------------------------------------------------------------
-def _setup(device):
-    from transhuman_amd.networks.cross_transformer import Network
-    from transhuman_amd.networks.renderer.if_clight_renderer import Renderer
-    cfg = get_cfg()
-    cfg.vit_depth, cfg.N_samples, cfg.num_class, cfg.perturb, cfg.raw_noise_std = 2, 16, 300, 0.0, 0.0
-    torch.manual_seed(0)
-    net = Network()
-    net.load_state_dict(synth.det_state_dict(net.state_dict(), seed=0, sigma_bias=SIGMA_BIAS))
-    net.train()
-    net = net.to(device)
-    r = Renderer(net, vertex_can=can64().numpy(), pc2voxel_ind=synth_assign(300))
-    b = synth.batch_to(synth.make_batch(20, 20, 3, seed=0, all_rays=False, focal=62.5), device)
-    return cfg, net, r, b
-
-
 def test_training_step_on_the_device_kernels_matches_the_reference(hip, gpu):
     """tests/test_train_path.py::test_training_step_matches_the_reference with cfg.train_kernels = "device": the same golden
     step of the real reference, the same bars"""
-    g = np.load(os.path.join(GOLD, "g18_train_step.npz"))
-    cfg, net, r, b = _setup(gpu)
-    try:
-        cfg.train_kernels = "device"
-        assert b["ray_o"].shape[1] == int(g["rays"])
-        ret = autograd_path.render(r, b)
-        for k, name in (("rgb_map", "rgb"), ("acc_map", "acc"), ("depth_map", "depth")):
-            d = float((ret[k][0].detach().cpu() - torch.from_numpy(g[name])).abs().max())
-            print(k, d)
-            assert d < 2e-5, (k, d)
-        target = torch.from_numpy(g["target"])[None].to(gpu)
-        loss = torch.mean((ret["rgb_map"] - target) ** 2) + 0.1 * ret["acc_map"].mean() + 0.01 * ret["depth_map"].mean()
-        assert abs(float(loss) - float(g["loss"])) < 1e-6
-        loss.backward()
-        params = dict(net.named_parameters())
-        keys = [k[5:] for k in g.files if k.startswith("grad:")]
-        assert len(keys) == 20
-        for k in keys:
-            ref = torch.from_numpy(g["grad:" + k])
-            got = params[k].grad
-            assert got is not None and got.shape == ref.shape, k
-            err = float((got.cpu() - ref).abs().max()) / float(ref.abs().max())
-            print(k, err)
-            assert err < 2e-3, (k, err)
-        missing = [k for k, p in params.items() if p.grad is None and not k.endswith(("cls_token", "mask_token"))
-                   and ".layer3." not in k and ".layer4." not in k and "PE" not in k]
-        assert not missing, missing
-    finally:
-        cfg.train_kernels, cfg.vit_depth, cfg.N_samples = "torch", 12, 64
+    with config.override(**STEP_CFG, train_kernels="device"):
+        check_step(golden(), *setup(gpu))
 
 
 def test_switch_defaults_to_torch_and_device_refuses_a_cpu_batch(hip, gpu):
     from types import SimpleNamespace
-    cfg = get_cfg()
-    assert cfg.train_kernels == "torch"
+    assert config.get_cfg().train_kernels == "torch"
     batch = {"ray_o": torch.zeros(1, 4, 3), "ray_d": torch.ones(1, 4, 3)}
-    try:
-        cfg.train_kernels = "device"
+    with config.override(train_kernels="device"):
         with pytest.raises(hip.HipError, match="MI355X"):
             autograd_path.render(SimpleNamespace(net=None), batch)
-    finally:
-        cfg.train_kernels = "torch"

@@ -6,13 +6,15 @@ the renderer re-pack its weights, and one iteration of trainer.Trainer.train.
 infinities included) and requires a NaN exactly where the oracle has one: IEEE 754 leaves the sign and payload of a NaN that an
 operation produces open, and x86 (the oracle) and gfx950 choose differently (inf - inf is 0xffc00000 on one, 0x7fc00000 on the
 other)."""
+import contextlib
 import copy
 
 import numpy as np
 import pytest
 import torch
 
-from transhuman_amd import train_optim as TO
+from transhuman_amd import config, train_optim as TO
+from train_step_case import STEP_CFG, setup
 
 pytestmark = pytest.mark.gpu
 
@@ -289,19 +291,14 @@ def test_refusals_on_the_device(hip, gpu):
     assert C.sizeof(C.c_void_p) == 8
 
 
-def _small_network(gpu):
-    from test_gpu_train_ops import _setup
-    return _setup(gpu)
-
-
 def test_version_counters_make_the_renderer_take_the_new_weights(hip, gpu):
     """render_fast, one DeviceAdam step through raw pointers, render_fast: the second image is the one a fresh Network loaded
     from the stepped state_dict renders -- hip._sync_weights saw the bumped version counters and re-packed the weight images"""
     from transhuman_amd.networks.cross_transformer import Network
     from transhuman_amd.networks.renderer.if_clight_renderer import Renderer
     from util import can64, synth_assign
-    cfg, model, r, b = _small_network(gpu)
-    try:
+    with config.override(**STEP_CFG):
+        model, r, b = setup(gpu)
         with torch.no_grad():
             first = r.render_fast(b, is_train=False)["rgb_map"].clone()
         gen = torch.Generator().manual_seed(4)
@@ -321,8 +318,6 @@ def test_version_counters_make_the_renderer_take_the_new_weights(hip, gpu):
         with torch.no_grad():
             third = r2.render_fast(b, is_train=False)["rgb_map"]
         assert torch.equal(second, third)
-    finally:
-        cfg.vit_depth, cfg.N_samples = 12, 64
 
 
 def test_one_iteration_of_the_trainer(hip, gpu, tmp_path, monkeypatch):
@@ -343,8 +338,9 @@ def test_one_iteration_of_the_trainer(hip, gpu, tmp_path, monkeypatch):
     from transhuman_amd.train_loss import NetworkWrapper
     from transhuman_amd.trainer import Recorder, Trainer
     from util import can64, synth_assign
-    cfg, model, _, b = _small_network(gpu)
-    try:
+    with config.override(**STEP_CFG) as cfg, contextlib.ExitStack() as at_exit:
+        at_exit.callback(torch.use_deterministic_algorithms, False)
+        model, _, b = setup(gpu)
         monkeypatch.setattr(cfg, "l2rec_weight", 1.0, raising=False)
         monkeypatch.setattr(cfg, "lpips_weight", 0.1, raising=False)
         pv, pl = write_weight_files(str(tmp_path), SEED, golden_lin(golden()))
@@ -402,6 +398,3 @@ def test_one_iteration_of_the_trainer(hip, gpu, tmp_path, monkeypatch):
             worst = max(worst, err / bar)
             assert err <= bar, (k, err, bar)
         print(f"worst err / bar over {len(g_d)} parameters: {worst:.3f}")
-    finally:
-        torch.use_deterministic_algorithms(False)
-        cfg.vit_depth, cfg.N_samples = 12, 64

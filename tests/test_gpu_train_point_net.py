@@ -22,17 +22,16 @@ The stress inputs are kept only where torch's own fp32 stays finite (asserted wh
 import ctypes as C
 import functools
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from transhuman_amd import synth
-from transhuman_amd.config import get_cfg
+from transhuman_amd import config
 from transhuman_amd.networks import autograd_path, train_ops
-from util import GOLD, SIGMA_BIAS, can64, make_net, maxdiff, synth_assign
+from train_step_case import STEP_CFG, check_step, golden, setup
+from util import make_net, maxdiff
 
 pytestmark = pytest.mark.gpu
 
@@ -355,12 +354,8 @@ def test_cross_view_attention_fn_gradient_is_the_kernels(hip, gpu):
 # 3: the whole network
 # ---------------------------------------------------------------------------
 def _net():
-    cfg = get_cfg()
-    keep = cfg.vit_depth
-    try:
+    with config.override(vit_depth=2):                     # (make_net sets the key and leaves it set)
         return make_net(2).train()
-    finally:
-        cfg.vit_depth = keep
 
 
 def _net_grads(fn, net, h, f, vd, g):
@@ -433,26 +428,6 @@ def test_point_network_on_the_device_vs_float64(hip, gpu, V, P):
 # ---------------------------------------------------------------------------
 # 4: the golden training step
 # ---------------------------------------------------------------------------
-SWITCHES = {"train_kernels": "torch", "train_attention": "torch", "train_vit_dense": "torch", "train_maps": "full",
-            "target_prep": "batch", "train_point_net": "torch"}
-
-
-def _setup(device):
-    """the step of tests/test_gpu_train_ops.py::_setup (g18_train_step)"""
-    from transhuman_amd.networks.cross_transformer import Network
-    from transhuman_amd.networks.renderer.if_clight_renderer import Renderer
-    cfg = get_cfg()
-    cfg.vit_depth, cfg.N_samples, cfg.num_class, cfg.perturb, cfg.raw_noise_std = 2, 16, 300, 0.0, 0.0
-    torch.manual_seed(0)
-    net = Network()
-    net.load_state_dict(synth.det_state_dict(net.state_dict(), seed=0, sigma_bias=SIGMA_BIAS))
-    net.train()
-    net = net.to(device)
-    r = Renderer(net, vertex_can=can64().numpy(), pc2voxel_ind=synth_assign(300))
-    b = synth.batch_to(synth.make_batch(20, 20, 3, seed=0, all_rays=False, focal=62.5), device)
-    return cfg, net, r, b
-
-
 ALL_DEVICE = {"train_kernels": "device", "train_attention": "device", "train_vit_dense": "device", "train_maps": "latents",
               "target_prep": "device"}
 
@@ -463,36 +438,5 @@ def test_training_step_with_the_point_network_on_the_device_matches_the_referenc
     """tests/test_gpu_train_ops.py::test_training_step_on_the_device_kernels_matches_the_reference with cfg.train_point_net =
     "device": the same golden step of the real reference, the same bars, under both values of cfg.train_kernels and with all five
     other training switches on their device values (the batch carries its rays, so cfg.target_prep = "device" takes them from it)"""
-    g = np.load(os.path.join(GOLD, "g18_train_step.npz"))
-    cfg, net, r, b = _setup(gpu)
-    try:
-        cfg.train_point_net = "device"
-        for k, v in others.items():
-            setattr(cfg, k, v)
-        assert b["ray_o"].shape[1] == int(g["rays"])
-        ret = autograd_path.render(r, b)
-        for k, name in (("rgb_map", "rgb"), ("acc_map", "acc"), ("depth_map", "depth")):
-            d = float((ret[k][0].detach().cpu() - torch.from_numpy(g[name])).abs().max())
-            print(k, d)
-            assert d < 2e-5, (k, d)
-        target = torch.from_numpy(g["target"])[None].to(gpu)
-        loss = torch.mean((ret["rgb_map"] - target) ** 2) + 0.1 * ret["acc_map"].mean() + 0.01 * ret["depth_map"].mean()
-        assert abs(float(loss) - float(g["loss"])) < 1e-6
-        loss.backward()
-        params = dict(net.named_parameters())
-        keys = [k[5:] for k in g.files if k.startswith("grad:")]
-        assert len(keys) == 20
-        for k in keys:
-            ref = torch.from_numpy(g["grad:" + k])
-            got = params[k].grad
-            assert got is not None and got.shape == ref.shape, k
-            err = float((got.cpu() - ref).abs().max()) / float(ref.abs().max())
-            print(k, err)
-            assert err < 2e-3, (k, err)
-        missing = [k for k, p in params.items() if p.grad is None and not k.endswith(("cls_token", "mask_token"))
-                   and ".layer3." not in k and ".layer4." not in k and "PE" not in k]
-        assert not missing, missing
-    finally:
-        for k, v in SWITCHES.items():
-            setattr(cfg, k, v)
-        cfg.vit_depth, cfg.N_samples = 12, 64
+    with config.override(**STEP_CFG, train_point_net="device", **others):
+        check_step(golden(), *setup(gpu))

@@ -10,7 +10,7 @@ from types import SimpleNamespace
 import pytest
 import torch
 
-from transhuman_amd.config import _defaults, get_cfg
+from transhuman_amd.config import _defaults, get_cfg, override
 from transhuman_amd.networks import autograd_path, train_ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,23 +19,17 @@ NAMES = ("th_latent_gather_bwd_ordered", "th_latent_gather_bwd_ordered_ws")
 
 def test_switch_defaults_to_atomic_refuses_a_bad_value_and_a_cpu_batch():
     from transhuman_amd import hip
-    cfg = get_cfg()
-    assert _defaults().train_gather_bwd == "atomic" and cfg.train_gather_bwd == "atomic"
-    assert autograd_path._gather_bwd_mode("atomic") == "atomic" and autograd_path._gather_bwd_mode("ordered") == "ordered"
+    assert _defaults().train_gather_bwd == "atomic" and get_cfg().train_gather_bwd == "atomic"
+    assert all(autograd_path._switch("train_gather_bwd", v, True) == v for v in ("atomic", "ordered"))
     batch = {"ray_o": torch.zeros(1, 4, 3), "ray_d": torch.ones(1, 4, 3)}
-    try:
-        cfg.train_maps, cfg.train_gather_bwd = "latents", "ordered"
-        with pytest.raises(hip.HipError, match="MI355X"):
-            autograd_path.render(SimpleNamespace(net=None), batch)
-        cfg.train_gather_bwd = "sorted"
-        with pytest.raises(ValueError, match="train_gather_bwd"):
-            autograd_path.render(SimpleNamespace(net=None), batch)
-        cfg.train_maps = "full"                                    # the key is read with "latents" only
+    with override(train_maps="latents", train_gather_bwd="ordered"), pytest.raises(hip.HipError, match="MI355X"):
+        autograd_path.render(SimpleNamespace(net=None), batch)
+    with override(train_maps="latents", train_gather_bwd="sorted"), pytest.raises(ValueError, match="train_gather_bwd"):
+        autograd_path.render(SimpleNamespace(net=None), batch)
+    with override(train_maps="full", train_gather_bwd="sorted"):   # the key is read with "latents" only
         with pytest.raises(Exception) as e:
             autograd_path.render(SimpleNamespace(net=None), batch)
-        assert "train_gather_bwd" not in str(e.value)
-    finally:
-        cfg.train_maps, cfg.train_gather_bwd = "full", "atomic"
+    assert "train_gather_bwd" not in str(e.value)
 
 
 def test_function_still_refuses_host_tensors_with_nine_and_with_ten_arguments():

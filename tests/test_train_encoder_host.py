@@ -11,7 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from transhuman_amd.config import get_cfg
+from transhuman_amd.config import get_cfg, override
 from transhuman_amd.networks import autograd_path, train_ops
 
 TOL = 1e-12
@@ -37,20 +37,14 @@ def test_switch_defaults_to_torch():
 def test_device_refuses_a_cpu_batch_and_a_bad_value_is_an_error():
     from transhuman_amd import hip
     from transhuman_amd.networks.encoder import SpatialEncoder
-    cfg = get_cfg()
     batch = {"ray_o": torch.zeros(1, 4, 3), "ray_d": torch.ones(1, 4, 3)}
     renderer = SimpleNamespace(net=None)
-    try:
-        cfg.train_encoder = "device"
-        with pytest.raises(hip.HipError, match="MI355X"):
-            autograd_path.render(renderer, batch)
-        cfg.train_encoder = "hip"
-        with pytest.raises(ValueError, match="train_encoder"):
-            autograd_path.render(renderer, batch)
-    finally:
-        cfg.train_encoder = "torch"
+    with override(train_encoder="device"), pytest.raises(hip.HipError, match="MI355X"):
+        autograd_path.render(renderer, batch)
+    with override(train_encoder="hip"), pytest.raises(ValueError, match="train_encoder"):
+        autograd_path.render(renderer, batch)
     with pytest.raises(ValueError, match="cfg.train_encoder must be 'torch' or 'device', not 'cuda'"):
-        autograd_path._encoder_mode("cuda")
+        autograd_path._switch("train_encoder", "cuda", True)
     enc = SpatialEncoder().train()
     img = torch.zeros(1, 3, 16, 16)
     for call in (lambda: autograd_path.trunk_device(enc, img), lambda: autograd_path.encode(enc, img, encoder="device"),

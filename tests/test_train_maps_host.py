@@ -13,7 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from transhuman_amd.config import get_cfg
+from transhuman_amd.config import get_cfg, override
 from transhuman_amd.networks import autograd_path, train_ops
 from transhuman_amd.networks.encoder import SpatialEncoder
 
@@ -114,18 +114,12 @@ def test_every_non_zero_tap_lies_in_three_rows_and_three_columns():
 
 def test_switch_defaults_to_full_refuses_a_cpu_batch_and_a_bad_value():
     from transhuman_amd import hip
-    cfg = get_cfg()
-    assert cfg.train_maps == "full"
+    assert get_cfg().train_maps == "full"
     batch = {"ray_o": torch.zeros(1, 4, 3), "ray_d": torch.ones(1, 4, 3)}
-    try:
-        cfg.train_maps = "latents"
-        with pytest.raises(hip.HipError, match="MI355X"):
-            autograd_path.render(SimpleNamespace(net=None), batch)
-        cfg.train_maps = "half"
-        with pytest.raises(ValueError, match="train_maps"):
-            autograd_path.render(SimpleNamespace(net=None), batch)
-    finally:
-        cfg.train_maps = "full"
+    with override(train_maps="latents"), pytest.raises(hip.HipError, match="MI355X"):
+        autograd_path.render(SimpleNamespace(net=None), batch)
+    with override(train_maps="half"), pytest.raises(ValueError, match="train_maps"):
+        autograd_path.render(SimpleNamespace(net=None), batch)
 
 
 def test_function_refuses_host_tensors_and_batch_gradients():

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from transhuman_amd.config import get_cfg
+from transhuman_amd.config import get_cfg, override
 from transhuman_amd.networks import autograd_path, train_ops
 from transhuman_amd.networks.encoder import SpatialEncoder
 
@@ -92,16 +92,46 @@ def test_inputs_without_a_gradient_path_are_refused():
 def test_switch_defaults_to_torch_and_device_refuses_a_cpu_batch():
     from transhuman_amd import hip
     from transhuman_amd.config import _defaults
-    cfg = get_cfg()
-    assert _defaults().train_kernels == "torch" and cfg.train_kernels == "torch"
+    assert _defaults().train_kernels == "torch" and get_cfg().train_kernels == "torch"
     batch = {"ray_o": torch.zeros(1, 4, 3), "ray_d": torch.ones(1, 4, 3)}
     renderer = SimpleNamespace(net=None)
-    try:
-        cfg.train_kernels = "device"
-        with pytest.raises(hip.HipError, match="MI355X"):
-            autograd_path.render(renderer, batch)
-        cfg.train_kernels = "hip"
-        with pytest.raises(ValueError, match="train_kernels"):
-            autograd_path.render(renderer, batch)
-    finally:
-        cfg.train_kernels = "torch"
+    with override(train_kernels="device"), pytest.raises(hip.HipError, match="MI355X"):
+        autograd_path.render(renderer, batch)
+    with override(train_kernels="hip"), pytest.raises(ValueError, match="train_kernels"):
+        autograd_path.render(renderer, batch)
+
+
+# ---- all seven switches: the table, the one reader, and the override the tests set them with ---------------------------------
+def test_override_restores_a_changed_key_deletes_an_absent_one_also_after_an_exception():
+    cfg = get_cfg()
+    before = cfg.N_samples
+    assert before != 7 and not hasattr(cfg, "no_such_key")
+    with override(N_samples=7, no_such_key=1) as live:
+        assert live is cfg and cfg.N_samples == 7 and cfg.no_such_key == 1
+    assert cfg.N_samples == before and not hasattr(cfg, "no_such_key")
+    with pytest.raises(RuntimeError, match="inside"):
+        with override(N_samples=7, no_such_key=1):
+            cfg.N_samples = 9                                      # (what the block itself assigns is put back too)
+            raise RuntimeError("inside")
+    assert cfg.N_samples == before and not hasattr(cfg, "no_such_key")
+
+
+def test_defaults_are_the_first_values_of_the_table():
+    from transhuman_amd.config import TRAIN_SWITCHES, _defaults
+    assert list(TRAIN_SWITCHES) == ["train_kernels", "train_attention", "train_vit_dense", "train_maps", "train_gather_bwd",
+                                    "train_point_net", "train_encoder"]
+    for key, values in TRAIN_SWITCHES.items():
+        assert len(values) == 2 and getattr(_defaults(), key) == getattr(get_cfg(), key) == values[0], key
+
+
+def test_the_one_reader_of_every_switch():
+    from transhuman_amd import hip
+    from transhuman_amd.config import TRAIN_SWITCHES
+    for key, values in TRAIN_SWITCHES.items():
+        for v in values:
+            assert autograd_path._switch(key, v, True) == v
+        assert autograd_path._switch(key, values[0], False) == values[0]
+        with pytest.raises(ValueError, match=f"cfg.{key} must be '{values[0]}' or '{values[1]}', not 'hip'"):
+            autograd_path._switch(key, "hip", True)
+        with pytest.raises(hip.HipError, match=f"cfg.{key} = '{values[1]}' needs the tokens on an MI355X .* use '{values[0]}' for"):
+            autograd_path._switch(key, values[1], False, "tokens")

@@ -12,7 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from transhuman_amd.config import get_cfg
+from transhuman_amd.config import get_cfg, override
 from transhuman_amd.networks import autograd_path, train_ops
 from util import make_net
 
@@ -82,18 +82,12 @@ def test_switch_defaults_to_torch():
 
 def test_device_refuses_a_cpu_batch_and_a_bad_value_is_an_error():
     from transhuman_amd import hip
-    cfg = get_cfg()
     batch = {"ray_o": torch.zeros(1, 4, 3), "ray_d": torch.ones(1, 4, 3)}
     renderer = SimpleNamespace(net=None)
-    try:
-        cfg.train_point_net = "device"
-        with pytest.raises(hip.HipError, match="MI355X"):
-            autograd_path.render(renderer, batch)
-        cfg.train_point_net = "hip"
-        with pytest.raises(ValueError, match="train_point_net"):
-            autograd_path.render(renderer, batch)
-    finally:
-        cfg.train_point_net = "torch"
+    with override(train_point_net="device"), pytest.raises(hip.HipError, match="MI355X"):
+        autograd_path.render(renderer, batch)
+    with override(train_point_net="hip"), pytest.raises(ValueError, match="train_point_net"):
+        autograd_path.render(renderer, batch)
     w, b = torch.zeros(256, 256, requires_grad=True), torch.zeros(256, requires_grad=True)
     row = torch.zeros(2, 3, 256, requires_grad=True)
     kv = torch.zeros(2, 3, 384, requires_grad=True)
@@ -103,12 +97,8 @@ def test_device_refuses_a_cpu_batch_and_a_bad_value_is_an_error():
 
 
 def _net64():
-    cfg = get_cfg()
-    keep = cfg.vit_depth
-    try:
+    with override(vit_depth=2):                            # (make_net sets the key and leaves it set)
         return make_net(2).double()
-    finally:
-        cfg.vit_depth = keep
 
 
 def _grads(fn, net, h, f, vd, g):

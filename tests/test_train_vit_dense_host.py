@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from transhuman_amd.config import get_cfg
+from transhuman_amd.config import get_cfg, override
 from transhuman_amd.networks import autograd_path, train_ops
 from util import make_net
 
@@ -83,20 +83,14 @@ def test_switch_defaults_to_torch():
 
 def test_device_refuses_a_cpu_batch_and_a_bad_value_is_an_error():
     from transhuman_amd import hip
-    cfg = get_cfg()
     batch = {"ray_o": torch.zeros(1, 4, 3), "ray_d": torch.ones(1, 4, 3)}
     renderer = SimpleNamespace(net=None)
     vit = make_net(2).ViT
     x, pe = torch.zeros(1, 5, 192), torch.zeros(1, 5, 3)
-    try:
-        cfg.train_vit_dense = "device"
-        with pytest.raises(hip.HipError, match="MI355X"):
-            autograd_path.render(renderer, batch)
-        cfg.train_vit_dense = "hip"
-        with pytest.raises(ValueError, match="train_vit_dense"):
-            autograd_path.render(renderer, batch)
-    finally:
-        cfg.train_vit_dense = "torch"
+    with override(train_vit_dense="device"), pytest.raises(hip.HipError, match="MI355X"):
+        autograd_path.render(renderer, batch)
+    with override(train_vit_dense="hip"), pytest.raises(ValueError, match="train_vit_dense"):
+        autograd_path.render(renderer, batch)
     with pytest.raises(hip.HipError, match="MI355X"):
         autograd_path.vit_forward(vit, x, pe, dense="device")
     with pytest.raises(ValueError, match="train_vit_dense"):

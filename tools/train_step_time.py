@@ -59,7 +59,7 @@ def setup(dev):
     pick = torch.from_numpy(np.sort(np.random.RandomState(0).choice(n, RAYS, replace=n < RAYS)))
     for k in ("ray_o", "ray_d", "near", "far"):
         b[k] = b[k][:, pick].contiguous()
-    return cfg, net, r, synth.batch_to(b, dev)
+    return net, r, synth.batch_to(b, dev)
 
 
 def step(net, r, b, target):
@@ -72,9 +72,9 @@ def step(net, r, b, target):
     return ret
 
 
-def run_mode(mode, cfg, net, r, b, target, steps, warmup):
+def run_mode(net, r, b, target, steps, warmup):
+    """in whatever mode cfg is in"""
     import torch
-    cfg.train_kernels = mode
     for _ in range(warmup):
         step(net, r, b, target)
     torch.cuda.synchronize()
@@ -94,7 +94,7 @@ def run_mode(mode, cfg, net, r, b, target, steps, warmup):
 
 
 def run_optim(kind, net, r, b, target, steps, warmup):
-    """forward + backward + clip at 40 + optimiser step, in whatever mode cfg is left in; the weights are put back"""
+    """forward + backward + clip at 40 + optimiser step, in whatever mode cfg is in; the weights are put back"""
     import torch
     from transhuman_amd.train_optim import DeviceAdam
     saved = {k: v.detach().clone() for k, v in net.state_dict().items()}
@@ -171,13 +171,13 @@ def main():
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         res["k17_kernels"] = kernel_times(args.rocprof, n) if p.returncode == 0 else {"error": p.stderr[-400:]}
     import torch
+    from transhuman_amd.config import override
     dev = torch.device("cuda:0")
     res["device"] = torch.cuda.get_device_name(0)
-    cfg, net, r, b = setup(dev)
+    net, r, b = setup(dev)
     target = torch.rand((1, RAYS, 3), device=dev)
     seen = {}
-    try:
-        cfg.train_attention, cfg.train_vit_dense = args.attention, args.vit_dense
+    with override(train_attention=args.attention, train_vit_dense=args.vit_dense):
         sweep = []
         for maps in args.maps.split(","):
             for gather_bwd in (args.gather_bwd.split(",") if maps == "latents" else ["atomic"]):
@@ -186,12 +186,13 @@ def main():
                         for mode in args.modes.split(","):
                             key = (mode if maps == "full" else f"{mode}+{maps}") + ("" if gather_bwd == "atomic" else "+ordered") + \
                                 ("" if point_net == "torch" else "+pointnet") + ("" if encoder == "torch" else "+encoder")
-                            sweep.append((key, mode, maps, gather_bwd, point_net, encoder))
+                            sweep.append((key, dict(train_kernels=mode, train_maps=maps, train_gather_bwd=gather_bwd,
+                                                    train_point_net=point_net, train_encoder=encoder)))
         rounds = {}
         for rnd in range(max(args.rounds, 1)):
-            for key, mode, maps, gather_bwd, point_net, encoder in (sweep if rnd % 2 == 0 else sweep[::-1]):
-                cfg.train_maps, cfg.train_gather_bwd, cfg.train_point_net, cfg.train_encoder = maps, gather_bwd, point_net, encoder
-                res[key], outs, grads = run_mode(mode, cfg, net, r, b, target, args.steps, args.warmup)
+            for key, switches in (sweep if rnd % 2 == 0 else sweep[::-1]):
+                with override(**switches):
+                    res[key], outs, grads = run_mode(net, r, b, target, args.steps, args.warmup)
                 rounds.setdefault(key, []).append(res[key])
                 seen[key] = (outs, grads)
         if args.rounds > 1:
@@ -201,12 +202,9 @@ def main():
                             "step_ms_highest_round": max(med), "step_ms_min": min(x["step_ms_min"] for x in rr),
                             "rounds": len(rr), "steps": args.steps,
                             "peak_allocated_MiB": max(x["peak_allocated_MiB"] for x in rr)}
-        for kind in [k for k in args.optim.split(",") if k]:
-            res[f"step+optim:{kind}"] = run_optim(kind, net, r, b, target, args.steps, args.warmup)
-    finally:
-        cfg.train_kernels, cfg.train_maps, cfg.train_point_net, cfg.train_encoder = "torch", "full", "torch", "torch"
-        cfg.train_gather_bwd = "atomic"
-        cfg.train_attention, cfg.train_vit_dense = "torch", "torch"
+        with override(**switches):                                  # (the optimiser runs in the last mode run)
+            for kind in [k for k in args.optim.split(",") if k]:
+                res[f"step+optim:{kind}"] = run_optim(kind, net, r, b, target, args.steps, args.warmup)
     if "torch" in seen and "device" in seen:
         (o0, g0), (o1, g1) = seen["torch"], seen["device"]
         res["device_vs_torch"] = {

@@ -10,7 +10,20 @@ use a plain namespace carrying the same defaults
 (configs/train_or_eval.yaml:16-127).
 """
 import sys
+from contextlib import contextmanager
 from types import SimpleNamespace
+
+# the switches of the training entry (autograd_path.render reads them in this order): key -> its allowed values.  The first
+# value is the default in _defaults() below, and the one a CPU batch can run
+TRAIN_SWITCHES = {
+    "train_kernels": ("torch", "device"),
+    "train_attention": ("torch", "device"),
+    "train_vit_dense": ("torch", "device"),
+    "train_maps": ("full", "latents"),
+    "train_gather_bwd": ("atomic", "ordered"),
+    "train_point_net": ("torch", "device"),
+    "train_encoder": ("torch", "device"),
+}
 
 
 def _defaults():
@@ -135,3 +148,26 @@ def cfg_get(name, default=None):
     if hasattr(_STANDALONE, name):
         return getattr(_STANDALONE, name)
     return default
+
+
+_ABSENT = object()
+
+
+@contextmanager
+def override(**values):
+    """Set top-level keys of the live cfg for the length of a ``with`` block.  On exit, after an exception too, every key holds
+    exactly what it held before; a key that was absent (the reference's cfg has none of the train_* keys) is deleted."""
+    c = get_cfg()
+    before = {k: getattr(c, k, _ABSENT) for k in values}
+    try:
+        for k, v in values.items():
+            setattr(c, k, v)
+        yield c
+    finally:
+        for k, v in before.items():
+            if v is not _ABSENT:
+                setattr(c, k, v)
+            elif isinstance(c, dict):               # (a yacs node keeps its keys as dict items)
+                c.pop(k, None)
+            elif hasattr(c, k):
+                delattr(c, k)

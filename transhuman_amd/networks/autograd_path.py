@@ -40,6 +40,10 @@ operators in the forward, site by site without a graph -- latents, running stati
 mode's bit for bit --, and HIP backwards with fixed-order sums (``train_ops.ConvFn`` / ``BnActFn`` / ``MaxPoolFn``, DESIGN.md
 K23).  The upsamples, ``upsample_color`` and ``reduction_layer`` stay what ``cfg.train_maps`` makes them.
 
+The allowed values of these six and of ``cfg.train_gather_bwd`` (the form of the latent gather's adjoint) are one table,
+``config.TRAIN_SWITCHES``, and ``_switch`` is their one reader: a value outside the table is a ValueError, a value other than
+the first on CPU tensors a HipError.
+
 Pinned by ``oracle/gen_golden_train.py`` (the real reference imported in the survey container: outputs and parameter
 gradients of one training step's forward/backward on a synthetic patch -> ``tests/golden/g18_train_step.npz``) and
 ``tests/test_train_path.py``.  Every function cites the reference lines it follows.
@@ -49,7 +53,22 @@ import math
 import torch
 import torch.nn.functional as F
 
-from ..config import get_cfg
+from ..config import TRAIN_SWITCHES, get_cfg
+
+
+# ---- the switches ------------------------------------------------------------------------------------------------------
+def _switch(key, value, on_device, noun="batch"):
+    """The one reader of config.TRAIN_SWITCHES: ``value`` of cfg.<key> as a str, one of the key's allowed values; any but the
+    first runs HIP kernels, so it is refused unless the tensors (the ``noun`` of the message) are on the device."""
+    allowed = TRAIN_SWITCHES[key]
+    mode = str(value)
+    if mode not in allowed:
+        raise ValueError(f"cfg.{key} must be {allowed[0]!r} or {allowed[1]!r}, not {mode!r}")
+    if mode != allowed[0] and not on_device:
+        from .. import hip
+        raise hip.HipError(f"cfg.{key} = '{mode}' needs the {noun} on an MI355X (the HIP kernels have no CPU form); "
+                           f"use '{allowed[0]}' for a CPU batch")
+    return mode
 
 
 # ---- sampling ----------------------------------------------------------------------------------------------------------
@@ -75,13 +94,6 @@ def embed_view(ray_d, view_res):
 
 
 # ---- encoder, painting, grouping ----------------------------------------------------------------------------------------
-def _encoder_mode(value):
-    mode = str(value)
-    if mode not in ("torch", "device"):
-        raise ValueError(f"cfg.train_encoder must be 'torch' or 'device', not {mode!r}")
-    return mode
-
-
 def _trunk_sites_have_batch_statistics(enc):
     """every BatchNorm site of the trunk is a train-mode nn.BatchNorm2d with a momentum: what th_bn_act_bwd is the backward of
     (eval mode normalises with the running statistics; SyncBatchNorm, after the reference trainer's conversion, with the
@@ -95,9 +107,7 @@ def trunk_device(enc, images):
     (K23).  A trunk whose BatchNorm sites do not all use batch statistics runs under torch autograd as a whole."""
     from .. import hip
     from . import train_ops as T
-    if not images.is_cuda:
-        raise hip.HipError("cfg.train_encoder = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
-                           "use 'torch' for a CPU batch")
+    _switch("train_encoder", "device", images.is_cuda)
     if not _trunk_sites_have_batch_statistics(enc):
         return enc.trunk(images, fused_bn=False)
     m = enc.model
@@ -120,7 +130,9 @@ def trunk_device(enc, images):
 
 
 def _trunk(enc, images, encoder):
-    return trunk_device(enc, images) if _encoder_mode(encoder) == "device" else enc.trunk(images, fused_bn=False)
+    if _switch("train_encoder", encoder, images.is_cuda) == "device":
+        return trunk_device(enc, images)
+    return enc.trunk(images, fused_bn=False)
 
 
 def encode(enc, images, encoder="torch"):
@@ -133,25 +145,12 @@ def encode(enc, images, encoder="torch"):
     return enc.reduction_layer(pix), pix
 
 
-def _maps_mode(value):
-    mode = str(value)
-    if mode not in ("full", "latents"):
-        raise ValueError(f"cfg.train_maps must be 'full' or 'latents', not {mode!r}")
-    return mode
-
-
-def _gather_bwd_mode(value):
-    mode = str(value)
-    if mode not in ("atomic", "ordered"):
-        raise ValueError(f"cfg.train_gather_bwd must be 'atomic' or 'ordered', not {mode!r}")
-    return mode
-
-
 def latent_features(enc, images, cams, scale, encoder="torch", gather_bwd="atomic"):
     """cfg.train_maps = "latents": the trunk as in ``encode`` (stock modules; torch autograd, or ``trunk_device``), each latent
     channels-last once; returns ``gather(points [N,3]) -> [N,V,384]``, the rows ``sample_map(pix, ...)`` would give (K19);
     ``gather_bwd``: the form of its adjoint (cfg.train_gather_bwd)"""
     from . import train_ops
+    gather_bwd = _switch("train_gather_bwd", gather_bwd, True)         # (the key has no CPU refusal of its own)
     lat = [l.permute(0, 2, 3, 1).contiguous() for l in _trunk(enc, images, encoder)]
     lift = enc.upsample_color
     return lambda pts: train_ops.LatentGatherFn.apply(*lat, lift.weight, lift.bias, images, pts, cams, scale, gather_bwd)
@@ -200,24 +199,17 @@ def pooling_matrix(offsets, members, n_verts, device, dtype):
 
 
 # ---- TransHE -------------------------------------------------------------------------------------------------------------
-def _attention_mode(value):
-    mode = str(value)
-    if mode not in ("torch", "device"):
-        raise ValueError(f"cfg.train_attention must be 'torch' or 'device', not {mode!r}")
-    return mode
-
-
-def _dense_mode(value):
-    mode = str(value)
-    if mode not in ("torch", "device"):
-        raise ValueError(f"cfg.train_vit_dense must be 'torch' or 'device', not {mode!r}")
-    return mode
+def _torch_attention(qkv, heads, scale):
+    """softmax(q k^T scale) v of a block from its qkv rows [V,N,3C] as torch operators -> [V,N,C]"""
+    V, N, C3 = qkv.shape
+    qkv = qkv.reshape(V, N, 3, heads, C3 // 3 // heads).permute(2, 0, 3, 1, 4)
+    s = (qkv[0] @ qkv[1].transpose(-2, -1)) * scale
+    return (s.softmax(dim=-1) @ qkv[2]).transpose(1, 2).reshape(V, N, C3 // 3)
 
 
 def _vit_forward_device_dense(vit, x, attention):
     """the blocks of vit_forward with every dense layer, LayerNorm and GELU on the HIP Functions of train_ops"""
     from . import train_ops as T
-    V, N, C = x.shape
     h = vit.num_heads
     x = x.contiguous()
     for blk in vit.blocks:
@@ -226,9 +218,7 @@ def _vit_forward_device_dense(vit, x, attention):
         if attention == "device":
             y = T.AttentionFn.apply(qkv, h)
         else:
-            qkv = qkv.reshape(V, N, 3, h, C // h).permute(2, 0, 3, 1, 4)
-            s = (qkv[0] @ qkv[1].transpose(-2, -1)) * a.scale
-            y = (s.softmax(dim=-1) @ qkv[2]).transpose(1, 2).reshape(V, N, C).contiguous()
+            y = _torch_attention(qkv, h, a.scale).contiguous()
         x = x + T.LinearFn.apply(y, a.proj.weight, a.proj.bias)
         u = T.NormLinearFn.apply(x, blk.norm2.weight, blk.norm2.bias, m.fc1.weight, m.fc1.bias, blk.norm2.eps)
         x = x + T.GeluLinearFn.apply(u, m.fc2.weight, m.fc2.bias)
@@ -239,32 +229,21 @@ def vit_forward(vit, x, pe_xyz, attention="torch", dense="torch"):
     """VisionTransformer.forward (vision_transformer.py:257-307, :362-383), mask = None.  attention = "device": every block's
     softmax(q k^T / 8) v through train_ops.AttentionFn (HIP forward and backward, no N x N tensor) instead of torch operators.
     dense = "device": every dense layer, LayerNorm and GELU through the HIP Functions of train_ops (k_vit_dense_bwd.hip)."""
-    attention = _attention_mode(attention)
-    dense = _dense_mode(dense)
-    if dense == "device":
-        from .. import hip
-        if not x.is_cuda:
-            raise hip.HipError("cfg.train_vit_dense = 'device' needs the tokens on an MI355X (the HIP kernels have no CPU "
-                               "form); use 'torch' for a CPU batch")
-    if attention == "device":
-        from .. import hip
-        from . import train_ops
-        if not x.is_cuda:
-            raise hip.HipError("cfg.train_attention = 'device' needs the tokens on an MI355X (the HIP kernels have no CPU "
-                               "form); use 'torch' for a CPU batch")
+    attention = _switch("train_attention", attention, True)          # (both values are checked before either refusal)
+    dense = _switch("train_vit_dense", dense, x.is_cuda, "tokens")
+    _switch("train_attention", attention, x.is_cuda, "tokens")
     x = x + vit.get_PE(pe_xyz).to(x.dtype)
     if dense == "device":
         return _vit_forward_device_dense(vit, x, attention)
-    V, N, C = x.shape
+    if attention == "device":
+        from . import train_ops
     h = vit.num_heads
     for blk in vit.blocks:
         y = blk.norm1(x)
         if attention == "device":
             y = train_ops.AttentionFn.apply(blk.attn.qkv(y).contiguous(), h)
         else:
-            qkv = blk.attn.qkv(y).reshape(V, N, 3, h, C // h).permute(2, 0, 3, 1, 4)
-            a = (qkv[0] @ qkv[1].transpose(-2, -1)) * blk.attn.scale
-            y = (a.softmax(dim=-1) @ qkv[2]).transpose(1, 2).reshape(V, N, C)
+            y = _torch_attention(blk.attn.qkv(y), h, blk.attn.scale)
         x = x + blk.attn.proj(y)
         x = x + blk.mlp.fc2(F.gelu(blk.mlp.fc1(blk.norm2(x))))
     return vit.norm(x)
@@ -304,13 +283,6 @@ def point_network(net, h, f, viewdir):
     c = F.relu(_lin(net.view_fc, feat)) + _lin(net.rgb_res_1, f)
     rgb = _lin(net.rgb_fc, F.relu(_lin(net.fc_4, c.mean(dim=1))))
     return torch.cat([rgb, sigma], dim=1)
-
-
-def _point_net_mode(value):
-    mode = str(value)
-    if mode not in ("torch", "device"):
-        raise ValueError(f"cfg.train_point_net must be 'torch' or 'device', not {mode!r}")
-    return mode
 
 
 def _point_net_device_ops():
@@ -380,39 +352,16 @@ def render(renderer, batch, chunk=32768):
     net = renderer.net
     assert cfg.time_steps == 1
     ray_o, ray_d = batch["ray_o"][0], batch["ray_d"][0]
-    mode = str(getattr(cfg, "train_kernels", "torch"))
-    if mode not in ("torch", "device"):
-        raise ValueError(f"cfg.train_kernels must be 'torch' or 'device', not {mode!r}")
-    if mode == "device" and not ray_o.is_cuda:
-        from .. import hip
-        raise hip.HipError("cfg.train_kernels = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
-                           "use 'torch' for a CPU batch")
-    attention = _attention_mode(getattr(cfg, "train_attention", "torch"))
-    if attention == "device" and not ray_o.is_cuda:
-        from .. import hip
-        raise hip.HipError("cfg.train_attention = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
-                           "use 'torch' for a CPU batch")
-    dense = _dense_mode(getattr(cfg, "train_vit_dense", "torch"))
-    if dense == "device" and not ray_o.is_cuda:
-        from .. import hip
-        raise hip.HipError("cfg.train_vit_dense = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
-                           "use 'torch' for a CPU batch")
-    maps = _maps_mode(getattr(cfg, "train_maps", "full"))
-    gather_bwd = _gather_bwd_mode(getattr(cfg, "train_gather_bwd", "atomic")) if maps == "latents" else "atomic"
-    if maps == "latents" and not ray_o.is_cuda:
-        from .. import hip
-        raise hip.HipError("cfg.train_maps = 'latents' needs the batch on an MI355X (the HIP kernels have no CPU form); "
-                           "use 'full' for a CPU batch")
-    point_net = _point_net_mode(getattr(cfg, "train_point_net", "torch"))
-    if point_net == "device" and not ray_o.is_cuda:
-        from .. import hip
-        raise hip.HipError("cfg.train_point_net = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
-                           "use 'torch' for a CPU batch")
-    encoder = _encoder_mode(getattr(cfg, "train_encoder", "torch"))
-    if encoder == "device" and not ray_o.is_cuda:
-        from .. import hip
-        raise hip.HipError("cfg.train_encoder = 'device' needs the batch on an MI355X (the HIP kernels have no CPU form); "
-                           "use 'torch' for a CPU batch")
+
+    def read(key, on_device=ray_o.is_cuda):
+        return _switch(key, getattr(cfg, key, TRAIN_SWITCHES[key][0]), on_device)
+
+    mode, attention, dense = read("train_kernels"), read("train_attention"), read("train_vit_dense")
+    # train_gather_bwd: read with "latents" only, no CPU refusal of its own, its value checked before train_maps' refusal
+    maps = read("train_maps", True)
+    gather_bwd = read("train_gather_bwd", True) if maps == "latents" else "atomic"
+    _switch("train_maps", maps, ray_o.is_cuda)
+    point_net, encoder = read("train_point_net"), read("train_encoder")
     near, far = batch["near"][0], batch["far"][0]
     dev = ray_o.device
     S = int(cfg.N_samples)
@@ -472,15 +421,15 @@ def render(renderer, batch, chunk=32768):
             noise = torch.randn(raw[..., 3].shape).to(raw) * noise_std
             raw = torch.cat([raw[..., :3], (raw[..., 3] + noise)[..., None]], -1)
         rgb, acc, depth = train_ops.CompositeFn.apply(raw.contiguous(), z, ray_d, bool(cfg.white_bkgd))
-        return {"rgb_map": rgb[None], "acc_map": acc[None], "depth_map": depth[None]}
-    for s0 in range(0, xyz.shape[0], chunk):                       # batchify_rays :607-656 without a mask
-        x = xyz[s0:s0 + chunk]
-        if maps == "latents":
-            f = f_lat[s0:s0 + chunk]
-        else:
-            f = sample_map(pix, project(x, R_in, T_in, K_in), net.encoder, image_shape).permute(2, 0, 1)
-        h = human_representation(net, pts_s[s0:s0 + chunk], centres, rot, tokens, int(cfg.KNN), float(cfg.KNN_DIST_ALPHA))
-        raws.append((point_network_device if point_net == "device" else point_network)(net, h, f, viewdir[s0:s0 + chunk]))
-    raw = torch.cat(raws, 0).view(-1, S, 4)
-    rgb, acc, depth = composite(raw, z, ray_d, noise_std, bool(cfg.white_bkgd))
+    else:
+        for s0 in range(0, xyz.shape[0], chunk):                   # batchify_rays :607-656 without a mask
+            x = xyz[s0:s0 + chunk]
+            if maps == "latents":
+                f = f_lat[s0:s0 + chunk]
+            else:
+                f = sample_map(pix, project(x, R_in, T_in, K_in), net.encoder, image_shape).permute(2, 0, 1)
+            h = human_representation(net, pts_s[s0:s0 + chunk], centres, rot, tokens, int(cfg.KNN), float(cfg.KNN_DIST_ALPHA))
+            raws.append((point_network_device if point_net == "device" else point_network)(net, h, f, viewdir[s0:s0 + chunk]))
+        raw = torch.cat(raws, 0).view(-1, S, 4)
+        rgb, acc, depth = composite(raw, z, ray_d, noise_std, bool(cfg.white_bkgd))
     return {"rgb_map": rgb[None], "acc_map": acc[None], "depth_map": depth[None]}
