@@ -999,6 +999,34 @@ void th_adam_plan_destroy(th_adam_plan_t* plan);                         /* drai
 int th_adam_step(th_ctx* ctx, th_adam_plan_t* plan, const th_adam_tensor* scalars, int n_tensors, float clip, int flags,
                  unsigned long long* nonfinite_out /* or NULL */, th_stream stream);
 
+/* ---- the gradient exchange of data-parallel training: every planned tensor into / out of ONE flat buffer (additions, ABI 12) ---- */
+/* What DistributedDataParallel does with buckets and a copy per tensor, as one launch over the chunk table of a th_adam_plan_t
+ * (one workgroup per chunk, 128-bit accesses where the flat buffer and the tensor are 16-byte aligned, 32-bit ones for tails and
+ * unaligned tensors; no atomics, no LDS; two calls write identical bytes).  transhuman_amd/train_dist.py, DESIGN.md 4.
+ *
+ * The layout rule (th_adam_flat_layout, a pure host call): slots follow plan order and exist only for tensors whose byte in `live`
+ * is non-zero (live NULL: every tensor); each slot starts at a multiple of 4 elements; the return value, flat_elems, is the end of
+ * the last slot rounded up to 4 (0: no slot).  offsets_out[i] (optional) is the slot's first element, -1 without a slot.
+ * -1 for a bad argument (n_tensors < 1, a count < 1).
+ *
+ * th_adam_pack: flat[offsets[i] + e] = grads[i][e] / (float)world for every tensor with a slot -- one correctly rounded fp32
+ * division (subnormals kept, NaN and +-inf pass through); world == 1 copies the bits.  grads[i] NULL writes zeros (this rank has no
+ * gradient for a tensor another rank has).  The padding behind a slot is written as zeros as well, so EVERY element of
+ * flat[0 : flat_elems) is written by every call.  A tensor without a slot (offsets[i] < 0) is not touched.  grads[i] may BE
+ * flat + offsets[i] (a gradient that already lives in its slot); any other overlap of a gradient with the flat buffer is undefined.
+ * th_adam_unpack: dst[i][e] = flat[offsets[i] + e], bit for bit, for every tensor with a slot.
+ *
+ * `offsets` / `flat_elems` must be what th_adam_flat_layout gives for the plan's counts (checked on the host, so no slot can reach
+ * past flat_elems), and flat[0 : flat_elems) must lie inside one device allocation (asked of the runtime
+ * whenever a call names another buffer or length than the plan's last call; a repeated call costs no query).  The per-call pointers
+ * and offsets travel through the plan's ring of pinned staging buffers like th_adam_step's table: one copy and one launch on
+ * `stream`, no allocation, no synchronisation beyond the ring's own. */
+long long th_adam_flat_layout(int n_tensors, const long long* counts, const uint8_t* live /* or NULL */, long long* offsets_out /* or NULL */);
+int th_adam_pack(th_ctx* ctx, th_adam_plan_t* plan, const void* const* grads, const long long* offsets, int n_tensors, int world,
+                 float* flat, long long flat_elems, th_stream stream);
+int th_adam_unpack(th_ctx* ctx, th_adam_plan_t* plan, void* const* dst, const long long* offsets, int n_tensors, const float* flat,
+                   long long flat_elems, th_stream stream);
+
 /* ---- K23: the backward of the encoder trunk in training (additions, ABI 12) ---- */
 /* The sites of SpatialEncoder.trunk (encoder.py:114-126: conv1 / bn1 / relu, the 3x3 / 2 max pool, layer1, layer2), backward only: the
  * forward stays the stock torch modules.  All tensors NCHW fp32, contiguous; H and W are the INPUT size of the convolution or the

@@ -20,9 +20,17 @@
 // Purely elementwise: no float atomics, no LDS, no scratch, bit-identical from run to run.  The only atomic is the integer
 // count of non-finite gradient elements (TH_ADAM_COUNT_NONFINITE), one per wave that saw any.
 // Bound: 16 B read + 12 B written per element (+ 4 B with TH_ADAM_ZERO_GRAD).
+//
+// The gradient exchange of data-parallel training (transhuman_amd/train_dist.py) walks the same chunk table:
+//   adam_pack_kernel     flat[off_i + e] = g_i[e] / world for every tensor with a slot (zeros for a NULL g_i and for the
+//                        padding behind a slot), so that ONE all-reduce of `flat` averages every gradient
+//   adam_unpack_kernel   dst_i[e] = flat[off_i + e]
+// with a per-call table of (pointer, slot offset) per tensor that travels through the same ring of staging buffers into a
+// region of its own behind the chunk table.  The slots follow ad_flat_layout, the one statement of the layout rule in C.
 #include "th_internal.h"
 
 #include <string.h>
+#include <vector>
 
 #define AD_THREADS 256
 #define AD_VEC (TH_ADAM_CHUNK / 4 / AD_THREADS)      // float4 groups per lane of a full chunk
@@ -41,9 +49,19 @@ struct AdHeader {
     unsigned long long pad[31];
 };
 
+// per-call entry of the pack / unpack kernels: the tensor's own memory and the offset of its slot (< 0: no slot)
+struct AdSlot {
+    void* ptr;
+    long long off;
+};
+static_assert(sizeof(AdSlot) <= sizeof(th_adam_tensor), "a slot table fits a staging buffer of the ring");
+
 static inline size_t ad_tensor_off() { return sizeof(AdHeader); }
 static inline size_t ad_chunk_off(int n_tensors) { return ad_tensor_off() + th_align((size_t)n_tensors * sizeof(th_adam_tensor)); }
 static inline long long ad_max_chunks(int n_tensors, long long total) { return total / TH_ADAM_CHUNK + n_tensors; }
+static inline size_t ad_slot_off(int n_tensors, long long total) {
+    return ad_chunk_off(n_tensors) + th_align((size_t)ad_max_chunks(n_tensors, total) * sizeof(AdChunk));
+}
 
 struct th_adam_plan_t {
     static constexpr int kRing = 16;
@@ -56,6 +74,11 @@ struct th_adam_plan_t {
     bool half_pending[2] = {false, false};
     hipStream_t half_stream[2] = {nullptr, nullptr};
     unsigned long long gen = 0;
+    std::vector<long long> counts;    // elements per tensor (the layout rule is checked against them)
+    size_t slot_table_off = 0;        // the AdSlot table of pack / unpack inside `table`
+    const void* checked_flat = nullptr;   // the flat buffer the runtime was last asked about (pack / unpack ask when it changes)
+    long long checked_elems = -1;
+    std::vector<AdSlot> slot_host;    // ... and where a call assembles it (sized once: a call allocates nothing)
 };
 
 struct AdScalars {
@@ -160,7 +183,7 @@ size_t th_adam_table_bytes(int n_tensors, long long total_elems) {
     if (n_tensors < 1 || total_elems < 1) return 0;
     const long long nc = ad_max_chunks(n_tensors, total_elems);
     if (nc > 0x7fffffffLL) return 0;
-    return ad_chunk_off(n_tensors) + th_align((size_t)nc * sizeof(AdChunk));
+    return ad_slot_off(n_tensors, total_elems) + th_align((size_t)n_tensors * sizeof(AdSlot));
 }
 
 static int ad_device_pointer(th_ctx* c, const void* ptr, const char* what, int i) {
@@ -210,6 +233,9 @@ int th_adam_plan(th_ctx* c, int n_tensors, const long long* counts, const void* 
     pl->table = (char*)table;
     pl->n_tensors = n_tensors;
     pl->slot_bytes = th_align((size_t)n_tensors * sizeof(th_adam_tensor));
+    pl->counts.assign(counts, counts + n_tensors);
+    pl->slot_table_off = ad_slot_off(n_tensors, total);
+    pl->slot_host.resize((size_t)n_tensors);
     auto fail = [&](int rc) { th_adam_plan_destroy(pl); return rc; };
     long long nc = 0;
     for (int i = 0; i < n_tensors; ++i) nc += (counts[i] + TH_ADAM_CHUNK - 1) / TH_ADAM_CHUNK;
@@ -246,12 +272,44 @@ int th_adam_plan(th_ctx* c, int n_tensors, const long long* counts, const void* 
     return 0;
 }
 
+// Copies `bytes` of a per-call table from host memory (free for reuse on return) to `dst` on the device through the next
+// staging buffer of the ring.  That buffer's previous copy was queued kRing calls ago; the event of its half of the ring was
+// recorded behind the LAST copy of that half, so one wait at the half's first buffer covers all of them.  *last_of_half is the
+// half whose event the caller records behind its kernel (ad_stage_done), or -1.
+static int ad_stage(th_ctx* c, th_adam_plan_t* pl, const void* src, size_t bytes, void* dst, hipStream_t s, int* last_of_half) {
+    const int slot = (int)(pl->gen % th_adam_plan_t::kRing), half = slot / (th_adam_plan_t::kRing / 2);
+    const bool first = slot % (th_adam_plan_t::kRing / 2) == 0, last = (slot + 1) % (th_adam_plan_t::kRing / 2) == 0;
+    if (first && pl->half_pending[half]) {
+        ThWaitClock wc(c);
+        TH_HIP(hipEventSynchronize(pl->half_ev[half]));
+        pl->half_pending[half] = false;
+    }
+    // (a caller that changes streams inside a half: the event below would only cover the new stream's copies)
+    if (!first && pl->half_stream[half] != s) TH_HIP(hipStreamSynchronize(pl->half_stream[half]));
+    pl->half_stream[half] = s;
+    char* stage = pl->pinned + (size_t)slot * pl->slot_bytes;
+    memcpy(stage, src, bytes);
+    ++pl->gen;
+    TH_HIP(hipMemcpyAsync(dst, stage, bytes, hipMemcpyHostToDevice, s));
+    *last_of_half = last ? half : -1;
+    return 0;
+}
+
+static int ad_stage_done(th_adam_plan_t* pl, int last_of_half, hipStream_t s) {
+    if (last_of_half >= 0) {
+        TH_HIP(hipEventRecord(pl->half_ev[last_of_half], s));
+        pl->half_pending[last_of_half] = true;
+    }
+    return 0;
+}
+
 int th_adam_step(th_ctx* c, th_adam_plan_t* pl, const th_adam_tensor* scalars, int n_tensors, float clip, int flags,
                  unsigned long long* nonfinite_out, th_stream stream) {
     TH_REQUIRE(c && pl && pl->ctx == c, "the plan belongs to another context");
     TH_REQUIRE((flags & ~(TH_ADAM_CLIP | TH_ADAM_ZERO_GRAD | TH_ADAM_COUNT_NONFINITE | TH_ADAM_CHECK_POINTERS)) == 0, "unknown flag");
     hipStream_t s = (hipStream_t)stream;
     if (n_tensors != 0) {
+        int last_of_half = -1;
         TH_REQUIRE(scalars && n_tensors == pl->n_tensors,
                    "the plan holds " + std::to_string(pl->n_tensors) + " tensors, the step names " + std::to_string(n_tensors));
         TH_REQUIRE(!(flags & TH_ADAM_CLIP) || clip >= 0.f, "the clip value must be >= 0 (and not NaN)");
@@ -268,32 +326,13 @@ int th_adam_step(th_ctx* c, th_adam_plan_t* pl, const th_adam_tensor* scalars, i
                 TH_TRY(ad_device_pointer(c, t.v, "exp_avg_sq", i));
             }
         }
-        // The staging slot of this step.  Its previous copy was queued kRing steps ago; the event of its half of the ring was
-        // recorded behind the LAST copy of that half, so one wait at the half's first slot covers all of them.
-        const int slot = (int)(pl->gen % th_adam_plan_t::kRing), half = slot / (th_adam_plan_t::kRing / 2);
-        const bool first = slot % (th_adam_plan_t::kRing / 2) == 0, last = (slot + 1) % (th_adam_plan_t::kRing / 2) == 0;
-        if (first && pl->half_pending[half]) {
-            ThWaitClock wc(c);
-            TH_HIP(hipEventSynchronize(pl->half_ev[half]));
-            pl->half_pending[half] = false;
-        }
-        // (a caller that changes streams inside a half: the event below would only cover the new stream's copies)
-        if (!first && pl->half_stream[half] != s) TH_HIP(hipStreamSynchronize(pl->half_stream[half]));
-        pl->half_stream[half] = s;
-        char* stage = pl->pinned + (size_t)slot * pl->slot_bytes;
-        const size_t bytes = (size_t)n_tensors * sizeof(th_adam_tensor);
-        memcpy(stage, scalars, bytes);
-        ++pl->gen;
-        TH_HIP(hipMemcpyAsync(pl->table + ad_tensor_off(), stage, bytes, hipMemcpyHostToDevice, s));
+        TH_TRY(ad_stage(c, pl, scalars, (size_t)n_tensors * sizeof(th_adam_tensor), pl->table + ad_tensor_off(), s, &last_of_half));
         hipLaunchKernelGGL(adam_step_kernel, dim3(pl->n_chunks), dim3(AD_THREADS), 0, s,
                            (const th_adam_tensor*)(pl->table + ad_tensor_off()),
                            (const AdChunk*)(pl->table + ad_chunk_off(pl->n_tensors)), clip, flags,
                            (unsigned long long*)pl->table);
         TH_LAUNCH_CHECK();
-        if (last) {
-            TH_HIP(hipEventRecord(pl->half_ev[half], s));
-            pl->half_pending[half] = true;
-        }
+        TH_TRY(ad_stage_done(pl, last_of_half, s));
     }
     if (nonfinite_out) {
         unsigned long long* word = (unsigned long long*)(pl->pinned + th_adam_plan_t::kRing * pl->slot_bytes);
@@ -303,4 +342,134 @@ int th_adam_step(th_ctx* c, th_adam_plan_t* pl, const th_adam_tensor* scalars, i
         *nonfinite_out = *word;
     }
     return 0;
+}
+
+// ---- the gradient exchange: every planned tensor into / out of one flat buffer ----
+// The layout rule (train_dist.flat_layout restates it): slots in plan order, only for tensors whose byte in `live` is set (NULL:
+// all), each starting at a multiple of 4 elements; the buffer ends at the last slot's end rounded up to 4.
+long long ad_flat_layout(int n_tensors, const long long* counts, const uint8_t* live, long long* offsets_out) {
+    long long end = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        const bool has = !live || live[i];
+        if (offsets_out) offsets_out[i] = has ? end : -1;
+        if (has) end = (end + counts[i] + 3) & ~3LL;
+    }
+    return end;
+}
+
+// One workgroup per chunk of the plan.  src may BE dst (a gradient that already lives in its slot): every element is read and
+// then written by the same lane, nothing else is read.  The lanes behind a tensor's last element write the slot's padding; a
+// chunk that is not its tensor's last ends on a multiple of TH_ADAM_CHUNK and has none.
+__global__ __launch_bounds__(AD_THREADS) void adam_pack_kernel(const AdSlot* __restrict__ slots, const AdChunk* __restrict__ chunks,
+                                                               float* flat_, float world, int copy) {
+    const AdChunk ch = chunks[blockIdx.x];
+    const AdSlot sl = slots[ch.tensor];
+    if (sl.off < 0) return;                                                       // no slot: not touched
+    AdGlobalF* dst = (AdGlobalF*)(uintptr_t)flat_ + sl.off + ch.offset;
+    const AdGlobalF* src = sl.ptr ? (const AdGlobalF*)(uintptr_t)sl.ptr + ch.offset : nullptr;
+    const int n = ch.count, tid = threadIdx.x;
+    const bool aligned = ((((uintptr_t)flat_) | ((uintptr_t)sl.ptr)) & 15) == 0;  // (slot and chunk offsets are multiples of 4)
+    int done = 0;
+    if (aligned) {
+        AdGlobalF4* d4 = (AdGlobalF4*)dst;
+        const AdGlobalF4* s4 = (const AdGlobalF4*)src;
+        const AdF4 z4 = {0.f, 0.f, 0.f, 0.f};
+        if (n == TH_ADAM_CHUNK && src) {
+            AdF4 G[AD_VEC];
+#pragma unroll
+            for (int r = 0; r < AD_VEC; ++r) G[r] = s4[r * AD_THREADS + tid];    // every load of the chunk in flight at once
+#pragma unroll
+            for (int r = 0; r < AD_VEC; ++r) {
+                if (!copy) G[r] = G[r] / world;                                  // (correctly rounded, element by element)
+                d4[r * AD_THREADS + tid] = G[r];
+            }
+            done = n;
+        } else {
+            const int n4 = n >> 2;
+            for (int i = tid; i < n4; i += AD_THREADS) {
+                AdF4 G = src ? s4[i] : z4;
+                if (!copy) G = G / world;
+                d4[i] = G;
+            }
+            done = n4 << 2;
+        }
+    }
+    for (int i = done + tid; i < n; i += AD_THREADS) {                           // tail, or a tensor off the 16-byte grid
+        float G = src ? src[i] : 0.f;
+        if (!copy) G = G / world;
+        dst[i] = G;
+    }
+    const int padded = (n + 3) & ~3;
+    if (tid < padded - n) dst[n + tid] = 0.f;
+}
+
+__global__ __launch_bounds__(AD_THREADS) void adam_unpack_kernel(const AdSlot* __restrict__ slots, const AdChunk* __restrict__ chunks,
+                                                                 const float* __restrict__ flat_) {
+    const AdChunk ch = chunks[blockIdx.x];
+    const AdSlot sl = slots[ch.tensor];
+    if (sl.off < 0 || sl.ptr == nullptr) return;
+    const AdGlobalF* __restrict__ src = (const AdGlobalF*)(uintptr_t)flat_ + sl.off + ch.offset;
+    AdGlobalF* __restrict__ dst = (AdGlobalF*)(uintptr_t)sl.ptr + ch.offset;
+    const int n = ch.count, tid = threadIdx.x;
+    const bool aligned = ((((uintptr_t)flat_) | ((uintptr_t)sl.ptr)) & 15) == 0;
+    int done = 0;
+    if (aligned) {
+        const AdGlobalF4* s4 = (const AdGlobalF4*)src;
+        AdGlobalF4* d4 = (AdGlobalF4*)dst;
+        const int n4 = n >> 2;
+        for (int i = tid; i < n4; i += AD_THREADS) d4[i] = s4[i];
+        done = n4 << 2;
+    }
+    for (int i = done + tid; i < n; i += AD_THREADS) dst[i] = src[i];
+}
+
+// the checks and the launch shared by th_adam_pack / th_adam_unpack (th_api.hip); ptrs[i] NULL: zeros (pack only)
+int th_adam_flat_launch(th_ctx* c, th_adam_plan_t* pl, int unpack, const void* const* ptrs, const long long* offsets, int n_tensors,
+                        int world, float* flat, long long flat_elems, hipStream_t s) {
+    TH_REQUIRE(c && pl && pl->ctx == c, "the plan belongs to another context");
+    TH_REQUIRE(ptrs && offsets && flat, "null argument");
+    TH_REQUIRE(n_tensors == pl->n_tensors,
+               "the plan holds " + std::to_string(pl->n_tensors) + " tensors, the call names " + std::to_string(n_tensors));
+    TH_REQUIRE(world >= 1 && world <= (1 << 20), "world is " + std::to_string(world) + ": 1 .. 2^20");
+    TH_REQUIRE(((uintptr_t)flat & 3) == 0, "the flat buffer is not 4-byte aligned");
+    // the offsets must BE the layout rule's: then every slot lies inside [0, flat_elems) and the slots with their padding tile it
+    long long end = 0;
+    std::vector<AdSlot>& slots = pl->slot_host;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (offsets[i] >= 0) {
+            TH_REQUIRE(offsets[i] == end, "the slot of tensor " + std::to_string(i) + " starts at " + std::to_string(offsets[i]) +
+                                              ", the layout rule puts it at " + std::to_string(end));
+            end = (end + pl->counts[i] + 3) & ~3LL;
+            TH_REQUIRE(!unpack || ptrs[i], "tensor " + std::to_string(i) + " has a slot and no destination");
+            TH_REQUIRE(((uintptr_t)ptrs[i] & 3) == 0, "tensor " + std::to_string(i) + " is not 4-byte aligned");
+        }
+        slots[i].ptr = offsets[i] >= 0 ? const_cast<void*>(ptrs[i]) : nullptr;
+        slots[i].off = offsets[i] >= 0 ? offsets[i] : -1;
+    }
+    TH_REQUIRE(end == flat_elems, "flat_elems is " + std::to_string(flat_elems) + ", the layout ends at " + std::to_string(end));
+    if (end == 0) return 0;
+    TH_HIP(hipSetDevice(c->device));
+    if (pl->checked_flat != (const void*)flat || pl->checked_elems != flat_elems) {   // asked of the runtime when the buffer is new
+        TH_TRY(ad_device_pointer(c, flat, "the flat buffer", -1));
+        hipDeviceptr_t base = nullptr;                                           // (the whole buffer, not just its first byte)
+        size_t size = 0;
+        const hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)flat);
+        if (e != hipSuccess) (void)hipGetLastError();
+        TH_REQUIRE(e == hipSuccess && (const char*)flat + (size_t)flat_elems * 4 <= (const char*)base + size,
+                   "the flat buffer's allocation holds fewer than flat_elems elements");
+        pl->checked_flat = flat;
+        pl->checked_elems = flat_elems;
+    }
+    int last_of_half = -1;
+    AdSlot* dev_slots = (AdSlot*)(pl->table + pl->slot_table_off);
+    TH_TRY(ad_stage(c, pl, slots.data(), (size_t)n_tensors * sizeof(AdSlot), dev_slots, s, &last_of_half));
+    const AdChunk* chunks = (const AdChunk*)(pl->table + ad_chunk_off(pl->n_tensors));
+    if (unpack)
+        hipLaunchKernelGGL(adam_unpack_kernel, dim3(pl->n_chunks), dim3(AD_THREADS), 0, s, (const AdSlot*)dev_slots, chunks,
+                           (const float*)flat);
+    else
+        hipLaunchKernelGGL(adam_pack_kernel, dim3(pl->n_chunks), dim3(AD_THREADS), 0, s, (const AdSlot*)dev_slots, chunks, flat,
+                           (float)world, world == 1 ? 1 : 0);
+    TH_LAUNCH_CHECK();
+    return ad_stage_done(pl, last_of_half, s);
 }

@@ -1779,6 +1779,27 @@ int th_conv2d_wgrad(th_ctx* c, const float* x, const float* g_y, int N, int cin,
     return th_conv2d_wgrad_launch(x, g_y, N, cin, cout, ks, stride, H, W, g_w, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- the gradient exchange's flat buffer (k_optim.hip) ----
+long long th_adam_flat_layout(int n_tensors, const long long* counts, const uint8_t* live, long long* offsets_out) {
+    if (n_tensors < 1 || n_tensors > (1 << 20) || !counts) return -1;
+    for (int i = 0; i < n_tensors; ++i)
+        if (counts[i] < 1 || counts[i] > (1LL << 40)) return -1;
+    return ad_flat_layout(n_tensors, counts, live, offsets_out);
+}
+
+int th_adam_pack(th_ctx* c, th_adam_plan_t* plan, const void* const* grads, const long long* offsets, int n_tensors, int world,
+                 float* flat, long long flat_elems, th_stream stream) {
+    TH_REQUIRE(c && plan && grads && offsets && flat, "null argument");
+    return th_adam_flat_launch(c, plan, 0, grads, offsets, n_tensors, world, flat, flat_elems, (hipStream_t)stream);
+}
+
+int th_adam_unpack(th_ctx* c, th_adam_plan_t* plan, void* const* dst, const long long* offsets, int n_tensors, const float* flat,
+                   long long flat_elems, th_stream stream) {
+    TH_REQUIRE(c && plan && dst && offsets && flat, "null argument");
+    return th_adam_flat_launch(c, plan, 1, (const void* const*)dst, offsets, n_tensors, 1, const_cast<float*>(flat), flat_elems,
+                               (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 static ThProf* prof_of(th_ctx* c) {

@@ -652,3 +652,8 @@ int th_patch_rays_launch(const float* ray_o, const float* ray_d, const float* ne
                          size_t ws_bytes, hipStream_t s);
 int th_segmean_masked_launch(const float* rows, int V, int width, const uint8_t* viz, int nv, const int32_t* off,
                              const int32_t* mem, int nc, float* out, hipStream_t s);
+// k_optim.hip: the gradient exchange's flat buffer over a th_adam_plan_t -- the layout rule, and the checks + launch behind
+// th_adam_pack (unpack = 0; ptrs[i] NULL: zeros) and th_adam_unpack (unpack = 1)
+long long ad_flat_layout(int n_tensors, const long long* counts, const uint8_t* live, long long* offsets_out);
+int th_adam_flat_launch(th_ctx* c, th_adam_plan_t* pl, int unpack, const void* const* ptrs, const long long* offsets, int n_tensors,
+                        int world, float* flat, long long flat_elems, hipStream_t s);

@@ -1037,6 +1037,22 @@ def adam_chunk_elems():
     return int(load_library().th_adam_chunk_elems())
 
 
+def adam_flat_layout(counts, live=None):
+    """th_adam_flat_layout (a pure host call) -> (offsets, flat_elems): where each tensor's slot starts in the flat buffer of the
+    gradient exchange (-1: no slot) and the buffer's length; ``live``: one truth value per tensor, None for all"""
+    import numpy as np
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    offsets = np.empty(len(counts), dtype=np.int64)
+    lv = None if live is None else np.ascontiguousarray(np.asarray(live) != 0, dtype=np.uint8)
+    if lv is not None and lv.shape != counts.shape:
+        raise HipError("adam_flat_layout: one entry of `live` per tensor")
+    end = int(load_library().th_adam_flat_layout(len(counts), counts.ctypes.data, None if lv is None else lv.ctypes.data,
+                                                 offsets.ctypes.data))
+    if end < 0:
+        raise HipError("adam_flat_layout: sizes out of range")
+    return offsets, end
+
+
 def adam_check_tensor(t, what):
     """the refusals of the optimiser step that a raw pointer cannot show: HipError, nothing is converted silently"""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
@@ -1065,6 +1081,7 @@ class AdamPlan:
         self.device = params[0].device
         self.n = len(params)
         counts = np.array([p.numel() for p in params], dtype=np.int64)
+        self.counts = [int(n) for n in counts]
         ptrs = np.array([p.data_ptr() for p in params], dtype=np.uint64)
         nbytes = int(lib.th_adam_table_bytes(self.n, int(counts.sum())))
         if nbytes == 0:
@@ -1092,6 +1109,47 @@ class AdamPlan:
             with torch.cuda.device(self.device):
                 _check(_lib.th_adam_step(ctx(self.device), self._h, table.ctypes.data, self.n, clip, flags, None, _stream()))
         self.steps += 1
+
+    def _flat_args(self, tensors, offsets, flat, flat_elems, what):
+        import numpy as np
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if len(tensors) != self.n or offsets.shape != (self.n,):
+            raise HipError(f"{what}: the plan holds {self.n} tensors")
+        adam_check_tensor(flat, "the flat buffer")
+        if flat.device != self.device or flat.numel() < flat_elems:
+            raise HipError(f"{what}: the flat buffer holds {flat.numel()} elements on {flat.device}, not {flat_elems} on {self.device}")
+        if isinstance(tensors, np.ndarray):                              # addresses the caller has checked before
+            assert tensors.dtype == np.uint64 and tensors.flags.c_contiguous
+            return tensors, offsets
+        ptrs = np.zeros(self.n, dtype=np.uint64)
+        for i, t in enumerate(tensors):
+            if t is None or offsets[i] < 0:
+                continue
+            adam_check_tensor(t, f"tensor {i}")
+            if t.numel() != self.counts[i] or t.device != self.device:
+                raise HipError(f"{what}: tensor {i} has {t.numel()} elements on {t.device}, the plan {self.counts[i]} on {self.device}")
+            ptrs[i] = t.data_ptr()
+        return ptrs, offsets
+
+    def _flat_call(self, fn, *args):
+        if torch._C._cuda_getDevice() == self.device.index:
+            _check(fn(ctx(self.device), self._h, *args, _stream()))
+        else:
+            with torch.cuda.device(self.device):
+                _check(fn(ctx(self.device), self._h, *args, _stream()))
+
+    def pack(self, grads, offsets, world, flat, flat_elems):
+        """th_adam_pack: flat[offsets[i] + e] = grads[i][e] / world; grads[i] None writes zeros; offsets[i] < 0: no slot.  A
+        gradient may be the view flat[offsets[i] : offsets[i] + n] itself.  ``grads`` may also be the uint64 array of addresses
+        that an earlier call with the same tensors returned."""
+        ptrs, offsets = self._flat_args(grads, offsets, flat, flat_elems, "adam_pack")
+        self._flat_call(_lib.th_adam_pack, ptrs.ctypes.data, offsets.ctypes.data, self.n, int(world), _p(flat), int(flat_elems))
+        return ptrs
+
+    def unpack(self, dst, offsets, flat, flat_elems):
+        """th_adam_unpack: dst[i][e] = flat[offsets[i] + e] for every tensor with a slot"""
+        ptrs, offsets = self._flat_args(dst, offsets, flat, flat_elems, "adam_unpack")
+        self._flat_call(_lib.th_adam_unpack, ptrs.ctypes.data, offsets.ctypes.data, self.n, _p(flat), int(flat_elems))
 
     def nonfinite(self):
         """gradient elements that were NaN or +-inf in the counted steps so far (synchronises the current stream)"""

@@ -2,8 +2,16 @@
 its checkpoint functions (lib/utils/net_utils.py:288-348), a small Recorder (lib/train/recorder.py without tensorboard) and
 the epoch loop of train_net.py:31-87, restated for this project.
 
-Single process only: DistributedDataParallel, SyncBatchNorm and the data loaders are out of scope; a
-``data_loader`` is any sized iterable of batches.
+One process per GPU: with a process group (``Trainer(..., group=)``, ``fit(..., group=)``; ``python -m torch.distributed.run -m
+transhuman_amd.trainer`` sets one up from RANK / WORLD_SIZE / LOCAL_RANK) every rank starts from rank 0's parameters and
+buffers, trains on its own batches, and the gradients are averaged between ``loss.backward()`` and the step by
+train_dist.GradExchange -- one pack launch, one all-reduce, DeviceAdam stepping out of the flat buffer -- in the place of the
+reference's DistributedDataParallel(find_unused_parameters=True) (lib/train/trainers/trainer.py:23-33).  The reference also
+converts every BatchNorm to SyncBatchNorm; ``sync_bn`` does the same (default: when distributed on a device), and the converted
+encoder trunk then runs under torch autograd whatever cfg.train_encoder says: the HIP backward of the trunk (K23) is that of
+rank-local batch statistics.  Without a group nothing differs from a single process.  The data loaders
+are out of scope; a ``data_loader`` is any sized iterable of batches (train_dist.DistributedSampler deals a data set to the
+ranks as the reference's sampler does).
 
 Checkpoints keep the reference's layout ``{net, optim, scheduler, recorder, epoch}`` and names (``latest.pth``,
 ``{epoch + 1}.pth``).  Ours hold tensors and plain numbers only and load with ``weights_only=True``.  The ``net`` and ``optim``
@@ -92,15 +100,37 @@ class Recorder:
 # trainer
 # ---------------------------------------------------------------------------
 class Trainer:
-    """Trainer(network_wrapper): ``network_wrapper(batch) -> (output, loss, loss_stats, image_stats)``."""
+    """Trainer(network_wrapper): ``network_wrapper(batch) -> (output, loss, loss_stats, image_stats)``.
+
+    group: a torch.distributed process group (``dist.group.WORLD`` for the default one) makes the trainer one rank of a
+    data-parallel job (:23-33): construction -- a collective, every rank builds its trainer at the same point -- copies rank
+    0's parameters and buffers to every rank, and ``train`` averages the gradients over the ranks before the clip and the
+    step, so DeviceAdam's in-kernel clip clips the averaged gradient as :84-86 does.  Only rank 0 records and logs (:88-89).
+    With DeviceAdam(zero_grad=True) a tensor that once had a gradient keeps its slot (train_dist.GradExchange, "Liveness").
+    sync_bn: convert BatchNorm to SyncBatchNorm (:24-26); None: when distributed and on a device, as the reference.  A
+    converted encoder trunk runs under torch autograd whatever cfg.train_encoder says (autograd_path._trunk_sites_have_batch_statistics)."""
 
     clip_value = 40.0                                          # trainer.py:85
 
-    def __init__(self, network, device=None):
+    def __init__(self, network, device=None, group=None, sync_bn=None):
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.device = torch.device(device)
         self.network = network.to(self.device)
+        self.group, self.exchange, self.rank = group, None, 0
+        if sync_bn is None:
+            sync_bn = group is not None and self.device.type == "cuda"
+        if group is None:
+            if sync_bn:
+                raise ValueError("Trainer: sync_bn needs a process group")
+            return
+        import torch.distributed as dist
+        from .train_dist import GradExchange
+        self.rank = dist.get_rank(group)
+        if sync_bn:
+            self.network = torch.nn.SyncBatchNorm.convert_sync_batchnorm(self.network, process_group=group)
+        self.exchange = GradExchange([p for p in self.network.parameters() if p.requires_grad], group=group)
+        self.exchange.broadcast_parameters(self.network, src=dist.get_global_rank(group, 0))
 
     @staticmethod
     def reduce_loss_stats(loss_stats):
@@ -122,8 +152,9 @@ class Trainer:
         return self.network.parameters()
 
     def train(self, epoch, data_loader, optimizer, recorder, log=None):
-        """One epoch (:61-125): forward, zero_grad, loss.mean().backward(), clip at 40, step.  A DeviceAdam clips inside
-        its kernel (its clip_value is set to the trainer's when it has none); any other optimiser gets clip_grad_value_."""
+        """One epoch (:61-125): forward, zero_grad, loss.mean().backward(), [the gradient exchange,] clip at 40, step.  A
+        DeviceAdam clips inside its kernel (its clip_value is set to the trainer's when it has none); any other optimiser gets
+        clip_grad_value_."""
         cfg = get_cfg()
         max_iter = len(data_loader)
         log_interval = int(_cfg_get(cfg, "log_interval"))
@@ -140,9 +171,13 @@ class Trainer:
             optimizer.zero_grad()
             loss = loss.mean()
             loss.backward()
+            if self.exchange is not None:
+                self.exchange.exchange()
             if not in_kernel:
                 torch.nn.utils.clip_grad_value_(self._parameters(), self.clip_value)
             optimizer.step()
+            if self.rank > 0:
+                continue
 
             recorder.step += 1
             recorder.update_loss_stats(self.reduce_loss_stats(loss_stats))
@@ -289,12 +324,13 @@ def load_model(net, optim, scheduler, recorder, model_dir, resume=True, epoch=-1
 # ---------------------------------------------------------------------------
 # the epoch loop
 # ---------------------------------------------------------------------------
-def fit(cfg, network, data_loader, log=print):
-    """train_net.py:31-87, single process: ``network`` is a NetworkWrapper (its ``net`` holds the trained parameters, as in
-    the reference, where the optimiser and the checkpoints are built on network.net), ``data_loader`` a sized iterable that
-    yields at most cfg.ep_iter batches per pass."""
+def fit(cfg, network, data_loader, log=print, group=None):
+    """train_net.py:31-87: ``network`` is a NetworkWrapper (its ``net`` holds the trained parameters, as in the reference,
+    where the optimiser and the checkpoints are built on network.net), ``data_loader`` a sized iterable that yields at most
+    cfg.ep_iter batches per pass (train_dist.iterations_per_rank of them on each rank of a job).  With a process group every
+    rank loads the checkpoint, only rank 0 writes one (:76-82) and logs, and the loader's sampler is told the epoch (:68-69)."""
     net = network.net if hasattr(network, "net") else network
-    trainer = Trainer(network)
+    trainer = Trainer(network, group=group)
     optimizer = make_optimizer(cfg, net)
     scheduler = make_lr_scheduler(cfg, optimizer)
     recorder = Recorder()
@@ -302,14 +338,104 @@ def fit(cfg, network, data_loader, log=print):
     begin_epoch = load_model(net, optimizer, scheduler, recorder, model_dir, resume=bool(_cfg_get(cfg, "resume")))
     tr = getattr(cfg, "train", None) or _STANDALONE.train
     save_freq, save_latest = int(_cfg_get(cfg, "save_freq")), int(_cfg_get(cfg, "save_latest_ep"))
+    writes = trainer.rank == 0
     for epoch in range(begin_epoch, int(tr.epoch)):
         recorder.epoch = epoch
         if hasattr(getattr(data_loader, "dataset", None), "set_epoch"):
             data_loader.dataset.set_epoch(epoch)
-        trainer.train(epoch, data_loader, optimizer, recorder, log=log)
+        if group is not None:
+            for sampler in (getattr(data_loader, "sampler", None),
+                            getattr(getattr(data_loader, "batch_sampler", None), "sampler", None)):
+                if hasattr(sampler, "set_epoch"):
+                    sampler.set_epoch(epoch)
+                    break
+        trainer.train(epoch, data_loader, optimizer, recorder, log=log if writes else None)
         scheduler.step()
-        if (epoch + 1) % save_freq == 0:
+        if writes and (epoch + 1) % save_freq == 0:
             save_model(net, optimizer, scheduler, recorder, model_dir, epoch)
-        if (epoch + 1) % save_latest == 0:
+        if writes and (epoch + 1) % save_latest == 0:
             save_model(net, optimizer, scheduler, recorder, model_dir, epoch, last=True)
+    if group is not None:
+        import torch.distributed as dist
+        dist.barrier(group=group)                             # (a rank that returns finds rank 0's last checkpoint written)
     return network
+
+
+# ---------------------------------------------------------------------------
+# one process per GPU
+# ---------------------------------------------------------------------------
+def init_distributed(backend=None, timeout_s=1800):
+    """The process group of a ``torch.distributed.run`` launch (train_net.py:116-123): RANK, WORLD_SIZE and LOCAL_RANK select
+    it, LOCAL_RANK the device.  -> (group, device), or (None, None) when the variables are absent: a single process.
+    backend: "nccl" (RCCL) on a device, "gloo" without one, unless given."""
+    if not all(k in os.environ for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK")):
+        return None, None
+    import datetime
+    import torch.distributed as dist
+    on_device = torch.cuda.is_available()
+    device = torch.device("cuda", int(os.environ["LOCAL_RANK"])) if on_device else torch.device("cpu")
+    if on_device:
+        torch.cuda.set_device(device)
+    if not dist.is_initialized():
+        dist.init_process_group(backend or ("nccl" if on_device else "gloo"), rank=int(os.environ["RANK"]),
+                                world_size=int(os.environ["WORLD_SIZE"]), timeout=datetime.timedelta(seconds=timeout_s))
+    return dist.group.WORLD, device
+
+
+def main(argv=None):
+    """``python -m transhuman_amd.trainer --steps N``: N steps per epoch on a seeded synthetic subject (synth.make_batch) with
+    target patches seeded per rank and step (the data loaders are out of scope) through ``fit`` -- under ``torch.distributed.run`` as one rank of
+    a data-parallel job, otherwise as a single process.  The MSE term alone unless cfg names the LPIPS weights."""
+    import argparse
+    from . import synth
+    from .networks.cross_transformer import Network
+    from .networks.renderer.if_clight_renderer import Renderer
+    from .train_loss import NetworkWrapper
+    ap = argparse.ArgumentParser(description=main.__doc__)
+    ap.add_argument("--steps", type=int, default=4)
+    ap.add_argument("--epochs", type=int, default=1)
+    ap.add_argument("--patch", type=int, default=20)
+    ap.add_argument("--backend", default=None)
+    ap.add_argument("--model-dir", default=None, help="where checkpoints go (default: cfg.trained_model_dir)")
+    args = ap.parse_args(argv)
+    group, device = init_distributed(args.backend)
+    rank, world = 0, 1
+    if group is not None:
+        import torch.distributed as dist
+        rank, world = dist.get_rank(), dist.get_world_size()
+    if device is None:
+        device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
+    cfg = get_cfg()
+    P = args.patch
+    masks = torch.ones((1, 1, P, P), dtype=torch.bool)
+    div = torch.tensor([[0, P * P]], dtype=torch.int64)
+
+    base = synth.make_batch(P, P, 3, seed=0)                    # one subject and pose; the targets differ per rank and step
+
+    def batch(k):
+        gen = torch.Generator().manual_seed(k)
+        return dict(base, patch_masks=masks, patch_div_indices=div, target_patches=torch.rand((1, 1, P, P, 3), generator=gen))
+
+    loader = [batch(1 + e * world + rank) for e in range(args.steps)]
+    from .config import override
+    keep = dict(lpips_weight=float(_cfg_get(cfg, "lpips_weight")) if getattr(cfg, "lpips_vgg16_path", None) else 0.0,
+                trained_model_dir=args.model_dir or _cfg_get(cfg, "trained_model_dir"))
+    with override(**keep):
+        torch.manual_seed(0)
+        net = Network().train().to(device)
+        body = loader[0]["tar_smpl_vertice_smplcoord"][0].numpy()
+        n_class = int(_cfg_get(cfg, "num_class"))
+        renderer = Renderer(net, vertex_can=body.astype("float64") * 1.02 + 0.001, pc2voxel_ind=synth.kmeans_assign(body, n_class))
+        tr = getattr(cfg, "train", None) or _STANDALONE.train
+        epochs, tr.epoch = tr.epoch, args.epochs
+        try:
+            fit(cfg, NetworkWrapper(net, renderer=renderer), loader, group=group)
+        finally:
+            tr.epoch = epochs
+    if group is not None:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
