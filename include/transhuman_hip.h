@@ -604,6 +604,32 @@ int th_marching_cubes_emit(th_ctx* ctx, const float* cube, int X, int Y, int Z, 
                            int x0, int x1, const double* scale_host /* [3] */, const double* origin_host /* [3] */,
                            double* verts, int32_t* tris, th_stream stream);
 
+/* ---- K24: connected components and the component filter of a triangle mesh (additions, ABI 12) ---- */
+/* What a user of a marching-cubes mesh does next by hand with trimesh (`max(mesh.split(), key=lambda m: len(m.faces))`), defined
+ * here (trimesh is absent): two faces are connected when they share a vertex INDEX (trimesh.split: an edge -- the rules differ only
+ * where parts touch in one vertex); the label of a vertex is the smallest vertex index of its component; a vertex no face
+ * references keeps its own index and belongs to no component with faces; a component's size is its number of faces.
+ * faces: int32 [n_faces][3] on the device, positions double [n_verts][3] (as K13 writes them); either count may be 0.
+ *   th_mesh_components    labels int32 [n_verts].  A multi-launch fixpoint of integer atomicMin hooks and pointer jumps (see
+ *                         csrc/k_meshcc.hip: no workgroup waits for another); waits for the stream once per batch of sweeps.
+ *                         info_host: {components with faces, sweeps, host reads of the sweep flags, label of the largest
+ *                         component (most faces, a tie to the smallest label) or -1, its face count}.  More than
+ *                         n_verts + 2 sweeps -- no valid mesh -- is an error.
+ *   th_mesh_filter_count  keep flags + prefix sums into `workspace` from the labels; min_faces = 0 keeps the largest component,
+ *                         n >= 1 every component with at least n faces; vertices without a face are always dropped.  Waits;
+ *                         counts_host: {kept vertices, kept faces, components with faces, label of the largest or -1}.
+ *   th_mesh_filter_emit   behind it, same workspace and arrays: kept vertices and faces in their original order, indices
+ *                         renumbered densely; vert_map int32 [n_verts] = new index or -1.  verts / verts_out may be null.
+ * A face index outside [0, n_verts) (th_mesh_filter_count: a label too) is found by a first pass, before anything is indexed by
+ * it, and makes the call fail.  Integer atomics only: results are bit-identical from run to run whatever `workspace` held. */
+size_t th_mesh_components_workspace_bytes(int n_verts, int n_faces);
+int th_mesh_components(th_ctx* ctx, const int32_t* faces, int n_faces, int n_verts, int32_t* labels, void* workspace,
+                       size_t workspace_bytes, int64_t* info_host /* [5] */, th_stream stream);
+int th_mesh_filter_count(th_ctx* ctx, const int32_t* faces, int n_faces, int n_verts, const int32_t* labels, int min_faces,
+                         void* workspace, size_t workspace_bytes, int64_t* counts_host /* [4] */, th_stream stream);
+int th_mesh_filter_emit(th_ctx* ctx, const double* verts, const int32_t* faces, int n_faces, int n_verts, const void* workspace,
+                        size_t workspace_bytes, double* verts_out, int32_t* faces_out, int32_t* vert_map, th_stream stream);
+
 /* ---- evaluator metrics: SSIM ------------------------------------------------ */
 /* lib/evaluators/if_nerf.py:108: skimage's structural_similarity(img_pred, img_gt, multichannel=True) of the evaluator's
  * cropped H x W x 3 float64 images, read as skimage 0.19 computes it for a float64 image without data_range: per channel a
@@ -942,6 +968,14 @@ size_t th_sigma_grid_workspace_bytes(const th_frame* f, int P);
 int th_eval_sigma_grid(th_ctx* ctx, const th_frame* f, const float* pts, int P, float* sigma_out,
                        void* workspace, size_t workspace_bytes, void* shade_pool, size_t shade_pool_bytes,
                        int64_t* stats_host, th_stream stream);
+/* The radiance field at arbitrary points (additions, ABI 12): pts [P,3] world space, dirs [P,3] viewing directions (normalised
+ * here; NULL: the zero embedding rows of if_mesh_renderer.py:62) -> raw_out [P,4] = {rgb logits, sigma_raw}.  Rows outside the
+ * hull are exactly 0; inside, sigma everywhere and the RGB logits where sigma > 0 (0 elsewhere): what MLP_forward_ori's
+ * progressive branch returns under the hull mask.  Workspace (th_sigma_grid_workspace_bytes), pool, statistics and range
+ * snapshot as th_eval_sigma_grid. */
+int th_eval_points(th_ctx* ctx, const th_frame* f, const float* pts, const float* dirs, int P, float* raw_out,
+                   void* workspace, size_t workspace_bytes, void* shade_pool, size_t shade_pool_bytes,
+                   int64_t* stats_host, th_stream stream);
 
 /* ---- K22: the optimiser step -- value clipping + Adam / AdamW for every parameter tensor in one launch (additions, ABI 12) ---- */
 /* What the reference's loop does per step with clip_grad_value_(., 40) and torch.optim.Adam over one parameter group per tensor

@@ -66,6 +66,12 @@ def _defaults():
         # mesh (configs/reconstruction.yaml:14-15)
         voxel_size=[0.005, 0.005, 0.005],
         mesh_th=20,
+        # what if_mesh_renderer.Renderer.render does to the mesh it returns (never to `cube`): mesh_components = "all" (as the
+        # reference: floaters included), "largest" or an int n (every component with >= n faces; mesh_clean.py, K24), then
+        # mesh_colors = "none" (as the reference: no colours) or "normal" (the field's RGB at every vertex, looked at against the
+        # vertex normal; mesh_color.py, th_eval_points)
+        mesh_components="all",
+        mesh_colors="none",
         exp_name="transhuman_amd",
         data_root="data/zju_mocap",
         # where the kmeans CSR fixtures live when ./kmeans_dict is absent

@@ -955,6 +955,33 @@ int th_marching_cubes_emit(th_ctx* c, const float* cube, int X, int Y, int Z, fl
     return th_mc_emit_launch(cube, X, Y, Z, iso, ws, x0, x1, scale_host, origin_host, verts, tris, (hipStream_t)stream);
 }
 
+// ---- K24: connected components and the component filter of a triangle mesh (k_meshcc.hip) ----
+size_t th_mesh_components_workspace_bytes(int n_verts, int n_faces) { return th_meshcc_ws(n_verts, n_faces); }
+
+int th_mesh_components(th_ctx* c, const int32_t* faces, int n_faces, int n_verts, int32_t* labels, void* ws, size_t ws_bytes,
+                       int64_t* info_host, th_stream stream) {
+    TH_REQUIRE(c && ws && info_host, "null argument");
+    TH_REQUIRE((faces || n_faces <= 0) && (labels || n_verts <= 0), "null argument");
+    return th_meshcc_components_launch(faces, n_faces, n_verts, labels, ws, ws_bytes, c->host_pinned + 8, info_host,
+                                       (hipStream_t)stream);
+}
+
+int th_mesh_filter_count(th_ctx* c, const int32_t* faces, int n_faces, int n_verts, const int32_t* labels, int min_faces, void* ws,
+                         size_t ws_bytes, int64_t* counts_host, th_stream stream) {
+    TH_REQUIRE(c && ws && counts_host, "null argument");
+    TH_REQUIRE((faces || n_faces <= 0) && (labels || n_verts <= 0), "null argument");
+    return th_meshcc_filter_count_launch(faces, n_faces, n_verts, labels, min_faces, ws, ws_bytes, c->host_pinned + 8, counts_host,
+                                         (hipStream_t)stream);
+}
+
+int th_mesh_filter_emit(th_ctx* c, const double* verts, const int32_t* faces, int n_faces, int n_verts, const void* ws,
+                        size_t ws_bytes, double* verts_out, int32_t* faces_out, int32_t* vert_map, th_stream stream) {
+    TH_REQUIRE(c && ws, "null argument");
+    TH_REQUIRE(n_verts >= 0 && n_faces >= 0 && ws_bytes >= th_meshcc_ws(n_verts, n_faces), "workspace too small");
+    TH_REQUIRE((faces || n_faces <= 0) && (vert_map || n_verts <= 0), "null argument");
+    return th_meshcc_filter_emit_launch(verts, faces, n_faces, n_verts, ws, verts_out, faces_out, vert_map, (hipStream_t)stream);
+}
+
 size_t th_smpl_workspace_bytes(int n_verts) { return th_smpl_ws(n_verts); }
 
 int th_smpl_lbs(th_ctx* c, const th_smpl_model* m, const float* pose_aa, const float* rot, const double* beta,
@@ -1423,8 +1450,11 @@ static int pregather_stage(th_ctx* c, const th_frame* f, const ThPointSrc& ps, c
 
 // shade_stage: token table, candidate grid, one fused launch over region A, the chunk loop, the scatter.  Needs the counts,
 // a complete map and (behind a prepass) its token `tk`, whose npre / pre_tokens it consumes.  Leaves raw[P,4] where masked.
+// Point mode (ray_mode false) is the sigma grid's unless `pt_rgb`: then th_eval_points' -- the progressive RGB branch (rgb_all 0)
+// with the view embedding rows of `pt_vd` ([P,27], indexed by the sample) or, with pt_vd null, the zero rows of cb.vdc.
 static int shade_stage(th_ctx* c, const th_frame* f, const ThPointSrc& ps, bool ray_mode, const ShadeWs& w, th_ctx::Prepass* tk,
-                       const HullCounts& k, void* pool, size_t pool_bytes, hipStream_t s) {
+                       const HullCounts& k, void* pool, size_t pool_bytes, hipStream_t s, bool pt_rgb = false,
+                       const float* pt_vd = nullptr) {
     const int S = ps.S, V = f->V, n = k.n, unmasked = k.unmasked;
     const int f_ld = frame_f_ld(f), fmt = mlp_row_format(c, V);
     const bool tex = tex_rows(c, f);
@@ -1493,6 +1523,9 @@ static int shade_stage(th_ctx* c, const th_frame* f, const ThPointSrc& ps, bool 
             ProfScope ps3(pf, TH_PROF_MLP, s);
             // ray mode: the [R,27] embedding table is indexed sample -> ray (sel / S); mesh mode: zero rows (cb.vdc)
             if (ray_mode) TH_TRY(mlp_dispatch(c, V, m, cb, f_ld, w.vd_all, sel, S, unmasked, s, w.tprime, f->n_clusters, tex_map, tex_stride));
+            // (th_eval_points: colour where sigma > 0, the caller's directions per point or the zero rows)
+            else if (pt_rgb) TH_TRY(mlp_dispatch(c, V, m, cb, f_ld, pt_vd ? pt_vd : cb.vdc, pt_vd ? sel : nullptr, 1, 0, s, w.tprime,
+                                                 f->n_clusters, tex_map, tex_stride));
             // (the sigma grid never looks at colour: skip the RGB branch, which the reference evaluates and drops,
             // if_mesh_renderer.py:84-99)
             else TH_TRY(mlp_dispatch(c, V, m, cb, f_ld, cb.vdc, nullptr, 1, 2, s, w.tprime, f->n_clusters, tex_map, tex_stride));
@@ -1718,6 +1751,41 @@ int th_eval_sigma_grid(th_ctx* c, const th_frame* f, const float* pts, int P, fl
     TH_TRY(shade_stage(c, f, ps, false, w, nullptr, k, pool, pool_bytes, s));
     hipLaunchKernelGGL(extract_sigma_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, (const float4*)w.raw, w.mask, (long long)P,
                        sigma_out);
+    TH_LAUNCH_CHECK();
+    const int snap = th_range_snapshot(c, stream);
+    TH_REQUIRE(snap >= 0, "range snapshot failed");
+    if (stats_host) stats_host[2] = snap;
+    return 0;
+}
+
+__global__ void extract_raw_kernel(const float4* __restrict__ raw, const uint8_t* __restrict__ mask, long long P,
+                                   float4* __restrict__ out) {
+    long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i < P) out[i] = mask[i] ? raw[i] : make_float4(0.f, 0.f, 0.f, 0.f);      // (raw is only written where shaded)
+}
+
+// th_eval_sigma_grid's sibling with the RGB branch: the point mode of hull_stage / shade_stage with the progressive branch
+// (rgb_all 0) and a view embedding per point.  Same workspace, pool, range snapshot and map completion.
+int th_eval_points(th_ctx* c, const th_frame* f, const float* pts, const float* dirs, int P, float* raw_out, void* ws,
+                   size_t ws_bytes, void* pool, size_t pool_bytes, int64_t* stats_host, th_stream stream) {
+    TH_REQUIRE(c && f && pts && raw_out && ws, "null argument");
+    TH_TRY(frame_ok(f));
+    hipStream_t s = (hipStream_t)stream;
+    if (P <= 0) return 0;
+    ShadeWs w;
+    TH_TRY(carve_shade_ws(f, P, P, ws, ws_bytes, w));
+    ThPointSrc ps{};
+    ps.pts = pts; ps.R = P; ps.S = 1;
+    TH_TRY(compact_ok(c, f));
+    if (pool != nullptr) c->after_shade_valid = false;      // (the pool's last user from here on: see th_render_rays)
+    HullCounts k;
+    TH_TRY(hull_stage(c, f, ps, P, false, w, s));
+    if (dirs != nullptr) TH_TRY(th_view_embed_launch(dirs, P, 4, w.vd_all, s));      // (one row per point; null: zero rows, :62)
+    TH_TRY(counts_now(c, w, stats_host, s, &k));
+    TH_TRY(complete_map(c, f, nullptr, k, s));
+    TH_TRY(shade_stage(c, f, ps, false, w, nullptr, k, pool, pool_bytes, s, true, dirs != nullptr ? w.vd_all : nullptr));
+    hipLaunchKernelGGL(extract_raw_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, (const float4*)w.raw, w.mask, (long long)P,
+                       (float4*)raw_out);
     TH_LAUNCH_CHECK();
     const int snap = th_range_snapshot(c, stream);
     TH_REQUIRE(snap >= 0, "range snapshot failed");

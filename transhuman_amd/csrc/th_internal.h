@@ -553,6 +553,14 @@ int th_mc_emit_launch(const float* cube, int X, int Y, int Z, float iso, const v
                       const double* origin, double* verts, int* tris, hipStream_t s);
 int th_mc_prefix_launch(const void* ws, int X, int Y, int Z, int x, long long* out_dev, hipStream_t s);
 int th_bound_mask_launch(const int32_t* corners_xy /* host [8][2] */, int H, int W, uint8_t* mask, hipStream_t s);
+// k_meshcc.hip (K24).  `pinned`: 8 int32 words of pinned host memory the calls read their flags / counts through (they wait).
+size_t th_meshcc_ws(int nv, int nf);
+int th_meshcc_components_launch(const int32_t* faces, int nf, int nv, int32_t* label, void* ws, size_t ws_bytes, int32_t* pinned,
+                                int64_t* info_host /* [5] */, hipStream_t s);
+int th_meshcc_filter_count_launch(const int32_t* faces, int nf, int nv, const int32_t* label, int min_faces, void* ws,
+                                  size_t ws_bytes, int32_t* pinned, int64_t* counts_host /* [4] */, hipStream_t s);
+int th_meshcc_filter_emit_launch(const double* verts, const int32_t* faces, int nf, int nv, const void* ws, double* verts_out,
+                                 int32_t* faces_out, int32_t* vert_map, hipStream_t s);
 // k_encoder.hip
 int th_upsample_concat_launch(const float* img, const float* lat0, const float* lat1, const float* lat2,
                               const int* dims, int V, int H, int W, const float* wc, const float* bc, float* out,

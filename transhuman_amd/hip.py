@@ -2163,6 +2163,35 @@ def eval_sigma_grid(net, frame, pts):
     return out, dict(valid_samples=stats[1])
 
 
+def eval_points(net, frame, pts, dirs=None):
+    """th_eval_points: the radiance field at arbitrary world-space points.  pts [P,3], dirs [P,3] viewing directions (normalised
+    on the device) or None (the zero embedding rows of if_mesh_renderer.py:62) -> (raw fp32 [P,4] = rgb logits + sigma_raw, stats).
+    Rows outside the hull are exactly 0; inside, sigma everywhere and the RGB logits where sigma > 0 (0 elsewhere).  Same guard
+    and retry as eval_sigma_grid."""
+    lib = load_library()
+    _sync_weights(net, "mlp")
+    p = _f32(pts).reshape(-1, 3)
+    P = p.shape[0]
+    d = None
+    if dirs is not None:
+        d = _f32(dirs).reshape(-1, 3)
+        assert d.shape[0] == P and d.device == p.device, "one direction per point, on the points' device"
+    out = torch.empty((P, 4), dtype=torch.float32, device=p.device)
+    if P == 0:
+        return out, dict(valid_samples=0)
+    ws = _cached_ws(lib.th_sigma_grid_workspace_bytes(C.byref(frame.c), P), p.device)
+    stats = (C.c_int64 * 4)()
+    for _ in range(3):
+        pool = _shade_pool(frame.c, P, False, p.device)        # (inside the loop: the guard may have changed the mode)
+        _check(lib.th_eval_points(ctx(p.device), C.byref(frame.c), _p(p), _p(d), P, _p(out), _p(ws), ws.numel(), _p(pool),
+                                  pool.numel(), stats, _stream()))
+        if _guard(p.device, int(stats[2])):
+            break
+        if (conv_fallback(p.device) or vit_fallback(p.device)) and frame.rebuild is not None:
+            frame = frame.rebuild()
+    return out, dict(valid_samples=stats[1])
+
+
 def set_tok_gather(on, device=None):
     """Token-branch hand-over K4 -> K6 on the fused path: True (default) = neighbour records, the fused kernel blends the
     rows of the per-frame token table on the matrix pipe; False = K4 blends them in fp32 (3.3 KB per sample through HBM;

@@ -7,7 +7,9 @@ evaluates (and discards) RGB for sigma>0 voxels (:84-99) -- `cube` only needs
 sigma_raw, which is what is produced here.  Marching cubes (:103, PyMCubes in the reference) runs on the device too
 (th_marching_cubes_*, K13): the padded cube never leaves HBM before the mesh exists; `mesh` is a
 transhuman_amd.mesh.Mesh (vertices / faces / export(path) like the trimesh object the visualiser uses,
-lib/visualizers/if_nerf_mesh.py:25-35).
+lib/visualizers/if_nerf_mesh.py:25-35).  Two options of ours act on that mesh, both off by default: cfg.mesh_components
+("all" | "largest" | n: drop the floaters, mesh_clean.py) and cfg.mesh_colors ("none" | "normal": the field's RGB at the vertices,
+mesh_color.py).
 """
 import os
 import sys
@@ -22,7 +24,7 @@ if _REPO not in sys.path:
 
 import numpy as np                                                  # noqa: E402
 
-from transhuman_amd.config import get_cfg                           # noqa: E402
+from transhuman_amd.config import get_cfg, cfg_get                  # noqa: E402
 from transhuman_amd import hip                                      # noqa: E402
 from transhuman_amd.networks.renderer.if_clight_renderer import Renderer as Base_Renderer   # noqa: E402
 
@@ -48,6 +50,16 @@ class Renderer(Base_Renderer):
         LB = can_bounds[0] - 10 * voxel                                                        # :107
         verts, tris = hip.marching_cubes(cube_d, cfg.mesh_th, scale=voxel, origin=LB)         # :103-108
         mesh = Mesh(verts, tris.to(torch.int64))
+        # ours, off by default (cfg_get: the reference's cfg has neither key): drop the floaters, then colour the vertices.  `cube`
+        # is never touched.
+        comps, colors = cfg_get("mesh_components", "all"), cfg_get("mesh_colors", "none")
+        if comps != "all":
+            mesh = mesh.filter_components(comps)
+        if colors != "none":
+            if colors != "normal":
+                raise ValueError(f"cfg.mesh_colors is {colors!r}: 'none' or 'normal'")
+            from transhuman_amd import mesh_color
+            mesh.vertex_colors = mesh_color.vertex_colors(self, batch, mesh, view="normal", frame=frame)
         # the reference hands the cube back as a numpy array (:99-109): copy it through a pinned staging buffer (a
         # pageable 276^3 fp32 copy takes 10+ ms of a 55 ms frame)
         key = (tuple(cube_d.shape), str(cube_d.device))
