@@ -791,6 +791,28 @@ int th_prep_views(th_ctx* ctx, const uint8_t* img_u8, const uint8_t* msk_u8, int
 int th_prep_mask(th_ctx* ctx, const uint8_t* a, const uint8_t* b_or_null, int V, int H0, int W0, int border, uint8_t* out,
                  th_stream stream);
 
+/* ---- K25: colour jitter of the raw camera frames, in front of K16 (additions, ABI 12) ---------------- */
+/* The reference's dataset puts the raw uint8 frame of the target view and of every input view through torchvision's ColorJitter
+ * before it undistorts them (lib/datasets/light_stage/can_smpl.py:629-637; training only).  torchvision is absent: the order of
+ * operations follows its documented ColorJitter and parity with it is UNPINNED; the arithmetic is Pillow's (ImageEnhance.Brightness /
+ * Contrast / Color, convert("HSV") / convert("RGB")), restated in numpy by transhuman_amd.preprocess.color_jitter_oracle, which the
+ * device equals bit for bit.  img uint8 [V][H][W][3] -> out uint8 [V][H][W][3], DEVICE pointers; out may be img
+ * itself (otherwise the two must not overlap).  Step k = 0..3 runs operation (order >> 2 k) & 3 -- 0 brightness, 1 contrast,
+ * 2 saturation, 3 hue; order must hold each once -- if bit `operation` of `enabled` is set.  Per pixel:
+ * L = (19595 R + 38470 G + 7471 B + 32768) >> 16; blend(d, x, f) = d + f (x - d) in fp32 (x - d in integers, product and sum rounded
+ * one by one), truncated for 0 <= f <= 1, otherwise 0 where <= 0, 255 where >= 255, else truncated; brightness blend(0, x, f);
+ * saturation blend(L, x, f); contrast blend(m, x, f) with m = (2 sum L + H W) / (2 H W) in integers over THAT image as it stands at
+ * that step; hue: Pillow's RGB -> HSV, H <- (H + hue_shift) & 255 (hue_shift = trunc(255 h) mod 256, 0..255), Pillow's HSV -> RGB,
+ * every product, quotient, sum and difference rounded on its own (no fused multiply-add); hue_shift = 0 still makes the lossy
+ * round trip.  Without contrast: one launch, no workspace read (it may be null).  With contrast: two launches; the first STORES one
+ * 64-bit partial sum of L per workgroup into the workspace, the second adds them per image -- no atomics, nothing to clear, correct
+ * whatever the workspace held, bit-identical from run to run.  No host wait.  1 <= H, W <= 16384, V <= 65535; enabled factors
+ * finite and >= 0; the workspace 8-byte aligned and at least th_color_jitter_workspace_bytes(V, H, W) (0 for sizes out of range). */
+size_t th_color_jitter_workspace_bytes(int V, int H, int W);
+int th_color_jitter(th_ctx* ctx, const uint8_t* img_u8, int V, int H, int W, uint32_t order, float brightness, float contrast,
+                    float saturation, int hue_shift, uint32_t enabled, uint8_t* out_u8, void* workspace, size_t workspace_bytes,
+                    th_stream stream);
+
 /* ---- K18: the training targets of a step -- patch ray sampling (additions, ABI 12) ---------------- */
 /* The train split of sample_ray_patch (lib/utils/if_nerf/if_nerf_data_utils.py:445-499 with :287-443), which the reference runs per
  * step in numpy inside its dataset, on the dense per-pixel arrays of th_gen_rays.  All pointers are DEVICE pointers.

@@ -49,6 +49,12 @@ def _defaults():
         # or "device" (made here from the raw camera frames input_imgs_raw / input_msks_raw / input_K_raw / input_D: undistort,
         # resize by `ratio`, background under the mask; transhuman_amd/preprocess.py, Renderer.frame_inputs)
         input_prep="batch",
+        # who applies the training colour jitter to the raw frames: "batch" (as the reference: its dataset did, or did not, before
+        # the frames got here; nothing is done) or "device" (a batch that carries `jitter_seed` -- the reference's
+        # index + epoch * cfg.seed -- gets input_imgs_raw and target_img_raw jittered in front of their preparation: read only
+        # where input_prep / target_prep = "device" prepare a raw frame; transhuman_amd/preprocess.py, K25).  This is not the
+        # reference's own `jitter` key, which keeps meaning that its dataset does it
+        input_jitter="batch",
         # architecture (train_or_eval.yaml:51-56)
         embed_size=192,
         img_feat_size=384,

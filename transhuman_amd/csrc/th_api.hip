@@ -837,6 +837,15 @@ int th_prep_mask(th_ctx* c, const uint8_t* a, const uint8_t* b, int V, int H0, i
     return th_prep_mask_launch(a, b, V, H0, W0, border, out, (hipStream_t)stream);
 }
 
+size_t th_color_jitter_workspace_bytes(int V, int H, int W) { return th_color_jitter_ws(V, H, W); }
+
+int th_color_jitter(th_ctx* c, const uint8_t* img, int V, int H, int W, uint32_t order, float brightness, float contrast,
+                    float saturation, int hue_shift, uint32_t enabled, uint8_t* out, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && img && out, "null argument");
+    return th_color_jitter_launch(img, V, H, W, order, brightness, contrast, saturation, hue_shift, enabled, out, ws, ws_bytes,
+                                  (hipStream_t)stream);
+}
+
 size_t th_patch_workspace_bytes(int H, int W) { return th_patch_ws(H, W); }
 
 int th_patch_rays(th_ctx* c, const float* ray_o, const float* ray_d, const float* near_in, const float* far_in,

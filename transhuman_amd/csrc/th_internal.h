@@ -649,6 +649,10 @@ int th_shade_mesh_launch(const float* verts, const float* normals, int nv, const
 int th_prep_views_launch(const uint8_t* img, const uint8_t* msk, int V, int H0, int W0, const float* K, const float* D, int n,
                          int mask_bkgd, int white_bkgd, const float* lut, float* out_img, uint8_t* out_msk, hipStream_t s);
 int th_prep_mask_launch(const uint8_t* a, const uint8_t* b, int V, int H0, int W0, int border, uint8_t* out, hipStream_t s);
+// K25 (k_jitter.hip): colour jitter of raw uint8 frames [V][H][W][3]; ws: th_color_jitter_ws bytes, read only with contrast enabled
+size_t th_color_jitter_ws(int V, int H, int W);
+int th_color_jitter_launch(const uint8_t* img, int V, int H, int W, uint32_t order, float brightness, float contrast,
+                           float saturation, int hue_shift, uint32_t enabled, uint8_t* out, void* ws, size_t ws_bytes, hipStream_t s);
 // k_patch.hip: the training targets of a step -- patch centres, windows and the gathered ray list of sample_ray_patch's train split
 size_t th_patch_ws(int H, int W);
 int th_patch_check(int H, int W, int N, int P);

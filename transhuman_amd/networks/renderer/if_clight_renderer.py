@@ -158,8 +158,10 @@ class Renderer:
         undistort, resize by cfg.ratio, background under the mask) -- ``batch['input_imgs_raw']`` (list[T] of uint8 [1,V,H0,W0,3]),
         ``batch['input_msks_raw']`` (list[T] of uint8 [1,V,H0,W0]), ``batch['input_K_raw']`` ([1,V,3,3]) and ``batch['input_D']``
         ([1,V,5]; the last two also as list[T]) -- on the current stream, without a host wait; ``input_imgs`` / ``input_K`` of the
-        batch, if any, are not read.  Returns a shallow copy with the two keys filled: ``batch`` is not mutated.  A batch that
-        came from here is returned as it is."""
+        batch, if any, are not read.  With cfg.input_jitter == "device" and ``batch['jitter_seed']`` (a Python int or a CPU int64
+        tensor) the raw pictures -- not the masks -- first get the training colour jitter of that seed (K25, one parameter set for
+        all views and time steps of the item).  Returns a shallow copy with the two keys filled: ``batch`` is not mutated.  A
+        batch that came from here is returned as it is."""
         mode = cfg_get("input_prep", "batch")
         if mode == "batch" or isinstance(batch, _PreparedBatch):
             return batch
@@ -167,9 +169,11 @@ class Renderer:
             raise ValueError(f'cfg.input_prep is {mode!r}: "batch" or "device"')
         from transhuman_amd import preprocess
         per_t = lambda x, t: x[t] if isinstance(x, (list, tuple)) else x
+        jitter = preprocess.batch_jitter(batch)
         imgs, Ks = [], []
         for t, (raw, raw_msk) in enumerate(zip(batch["input_imgs_raw"], batch["input_msks_raw"])):
-            im, _, K = preprocess.prepare_views(raw[0], raw_msk[0], per_t(batch["input_K_raw"], t)[0], per_t(batch["input_D"], t)[0],
+            frames = raw[0] if jitter is None else preprocess.color_jitter(raw[0], jitter)
+            im, _, K = preprocess.prepare_views(frames, raw_msk[0], per_t(batch["input_K_raw"], t)[0], per_t(batch["input_D"], t)[0],
                                                  mask_bkgd=bool(cfg_get("mask_bkgd", True)))
             imgs.append(im[None])
             Ks.append(K[None])
@@ -636,7 +640,9 @@ class Renderer:
         this method raises like every other.
         cfg.target_prep == "device": a training call whose batch has no ``ray_o`` gets its rays and patch targets made on the
         device from the target view (transhuman_amd.train_targets.add_targets, K18); they are ADDED TO ``batch`` -- the one
-        exception to "nothing here mutates batch", because the trainer reads them from it after this returns."""
+        exception to "nothing here mutates batch", because the trainer reads them from it after this returns.
+        cfg.input_prep == "device": a training call whose batch has no ``input_imgs`` gets its input views through ``frame_inputs``
+        (raw frames, jittered under cfg.input_jitter == "device"); a batch that has ``input_imgs`` is read as it is."""
         cfg = get_cfg()
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.net.parameters())
         randomised = (float(getattr(cfg, "perturb", 0.0)) > 0.0 and self.net.training) or \
@@ -652,6 +658,8 @@ class Renderer:
             if not batch["ray_o"].is_cuda:
                 raise hip.HipError("Renderer.render needs the batch on an MI355X (there is no CPU path)")
             from transhuman_amd.networks import autograd_path
+            if "input_imgs" not in batch and cfg_get("input_prep", "batch") == "device":
+                batch = self.frame_inputs(batch)                # (a shallow copy: the caller's batch keeps its keys)
             n_rays = int(batch["ray_o"].shape[1])
             if wants_grad and not randomised and n_rays > 4 * 2400:
                 # the reference trains on patches of <= 2400 rays (:551); a whole frame with gradients enabled is almost

@@ -35,8 +35,13 @@ numpy restatement below bit for bit, not approximately.
 ``prepare_views`` / ``combine_masks`` run on the device (no host wait); ``prepare_views_oracle`` / ``combine_masks_oracle`` restate the
 definition in numpy and import without a GPU.  tests/test_preprocess_host.py checks the restatement against scipy.ndimage
 (map_coordinates on the quantised coordinates, minimum_filter / maximum_filter); tests/test_gpu_preprocess.py holds the device to
-the restatement at every pixel.  Colour jitter (training only, through PIL) is not part of this.
+the restatement at every pixel.
+
+Colour jitter (training only; the reference applies it to the raw frames before all of the above) is K25, further down:
+``jitter_params`` / ``color_jitter`` (device) / ``color_jitter_oracle`` (numpy), with its own definition there.
 """
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 
@@ -170,6 +175,121 @@ def prepare_views(imgs_u8, msks_u8, K, D, ratio=None, mask_bkgd=True, white_bkgd
 
 
 # ---------------------------------------------------------------------------
+# colour jitter of the raw frames (csrc/k_jitter.hip, K25)
+# ---------------------------------------------------------------------------
+# The reference trains with ``jitter: True``: process_loaded (can_smpl.py:629-637) puts the RAW uint8 frame of the target view and of
+# every input view through torchvision's ColorJitter(brightness=(0.2, 2), contrast=(0.3, 2), saturation=(0.2, 2), hue=(-0.5, 0.5))
+# before it undistorts them, reseeded with the same number for all views of an item.  torchvision is absent wherever this project
+# builds or runs: the draws and the order of operations follow its documented ColorJitter and PARITY WITH torchvision IS UNPINNED;
+# the image arithmetic is Pillow's (ImageEnhance.Brightness / Contrast / Color, convert("HSV") / convert("RGB")), which
+# tests/test_jitter_host.py holds ``color_jitter_oracle`` to byte for byte.  Definition, per uint8 pixel:
+#   grey        L = (19595 R + 38470 G + 7471 B + 32768) >> 16
+#   blend       blend(d, x, f) = d + f (x - d) in fp32 (x - d in integers, f rounded to fp32, product and sum rounded one by one);
+#               0 <= f <= 1: truncated; otherwise 0 where <= 0, 255 where >= 255, else truncated
+#   brightness  blend(0, x, f) per channel          saturation  blend(L, x, f) per channel, L of that pixel
+#   contrast    blend(m, x, f), m = int(sum L / n + 0.5) = (2 sum L + n) // (2 n) over the n pixels of THAT image as it stands then
+#   hue h       RGB -> HSV, H <- (H + d) mod 256 with d = trunc(255 h) mod 256, HSV -> RGB; d = 0 is no shortcut (the round trip is
+#               lossy).  RGB -> HSV: V = max; max == min: H = S = 0; else in fp32 c = max - min, s = c / max, rc, gc, bc = (max - R) / c,
+#               ...; h = bc - gc if R == max, else 2.0 + rc - bc if G == max, else 4.0 + gc - rc, evaluated in double and rounded to
+#               fp32; h <- fp32(fmod(double(h) / 6.0 + 1.0, 1.0)); H = clip(int(double(h) 255.0)), S = clip(int(double(s) 255.0)).
+#               HSV -> RGB: S == 0: R = G = B = V; else in double x = H 6.0 / 255.0, i = floor(x), f = x - i, fs = S / 255.0,
+#               p = round(V (1 - fs)), q = round(V (1 - fs f)), t = round(V (1 - fs (1 - f))) (half away from zero, clipped to
+#               0..255, every product and difference rounded on its own: no fused multiply-add), (R, G, B) by i mod 6:
+#               (V,t,p) (q,V,p) (p,V,t) (p,q,V) (t,p,V) (V,p,q)
+#   parameters  ``order`` = randperm(4), then b, c, s, h uniform in their ranges, on a local generator seeded with the item's seed;
+#               the operations run in ``order`` (0 brightness, 1 contrast, 2 saturation, 3 hue); None switches one off
+JITTER_RANGES = dict(brightness=(0.2, 2), contrast=(0.3, 2), saturation=(0.2, 2), hue=(-0.5, 0.5))
+JITTER_MODES = ("batch", "device")
+BRIGHTNESS, CONTRAST, SATURATION, HUE = range(4)
+
+
+class JitterParams(NamedTuple):
+    """``order``: the four operation numbers in the order they run; a factor that is None switches its operation off"""
+    order: tuple
+    brightness: Optional[float]
+    contrast: Optional[float]
+    saturation: Optional[float]
+    hue: Optional[float]
+
+
+def jitter_params(seed, brightness=JITTER_RANGES["brightness"], contrast=JITTER_RANGES["contrast"],
+                  saturation=JITTER_RANGES["saturation"], hue=JITTER_RANGES["hue"]):
+    """The parameter set of one item: torchvision's ColorJitter.get_params on a LOCAL generator seeded with ``seed`` (the global
+    generator is neither reseeded nor advanced): order = randperm(4), then one uniform draw per range that is not None."""
+    g = torch.Generator().manual_seed(int(seed))
+    order = tuple(int(i) for i in torch.randperm(4, generator=g))
+    draw = lambda r: None if r is None else float(torch.empty(1).uniform_(float(r[0]), float(r[1]), generator=g))
+    return JitterParams(order, draw(brightness), draw(contrast), draw(saturation), draw(hue))
+
+
+def hue_shift(h):
+    """d = trunc(255 h) mod 256: what is added to the H plane"""
+    return int(float(h) * 255.0) % 256
+
+
+def _jitter_args(params):
+    """(order, [b, c, s] as fp32 or None, d or None) of a JitterParams or a plain 5-tuple, checked"""
+    order, b, c, s, h = params
+    order = tuple(int(i) for i in order)
+    if sorted(order) != [0, 1, 2, 3]:
+        raise ValueError(f"jitter order is {order}: a permutation of 0, 1, 2, 3")
+    factors = []
+    for name, f in (("brightness", b), ("contrast", c), ("saturation", s)):
+        if f is not None and not (0.0 <= float(f) < float("inf")):
+            raise ValueError(f"{name} factor is {f}: a finite value >= 0, or None")
+        factors.append(None if f is None else np.float32(f))
+    if h is not None and not -0.5 <= float(h) <= 0.5:
+        raise ValueError(f"hue is {h}: -0.5 <= hue <= 0.5, or None")
+    return order, factors, None if h is None else hue_shift(h)
+
+
+def batch_jitter(batch):
+    """The parameter set that cfg.input_jitter asks for on this batch, or None.  "batch" (default): None -- the dataset did it, as
+    in the reference.  "device": ``jitter_params(batch['jitter_seed'])`` -- the seed a Python int or a CPU int64 tensor, the
+    reference's ``index + epoch * cfg.seed`` (no device read is made for it); a batch without a seed (the reference's test split)
+    is not jittered."""
+    mode = cfg_get("input_jitter", "batch")
+    if mode not in JITTER_MODES:
+        raise ValueError(f'cfg.input_jitter is {mode!r}: "batch" or "device"')
+    if mode == "batch" or "jitter_seed" not in batch:
+        return None
+    seed = batch["jitter_seed"]
+    if torch.is_tensor(seed):
+        if seed.is_cuda or seed.numel() != 1 or seed.dtype.is_floating_point:
+            raise TypeError("batch['jitter_seed'] must be a Python int or a CPU integer tensor of one element")
+        seed = seed.item()
+    return jitter_params(int(seed))
+
+
+def _frames(shape):
+    if len(shape) < 3 or shape[-1] != 3 or 0 in shape:
+        raise ValueError(f"imgs_u8 has shape {tuple(shape)}: [V,H,W,3] or [H,W,3]")
+    H, W = (int(n) for n in shape[-3:-1])
+    _check_sizes(H, W, 1)
+    V = int(np.prod(shape[:-3], dtype=np.int64))
+    if V > 65535:
+        raise ValueError(f"{V} images: at most 65535")
+    return V, H, W
+
+
+def color_jitter(imgs_u8, params):
+    """th_color_jitter: imgs_u8 uint8 [V,H,W,3] (or [H,W,3], or more leading dimensions; device tensor or ndarray), ``params`` a
+    JitterParams or a plain (order, brightness, contrast, saturation, hue) -> a new uint8 device tensor of the same shape, every
+    image with the definition above applied (the contrast mean is each image's own).  No host wait."""
+    order, factors, d = _jitter_args(params)
+    img = _u8_dev(imgs_u8, "imgs_u8")
+    V, H, W = _frames(img.shape)
+    lib = hip.load_library()
+    out = torch.empty_like(img)
+    ws = hip._ws(lib.th_color_jitter_workspace_bytes(V, H, W), img.device)
+    enabled = sum(1 << op for op, f in enumerate(factors + [d]) if f is not None)
+    b, c, s = (0.0 if f is None else float(f) for f in factors)
+    hip._check(lib.th_color_jitter(hip.ctx(img.device), hip._p(img), V, H, W, sum(op << (2 * k) for k, op in enumerate(order)), b, c, s,
+                                   d or 0, enabled, hip._p(out), hip._p(ws), ws.numel(), hip._stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # numpy restatement of the definition
 # ---------------------------------------------------------------------------
 def _np(x, dtype=None):
@@ -299,3 +419,88 @@ def combine_masks_oracle(msk, msk_cihp=None, border=0):
                 dil = np.maximum(dil, hi[..., dy:dy + H0, dx:dx + W0])
         out[(dil - ero) == 1] = 100
     return out
+
+
+def grey_oracle(x):
+    """L of int64 [...,3] pixels"""
+    return (19595 * x[..., 0] + 38470 * x[..., 1] + 7471 * x[..., 2] + 32768) >> 16
+
+
+def blend_oracle(d, x, f):
+    """blend(d, x, f) of the definition: d, x int64 arrays (broadcast), f a float -> int64"""
+    f = np.float32(f)
+    t = d.astype(np.float32) + f * (x - d).astype(np.float32)
+    assert t.dtype == np.float32
+    if 0.0 <= f <= 1.0:
+        return t.astype(np.int64)
+    return np.where(t <= 0, 0, np.where(t >= 255, 255, np.clip(t, 0, 255).astype(np.int64)))
+
+
+def rgb_to_hsv_oracle(x):
+    """int64 [...,3] RGB -> int64 [...,3] HSV, Pillow's integer HSV"""
+    r, g, b = x[..., 0], x[..., 1], x[..., 2]
+    mx, mn = x.max(-1), x.min(-1)
+    flat = mx == mn
+    f32 = lambda a: a.astype(np.float32)
+    with np.errstate(all="ignore"):
+        c = f32(np.where(flat, 1, mx - mn))
+        s = c / f32(np.maximum(mx, 1))
+        rc, gc, bc = (f32(mx - ch) / c for ch in (r, g, b))
+        d = lambda a: a.astype(np.float64)
+        h = np.where(r == mx, d(bc) - d(gc), np.where(g == mx, (2.0 + d(rc)) - d(bc), (4.0 + d(gc)) - d(rc))).astype(np.float32)
+        h = np.fmod(d(h) / 6.0 + 1.0, 1.0).astype(np.float32)
+        H = np.clip((d(h) * 255.0).astype(np.int64), 0, 255)
+        S = np.clip((d(s) * 255.0).astype(np.int64), 0, 255)
+    return np.stack([np.where(flat, 0, H), np.where(flat, 0, S), mx], -1)
+
+
+def _round_u8(v):
+    """half away from zero (v >= 0 here), clipped to 0..255"""
+    lo = np.floor(v)
+    return np.clip((lo + ((v - lo) >= 0.5)).astype(np.int64), 0, 255)
+
+
+def hsv_to_rgb_oracle(x):
+    """int64 [...,3] HSV -> int64 [...,3] RGB, Pillow's"""
+    H, S, V = (x[..., k].astype(np.float64) for k in range(3))
+    t6 = H * 6.0 / 255.0
+    i = np.floor(t6)
+    f = t6 - i
+    fs = S / 255.0
+    p = _round_u8(V * (1.0 - fs))
+    q = _round_u8(V * (1.0 - fs * f))
+    t = _round_u8(V * (1.0 - fs * (1.0 - f)))
+    v = x[..., 2]
+    sextant = i.astype(np.int64) % 6
+    table = ((v, t, p), (q, v, p), (p, v, t), (p, q, v), (t, p, v), (v, p, q))
+    out = np.stack([np.choose(sextant, [row[k] for row in table]) for k in range(3)], -1)
+    return np.where((x[..., 1] == 0)[..., None], v[..., None], out)
+
+
+def hue_oracle(x, d):
+    """the hue operation with the integer shift d on int64 [...,3] pixels"""
+    hsv = rgb_to_hsv_oracle(x)
+    hsv[..., 0] = (hsv[..., 0] + int(d)) % 256
+    return hsv_to_rgb_oracle(hsv)
+
+
+def color_jitter_oracle(imgs_u8, params):
+    """The definition on the host: uint8 ndarray of the shape of ``imgs_u8`` ([V,H,W,3], [H,W,3] or more leading dimensions)."""
+    order, (b, c, s), d = _jitter_args(params)
+    imgs = _u8_np(imgs_u8, "imgs_u8")
+    V, H, W = _frames(imgs.shape)
+    out = np.empty((V, H, W, 3), np.uint8)
+    for v, img in enumerate(imgs.reshape(V, H, W, 3)):
+        x = img.astype(np.int64)
+        for op in order:
+            if op == BRIGHTNESS and b is not None:
+                x = blend_oracle(np.zeros_like(x), x, b)
+            elif op == CONTRAST and c is not None:
+                total, n = int(grey_oracle(x).sum()), H * W
+                x = blend_oracle(np.full_like(x, (2 * total + n) // (2 * n)), x, c)
+            elif op == SATURATION and s is not None:
+                x = blend_oracle(np.broadcast_to(grey_oracle(x)[..., None], x.shape), x, s)
+            elif op == HUE and d is not None:
+                x = hue_oracle(x, d)
+        out[v] = x
+    return out.reshape(imgs.shape)

@@ -198,7 +198,9 @@ def add_targets(batch):
     Reads ``target_R``, ``target_T`` [1,3,3] / [1,3,1], ``can_bounds`` [1,2,3] and either ``target_K`` [1,3,3] with the prepared view
     ``target_img`` float32 [1,H,W,3] + ``target_msk`` uint8 [1,H,W], or the raw frame ``target_img_raw`` uint8 [1,H0,W0,3],
     ``target_msk_raw`` [1,H0,W0], optional ``target_msk_cihp_raw``, ``target_K_raw`` [1,3,3], ``target_D`` [1,5], which goes through
-    ``combine_masks(border=5)`` and ``prepare_views`` (can_smpl.py:118-158, :629-660; the scaled K is used in place of target_K).
+    ``combine_masks(border=5)`` and ``prepare_views`` (can_smpl.py:118-158, :629-660; the scaled K is used in place of target_K);
+    with cfg.input_jitter == "device" and ``jitter_seed`` in the batch the raw frame first gets the colour jitter of that seed, the
+    parameter set the input views get (can_smpl.py:629-637; ``preprocess.batch_jitter``, K25).
     Optional ``patch_draws`` float64 [1,N,2]."""
     patch = cfg_get("patch")
     if not bool(patch.use_patch_sampling):
@@ -218,7 +220,9 @@ def add_targets(batch):
         from . import preprocess
         cihp = batch.get("target_msk_cihp_raw")
         m = preprocess.combine_masks(batch["target_msk_raw"][0], None if cihp is None else cihp[0], border=5)
-        imgs, msks, Ks = preprocess.prepare_views(batch["target_img_raw"], m[None], batch["target_K_raw"], batch["target_D"],
+        jitter = preprocess.batch_jitter(batch)
+        frame = batch["target_img_raw"] if jitter is None else preprocess.color_jitter(batch["target_img_raw"], jitter)
+        imgs, msks, Ks = preprocess.prepare_views(frame, m[None], batch["target_K_raw"], batch["target_D"],
                                                   mask_bkgd=bool(cfg_get("mask_bkgd", True)))
         img, msk, K = imgs[0], msks[0], Ks[0]
     draws = batch.get("patch_draws")
