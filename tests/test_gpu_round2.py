@@ -132,7 +132,7 @@ def test_range_guard_detects_and_falls_back(hip, gpu, net, log2c, kind):
     with pytest.warns(RuntimeWarning, match="fp16 hi/lo split"):
         raw = hip.network_forward(n2, *dev_args).cpu()
     try:
-        assert hip._range_fallback.get(gpu.index or 0), "context must be on the fp32 path now"
+        assert hip.guard_state(gpu)["mlp_fp32_fallback"], "context must be on the fp32 path now"
         ref = O.network_forward(_sd_of(n2), *cpu_args)
         assert torch.isfinite(raw).all()
         assert maxdiff(raw, ref) < 1e-4, kind
@@ -145,7 +145,7 @@ def test_range_guard_detects_and_falls_back(hip, gpu, net, log2c, kind):
     finally:
         # other weights -> back to the fused kernel (the guard checks them afresh)
         raw3 = hip.network_forward(net, *dev_args).cpu()
-        assert not hip._range_fallback.get(gpu.index or 0)
+        assert not hip.guard_state(gpu)["mlp_fp32_fallback"]
     assert maxdiff(raw3, O.network_forward(make_sd(), *cpu_args)) < 1e-4
 
 
@@ -159,7 +159,41 @@ def test_range_guard_flags_non_finite_inputs(hip, gpu, net):
         hip.network_forward(net, pf, *dev_args[1:])
     assert hip.last_range is not None
     hip.set_mlp_mode(1)                              # leave the fallback for the following tests
-    assert not hip._range_fallback.get(gpu.index or 0)
+    assert not hip.guard_state(gpu)["mlp_fp32_fallback"]
+
+
+def test_range_guard_switches_transhe_to_the_fp32_gemms(hip, gpu, net):
+    """Slot vit_in: an operand of TransHE's fp16-split dense layers beyond 6.0e4 is seen in the snapshot of the NEXT guarded
+    call (the slot is sticky), which warns, switches TransHE to the fp32 GEMMs, bumps both epochs once and leaves the MLP
+    alone; new TransHE weights undo it.  Every dense layer of a block reads its input behind a LayerNorm (or behind attention /
+    GELU of one), so a finite scale never reaches the operands: x 1.0e5 leaves the slot at 5.8 and x 1.0e30 at 0.31 (V = N = 1,
+    measured).  The scale is the one that takes |x| > 1.14 to inf, whose LayerNorm is NaN (bits 0x7e00 in the slot)."""
+    vit = net.ViT
+    x = torch.from_numpy(synth.smooth_noise((1, 1, 192), 32, passes=0)).to(gpu) * 3.0e38
+    assert torch.isinf(x).any()
+    pe = vit.get_PE((torch.rand(1, 1, 3, generator=torch.Generator().manual_seed(1)) * 2 - 1).to(gpu))
+    dev_args, cpu_args = _forward_case(gpu, P=600)
+    clean = {"mlp_fp32_fallback": False, "conv_fallback": False, "vit_fp32_fallback": False}
+    assert {**hip.guard_state(gpu), "epoch": None} == {**clean, "epoch": None}
+    try:
+        hip.vit_forward(vit, x, pe)
+        e0, g0 = hip.range_epoch(gpu), hip.graph_epoch()
+        with pytest.warns(RuntimeWarning, match="TransHE"):
+            raw = hip.network_forward(net, *dev_args).cpu()
+        print("range table:", [hex(v) for v in hip.last_range], "guard state:", hip.guard_state(gpu))
+        assert hip.vit_fallback(gpu)
+        assert hip.range_epoch(gpu) == e0 + 1
+        assert hip.graph_epoch() > g0
+        assert hip.guard_state(gpu) == {**clean, "vit_fp32_fallback": True, "epoch": e0 + 1}    # (the MLP itself did not trip)
+        assert torch.isfinite(raw).all()
+        assert maxdiff(raw, O.network_forward(make_sd(), *cpu_args)) < 1e-4
+    finally:
+        # new TransHE weights -> back to the fp16-split dense layers (the upload clears the sticky slot)
+        with torch.no_grad():
+            next(vit.parameters()).add_(0.0)
+        hip._sync_weights(vit, "vit")
+    assert not hip.vit_fallback(gpu)
+    assert hip.guard_state(gpu) == {**clean, "epoch": e0 + 1}
 
 
 def test_torch_default_init_vs_oracle(hip, gpu):
@@ -190,7 +224,7 @@ def test_torch_default_init_vs_oracle(hip, gpu):
     assert float(ref["acc_map"].max()) > 0.05, "degenerate frame"
     assert maxdiff(out["rgb_map"].cpu(), ref["rgb_map"]) < 1e-4
     assert maxdiff(out["acc_map"].cpu(), ref["acc_map"]) < 1e-4
-    print("default-init range table:", [hex(v) for v in hip.last_range], "fallback:", dict(hip._range_fallback))
+    print("default-init range table:", [hex(v) for v in hip.last_range], "guard state:", hip.guard_state(gpu))
 
 
 def test_bound_2d_mask_equals_oracle(hip, gpu):

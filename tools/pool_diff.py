@@ -31,7 +31,7 @@ for i in range(N):
     out = r.render_fast(b)
     torch.cuda.synchronize()
     n = int(r.last_stats["valid_samples"])
-    pool = hip._pool_cache[str(dev)]
+    pool = hip.shared_pool(dev)
     a_f = al(n * 3 * 272 * 4)
     a_h = al((n + 32) * 64 + (n // 32 + 2) * 512)
     a_pe = al(n * 256)

@@ -1741,43 +1741,20 @@ __global__ void extract_sigma_kernel(const float4* __restrict__ raw, const uint8
 
 size_t th_sigma_grid_workspace_bytes(const th_frame* f, int P) { return shade_ws_bytes(f, P, P); }
 
-int th_eval_sigma_grid(th_ctx* c, const th_frame* f, const float* pts, int P, float* sigma_out, void* ws,
-                       size_t ws_bytes, void* pool, size_t pool_bytes, int64_t* stats_host, th_stream stream) {
-    TH_REQUIRE(c && f && pts && sigma_out && ws, "null argument");
-    TH_TRY(frame_ok(f));
-    hipStream_t s = (hipStream_t)stream;
-    if (P <= 0) return 0;
-    ShadeWs w;
-    TH_TRY(carve_shade_ws(f, P, P, ws, ws_bytes, w));
-    ThPointSrc ps{};
-    ps.pts = pts; ps.R = P; ps.S = 1;
-    TH_TRY(compact_ok(c, f));
-    if (pool != nullptr) c->after_shade_valid = false;      // (the pool's last user from here on: see th_render_rays)
-    HullCounts k;
-    TH_TRY(hull_stage(c, f, ps, P, false, w, s));
-    TH_TRY(counts_now(c, w, stats_host, s, &k));
-    TH_TRY(complete_map(c, f, nullptr, k, s));
-    TH_TRY(shade_stage(c, f, ps, false, w, nullptr, k, pool, pool_bytes, s));
-    hipLaunchKernelGGL(extract_sigma_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, (const float4*)w.raw, w.mask, (long long)P,
-                       sigma_out);
-    TH_LAUNCH_CHECK();
-    const int snap = th_range_snapshot(c, stream);
-    TH_REQUIRE(snap >= 0, "range snapshot failed");
-    if (stats_host) stats_host[2] = snap;
-    return 0;
-}
-
 __global__ void extract_raw_kernel(const float4* __restrict__ raw, const uint8_t* __restrict__ mask, long long P,
                                    float4* __restrict__ out) {
     long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (i < P) out[i] = mask[i] ? raw[i] : make_float4(0.f, 0.f, 0.f, 0.f);      // (raw is only written where shaded)
 }
 
-// th_eval_sigma_grid's sibling with the RGB branch: the point mode of hull_stage / shade_stage with the progressive branch
-// (rgb_all 0) and a view embedding per point.  Same workspace, pool, range snapshot and map completion.
-int th_eval_points(th_ctx* c, const th_frame* f, const float* pts, const float* dirs, int P, float* raw_out, void* ws,
-                   size_t ws_bytes, void* pool, size_t pool_bytes, int64_t* stats_host, th_stream stream) {
-    TH_REQUIRE(c && f && pts && raw_out && ws, "null argument");
+// The point mode of hull_stage / shade_stage behind both entry points below.  `rgb` false: the sigma grid (out = P floats);
+// true: th_eval_points -- the progressive RGB branch (rgb_all 0) with a view embedding per point (out = P float4).
+// `entry`: the exported function's name, for its error texts.
+static int eval_point_mode(const char* entry, th_ctx* c, const th_frame* f, const float* pts, const float* dirs, int P, bool rgb,
+                           float* out, void* ws, size_t ws_bytes, void* pool, size_t pool_bytes, int64_t* stats_host,
+                           th_stream stream) {
+    auto fail = [entry](const char* msg) { th_set_error(std::string(entry) + ": " + msg); return -1; };
+    if (!(c && f && pts && out && ws)) return fail("null argument");
     TH_TRY(frame_ok(f));
     hipStream_t s = (hipStream_t)stream;
     if (P <= 0) return 0;
@@ -1792,14 +1769,28 @@ int th_eval_points(th_ctx* c, const th_frame* f, const float* pts, const float* 
     if (dirs != nullptr) TH_TRY(th_view_embed_launch(dirs, P, 4, w.vd_all, s));      // (one row per point; null: zero rows, :62)
     TH_TRY(counts_now(c, w, stats_host, s, &k));
     TH_TRY(complete_map(c, f, nullptr, k, s));
-    TH_TRY(shade_stage(c, f, ps, false, w, nullptr, k, pool, pool_bytes, s, true, dirs != nullptr ? w.vd_all : nullptr));
-    hipLaunchKernelGGL(extract_raw_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, (const float4*)w.raw, w.mask, (long long)P,
-                       (float4*)raw_out);
+    TH_TRY(shade_stage(c, f, ps, false, w, nullptr, k, pool, pool_bytes, s, rgb, dirs != nullptr ? w.vd_all : nullptr));
+    if (rgb)
+        hipLaunchKernelGGL(extract_raw_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, (const float4*)w.raw, w.mask, (long long)P,
+                           (float4*)out);
+    else
+        hipLaunchKernelGGL(extract_sigma_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, (const float4*)w.raw, w.mask,
+                           (long long)P, out);
     TH_LAUNCH_CHECK();
     const int snap = th_range_snapshot(c, stream);
-    TH_REQUIRE(snap >= 0, "range snapshot failed");
+    if (snap < 0) return fail("range snapshot failed");
     if (stats_host) stats_host[2] = snap;
     return 0;
+}
+
+int th_eval_sigma_grid(th_ctx* c, const th_frame* f, const float* pts, int P, float* sigma_out, void* ws,
+                       size_t ws_bytes, void* pool, size_t pool_bytes, int64_t* stats_host, th_stream stream) {
+    return eval_point_mode(__func__, c, f, pts, nullptr, P, false, sigma_out, ws, ws_bytes, pool, pool_bytes, stats_host, stream);
+}
+
+int th_eval_points(th_ctx* c, const th_frame* f, const float* pts, const float* dirs, int P, float* raw_out, void* ws,
+                   size_t ws_bytes, void* pool, size_t pool_bytes, int64_t* stats_host, th_stream stream) {
+    return eval_point_mode(__func__, c, f, pts, dirs, P, true, raw_out, ws, ws_bytes, pool, pool_bytes, stats_host, stream);
 }
 
 // ---- K23: the backward of the encoder trunk (k_encoder_bwd.hip) ----

@@ -8,6 +8,7 @@ the shared library is missing or a call fails this module raises.
 import ctypes as C
 import os
 import sys
+import warnings
 
 import torch
 
@@ -28,7 +29,6 @@ ThLinear, ThMlpWeights, ThVitBlock, ThPoints, ThSmplModel, ThMapSource, ThFrame 
                             "th_frame"))
 
 _lib = None
-_ctx = {}
 
 
 class HipError(RuntimeError):
@@ -61,8 +61,8 @@ def _check(rc):
         raise HipError(_lib.th_last_error().decode())
 
 
-_ctx_by_device = {}      # torch.device with an explicit index -> handle (the per-call path: no torch.cuda queries)
 _have_gpu = None
+_NO_GPU = "no HIP device visible: the TransHuman hot path needs an MI355X (gfx950)"
 
 
 def _gpu_visible():
@@ -74,21 +74,49 @@ def _gpu_visible():
     return _have_gpu
 
 
+class DeviceState:
+    """Everything this module keeps about ONE device; found through _state() only."""
+    def __init__(self, index):
+        self.index, self.handle = index, None       # (handle: the th_ctx*, created by ctx())
+        # what the caller asked for through set_mlp_mode / set_vit_mode, set_tex_rows, set_fused_waves (None = never: the default)
+        self.mode, self.tex_rows, self.fused_waves = {"mlp": None, "vit": None}, None, None
+        # what the range guard has switched until new weights: per-layer fp32 MLP launches, stock stem convolutions, fp32 TransHE GEMMs
+        self.fallback = {"mlp": False, "conv": False, "vit": False}
+        self.epoch = 0                   # number of switches so far (frames queued earlier are re-rendered)
+        self.owner = {}                  # "mlp" / "vit" -> (weakref to the module whose weights the ctx holds, version tuple)
+        self.workspaces, self.pools = {}, {}   # slot -> render workspace (_cached_ws) / shading pool, None: the shared one (_shade_pool)
+
+
+_states = {}      # device index -> DeviceState; a torch.device that carried an index is kept as a second key of its record
+
+
+def _state(device=None):
+    """The record of ``device``: None, an index, "cuda", "cuda:1" or a torch.device; without an index: the current device."""
+    st = _states.get(device)             # (the per-call path: one lookup, no torch.cuda query)
+    if st is None:
+        index = device if isinstance(device, int) else None if device is None else torch.device(device).index
+        if index is None:
+            if not _gpu_visible():
+                raise HipError(_NO_GPU)
+            index = torch.cuda.current_device()
+        st = _states.get(index) or _states.setdefault(index, DeviceState(index))
+        if isinstance(device, torch.device) and device.index is not None:
+            _states[device] = st
+    return st
+
+
 def ctx(device=None):
-    h = _ctx_by_device.get(device) if device is not None else None
-    if h is not None:
-        return h
-    lib = load_library()
-    if not _gpu_visible():
-        raise HipError("no HIP device visible: the TransHuman hot path needs an MI355X (gfx950)")
-    dev = torch.cuda.current_device() if device is None else torch.device(device).index or 0
-    if dev not in _ctx:
-        h = C.c_void_p()
-        _check(lib.th_ctx_create(dev, C.byref(h)))
-        _ctx[dev] = h
-    if isinstance(device, torch.device) and device.index is not None:
-        _ctx_by_device[device] = _ctx[dev]
-    return _ctx[dev]
+    st = _states.get(device)
+    if st is None or st.handle is None:
+        lib = load_library()
+        if not _gpu_visible():
+            raise HipError(_NO_GPU)
+        st = _state(device)
+        if st.handle is None:
+            h = C.c_void_p()
+            _check(lib.th_ctx_create(st.index, C.byref(h)))
+            st.handle = h
+    return st.handle
 
 
 def _stream():
@@ -163,13 +191,12 @@ def set_vit_weights(vit):
                                   _stream()))
 
 
-_ctx_owner = {}        # (device index, kind) -> (weakref to the module whose weights the ctx holds, version tuple)
 _param_lists = {}      # id(module) -> [weakref(module), parameter list, calls since the last walk]
 
 
 def _sync_weights(mod, kind):
     """Re-upload when the device context does not hold THIS module's current weights: a th_ctx has one MLP and
-    one ViT weight image per device, so ownership is tracked per (device, kind) -- rendering with net A, then
+    one ViT weight image per device, so ownership is tracked per device and kind -- rendering with net A, then
     net B, then A again re-uploads A (a cache keyed by id(module) alone would find A's old version tuple and
     shade A with B's weights; the same for a new module that lands on a freed module's id()).  Any parameter
     change (load_state_dict, .cuda(), optimiser step) bumps the version tuple.
@@ -179,7 +206,7 @@ def _sync_weights(mod, kind):
     310-tensor Network: the walk used to leave the GPU idle in front of the per-sample stage)."""
     import weakref
     if not _gpu_visible():
-        raise HipError("no HIP device visible: the TransHuman hot path needs an MI355X (gfx950); there is no CPU fallback")
+        raise HipError(_NO_GPU + "; there is no CPU fallback")
     ent = _param_lists.get(id(mod))
     if ent is None or ent[0]() is not mod or ent[2] >= 256:
         ent = [weakref.ref(mod), list(mod.parameters()), 0]
@@ -191,8 +218,8 @@ def _sync_weights(mod, kind):
     pl = ent[1]
     ver = (tuple(p._version for p in pl), pl[0].data_ptr(), pl[-1].data_ptr(), len(pl))
     dev = pl[0].device
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), kind)
-    own = _ctx_owner.get(key)
+    st = _state(dev)
+    own = st.owner.get(kind)
     if own is None or own[0]() is not mod or own[1] != ver:
         # The context's packed weight image is rewritten in place on the CURRENT stream.  Frame pipelines call this from a
         # side stream while kernels of earlier frames may still read the image on the shading stream (and the other way
@@ -201,19 +228,15 @@ def _sync_weights(mod, kind):
         if own is not None:
             torch.cuda.synchronize(dev)
         (set_mlp_weights if kind == "mlp" else set_vit_weights)(mod)
-        _ctx_owner[key] = (weakref.ref(mod), ver)
+        st.owner[kind] = (weakref.ref(mod), ver)
         if kind == "vit":
             _vit_graph_epoch[0] += 1
         # new weights: back to the modes the caller asked for (the guard re-checks them).  The Network's parameter set
         # includes the encoder, so the stem convolutions return to the HIP kernels with it (th_set_mlp_weights clears
         # their sticky range slot, th_set_vit_weights TransHE's).
+        _restore(st, kind)
         if kind == "mlp":
-            if _range_fallback.pop(key[0], None):
-                _check(load_library().th_set_mlp_mode(ctx(dev), _user_mode.get(key[0], 1)))
-            _conv_fallback.pop(key[0], None)
-        elif _vit_fallback.pop(key[0], None):
-            _vit_graph_epoch[0] += 1
-            _check(load_library().th_set_vit_mode(ctx(dev), _user_vit_mode.get(key[0], 1)))
+            _restore(st, "conv")
 
 
 # ---------------------------------------------------------------------------
@@ -223,36 +246,29 @@ RANGE_NAMES = ("f", "s", "p", "n", "inter", "fc4_in", "conv_in", "vit_in")
 RANGE_FP16_LIMIT = _H.constants["TH_RANGE_FP16_LIMIT"]     # 6.0e4 as an fp16 bit pattern (inf / NaN are larger)
 RANGE_FP16_FLOOR = _H.constants["TH_RANGE_FP16_FLOOR"]     # 2^-6
 RANGE_FP32_LIMIT = 0x476A6000      # 6.0e4 as an fp32 bit pattern (slot conv_in)
-_user_mode = {}                    # device index -> mode requested through set_mlp_mode (default 1)
-_range_fallback = {}               # device index -> True while the guard forces mode 0 on this context
-_range_epoch = {}                  # device index -> number of fallbacks so far (frames queued earlier are re-rendered)
-_conv_fallback = {}                # device index -> True once the stem convolutions' input left the fp16 range: stock convolutions
-_user_vit_mode = {}                # device index -> the TransHE mode the caller asked for (set_vit_mode): restored with new weights
-_vit_fallback = {}                 # device index -> True once an operand of TransHE's fp16-split GEMMs left the fp16 range: fp32 MFMA GEMMs
 last_range = None                  # the last table read (debugging / tests)
-
-
-def _dev_index(device):
-    return torch.device(device).index if device is not None and torch.device(device).index is not None \
-        else torch.cuda.current_device()
 
 
 def conv_fallback(device=None):
     """True while the stem convolutions of this device run through the stock modules (range guard)."""
-    return bool(_conv_fallback.get(_dev_index(device)))
+    return _state(device).fallback["conv"]
 
 
 def vit_fallback(device=None):
     """True while TransHE's dense layers of this device run on the fp32 MFMA GEMMs (range guard)."""
-    return bool(_vit_fallback.get(_dev_index(device)))
+    return _state(device).fallback["vit"]
 
 
 def guard_state(device=None):
     """What the range guard has switched on this device: every entry False = the fast paths are in use (a tripped MLP
     guard means per-layer fp32 MFMA launches, ~7x slower frames)."""
-    d = _dev_index(device)
-    return {"mlp_fp32_fallback": bool(_range_fallback.get(d)), "conv_fallback": bool(_conv_fallback.get(d)),
-            "vit_fp32_fallback": bool(_vit_fallback.get(d)), "epoch": _range_epoch.get(d, 0)}
+    st = _state(device)
+    return {"mlp_fp32_fallback": st.fallback["mlp"], "conv_fallback": st.fallback["conv"],
+            "vit_fp32_fallback": st.fallback["vit"], "epoch": st.epoch}
+
+
+def range_epoch(device=None):
+    return _state(device).epoch
 
 
 def range_read(slot, device=None):
@@ -280,35 +296,58 @@ def range_verdict(vals):
     return "; ".join(bad) if bad else None
 
 
-def _conv_range_bad(vals):
-    return vals[6] >= RANGE_FP32_LIMIT
+def range_trips(vals, fallback):
+    """The switches the range table ``vals`` (8 words) trips on a device whose switches stand as ``fallback`` says, one that is
+    set already left out: [(kind, text of the warning)] in the order the warnings appear.  No library call, no torch call."""
+    trips = []
+    if vals[7] >= RANGE_FP16_LIMIT and not fallback["vit"]:
+        trips.append(("vit", "an operand of TransHE's dense layers left the fp16 range; using the fp32 MFMA GEMMs until new "
+                             "weights are uploaded"))
+    if vals[6] >= RANGE_FP32_LIMIT and not fallback["conv"]:
+        trips.append(("conv", "the ResNet-stem convolution input left the fp16 range; using the stock convolutions until new "
+                              "weights are uploaded"))
+    why = range_verdict(vals)
+    if why is not None and not fallback["mlp"]:
+        trips.append(("mlp", "activations left the range of the fp16 hi/lo split MFMA kernel (" + why + "); re-rendering and "
+                             "continuing on the per-layer fp32 MFMA path for these weights"))
+    return trips
 
 
-def _enter_fallback(device, why):
-    """Force the per-layer fp32 MFMA form of the MLP on this device until new weights are uploaded."""
-    import warnings
-    d = _dev_index(device)
-    warnings.warn("transhuman_amd: activations left the range of the fp16 hi/lo split MFMA kernel (" + why +
-                  "); re-rendering and continuing on the per-layer fp32 MFMA path for these weights", RuntimeWarning)
-    _check(load_library().th_set_mlp_mode(ctx(device), 0))
-    _range_fallback[d] = True
-    _range_epoch[d] = _range_epoch.get(d, 0) + 1
+def _set_mode(st, kind, mode):
+    _check(getattr(load_library(), "th_set_%s_mode" % kind)(ctx(st.index), mode))
+    if kind == "vit":
+        _vit_graph_epoch[0] += 1         # (captured TransHE graphs hold the other arithmetic)
+
+
+def _trip(st, kind, text):
+    """The one place a switch is set ("conv" has no mode in the library: conv2d_supported asks the flag)."""
+    warnings.warn("transhuman_amd: " + text, RuntimeWarning)
+    if kind != "conv":
+        _set_mode(st, kind, 0)
+    st.fallback[kind] = True
+    st.epoch += 1
+
+
+def _restore(st, kind, mode=None):
+    """The one place a switch is cleared.  ``mode`` None: new weights, a tripped switch goes back to the mode the caller asked for.
+    Else the caller asks for ``mode`` now; TransHE's fp32 form leaves a tripped switch standing (its slot is sticky)."""
+    if mode is not None:
+        _set_mode(st, kind, mode)
+        st.mode[kind] = mode
+        if kind == "vit" and mode == 0:
+            return
+    elif st.fallback[kind] and kind != "conv":
+        _set_mode(st, kind, 1 if st.mode[kind] is None else st.mode[kind])
+    st.fallback[kind] = False
 
 
 def force_conv_fallback(device, why):
     """Switch the stem convolutions of this device to the stock modules (what the range guard does when slot conv_in trips)
     on evidence from outside the context's own range table -- e.g. non-finite stem latents received from another rank
     (dist.StemExchange).  Bumps the epoch: frames built before are rebuilt."""
-    import warnings
-    d = _dev_index(device)
-    if not _conv_fallback.get(d):
-        warnings.warn("transhuman_amd: " + why + "; using the stock convolutions until new weights are uploaded", RuntimeWarning)
-        _conv_fallback[d] = True
-        _range_epoch[d] = _range_epoch.get(d, 0) + 1
-
-
-def range_epoch(device=None):
-    return _range_epoch.get(_dev_index(device), 0)
+    st = _state(device)
+    if not st.fallback["conv"]:
+        _trip(st, "conv", why + "; using the stock convolutions until new weights are uploaded")
 
 
 def _guard(device, slot):
@@ -322,29 +361,24 @@ def _guard(device, slot):
     vals = range_read(slot, device)
     if vals is None:             # overwritten snapshot: the frame is unchecked -> render it again (its own snapshot is read at once)
         return False
-    d = _dev_index(device)
-    ok = True
-    if vals[7] >= RANGE_FP16_LIMIT and not _vit_fallback.get(d):
-        import warnings
-        warnings.warn("transhuman_amd: an operand of TransHE's dense layers left the fp16 range; using the fp32 MFMA "
-                      "GEMMs until new weights are uploaded", RuntimeWarning)
-        _check(load_library().th_set_vit_mode(ctx(device), 0))
-        _vit_graph_epoch[0] += 1
-        _vit_fallback[d] = True
-        _range_epoch[d] = _range_epoch.get(d, 0) + 1
-        ok = False
-    if _conv_range_bad(vals) and not _conv_fallback.get(d):
-        import warnings
-        warnings.warn("transhuman_amd: the ResNet-stem convolution input left the fp16 range; using the stock "
-                      "convolutions until new weights are uploaded", RuntimeWarning)
-        _conv_fallback[d] = True
-        _range_epoch[d] = _range_epoch.get(d, 0) + 1
-        ok = False
-    why = range_verdict(vals)
-    if why is not None and not _range_fallback.get(d):
-        _enter_fallback(device, why)
-        ok = False
-    return ok
+    st = _state(device)
+    trips = range_trips(vals, st.fallback)
+    for kind, text in trips:
+        _trip(st, kind, text)
+    return not trips
+
+
+def _guarded(device, launch, launches, frame=None, check_last=True):
+    """``launch(frame, i)`` queues try ``i`` and returns its snapshot id.  A snapshot that is not clean (or was overwritten before
+    it could be read) means the paths the guard switched are in effect now: the frame's constants are built again if the stem or
+    TransHE was switched, and the next try's snapshot is checked too -- bounded by ``launches``: every switch is one-way, three
+    cover MLP + stem + TransHE tripping one after the other.  ``check_last`` False: the last try's snapshot is left unread."""
+    for i in range(launches):
+        slot = launch(frame, i)
+        if (i + 1 == launches and not check_last) or _guard(device, slot):
+            break
+        if frame is not None and frame.rebuild is not None and (conv_fallback(device) or vit_fallback(device)):
+            frame = frame.rebuild()
 
 
 # ---------------------------------------------------------------------------
@@ -769,7 +803,7 @@ def _vit_forward_graphed(vit, x, pe):
     if os.environ.get("TH_VIT_GRAPH", "1") == "0" or _graphs_off[0] or (torch.is_grad_enabled() and x.requires_grad):
         return None
     key = (id(vit), tuple(x.shape), str(x.device))
-    ver = (_vit_graph_epoch[0], pe.data_ptr(), _ctx_owner.get((_dev_index(x.device), "vit"), (None, None))[1])
+    ver = (_vit_graph_epoch[0], pe.data_ptr(), _state(x.device).owner.get("vit", (None, None))[1])
     st = _vit_graphs.get(key)
     if st is not None and st.get("eager_only"):
         st["same"] = st["same"] + 1 if st["ver"] == ver else 0          # (a version that has settled gets its graphs back)
@@ -1405,11 +1439,11 @@ def network_forward(net, pixel_feat, viewdir, pts_smpl, centres, rot, tokens, ma
     if P == 0:
         return raw
     ws = _ws(lib.th_network_workspace_bytes(V, P), pf.device)
-    for _ in range(3):
+    def launch(_frame, _i):
         _check(lib.th_network_forward(ctx(pf.device), _p(pf), _p(vd), _p(ps), _p(m), P, _p(c), _p(r), _p(t), V, t.shape[1],
                                       _p(raw), _p(ws), ws.numel(), _stream()))
-        if _guard(pf.device, lib.th_range_last_slot(ctx(pf.device))):
-            break                                    # (else: the context is on the fp32 path now -- run again)
+        return lib.th_range_last_slot(ctx(pf.device))
+    _guarded(pf.device, launch, 3)                   # (a switch: the context is on the fp32 path now -- run again)
     return raw
 
 
@@ -1943,22 +1977,16 @@ class Frame:
         self.c.tokens = self.tokens.data_ptr()
 
 
-_ws_cache = {}
-
-
 def _cached_ws(nbytes, device, slot=0):
     """Render workspace, grown on demand.  ``slot`` selects one of several independent workspaces (the frame
     pipeline of Renderer.render_sequence runs the hull stage of frame i+1 while frame i is still shading)."""
-    key = (str(device), slot)
-    cur = _ws_cache.get(key)
+    cache = _state(device).workspaces
+    cur = cache.get(slot)
     if cur is None or cur.numel() < nbytes:
-        _ws_cache[key] = None
+        cache[slot] = None
         cur = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-        _ws_cache[key] = cur
+        cache[slot] = cur
     return cur
-
-
-_pool_cache = {}
 
 
 def _shade_pool(frame_c, n_valid, with_pregather, device, slot=None):
@@ -1968,15 +1996,20 @@ def _shade_pool(frame_c, n_valid, with_pregather, device, slot=None):
     need = int(load_library().th_shade_pool_bytes(ctx(device), C.byref(frame_c), int(n_valid), int(with_pregather)))
     # (slot: a frame pipeline that forms the NEXT frame's records while this frame shades gives every frame in flight a pool of
     # its own -- Renderer.render_sequence; None: the context's one shared pool)
-    key = str(device) if slot is None else (str(device), int(slot))
-    cur = _pool_cache.get(key)
+    cache, key = _state(device).pools, None if slot is None else int(slot)
+    cur = cache.get(key)
     if cur is None or cur.numel() < need:
-        _pool_cache[key] = None
+        cache[key] = None
         # (headroom: frames of a sequence differ by a few per cent; a pool that grows every other frame would thrash)
         cur = torch.empty(int(need * 1.0625) + 4096, dtype=torch.uint8, device=device)
-        _pool_cache[key] = cur
+        cache[key] = cur
     cur.record_stream(torch.cuda.current_stream(device))
     return cur
+
+
+def shared_pool(device=None):
+    """the context's shared shading pool as it is cached now (a uint8 device tensor), or None"""
+    return _state(device).pools.get(None)
 
 
 def _prepass_counts(ws, device):
@@ -1993,13 +2026,9 @@ def drop_workspaces(device=None):
     """Forget the cached render workspaces and the shading pool (GBs at full frame size) -- e.g. between unrelated
     workloads of one process; pending prepasses of those workspaces are cancelled."""
     lib = load_library()
-    for key in list(_pool_cache.keys()):
-        dev = key if isinstance(key, str) else key[0]
-        if device is None or str(device) == dev:
-            _pool_cache.pop(key, None)
-    for (dev, _slot) in list(_ws_cache.keys()):
-        if device is None or str(device) == dev:
-            _ws_cache.pop((dev, _slot), None)
+    for st in (set(_states.values()) if device is None else [_state(device)]):
+        st.pools.clear()
+        st.workspaces.clear()
     try:
         _check(lib.th_render_prepass_cancel(ctx(device)))
     except HipError:
@@ -2115,52 +2144,55 @@ def render_rays(net, frame, points, white_bkgd=False, defer_guard=False, small_f
         ws = _cached_ws(need, dev)
         _check(lib.th_render_prepass_drop(ctx(dev), _p(ws)))  # a token queued there for other (possibly freed) rays
     points._pregathered = False
-    # the shading pool: sized from the valid-sample count when a prepass has put it on the host, else for the chunk
-    # buffers only (the count bounds the chunk, not the pool)
-    stats = (C.c_int64 * 4)()
+    stats, st = (C.c_int64 * 4)(), {}
 
-    def shade(pool):                             # (reads ``fc`` as it is when called) -> statistics, range-guard slot
+    def shade(fr, i):                            # try i on frame ``fr`` -> range-guard slot; the statistics into ``st``
+        nonlocal fc, n_bound, pre
+        if i > 0:
+            if fr is not frame:                  # rebuilt (the guard switched the stem / TransHE): this call's R' threshold again
+                keep_sfr, fc = fc.small_frame_rays, ThFrame.from_buffer_copy(fr.c)
+                fc.small_frame_rays = keep_sfr
+            _check(lib.th_render_prepass_drop(ctx(dev), _p(ws)))
+            n_bound, pre = st["valid_samples"], False      # (the guard may have changed the mode: other row formats)
+        # the shading pool: sized from the valid-sample count when a prepass (or an earlier try) has put it on the host, else
+        # for the chunk buffers only (the count bounds the chunk, not the pool)
+        pool = _shade_pool(fc, n_bound, pre, dev, pool_slot)
         _check(lib.th_render_rays(ctx(dev), C.byref(fc), C.byref(points.c), _p(rgb), _p(acc), _p(dep), int(white_bkgd),
                                   _p(ws), ws.numel(), _p(pool), pool.numel(), stats, _stream()))
-        return dict(hit_rays=stats[0], valid_samples=stats[1], unmasked=stats[3]), int(stats[2])
-    st, slot = shade(_shade_pool(fc, n_bound, pre, dev, pool_slot))
+        st.update(hit_rays=stats[0], valid_samples=stats[1], unmasked=stats[3])
+        return int(stats[2])
     if defer_guard:
+        slot = shade(frame, 0)
         return rgb, acc, dep, st, (lambda: _guard(dev, slot))
-    # a snapshot that is not clean (or was overwritten before it could be read) -> the paths the guard switched are in
-    # effect now: render again and check THAT frame's snapshot too (bounded: every switch is one-way, three tries cover
-    # MLP + stem + TransHE tripping one after the other)
-    for _ in range(3):
-        if _guard(dev, slot):
-            break
-        if (conv_fallback(dev) or vit_fallback(dev)) and frame.rebuild is not None:
-            frame = frame.rebuild()                  # frame constants again, through the stock convolutions
-            keep_sfr = fc.small_frame_rays
-            fc = ThFrame.from_buffer_copy(frame.c)
-            fc.small_frame_rays = keep_sfr
-        _check(lib.th_render_prepass_drop(ctx(dev), _p(ws)))
-        st, slot = shade(_shade_pool(fc, st["valid_samples"], False, dev, pool_slot))   # (the guard may have changed the mode: other row formats)
+    _guarded(dev, shade, 4, frame, check_last=False)
     return rgb, acc, dep, st
 
 
-def eval_sigma_grid(net, frame, pts):
+def _eval_point_mode(net, frame, pts, dirs, rgb):
+    """the body of eval_sigma_grid (``rgb`` False: out [P]) and eval_points (True: out [P,4])"""
     lib = load_library()
     _sync_weights(net, "mlp")
     p = _f32(pts).reshape(-1, 3)
     P = p.shape[0]
-    out = torch.empty(P, dtype=torch.float32, device=p.device)
+    d = None if dirs is None else _f32(dirs).reshape(-1, 3)
+    assert d is None or (d.shape[0] == P and d.device == p.device), "one direction per point, on the points' device"
+    out = torch.empty((P, 4) if rgb else P, dtype=torch.float32, device=p.device)
     if P == 0:
         return out, dict(valid_samples=0)
     ws = _cached_ws(lib.th_sigma_grid_workspace_bytes(C.byref(frame.c), P), p.device)
     stats = (C.c_int64 * 4)()
-    for _ in range(3):
-        pool = _shade_pool(frame.c, P, False, p.device)        # (inside the loop: the guard may have changed the mode)
-        _check(lib.th_eval_sigma_grid(ctx(p.device), C.byref(frame.c), _p(p), P, _p(out), _p(ws), ws.numel(), _p(pool),
-                                      pool.numel(), stats, _stream()))
-        if _guard(p.device, int(stats[2])):
-            break
-        if (conv_fallback(p.device) or vit_fallback(p.device)) and frame.rebuild is not None:
-            frame = frame.rebuild()
+
+    def launch(fr, _i):
+        pool = _shade_pool(fr.c, P, False, p.device)           # (per try: the guard may have changed the mode)
+        fn, head = (lib.th_eval_points, (_p(p), _p(d), P)) if rgb else (lib.th_eval_sigma_grid, (_p(p), P))
+        _check(fn(ctx(p.device), C.byref(fr.c), *head, _p(out), _p(ws), ws.numel(), _p(pool), pool.numel(), stats, _stream()))
+        return int(stats[2])
+    _guarded(p.device, launch, 3, frame)
     return out, dict(valid_samples=stats[1])
+
+
+def eval_sigma_grid(net, frame, pts):
+    return _eval_point_mode(net, frame, pts, None, False)
 
 
 def eval_points(net, frame, pts, dirs=None):
@@ -2168,28 +2200,7 @@ def eval_points(net, frame, pts, dirs=None):
     on the device) or None (the zero embedding rows of if_mesh_renderer.py:62) -> (raw fp32 [P,4] = rgb logits + sigma_raw, stats).
     Rows outside the hull are exactly 0; inside, sigma everywhere and the RGB logits where sigma > 0 (0 elsewhere).  Same guard
     and retry as eval_sigma_grid."""
-    lib = load_library()
-    _sync_weights(net, "mlp")
-    p = _f32(pts).reshape(-1, 3)
-    P = p.shape[0]
-    d = None
-    if dirs is not None:
-        d = _f32(dirs).reshape(-1, 3)
-        assert d.shape[0] == P and d.device == p.device, "one direction per point, on the points' device"
-    out = torch.empty((P, 4), dtype=torch.float32, device=p.device)
-    if P == 0:
-        return out, dict(valid_samples=0)
-    ws = _cached_ws(lib.th_sigma_grid_workspace_bytes(C.byref(frame.c), P), p.device)
-    stats = (C.c_int64 * 4)()
-    for _ in range(3):
-        pool = _shade_pool(frame.c, P, False, p.device)        # (inside the loop: the guard may have changed the mode)
-        _check(lib.th_eval_points(ctx(p.device), C.byref(frame.c), _p(p), _p(d), P, _p(out), _p(ws), ws.numel(), _p(pool),
-                                  pool.numel(), stats, _stream()))
-        if _guard(p.device, int(stats[2])):
-            break
-        if (conv_fallback(p.device) or vit_fallback(p.device)) and frame.rebuild is not None:
-            frame = frame.rebuild()
-    return out, dict(valid_samples=stats[1])
+    return _eval_point_mode(net, frame, pts, dirs, True)
 
 
 def set_tok_gather(on, device=None):
@@ -2199,23 +2210,24 @@ def set_tok_gather(on, device=None):
     _check(load_library().th_set_tok_gather(ctx(device), 1 if on else 0))
 
 
-_tex_rows = {}                     # device index -> mode set through set_tex_rows (default: env TH_ROWS_TEX, else on)
+def _asked(device, name, default):
+    """what set_<name> last chose on this device, else ``default`` (nothing set anywhere: no CUDA call on a host without one)"""
+    if all(getattr(st, name) is None for st in _states.values()):
+        return default
+    v = getattr(_state(device), name)
+    return default if v is None else v
 
 
 def tex_rows_enabled(device=None):
     """Whether new frames of this device's context take the texel hand-over (include/transhuman_hip.h: th_set_tex_rows); it
     applies to the fused path on frames with a split map (Renderer.prepare_frame's default)."""
-    if _tex_rows:                      # (only a set_tex_rows call needs the device: no CUDA call on a host without one)
-        d = _dev_index(device)
-        if d in _tex_rows:
-            return _tex_rows[d]
-    return os.environ.get("TH_ROWS_TEX", "1")[:1] != "0"
+    return _asked(device, "tex_rows", os.environ.get("TH_ROWS_TEX", "1")[:1] != "0")
 
 
 def mlp_is_fused(device=None):
     """the fused fp16-split kernel shades this device's frames (mode 1 requested and the range guard has not switched it off)"""
-    d = _dev_index(device)
-    return _user_mode.get(d, 1) == 1 and not _range_fallback.get(d)
+    st = _state(device)
+    return st.mode["mlp"] in (None, 1) and not st.fallback["mlp"]
 
 
 def set_tex_rows(on, device=None):
@@ -2223,33 +2235,24 @@ def set_tex_rows(on, device=None):
     copies the distinct texels into LDS and blends them itself (same operand bits, 160 B instead of 3.3 KB per sample through
     HBM); False = K5 writes the rows.  The shading pool is sized per mode (cached pools are re-made on demand)."""
     _check(load_library().th_set_tex_rows(ctx(device), 1 if on else 0))
-    _tex_rows[_dev_index(device)] = bool(on)
+    _state(device).tex_rows = bool(on)
 
 
 def set_mlp_mode(mode, device=None):
     """1 = fused fp16-split MFMA kernel (default), 0 = layer-by-layer fp32 MFMA GEMMs."""
-    _check(load_library().th_set_mlp_mode(ctx(device), int(mode)))
-    d = _dev_index(device)
-    _user_mode[d] = int(mode)
-    _range_fallback.pop(d, None)
-
-
-_fused_waves = {}
+    _restore(_state(device), "mlp", int(mode))
 
 
 def set_fused_waves(waves, device=None):
     """Form of the fused MLP kernel on the frame-level path: 8 = two waves per SIMD (512-thread workgroups, default), 4 = the
     256-thread form of rounds 2-5."""
     _check(load_library().th_set_fused_waves(ctx(device), int(waves)))
-    _fused_waves[_dev_index(device)] = int(waves)
+    _state(device).fused_waves = int(waves)
 
 
 def fused_waves(device=None):
     """what set_fused_waves last chose on this device (default: TH_FUSED_WAVES, else 8)"""
-    dflt = 4 if os.environ.get("TH_FUSED_WAVES", "8")[:1] == "4" else 8
-    if device is None and not torch.cuda.is_available():
-        return dflt
-    return _fused_waves.get(_dev_index(device), dflt)
+    return _asked(device, "fused_waves", 4 if os.environ.get("TH_FUSED_WAVES", "8")[:1] == "4" else 8)
 
 
 def set_chunk_samples(n):
@@ -2297,9 +2300,4 @@ def host_wait_read(device=None):
 
 def set_vit_mode(mode, device=None):
     """th_set_vit_mode: 0 = TransHE's dense layers on the fp32 MFMA GEMMs, 1 (default) = fp16-split arithmetic."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    _check(load_library().th_set_vit_mode(ctx(dev), int(mode)))
-    _vit_graph_epoch[0] += 1
-    _user_vit_mode[_dev_index(dev)] = int(mode)
-    if int(mode) != 0:
-        _vit_fallback.pop(_dev_index(dev), None)
+    _restore(_state(device), "vit", int(mode))
