@@ -1,5 +1,5 @@
-"""The training form of the per-point network on the device (K20): th_linear_relu_forward / th_linear_relu_bwd,
-th_xview_attention / th_xview_attention_bwd (k_pointnet_bwd.hip), train_ops.ReluLinearFn / CrossViewAttentionFn,
+"""The training form of the per-point network on the device (K20): th_linear_relu_forward / th_linear_relu_bwd
+(k_vit_dense_bwd.hip), th_xview_attention / th_xview_attention_bwd (k_pointnet_bwd.hip), train_ops.ReluLinearFn / CrossViewAttentionFn,
 autograd_path.point_network_device and cfg.train_point_net = "device".
 
 The bars are those of tests/test_gpu_train_vit_dense.py: inputs are fp32 values widened to float64 for the truth; with t64 torch's

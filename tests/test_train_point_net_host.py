@@ -1,5 +1,6 @@
 """The training form of the per-point network on the host: the float64 restatements of its two new adjoints
-(train_ops.relu_linear_grad_oracle, xview_attention_oracle / xview_attention_grad_oracle, the formulas of k_pointnet_bwd.hip)
+(train_ops.relu_linear_grad_oracle, xview_attention_oracle / xview_attention_grad_oracle, the formulas of
+k_vit_dense_bwd.hip's ReLU layers and of k_pointnet_bwd.hip)
 against torch's float64 autograd, the switch cfg.train_point_net ("torch" by default, "device" refuses a CPU batch, anything else
 is a ValueError), and the re-association of autograd_path.point_network_device -- padded layers, fused key | value layers, one
 attention operator -- which is exact algebra: the same composition code, run on plain-torch operators in float64, gives

@@ -1,31 +1,11 @@
 // K20: the training form of the per-point network (MLP_forward_ori, cross_transformer.py:273-353), layer by layer like
 // th_mlp_forward (k_mlp.hip).  Nothing in this file is launched by inference or by bench.py.
 //
-// The dense layers are th_gemm launches on the fp32 MFMA pipe and the backward machinery of k_vit_dense_bwd.hip (the image of
-// W^T for the input gradient, wgrad_kernel's 256-row chunks added in chunk order).  New arithmetic is two small pieces:
-//
-//   a ReLU on a layer's OUTPUT   Y = relu(A W^T + b) is th_gemm's TH_ACT_RELU epilogue; the backward is th_linear_bwd form 0
-//                                with g_C = g_Y * [Y > 0] (torch's rule: 0 at Y == 0): gated on g_Y's way into LDS in
-//                                wgrad_kernel<OP_PLAIN, true>, and by one elementwise pass into the workspace for the input gradient
-//   the V x V cross-view attention (cross_transformer.py:128-149)   forward: xattn_kernel of k_mlp.hip as it is; backward:
-//                                xattn_bwd_kernel below, one wave per sample, the probabilities recomputed from the keys
+// The dense layers, with and without a ReLU on their output, are the entries of k_vit_dense_bwd.hip (th_linear_relu_* /
+// th_linear_train_forward / th_linear_bwd).  What is left here is the V x V cross-view attention (cross_transformer.py:128-149):
+// forward: xattn_kernel of k_mlp.hip as it is; backward: xattn_bwd_kernel below, one wave per sample, the probabilities recomputed
+// from the keys
 #include "th_internal.h"
-
-// G'[m, :] = G[m, :] * [Y[m, :] > 0] (dense G', n % 4 == 0)
-__global__ void relu_gate_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ Y, int ldy, int M, int n,
-                                 float* __restrict__ O) {
-    const int n4 = n >> 2;
-    const long long total = (long long)M * n4;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long m = i / n4;
-        const int c = 4 * (int)(i - m * n4);
-        const float4 y = *reinterpret_cast<const float4*>(Y + m * ldy + c);
-        float4 g = *reinterpret_cast<const float4*>(G + m * ldg + c);
-        g.x = y.x > 0.f ? g.x : 0.f; g.y = y.y > 0.f ? g.y : 0.f;
-        g.z = y.z > 0.f ? g.z : 0.f; g.w = y.w > 0.f ? g.w : 0.f;
-        *reinterpret_cast<float4*>(O + m * n + c) = g;
-    }
-}
 
 // ---- cross-view attention, backward ---------------------------------------------------------------------------------------------
 // Rows as xattn_kernel: [key(128) | value(256)].  With A[j][i] = softmax_j(kp_j . ks_i / sqrt(128)) and n_i = vs_i + sum_j A[j][i] vp_j:
@@ -131,80 +111,9 @@ __global__ __launch_bounds__(256) void xattn_bwd_kernel(const float* __restrict_
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-static bool pn_shape_ok(int M, int out_f, int in_f) {
-    return M >= 1 && M <= (1 << 24) && out_f >= 16 && in_f >= 16 && (out_f & 15) == 0 && (in_f & 15) == 0 && out_f <= 65536 &&
-           in_f <= 65536;
-}
 static bool pn_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-struct PnBwdWs { size_t pack, gate, part, total; };
-static PnBwdWs pn_bwd_layout(int M, int out_f, int in_f) {
-    PnBwdWs w{};
-    w.pack = 0;
-    size_t off = ThPacked::bytes(in_f, out_f);
-    w.gate = off;
-    off += th_align((size_t)M * out_f * sizeof(float));
-    w.part = off;
-    off += th_align((size_t)th_wgrad_chunks(M) * ((size_t)out_f * in_f + out_f) * sizeof(float));
-    w.total = off;
-    return w;
-}
-
-#define PN_SHAPE_MSG "unsupported shape: M >= 1, in_f and out_f multiples of 16"
-
 extern "C" {
-
-size_t th_linear_relu_workspace_bytes(int M, int out_f, int in_f) {
-    if (!pn_shape_ok(M, out_f, in_f)) return 0;
-    return ThPacked::bytes(out_f, in_f);
-}
-
-int th_linear_relu_forward(th_ctx* c, const float* A, int lda, int M, const th_linear* lin, float* Y, int ldy, void* ws,
-                           size_t ws_bytes, th_stream stream) {
-    TH_REQUIRE(c && A && lin && Y && ws, "null argument");
-    TH_REQUIRE(lin->w != nullptr, "null argument (the layer's weight)");
-    TH_REQUIRE(pn_shape_ok(M, lin->out_f, lin->in_f), PN_SHAPE_MSG);
-    TH_REQUIRE(lda >= lin->in_f && ldy >= lin->out_f && (lda & 3) == 0 && (ldy & 3) == 0, "lda / ldy: >= the row, multiples of 4");
-    TH_REQUIRE(pn_al16(A) && pn_al16(Y) && pn_al16(ws) && pn_al16(lin->w), "pointers must be 16-byte aligned");
-    TH_REQUIRE(ws_bytes >= th_linear_relu_workspace_bytes(M, lin->out_f, lin->in_f), "workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    ThPacked P;
-    TH_TRY(th_pack_linear(*lin, ws, &P, s));
-    return th_gemm(A, lda, M, P, TH_ACT_RELU, Y, ldy, s);
-}
-
-size_t th_linear_relu_bwd_workspace_bytes(int M, int out_f, int in_f) {
-    if (!pn_shape_ok(M, out_f, in_f)) return 0;
-    return pn_bwd_layout(M, out_f, in_f).total;
-}
-
-int th_linear_relu_bwd(th_ctx* c, const float* A, int lda, const float* Y, int ldy, int M, const th_linear* lin, const float* g_Y,
-                       int ldg, float* g_A, int ldga, float* g_W, float* g_b, void* ws, size_t ws_bytes, th_stream stream) {
-    TH_REQUIRE(c && A && Y && lin && g_Y && g_W && ws, "null argument");
-    TH_REQUIRE(lin->w != nullptr, "null argument (the layer's weight)");
-    const int out_f = lin->out_f, in_f = lin->in_f;
-    TH_REQUIRE(pn_shape_ok(M, out_f, in_f), PN_SHAPE_MSG);
-    TH_REQUIRE(lda >= in_f && ldy >= out_f && ldg >= out_f && (lda & 3) == 0 && (ldy & 3) == 0 && (ldg & 3) == 0 &&
-                   (g_A == nullptr || (ldga >= in_f && (ldga & 3) == 0)),
-               "lda / ldy / ldg / ldga: >= the row, multiples of 4");
-    TH_REQUIRE(pn_al16(A) && pn_al16(Y) && pn_al16(g_Y) && pn_al16(g_A) && pn_al16(g_W) && pn_al16(ws) && pn_al16(lin->w),
-               "pointers must be 16-byte aligned");
-    const PnBwdWs L = pn_bwd_layout(M, out_f, in_f);
-    TH_REQUIRE(ws_bytes >= L.total, "workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)ws;
-    if (g_A != nullptr) {
-        float* gated = (float*)(base + L.gate);
-        const long long n4 = (long long)M * (out_f >> 2);
-        hipLaunchKernelGGL(relu_gate_kernel, dim3((unsigned)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192)), dim3(256), 0, s,
-                           g_Y, ldg, Y, ldy, M, out_f, gated);
-        TH_LAUNCH_CHECK();
-        ThPacked P;
-        TH_TRY(th_pack_linear_t(lin->w, out_f, in_f, base + L.pack, &P, s));
-        TH_TRY(th_gemm(gated, out_f, M, P, TH_ACT_NONE, g_A, ldga, s));
-    }
-    return th_wgrad_relu_launch(g_Y, ldg, Y, ldy, A, lda, M, out_f, in_f, (float*)(base + L.part), g_W, g_b, s);
-}
 
 int th_xview_attention(th_ctx* c, const float* kvp, const float* kvs, int P, int V, float* n, th_stream stream) {
     TH_REQUIRE(c && kvp && kvs && n, "null argument");

@@ -1,5 +1,6 @@
 // K3 training form, dense half: the backward of TransHE's Linear / LayerNorm / GELU layers (and the thin forward entries
-// that th_linear_forward does not serve).  Nothing in this file is launched by inference or by bench.py.
+// that th_linear_forward does not serve), and the same layer with a ReLU on its OUTPUT, which the per-point network's training
+// form is made of (K20, th_linear_relu_*).  Nothing in this file is launched by inference or by bench.py.
 //
 // For y = Linear(op(A)) with W [out, in] row-major and g_C = dL/dy [M, out]:
 //
@@ -21,6 +22,10 @@
 // the chunk count depends on M alone.  Every chunk writes its partial tile (and, from the in-tile-0 workgroups, its partial
 // bias sums) to the workspace and reduce_kernel adds the partials IN CHUNK ORDER: no atomics, the result does not depend on
 // scheduling.  LayerNorm's parameter gradients take the same two stages (ln_bwd_kernel's per-block column sums).
+//
+// A ReLU on the output: Y = relu(A W^T + b) is th_gemm's TH_ACT_RELU epilogue; the backward is form 0 with g_C = g_Y * [Y > 0]
+// (torch's rule: 0 at Y == 0), gated on g_Y's way into LDS in wgrad_kernel<OP_PLAIN, true> and by one elementwise pass into the
+// workspace (relu_gate_kernel) for the input gradient.
 #include <algorithm>
 
 #include "th_internal.h"
@@ -215,6 +220,22 @@ __global__ void gelu_bwd_kernel(const float* __restrict__ U, int ldu, float* __r
     }
 }
 
+// G'[m, :] = G[m, :] * [Y[m, :] > 0] (dense G', n % 4 == 0)
+__global__ void relu_gate_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ Y, int ldy, int M, int n,
+                                 float* __restrict__ O) {
+    const int n4 = n >> 2;
+    const long long total = (long long)M * n4;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long m = i / n4;
+        const int c = 4 * (int)(i - m * n4);
+        const float4 y = *reinterpret_cast<const float4*>(Y + m * ldy + c);
+        float4 g = *reinterpret_cast<const float4*>(G + m * ldg + c);
+        g.x = y.x > 0.f ? g.x : 0.f; g.y = y.y > 0.f ? g.y : 0.f;
+        g.z = y.z > 0.f ? g.z : 0.f; g.w = y.w > 0.f ? g.w : 0.f;
+        *reinterpret_cast<float4*>(O + m * n + c) = g;
+    }
+}
+
 // o[m, :] = gelu(u[m, :]) (dense o, n % 4 == 0): fc2's input in the forward
 __global__ void gelu_fwd_kernel(const float* __restrict__ U, int ldu, float* __restrict__ O, int M, int n) {
     const int n4 = n >> 2;
@@ -230,7 +251,7 @@ __global__ void gelu_fwd_kernel(const float* __restrict__ U, int ldu, float* __r
 }
 
 // grid (ceil(out / 64), ceil(in / 64), chunks); part[chunk][out in + out]
-// GATE (k_pointnet_bwd.hip, the layers with a ReLU on their output): g_C = G * [Y > 0], applied on G's way into LDS
+// GATE (the layers with a ReLU on their output): g_C = G * [Y > 0], applied on G's way into LDS
 template <int FORM, bool GATE = false>
 __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ A,
                                                     int lda, int M, int out_f, int in_f, const float* __restrict__ stats,
@@ -334,12 +355,20 @@ static bool vd_shape_ok(int M, int out_f, int in_f, int form) {
 static bool vd_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static int vd_chunks(int M) { return th_cdiv(M, WG_CHUNK); }
 static int vd_ln_blocks(int M) { return th_cdiv(M, LN_ROWS); }
+static unsigned vd_grid4(int M, int n) { return (unsigned)std::min<long long>(((long long)M * (n >> 2) + 255) / 256, 8192); }
 
-struct VdBwdWs { size_t pack, stats, part, lnpart, total; };
-static VdBwdWs vd_bwd_layout(int M, int out_f, int in_f, int form) {
+#define VD_SHAPE_MSG "unsupported shape: M >= 1, in_f and out_f multiples of 16; form 1 (LayerNorm) also in_f <= 256, M <= 8192"
+#define VD_FORM_MSG "form must be 0 (A), 1 (LayerNorm(A)) or 2 (gelu(A))"
+
+// the backward's workspace: the image of W^T, then -- each only where the layer has it -- the gated g_Y (a ReLU on the output),
+// the row statistics (LayerNorm), wgrad_kernel's partial tiles, ln_bwd_kernel's partial column sums (LayerNorm)
+struct VdBwdWs { size_t pack, gate, stats, part, lnpart, total; };
+static VdBwdWs vd_bwd_layout(int M, int out_f, int in_f, int form, int act) {
     VdBwdWs w{};
     w.pack = 0;
     size_t off = ThPacked::bytes(in_f, out_f);
+    w.gate = off;
+    if (act == TH_ACT_RELU) off += th_align((size_t)M * out_f * sizeof(float));
     w.stats = off;
     if (form == OP_LN) off += th_align((size_t)M * 2 * sizeof(float));
     w.part = off;
@@ -350,10 +379,8 @@ static VdBwdWs vd_bwd_layout(int M, int out_f, int in_f, int form) {
     return w;
 }
 
-// ---- shared with k_pointnet_bwd.hip (th_internal.h) ----
-int th_wgrad_chunks(int M) { return vd_chunks(M); }
-
-int th_pack_linear_t(const float* W, int out_f, int in_f, void* storage, ThPacked* P, hipStream_t s) {
+// the image of W^T for the input gradient (storage: ThPacked::bytes(in_f, out_f))
+static int vd_pack_linear_t(const float* W, int out_f, int in_f, void* storage, ThPacked* P, hipStream_t s) {
     P->N = in_f; P->K = out_f; P->NB = in_f / 16; P->KB = out_f / 16;
     P->w = (float*)storage;
     P->b = (float*)((char*)storage + th_align((size_t)P->NB * P->KB * 256 * sizeof(float)));
@@ -364,24 +391,110 @@ int th_pack_linear_t(const float* W, int out_f, int in_f, void* storage, ThPacke
     return 0;
 }
 
-int th_wgrad_relu_launch(const float* g_Y, int ldg, const float* Y, int ldy, const float* A, int lda, int M, int out_f, int in_f,
-                         float* part, float* g_W, float* g_b, hipStream_t s) {
-    const int chunks = vd_chunks(M);
-    dim3 grid(th_cdiv(out_f, WG_TILE), th_cdiv(in_f, WG_TILE), chunks);
-    hipLaunchKernelGGL((wgrad_kernel<OP_PLAIN, true>), grid, dim3(256), 0, s, g_Y, ldg, A, lda, M, out_f, in_f, nullptr, nullptr,
-                       nullptr, part, Y, ldy);
-    const long long n1 = (long long)out_f * in_f, n = n1 + out_f;
-    hipLaunchKernelGGL(reduce_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, part, chunks, n, n1, n, g_W, g_b);
-    TH_LAUNCH_CHECK();
-    return 0;
-}
-
 static int vd_ln_bwd_launch(const float* x, int ldx, int M, int dim, const float* w, float eps, const float* g, int ldg,
                             float* gx, int ldgx, float* g_w, float* g_b, float* part, hipStream_t s) {
     const int blocks = vd_ln_blocks(M);
     hipLaunchKernelGGL(ln_bwd_kernel, dim3(blocks), dim3(256), 0, s, x, ldx, M, dim, w, eps, g, ldg, gx, ldgx, part);
     hipLaunchKernelGGL(reduce_kernel, dim3(th_cdiv(2 * dim, 256)), dim3(256), 0, s, part, blocks, (long long)2 * dim,
                        (long long)dim, (long long)2 * dim, g_w, g_b);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+// C = act(op(A) W^T + b): the one forward behind th_linear_train_forward (act = TH_ACT_NONE) and th_linear_relu_forward
+// (form 0, act = TH_ACT_RELU in the GEMM's epilogue)
+static int vd_forward(th_ctx* c, const float* A, int lda, int M, int form, const float* ln_w, const float* ln_b, float ln_eps,
+                      const th_linear* lin, int act, float* C, int ldc, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && A && lin && C && ws, "null argument");
+    TH_REQUIRE(lin->w != nullptr, "null argument (the layer's weight)");
+    TH_REQUIRE(form >= OP_PLAIN && form <= OP_GELU && (act == TH_ACT_NONE || form == OP_PLAIN), VD_FORM_MSG);
+    TH_REQUIRE(form != OP_LN || (ln_w && ln_b), "null argument (LayerNorm parameters of form 1)");
+    TH_REQUIRE(vd_shape_ok(M, lin->out_f, lin->in_f, form), VD_SHAPE_MSG);
+    TH_REQUIRE(lda >= lin->in_f && ldc >= lin->out_f && (lda & 3) == 0 && (ldc & 3) == 0,
+               "lda / ldc (ldy): >= the row, multiples of 4");
+    TH_REQUIRE(vd_al16(A) && vd_al16(C) && vd_al16(ws) && vd_al16(lin->w) && (form != OP_LN || (vd_al16(ln_w) && vd_al16(ln_b))),
+               "pointers must be 16-byte aligned");
+    TH_REQUIRE(ws_bytes >= th_linear_train_workspace_bytes(M, lin->out_f, lin->in_f, form), "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    ThPacked P;
+    TH_TRY(th_pack_linear(*lin, ws, &P, s));
+    if (form == OP_LN) return th_gemm_ln(A, lda, M, P, ln_w, ln_b, ln_eps, TH_ACT_NONE, C, ldc, s);
+    if (form == OP_GELU) {
+        float* t = (float*)((char*)ws + ThPacked::bytes(lin->out_f, lin->in_f));
+        hipLaunchKernelGGL(gelu_fwd_kernel, dim3(vd_grid4(M, lin->in_f)), dim3(256), 0, s, A, lda, t, M, lin->in_f);
+        TH_LAUNCH_CHECK();
+        return th_gemm(t, lin->in_f, M, P, TH_ACT_NONE, C, ldc, s);
+    }
+    return th_gemm(A, lda, M, P, act, C, ldc, s);
+}
+
+// the one backward behind th_linear_bwd (act = TH_ACT_NONE, Y unused) and th_linear_relu_bwd (form 0, act = TH_ACT_RELU, Y the
+// forward's output: g_C = g_Y * [Y > 0]).  Launches: [row statistics] -> ([gate] -> pack W^T -> th_gemm -> [gelu' | LN bwd]) ->
+// wgrad_kernel -> reduce_kernel
+static int vd_backward(th_ctx* c, const float* A, int lda, int M, int form, const float* ln_w, const float* ln_b, float ln_eps,
+                       const th_linear* lin, int act, const float* Y, int ldy, const float* g_C, int ldg, float* g_A, int ldga,
+                       float* g_W, float* g_b, float* g_ln_w, float* g_ln_b, void* ws, size_t ws_bytes, th_stream stream) {
+    const bool gate = act == TH_ACT_RELU;
+    TH_REQUIRE(c && A && lin && g_C && g_W && ws && (!gate || Y), "null argument");
+    TH_REQUIRE(lin->w != nullptr, "null argument (the layer's weight)");
+    TH_REQUIRE(form >= OP_PLAIN && form <= OP_GELU && (!gate || form == OP_PLAIN), VD_FORM_MSG);
+    TH_REQUIRE(form != OP_LN || (ln_w && ln_b), "null argument (LayerNorm parameters of form 1)");
+    TH_REQUIRE(form != OP_LN || g_A == nullptr || (g_ln_w && g_ln_b), "null argument (g_ln_w / g_ln_b go with g_A in form 1)");
+    const int out_f = lin->out_f, in_f = lin->in_f;
+    TH_REQUIRE(vd_shape_ok(M, out_f, in_f, form), VD_SHAPE_MSG);
+    TH_REQUIRE(lda >= in_f && ldg >= out_f && (lda & 3) == 0 && (ldg & 3) == 0 && (!gate || (ldy >= out_f && (ldy & 3) == 0)) &&
+                   (g_A == nullptr || (ldga >= in_f && (ldga & 3) == 0)),
+               "lda / ldy / ldg / ldga: >= the row, multiples of 4");
+    TH_REQUIRE(vd_al16(A) && (!gate || vd_al16(Y)) && vd_al16(g_C) && vd_al16(g_A) && vd_al16(g_W) && vd_al16(ws) &&
+                   vd_al16(lin->w) && (form != OP_LN || (vd_al16(ln_w) && vd_al16(ln_b))),
+               "pointers must be 16-byte aligned");
+    const VdBwdWs L = vd_bwd_layout(M, out_f, in_f, form, act);
+    TH_REQUIRE(ws_bytes >= L.total, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)ws;
+    float* stats = (float*)(base + L.stats);
+    float* part = (float*)(base + L.part);
+    if (form == OP_LN) {
+        hipLaunchKernelGGL(ln_stats_kernel, dim3(th_cdiv(M, 16)), dim3(256), 0, s, A, lda, M, in_f, ln_eps, stats);
+        TH_LAUNCH_CHECK();
+    }
+    if (g_A != nullptr) {
+        const float* g = g_C;
+        int ld = ldg;
+        if (gate) {
+            float* gated = (float*)(base + L.gate);
+            hipLaunchKernelGGL(relu_gate_kernel, dim3(vd_grid4(M, out_f)), dim3(256), 0, s, g_C, ldg, Y, ldy, M, out_f, gated);
+            TH_LAUNCH_CHECK();
+            g = gated;
+            ld = out_f;
+        }
+        ThPacked P;
+        TH_TRY(vd_pack_linear_t(lin->w, out_f, in_f, base + L.pack, &P, s));
+        TH_TRY(th_gemm(g, ld, M, P, TH_ACT_NONE, g_A, ldga, s));
+        if (form == OP_GELU) {
+            hipLaunchKernelGGL(gelu_bwd_kernel, dim3(vd_grid4(M, in_f)), dim3(256), 0, s, A, lda, g_A, ldga, M, in_f);
+            TH_LAUNCH_CHECK();
+        } else if (form == OP_LN) {
+            TH_TRY(vd_ln_bwd_launch(A, lda, M, in_f, ln_w, ln_eps, g_A, ldga, g_A, ldga, g_ln_w, g_ln_b,
+                                    (float*)(base + L.lnpart), s));
+        }
+    }
+    const int chunks = vd_chunks(M);
+    dim3 grid(th_cdiv(out_f, WG_TILE), th_cdiv(in_f, WG_TILE), chunks);
+    if (form == OP_LN)
+        hipLaunchKernelGGL(wgrad_kernel<OP_LN>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, stats, ln_w, ln_b, part,
+                           nullptr, 0);
+    else if (form == OP_GELU)
+        hipLaunchKernelGGL(wgrad_kernel<OP_GELU>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, nullptr, nullptr,
+                           nullptr, part, nullptr, 0);
+    else if (gate)
+        hipLaunchKernelGGL((wgrad_kernel<OP_PLAIN, true>), grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, nullptr, nullptr,
+                           nullptr, part, Y, ldy);
+    else
+        hipLaunchKernelGGL(wgrad_kernel<OP_PLAIN>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, nullptr, nullptr,
+                           nullptr, part, nullptr, 0);
+    const long long n1 = (long long)out_f * in_f, n = n1 + out_f;
+    hipLaunchKernelGGL(reduce_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, part, chunks, n, n1, n, g_W, g_b);
     TH_LAUNCH_CHECK();
     return 0;
 }
@@ -399,91 +512,40 @@ size_t th_linear_train_workspace_bytes(int M, int out_f, int in_f, int form) {
 int th_linear_train_forward(th_ctx* c, const float* A, int lda, int M, int form, const float* ln_w, const float* ln_b,
                             float ln_eps, const th_linear* lin, float* C, int ldc, void* ws, size_t ws_bytes,
                             th_stream stream) {
-    TH_REQUIRE(c && A && lin && C && ws, "null argument");
-    TH_REQUIRE(lin->w != nullptr, "null argument (the layer's weight)");
-    TH_REQUIRE(form >= OP_PLAIN && form <= OP_GELU, "form must be 0 (A), 1 (LayerNorm(A)) or 2 (gelu(A))");
-    TH_REQUIRE(form != OP_LN || (ln_w && ln_b), "null argument (LayerNorm parameters of form 1)");
-    TH_REQUIRE(vd_shape_ok(M, lin->out_f, lin->in_f, form),
-               "unsupported shape: M >= 1, in_f and out_f multiples of 16; form 1 (LayerNorm) also in_f <= 256, M <= 8192");
-    TH_REQUIRE(lda >= lin->in_f && ldc >= lin->out_f && (lda & 3) == 0 && (ldc & 3) == 0, "lda / ldc: >= the row, multiples of 4");
-    TH_REQUIRE(vd_al16(A) && vd_al16(C) && vd_al16(ws) && vd_al16(lin->w) && (form != OP_LN || (vd_al16(ln_w) && vd_al16(ln_b))),
-               "pointers must be 16-byte aligned");
-    TH_REQUIRE(ws_bytes >= th_linear_train_workspace_bytes(M, lin->out_f, lin->in_f, form), "workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    ThPacked P;
-    TH_TRY(th_pack_linear(*lin, ws, &P, s));
-    if (form == OP_LN) return th_gemm_ln(A, lda, M, P, ln_w, ln_b, ln_eps, TH_ACT_NONE, C, ldc, s);
-    if (form == OP_GELU) {
-        float* t = (float*)((char*)ws + ThPacked::bytes(lin->out_f, lin->in_f));
-        const long long n4 = (long long)M * (lin->in_f >> 2);
-        hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, A, lda,
-                           t, M, lin->in_f);
-        TH_LAUNCH_CHECK();
-        return th_gemm(t, lin->in_f, M, P, TH_ACT_NONE, C, ldc, s);
-    }
-    return th_gemm(A, lda, M, P, TH_ACT_NONE, C, ldc, s);
+    return vd_forward(c, A, lda, M, form, ln_w, ln_b, ln_eps, lin, TH_ACT_NONE, C, ldc, ws, ws_bytes, stream);
 }
 
 size_t th_linear_bwd_workspace_bytes(int M, int out_f, int in_f, int form) {
     if (!vd_shape_ok(M, out_f, in_f, form)) return 0;
-    return vd_bwd_layout(M, out_f, in_f, form).total;
+    return vd_bwd_layout(M, out_f, in_f, form, TH_ACT_NONE).total;
 }
 
 int th_linear_bwd(th_ctx* c, const float* A, int lda, int M, int form, const float* ln_w, const float* ln_b, float ln_eps,
                   const th_linear* lin, const float* g_C, int ldg, float* g_A, int ldga, float* g_W, float* g_b,
                   float* g_ln_w, float* g_ln_b, void* ws, size_t ws_bytes, th_stream stream) {
-    TH_REQUIRE(c && A && lin && g_C && g_W && ws, "null argument");
-    TH_REQUIRE(lin->w != nullptr, "null argument (the layer's weight)");
-    TH_REQUIRE(form >= OP_PLAIN && form <= OP_GELU, "form must be 0 (A), 1 (LayerNorm(A)) or 2 (gelu(A))");
-    TH_REQUIRE(form != OP_LN || (ln_w && ln_b), "null argument (LayerNorm parameters of form 1)");
-    TH_REQUIRE(form != OP_LN || g_A == nullptr || (g_ln_w && g_ln_b), "null argument (g_ln_w / g_ln_b go with g_A in form 1)");
-    const int out_f = lin->out_f, in_f = lin->in_f;
-    TH_REQUIRE(vd_shape_ok(M, out_f, in_f, form),
-               "unsupported shape: M >= 1, in_f and out_f multiples of 16; form 1 (LayerNorm) also in_f <= 256, M <= 8192");
-    TH_REQUIRE(lda >= in_f && ldg >= out_f && (lda & 3) == 0 && (ldg & 3) == 0 && (g_A == nullptr || (ldga >= in_f && (ldga & 3) == 0)),
-               "lda / ldg / ldga: >= the row, multiples of 4");
-    TH_REQUIRE(vd_al16(A) && vd_al16(g_C) && vd_al16(g_A) && vd_al16(g_W) && vd_al16(ws) && vd_al16(lin->w) &&
-                   (form != OP_LN || (vd_al16(ln_w) && vd_al16(ln_b))),
-               "pointers must be 16-byte aligned");
-    const VdBwdWs L = vd_bwd_layout(M, out_f, in_f, form);
-    TH_REQUIRE(ws_bytes >= L.total, "workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)ws;
-    float* stats = (float*)(base + L.stats);
-    float* part = (float*)(base + L.part);
-    if (form == OP_LN) {
-        hipLaunchKernelGGL(ln_stats_kernel, dim3(th_cdiv(M, 16)), dim3(256), 0, s, A, lda, M, in_f, ln_eps, stats);
-        TH_LAUNCH_CHECK();
-    }
-    if (g_A != nullptr) {
-        ThPacked P;
-        TH_TRY(th_pack_linear_t(lin->w, out_f, in_f, base + L.pack, &P, s));
-        TH_TRY(th_gemm(g_C, ldg, M, P, TH_ACT_NONE, g_A, ldga, s));
-        if (form == OP_GELU) {
-            const long long n4 = (long long)M * (in_f >> 2);
-            hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, A,
-                               lda, g_A, ldga, M, in_f);
-            TH_LAUNCH_CHECK();
-        } else if (form == OP_LN) {
-            TH_TRY(vd_ln_bwd_launch(A, lda, M, in_f, ln_w, ln_eps, g_A, ldga, g_A, ldga, g_ln_w, g_ln_b,
-                                    (float*)(base + L.lnpart), s));
-        }
-    }
-    const int chunks = vd_chunks(M);
-    dim3 grid(th_cdiv(out_f, WG_TILE), th_cdiv(in_f, WG_TILE), chunks);
-    if (form == OP_LN)
-        hipLaunchKernelGGL(wgrad_kernel<OP_LN>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, stats, ln_w, ln_b, part,
-                           nullptr, 0);
-    else if (form == OP_GELU)
-        hipLaunchKernelGGL(wgrad_kernel<OP_GELU>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, nullptr, nullptr,
-                           nullptr, part, nullptr, 0);
-    else
-        hipLaunchKernelGGL(wgrad_kernel<OP_PLAIN>, grid, dim3(256), 0, s, g_C, ldg, A, lda, M, out_f, in_f, nullptr, nullptr,
-                           nullptr, part, nullptr, 0);
-    const long long n1 = (long long)out_f * in_f, n = n1 + out_f;
-    hipLaunchKernelGGL(reduce_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, part, chunks, n, n1, n, g_W, g_b);
-    TH_LAUNCH_CHECK();
-    return 0;
+    return vd_backward(c, A, lda, M, form, ln_w, ln_b, ln_eps, lin, TH_ACT_NONE, nullptr, 0, g_C, ldg, g_A, ldga, g_W, g_b,
+                       g_ln_w, g_ln_b, ws, ws_bytes, stream);
+}
+
+// the same layer with a ReLU on its output (K20): form 0 of the bodies above
+size_t th_linear_relu_workspace_bytes(int M, int out_f, int in_f) {
+    return th_linear_train_workspace_bytes(M, out_f, in_f, OP_PLAIN);
+}
+
+int th_linear_relu_forward(th_ctx* c, const float* A, int lda, int M, const th_linear* lin, float* Y, int ldy, void* ws,
+                           size_t ws_bytes, th_stream stream) {
+    return vd_forward(c, A, lda, M, OP_PLAIN, nullptr, nullptr, 0.f, lin, TH_ACT_RELU, Y, ldy, ws, ws_bytes, stream);
+}
+
+size_t th_linear_relu_bwd_workspace_bytes(int M, int out_f, int in_f) {
+    if (!vd_shape_ok(M, out_f, in_f, OP_PLAIN)) return 0;
+    return vd_bwd_layout(M, out_f, in_f, OP_PLAIN, TH_ACT_RELU).total;
+}
+
+int th_linear_relu_bwd(th_ctx* c, const float* A, int lda, const float* Y, int ldy, int M, const th_linear* lin, const float* g_Y,
+                       int ldg, float* g_A, int ldga, float* g_W, float* g_b, void* ws, size_t ws_bytes, th_stream stream) {
+    return vd_backward(c, A, lda, M, OP_PLAIN, nullptr, nullptr, 0.f, lin, TH_ACT_RELU, Y, ldy, g_Y, ldg, g_A, ldga, g_W, g_b,
+                       nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 int th_layernorm_forward(th_ctx* c, const float* x, int ldx, int M, int dim, const float* w, const float* b, float eps,

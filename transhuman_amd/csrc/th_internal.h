@@ -528,13 +528,6 @@ int th_attention_train_launch(const float* qkv, int V, int N, int heads, int for
 size_t th_attn_bwd_ws(int V, int N, int heads);
 int th_attention_bwd_launch(const float* qkv, const float* out, const float* lse, const float* g_out, int V, int N, int heads,
                             float* g_qkv, void* ws, size_t ws_bytes, hipStream_t s);
-// k_vit_dense_bwd.hip, shared with k_pointnet_bwd.hip: the chunk count of wgrad_kernel, the image of W^T for the input gradient
-// (storage: ThPacked::bytes(in_f, out_f)), and wgrad_kernel + reduce_kernel with g_C = g_Y * [Y > 0] gated on its way into LDS
-// (part: chunks * (out_f in_f + out_f) floats; g_b may be null)
-int th_wgrad_chunks(int M);
-int th_pack_linear_t(const float* W, int out_f, int in_f, void* storage, ThPacked* P, hipStream_t s);
-int th_wgrad_relu_launch(const float* g_Y, int ldg, const float* Y, int ldy, const float* A, int lda, int M, int out_f, int in_f,
-                         float* part, float* g_W, float* g_b, hipStream_t s);
 // k_mlp.hip: xattn_kernel on its own -- n [P,V,256] from the [key(128) | value(256)] rows kvp, kvs [P,V,384], V in 1..4
 int th_xattn_launch(const float* kvp, const float* kvs, int P, int V, float* n, hipStream_t s);
 

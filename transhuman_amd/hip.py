@@ -1222,10 +1222,9 @@ def _train_vec(fn, t, n):
     return t.detach()
 
 
-def linear_train_forward(a, weight, bias, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1e-6):
-    """th_linear_train_forward: op(a) W^T + b with op = identity / LayerNorm / gelu (form), a [..., in] -> [..., out]"""
+def _dense_forward(fn, a, weight, bias, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1e-6, relu=False):
+    """the one forward of a dense training layer: th_linear_train_forward, or with ``relu`` (form 0 only) th_linear_relu_forward"""
     lib = load_library()
-    fn = "linear_train_forward"
     w = _train_rows(fn, weight)
     out_f, in_f = w.shape
     a2 = _train_rows(fn, a, in_f)
@@ -1234,25 +1233,31 @@ def linear_train_forward(a, weight, bias, form=OPERAND_PLAIN, ln_w=None, ln_b=No
     M = a2.shape[0]
     lin = ThLinear(_p(w), _p(b), out_f, in_f)
     out = torch.empty((*a.shape[:-1], out_f), dtype=torch.float32, device=a.device)
-    ws = _ws(lib.th_linear_train_workspace_bytes(M, out_f, in_f, int(form)), a.device)
-    _check(lib.th_linear_train_forward(ctx(a.device), _p(a2), in_f, M, int(form), _p(lw), _p(lb), float(eps), C.byref(lin),
-                                       _p(out), out_f, _p(ws), ws.numel(), _stream()))
+    head = (ctx(a.device), _p(a2), in_f, M)
+    tail = (C.byref(lin), _p(out), out_f)
+    if relu:
+        ws = _ws(lib.th_linear_relu_workspace_bytes(M, out_f, in_f), a.device)
+        _check(lib.th_linear_relu_forward(*head, *tail, _p(ws), ws.numel(), _stream()))
+    else:
+        ws = _ws(lib.th_linear_train_workspace_bytes(M, out_f, in_f, int(form)), a.device)
+        _check(lib.th_linear_train_forward(*head, int(form), _p(lw), _p(lb), float(eps), *tail, _p(ws), ws.numel(), _stream()))
     return out
 
 
-def linear_bwd(a, weight, g_out, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1e-6, need_input=True, need_bias=True):
-    """th_linear_bwd: the gradients of linear_train_forward from g_out [..., out] -> (g_a or None, g_W, g_b or None, g_ln_w,
-    g_ln_b); the last two are None unless form = OPERAND_LN with need_input.  g_a is the gradient of `a` itself (through the
-    LayerNorm / the gelu).  Bit-identical from run to run."""
+def _dense_bwd(fn, a, weight, g_out, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1e-6, y=None, need_input=True,
+               need_bias=True):
+    """the one backward of a dense training layer: th_linear_bwd, or with the output ``y`` of a ReLU layer (form 0 only)
+    th_linear_relu_bwd -> (g_a or None, g_W, g_b or None, g_ln_w, g_ln_b)"""
     lib = load_library()
-    fn = "linear_bwd"
     w = _train_rows(fn, weight)
     out_f, in_f = w.shape
     a2, g2 = _train_rows(fn, a, in_f), _train_rows(fn, g_out, out_f)
-    if a2.shape[0] != g2.shape[0]:
-        raise ValueError(f"{fn}: {a2.shape[0]} operand rows, {g2.shape[0]} gradient rows")
-    lw, lb = _train_vec(fn, ln_w, in_f), _train_vec(fn, ln_b, in_f)
+    y2 = None if y is None else _train_rows(fn, y, out_f)
     M = a2.shape[0]
+    if g2.shape[0] != M or (y2 is not None and y2.shape[0] != M):
+        rows = "" if y2 is None else f"{y2.shape[0]} output rows, "
+        raise ValueError(f"{fn}: {M} operand rows, {rows}{g2.shape[0]} gradient rows")
+    lw, lb = _train_vec(fn, ln_w, in_f), _train_vec(fn, ln_b, in_f)
     lin = ThLinear(_p(w), None, out_f, in_f)
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=a.device)
     g_a = new(*a.shape) if need_input else None
@@ -1260,48 +1265,39 @@ def linear_bwd(a, weight, g_out, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1
     g_b = new(out_f) if need_bias else None
     ln = need_input and int(form) == OPERAND_LN
     g_lw, g_lb = (new(in_f), new(in_f)) if ln else (None, None)
-    ws = _ws(lib.th_linear_bwd_workspace_bytes(M, out_f, in_f, int(form)), a.device)
-    _check(lib.th_linear_bwd(ctx(a.device), _p(a2), in_f, M, int(form), _p(lw), _p(lb), float(eps), C.byref(lin), _p(g2), out_f,
-                             _p(g_a), in_f, _p(g_w), _p(g_b), _p(g_lw), _p(g_lb), _p(ws), ws.numel(), _stream()))
+    grads = (_p(g2), out_f, _p(g_a), in_f, _p(g_w), _p(g_b))
+    if y is None:
+        ws = _ws(lib.th_linear_bwd_workspace_bytes(M, out_f, in_f, int(form)), a.device)
+        _check(lib.th_linear_bwd(ctx(a.device), _p(a2), in_f, M, int(form), _p(lw), _p(lb), float(eps), C.byref(lin), *grads,
+                                 _p(g_lw), _p(g_lb), _p(ws), ws.numel(), _stream()))
+    else:
+        ws = _ws(lib.th_linear_relu_bwd_workspace_bytes(M, out_f, in_f), a.device)
+        _check(lib.th_linear_relu_bwd(ctx(a.device), _p(a2), in_f, _p(y2), out_f, M, C.byref(lin), *grads, _p(ws), ws.numel(),
+                                      _stream()))
     return g_a, g_w, g_b, g_lw, g_lb
+
+
+def linear_train_forward(a, weight, bias, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1e-6):
+    """th_linear_train_forward: op(a) W^T + b with op = identity / LayerNorm / gelu (form), a [..., in] -> [..., out]"""
+    return _dense_forward("linear_train_forward", a, weight, bias, form, ln_w, ln_b, eps)
+
+
+def linear_bwd(a, weight, g_out, form=OPERAND_PLAIN, ln_w=None, ln_b=None, eps=1e-6, need_input=True, need_bias=True):
+    """th_linear_bwd: the gradients of linear_train_forward from g_out [..., out] -> (g_a or None, g_W, g_b or None, g_ln_w,
+    g_ln_b); the last two are None unless form = OPERAND_LN with need_input.  g_a is the gradient of `a` itself (through the
+    LayerNorm / the gelu).  Bit-identical from run to run."""
+    return _dense_bwd("linear_bwd", a, weight, g_out, form, ln_w, ln_b, eps, need_input=need_input, need_bias=need_bias)
 
 
 def linear_relu_forward(a, weight, bias):
     """th_linear_relu_forward: relu(a W^T + b), a [..., in] -> [..., out] (the ReLU in the GEMM's epilogue)"""
-    lib = load_library()
-    fn = "linear_relu_forward"
-    w = _train_rows(fn, weight)
-    out_f, in_f = w.shape
-    a2 = _train_rows(fn, a, in_f)
-    b = _train_vec(fn, bias, out_f)
-    M = a2.shape[0]
-    lin = ThLinear(_p(w), _p(b), out_f, in_f)
-    out = torch.empty((*a.shape[:-1], out_f), dtype=torch.float32, device=a.device)
-    ws = _ws(lib.th_linear_relu_workspace_bytes(M, out_f, in_f), a.device)
-    _check(lib.th_linear_relu_forward(ctx(a.device), _p(a2), in_f, M, C.byref(lin), _p(out), out_f, _p(ws), ws.numel(), _stream()))
-    return out
+    return _dense_forward("linear_relu_forward", a, weight, bias, relu=True)
 
 
 def linear_relu_bwd(a, y, weight, g_out, need_input=True, need_bias=True):
     """th_linear_relu_bwd: the gradients of linear_relu_forward from its output y and g_out [..., out] -> (g_a or None, g_W,
     g_b or None).  Bit-identical from run to run."""
-    lib = load_library()
-    fn = "linear_relu_bwd"
-    w = _train_rows(fn, weight)
-    out_f, in_f = w.shape
-    a2, y2, g2 = _train_rows(fn, a, in_f), _train_rows(fn, y, out_f), _train_rows(fn, g_out, out_f)
-    if not a2.shape[0] == y2.shape[0] == g2.shape[0]:
-        raise ValueError(f"{fn}: {a2.shape[0]} operand rows, {y2.shape[0]} output rows, {g2.shape[0]} gradient rows")
-    M = a2.shape[0]
-    lin = ThLinear(_p(w), None, out_f, in_f)
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=a.device)
-    g_a = new(*a.shape) if need_input else None
-    g_w = new(out_f, in_f)
-    g_b = new(out_f) if need_bias else None
-    ws = _ws(lib.th_linear_relu_bwd_workspace_bytes(M, out_f, in_f), a.device)
-    _check(lib.th_linear_relu_bwd(ctx(a.device), _p(a2), in_f, _p(y2), out_f, M, C.byref(lin), _p(g2), out_f, _p(g_a), in_f,
-                                  _p(g_w), _p(g_b), _p(ws), ws.numel(), _stream()))
-    return g_a, g_w, g_b
+    return _dense_bwd("linear_relu_bwd", a, weight, g_out, y=y, need_input=need_input, need_bias=need_bias)[:3]
 
 
 def _xview_rows(fn, kvp, kvs):

@@ -102,31 +102,22 @@ def _trunk_sites_have_batch_statistics(enc):
 
 
 def trunk_device(enc, images):
-    """SpatialEncoder.trunk(images, fused_bn=False) and BasicBlock.forward (encoder.py:114-126) restated on the per-site Functions
-    of train_ops: the same torch operators in the forward, called without recording a graph, and k_encoder_bwd.hip in the backward
-    (K23).  A trunk whose BatchNorm sites do not all use batch statistics runs under torch autograd as a whole."""
+    """SpatialEncoder.trunk(images, fused_bn=False) (encoder.walk_trunk) on the per-site Functions of train_ops: the same torch
+    operators in the forward, called without recording a graph, and k_encoder_bwd.hip in the backward (K23).  A trunk whose
+    BatchNorm sites do not all use batch statistics runs under torch autograd as a whole."""
     from .. import hip
     from . import train_ops as T
+    from .encoder import walk_trunk
     _switch("train_encoder", "device", images.is_cuda)
     if not _trunk_sites_have_batch_statistics(enc):
         return enc.trunk(images, fused_bn=False)
-    m = enc.model
 
     def conv_bn(conv, bn, t, residual=None, relu=True):
         if conv.bias is not None:
             raise hip.HipError("cfg.train_encoder = 'device': the trunk's convolutions have no bias in the HIP backward")
         return T.BnActFn.apply(T.ConvFn.apply(t, conv.weight, conv.stride[0]), bn, residual, relu, bn.weight, bn.bias)
 
-    x = conv_bn(m.conv1, m.bn1, images)
-    lat = [x]
-    x = T.MaxPoolFn.apply(x)
-    for layer in (m.layer1, m.layer2):
-        for blk in layer:
-            idt = x if blk.downsample is None else conv_bn(blk.downsample[0], blk.downsample[1], x, relu=False)
-            y = conv_bn(blk.conv1, blk.bn1, x)
-            x = conv_bn(blk.conv2, blk.bn2, y, residual=idt)
-        lat.append(x)
-    return lat
+    return walk_trunk(enc.model, images, conv_bn, T.MaxPoolFn.apply)
 
 
 def _trunk(enc, images, encoder):
@@ -207,22 +198,24 @@ def _torch_attention(qkv, heads, scale):
     return (s.softmax(dim=-1) @ qkv[2]).transpose(1, 2).reshape(V, N, C3 // 3)
 
 
-def _vit_forward_device_dense(vit, x, attention):
-    """the blocks of vit_forward with every dense layer, LayerNorm and GELU on the HIP Functions of train_ops"""
-    from . import train_ops as T
-    h = vit.num_heads
-    x = x.contiguous()
-    for blk in vit.blocks:
-        a, m = blk.attn, blk.mlp
-        qkv = T.NormLinearFn.apply(x, blk.norm1.weight, blk.norm1.bias, a.qkv.weight, a.qkv.bias, blk.norm1.eps)
-        if attention == "device":
-            y = T.AttentionFn.apply(qkv, h)
-        else:
-            y = _torch_attention(qkv, h, a.scale).contiguous()
-        x = x + T.LinearFn.apply(y, a.proj.weight, a.proj.bias)
-        u = T.NormLinearFn.apply(x, blk.norm2.weight, blk.norm2.bias, m.fc1.weight, m.fc1.bias, blk.norm2.eps)
-        x = x + T.GeluLinearFn.apply(u, m.fc2.weight, m.fc2.bias)
-    return T.LayerNormFn.apply(x, vit.norm.weight, vit.norm.bias, vit.norm.eps)
+def _layer_norm(x, w, b, eps):
+    return F.layer_norm(x, w.shape, w, b, eps)
+
+
+def _vit_ops(dense):
+    """the four operators vit_forward is composed from: the modules' own torch operators, or the HIP Functions of train_ops"""
+    if dense == "device":
+        from . import train_ops as T
+        return {"norm_linear": T.NormLinearFn.apply, "linear": T.LinearFn.apply, "gelu_linear": T.GeluLinearFn.apply,
+                "layernorm": T.LayerNormFn.apply}
+    return {"norm_linear": lambda x, lw, lb, W, b, eps: F.linear(_layer_norm(x, lw, lb, eps), W, b), "linear": F.linear,
+            "gelu_linear": lambda u, W, b: F.linear(F.gelu(u), W, b), "layernorm": _layer_norm}
+
+
+def _device_attention(qkv, heads, scale):
+    """_torch_attention's result through train_ops.AttentionFn (the kernels have the blocks' own scale, 1 / 8, built in)"""
+    from . import train_ops
+    return train_ops.AttentionFn.apply(qkv, heads)
 
 
 def vit_forward(vit, x, pe_xyz, attention="torch", dense="torch"):
@@ -232,21 +225,20 @@ def vit_forward(vit, x, pe_xyz, attention="torch", dense="torch"):
     attention = _switch("train_attention", attention, True)          # (both values are checked before either refusal)
     dense = _switch("train_vit_dense", dense, x.is_cuda, "tokens")
     _switch("train_attention", attention, x.is_cuda, "tokens")
+    ops = _vit_ops(dense)
+    attend = _device_attention if attention == "device" else _torch_attention
     x = x + vit.get_PE(pe_xyz).to(x.dtype)
     if dense == "device":
-        return _vit_forward_device_dense(vit, x, attention)
-    if attention == "device":
-        from . import train_ops
-    h = vit.num_heads
+        x = x.contiguous()                       # (the HIP Functions take contiguous rows; the sum keeps the strides of the pooled tokens)
     for blk in vit.blocks:
-        y = blk.norm1(x)
-        if attention == "device":
-            y = train_ops.AttentionFn.apply(blk.attn.qkv(y).contiguous(), h)
-        else:
-            y = _torch_attention(blk.attn.qkv(y), h, blk.attn.scale)
-        x = x + blk.attn.proj(y)
-        x = x + blk.mlp.fc2(F.gelu(blk.mlp.fc1(blk.norm2(x))))
-    return vit.norm(x)
+        a, m = blk.attn, blk.mlp
+        qkv = ops["norm_linear"](x, blk.norm1.weight, blk.norm1.bias, a.qkv.weight, a.qkv.bias, blk.norm1.eps)
+        # (for the HIP Functions again: neither call copies here, a Linear's rows and _torch_attention's reshape are contiguous)
+        y = attend(qkv.contiguous(), vit.num_heads, a.scale).contiguous()
+        x = x + ops["linear"](y, a.proj.weight, a.proj.bias)
+        u = ops["norm_linear"](x, blk.norm2.weight, blk.norm2.bias, m.fc1.weight, m.fc1.bias, blk.norm2.eps)
+        x = x + ops["gelu_linear"](u, m.fc2.weight, m.fc2.bias)
+    return ops["layernorm"](x, vit.norm.weight, vit.norm.bias, vit.norm.eps)
 
 
 # ---- per-point network ---------------------------------------------------------------------------------------------------
@@ -397,39 +389,36 @@ def render(renderer, batch, chunk=32768):
     M64 = pooling_matrix_cached(renderer, nv, dev, blend.dtype)        # (float64 mean, :544)
     rot = (M64 @ blend.reshape(nv, 16)).reshape(-1, 4, 4)[:, :3, :3].to(torch.float32)             # cross_transformer.py:185
 
-    noise_std = float(getattr(cfg, "raw_noise_std", 0.0))
-    raws = []
+    # chosen once: the per-chunk providers of the pixel rows f and the token rows h, the point network, the compositor
+    chunks = [slice(s0, s0 + chunk) for s0 in range(0, xyz.shape[0], chunk)]       # batchify_rays :607-656 without a mask
+    shade = point_network_device if point_net == "device" else point_network
     if mode == "device":
         from .. import hip
         from . import train_ops
         if int(cfg.KNN) != 7 or float(cfg.KNN_DIST_ALPHA) != 0.5:
             raise hip.HipError("cfg.train_kernels = 'device': K4 is built for KNN = 7, KNN_DIST_ALPHA = 0.5")
         # K5 and K4 once over all P samples: one map-sized gradient per step, nothing of the blends kept for backward
-        if maps == "latents":
-            f_all = f_lat
-        else:
+        if maps != "latents":
             scale = hip.feat_scale(net.encoder.feat_scale(*pix.shape[2:]), image_shape, dev)
-            f_all = train_ops.PixelGatherFn.apply(pix.permute(0, 2, 3, 1).contiguous(), xyz, hip.pack_cams(R_in, T_in, K_in), scale)
-        h_all = train_ops.HumanRepresentationFn.apply(tokens.contiguous(), pts_s, centres, rot)
-        for f, h, vd in zip(f_all.split(chunk), h_all.split(chunk), viewdir.split(chunk)):
-            if point_net == "device":
-                raws.append(point_network_device(net, h, f, vd))            # (K4's rows with their zero pad column)
-            else:
-                raws.append(point_network(net, h[..., :255], f, vd))
-        raw = torch.cat(raws, 0).view(-1, S, 4)
-        if noise_std > 0.0:                                        # nerf_net_utils.py:39-44, drawn by torch
-            noise = torch.randn(raw[..., 3].shape).to(raw) * noise_std
-            raw = torch.cat([raw[..., :3], (raw[..., 3] + noise)[..., None]], -1)
-        rgb, acc, depth = train_ops.CompositeFn.apply(raw.contiguous(), z, ray_d, bool(cfg.white_bkgd))
+            f_lat = train_ops.PixelGatherFn.apply(pix.permute(0, 2, 3, 1).contiguous(), xyz, hip.pack_cams(R_in, T_in, K_in), scale)
+        fs = f_lat.split(chunk)
+        hs = train_ops.HumanRepresentationFn.apply(tokens.contiguous(), pts_s, centres, rot).split(chunk)
+        if point_net != "device":
+            hs = (h[..., :255] for h in hs)                        # (K4's rows carry a zero pad column, point_network_device takes it)
+        compose = lambda raw: train_ops.CompositeFn.apply(raw.contiguous(), z, ray_d, bool(cfg.white_bkgd))
     else:
-        for s0 in range(0, xyz.shape[0], chunk):                   # batchify_rays :607-656 without a mask
-            x = xyz[s0:s0 + chunk]
-            if maps == "latents":
-                f = f_lat[s0:s0 + chunk]
-            else:
-                f = sample_map(pix, project(x, R_in, T_in, K_in), net.encoder, image_shape).permute(2, 0, 1)
-            h = human_representation(net, pts_s[s0:s0 + chunk], centres, rot, tokens, int(cfg.KNN), float(cfg.KNN_DIST_ALPHA))
-            raws.append((point_network_device if point_net == "device" else point_network)(net, h, f, viewdir[s0:s0 + chunk]))
-        raw = torch.cat(raws, 0).view(-1, S, 4)
-        rgb, acc, depth = composite(raw, z, ray_d, noise_std, bool(cfg.white_bkgd))
+        if maps == "latents":
+            fs = (f_lat[c] for c in chunks)
+        else:
+            fs = (sample_map(pix, project(xyz[c], R_in, T_in, K_in), net.encoder, image_shape).permute(2, 0, 1) for c in chunks)
+        hs = (human_representation(net, pts_s[c], centres, rot, tokens, int(cfg.KNN), float(cfg.KNN_DIST_ALPHA)) for c in chunks)
+        compose = lambda raw: composite(raw, z, ray_d, 0.0, bool(cfg.white_bkgd))
+
+    raws = [shade(net, h, f, viewdir[c]) for f, h, c in zip(fs, hs, chunks)]       # (the generators run chunk by chunk)
+    raw = torch.cat(raws, 0).view(-1, S, 4)
+    noise_std = float(getattr(cfg, "raw_noise_std", 0.0))
+    if noise_std > 0.0:                                            # nerf_net_utils.py:39-44, drawn by torch
+        noise = torch.randn(raw[..., 3].shape).to(raw) * noise_std
+        raw = torch.cat([raw[..., :3], (raw[..., 3] + noise)[..., None]], -1)
+    rgb, acc, depth = compose(raw)
     return {"rgb_map": rgb[None], "acc_map": acc[None], "depth_map": depth[None]}

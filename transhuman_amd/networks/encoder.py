@@ -88,6 +88,36 @@ class ResNet18Trunk(nn.Module):
         self.fc = nn.Sequential()
 
 
+def trunk_sites(model):
+    """the (conv, bn) sites of the executed trunk (conv1, layer1, layer2), in the order ``walk_trunk`` runs them"""
+    yield model.conv1, model.bn1
+    for layer in (model.layer1, model.layer2):
+        for blk in layer:
+            if blk.downsample is not None:
+                yield blk.downsample[0], blk.downsample[1]
+            yield blk.conv1, blk.bn1
+            yield blk.conv2, blk.bn2
+
+
+def walk_trunk(model, x, conv_bn, pool):
+    """The one walk over the executed trunk (encoder.py:114-126 with BasicBlock.forward inlined) -> the three latents (64ch @H/2,
+    64ch @H/4, 128ch @H/8).  ``conv_bn(conv, bn, x, residual=None, relu=True)`` is one site: relu(bn(conv(x)) + residual);
+    ``pool(x)`` is the 3 x 3 / 2 max pooling.  The stock modules, the inference HIP stem and the training Functions
+    (autograd_path.trunk_device) are three such operator pairs.  No path of this project calls layer1 / layer2 or
+    BasicBlock.forward any more (the stock operator uses the trunk's one ReLU module for every site): that method stays as the
+    module's definition, for a caller that runs the blocks as modules."""
+    x = conv_bn(model.conv1, model.bn1, x)
+    lat = [x]
+    x = pool(x)
+    for layer in (model.layer1, model.layer2):
+        for blk in layer:
+            idt = x if blk.downsample is None else conv_bn(blk.downsample[0], blk.downsample[1], x, relu=False)
+            y = conv_bn(blk.conv1, blk.bn1, x)
+            x = conv_bn(blk.conv2, blk.bn2, y, residual=idt)
+        lat.append(x)
+    return lat
+
+
 class SpatialEncoder(nn.Module):
     def __init__(self):
         super().__init__()
@@ -117,21 +147,17 @@ class SpatialEncoder(nn.Module):
                 if lat is not None:
                     return lat
             return self._trunk_fused_bn(x)
-        x = m.relu(m.bn1(m.conv1(x)))
-        lat = [x]
-        x = m.layer1(m.maxpool(x))
-        lat.append(x)
-        x = m.layer2(x)
-        lat.append(x)
-        return lat
+
+        def conv_bn(conv, bn, t, residual=None, relu=True):
+            y = bn(conv(t))
+            if residual is not None:
+                y = y + residual
+            return m.relu(y) if relu else y
+
+        return walk_trunk(m, x, conv_bn, m.maxpool)
 
     def _bn_sites(self):
-        m = self.model
-        sites = [m.bn1]
-        for layer in (m.layer1, m.layer2):
-            for blk in layer:
-                sites += [blk.bn1, blk.bn2] + ([blk.downsample[1]] if blk.downsample is not None else [])
-        return sites
+        return [bn for _, bn in trunk_sites(self.model)]
 
     def _bn_sites_fusable(self):
         """train(): batch statistics (momentum given); eval(): running statistics -- both have a HIP form"""
@@ -156,15 +182,7 @@ class SpatialEncoder(nn.Module):
                 return hip.bn_act(hip.conv2d(t.contiguous(), mod), bn, residual=residual, relu=relu)
             return hip.bn_act(mod(t), bn, residual=residual, relu=relu)
 
-        x = conv_bn(m.conv1, m.bn1, x)
-        lat = [x]
-        x = m.maxpool(x) if stock_conv else hip.maxpool3x3s2(x)
-        for layer in (m.layer1, m.layer2):
-            for blk in layer:
-                idt = x if blk.downsample is None else conv_bn(blk.downsample[0], blk.downsample[1], x, relu=False)
-                y = conv_bn(blk.conv1, blk.bn1, x)
-                x = conv_bn(blk.conv2, blk.bn2, y, residual=idt)
-            lat.append(x)
+        lat = walk_trunk(m, x, conv_bn, m.maxpool if stock_conv else hip.maxpool3x3s2)
         counters = [b.num_batches_tracked for b in self._bn_sites()
                     if b.training and b.track_running_stats and b.num_batches_tracked is not None]
         if counters:
@@ -185,9 +203,7 @@ class SpatialEncoder(nn.Module):
 
     def _graph_version(self, x):
         from .. import hip
-        m = self.model
-        convs = [m.conv1] + [c for layer in (m.layer1, m.layer2) for blk in layer
-                             for c in ([blk.downsample[0]] if blk.downsample is not None else []) + [blk.conv1, blk.conv2]]
+        convs = [conv for conv, _ in trunk_sites(self.model)]
         if os.environ.get("TH_STOCK_CONV") == "1" or not all(hip.conv2d_supported(c) for c in convs):
             return None
         v = [(c.weight._version, c.weight.data_ptr()) for c in convs]

@@ -31,7 +31,8 @@ weight-gradient kernel -- and returns the gradients of the Parameters themselves
     LayerNormFn             x, w, b              -> LN(x)              keeps x          the final norm
 
 ``cfg.train_point_net = "device"`` does it for the per-point network (MLP_forward_ori), layer by layer like th_mlp_forward
-(k_pointnet_bwd.hip; composed by ``autograd_path.point_network_device`` from these two and ``LinearFn``):
+(k_vit_dense_bwd.hip / k_pointnet_bwd.hip; composed by ``autograd_path.point_network_device`` from these two and
+``LinearFn``):
 
     ReluLinearFn            a, W, b              -> relu(Linear(a))    keeps a, y       s, p, fc_1, fc_2, fc_3, view_fc, fc_4
     CrossViewAttentionFn    kvp, kvs [P,V,384]   -> n [P,V,256]        keeps kvp, kvs   gradient: both; A is recomputed
@@ -197,21 +198,29 @@ def _dense_inputs(fn, **tensors):
 
 
 class _DenseFn(torch.autograd.Function):
-    """Linear(op(a)) of one TransHE layer: th_linear_train_forward / th_linear_bwd with the operand form of the subclass"""
+    """act(Linear(op(a))) of one dense layer: th_linear_train_forward / th_linear_bwd with the operand form of the subclass, or,
+    for a subclass with RELU, th_linear_relu_forward / th_linear_relu_bwd (which also keep the output y)"""
     FORM = 0
+    RELU = False
 
     @classmethod
     def _fwd(cls, ctx, a, W, b, ln_w=None, ln_b=None, eps=1e-6):
         name = cls.__name__
         _dense_inputs(name, a=a, W=W, b=b, **({"ln_w": ln_w, "ln_b": ln_b} if ln_w is not None else {}))
         ctx.eps = float(eps)
+        if cls.RELU:
+            y = hip.linear_relu_forward(a.detach(), W.detach(), b.detach())
+            ctx.save_for_backward(a, W, y)
+            return y
         ctx.save_for_backward(a, W, *((ln_w, ln_b) if ln_w is not None else ()))
         return hip.linear_train_forward(a.detach(), W.detach(), b.detach(), cls.FORM, ln_w, ln_b, ctx.eps)
 
     @classmethod
     def _bwd(cls, ctx, grad_out):
-        a, W, *ln = ctx.saved_tensors
-        ln_w, ln_b = ln if ln else (None, None)
+        a, W, *rest = ctx.saved_tensors
+        if cls.RELU:
+            return hip.linear_relu_bwd(a, rest[0], W, grad_out.contiguous(), need_input=ctx.needs_input_grad[0])
+        ln_w, ln_b = rest if rest else (None, None)
         return hip.linear_bwd(a, W, grad_out.contiguous(), cls.FORM, ln_w, ln_b, ctx.eps)
 
 
@@ -258,21 +267,19 @@ class GeluLinearFn(_DenseFn):
         return g_u, g_w, g_b
 
 
-class ReluLinearFn(torch.autograd.Function):
+class ReluLinearFn(_DenseFn):
     """relu(nn.Linear(a)) on rows: the ReLU is the GEMM's epilogue; the backward gates g_out by [y > 0] on its way into the
     weight-gradient kernel (th_linear_relu_forward / th_linear_relu_bwd).  Kept: a and the output y, which autograd keeps anyway."""
+    FORM = hip.OPERAND_PLAIN
+    RELU = True
 
     @staticmethod
     def forward(ctx, a, W, b):
-        _dense_inputs("ReluLinearFn", a=a, W=W, b=b)
-        y = hip.linear_relu_forward(a.detach(), W.detach(), b.detach())
-        ctx.save_for_backward(a, W, y)
-        return y
+        return ReluLinearFn._fwd(ctx, a, W, b)
 
     @staticmethod
     def backward(ctx, grad_out):
-        a, W, y = ctx.saved_tensors
-        return hip.linear_relu_bwd(a, y, W, grad_out.contiguous(), need_input=ctx.needs_input_grad[0])
+        return ReluLinearFn._bwd(ctx, grad_out)
 
 
 class CrossViewAttentionFn(torch.autograd.Function):
