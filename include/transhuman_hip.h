@@ -1125,6 +1125,42 @@ size_t th_conv2d_wgrad_workspace_bytes(int N, int cin, int cout, int ks, int str
 int th_conv2d_wgrad(th_ctx* ctx, const float* x, const float* g_y, int N, int cin, int cout, int ks, int stride, int H, int W,
                     float* g_w, void* workspace, size_t workspace_bytes, th_stream stream);
 
+/* ---- K26: the dataset's other targets -- sample_ray_h36m, both splits, and get_acc (additions, ABI 12) ---------------- */
+/* sample_ray_h36m (lib/utils/if_nerf/if_nerf_data_utils.py:516-614) and get_acc (:635-641), which the reference's dataset runs in
+ * numpy for every test / evaluation batch and for the training batch without patch sampling (can_smpl.py:518-535), on the dense
+ * per-pixel arrays of th_gen_rays.  All pointers are DEVICE pointers; ray_o, ray_d, near, far, ray_mask, msk, bound_mask and img
+ * with its two strides are th_patch_rays' inputs.
+ * m = msk * bound_mask in uint8; body = (m == 1), face = (m == 13), rand_set = (bound_mask == 1) & (m != 100).
+ * th_ray_sample_train: draws fp64 [4][3][nrays] in [0, 1).  n = 0; while n < nrays: rem = nrays - n, n_body = (int)(rem body_ratio),
+ * n_face = (int)(rem face_ratio) (fp64 products), n_rand = rem - n_body - n_face; the candidates of iteration i are, in this
+ * order, n_body body pixels (an empty body class: the ONE pixel (1,1)), n_face face pixels (an empty face class: none), n_rand
+ * rand_set pixels (an empty rand_set: the ONE pixel (0,0)); pick j of class c (0 body, 1 face, 2 rand) is the class's k-th pixel
+ * in row-major order, k = min(floor(draws[i][c][j] n_c), n_c - 1); the candidates whose ray_mask holds are appended in order and
+ * n grows by their number, so the final count can be nrays + 1.  Rows (allocated at nrays + 4): out_rgb, out_ray_o, out_ray_d
+ * fp32 [.][3], out_near, out_far fp32 [.], out_coord int64 [.][2] = (row, col).  info int32 [4] = the ray count, the iterations
+ * used, status bits (1: an iteration added nothing, 2: unfinished after 4 iterations, 4: a negative class count) and the last
+ * iteration's candidate count; the rows below info[0] are written, nothing else is.  One workgroup runs the whole loop: no host
+ * read between iterations.
+ * th_ray_sample_test: the rows of the five dense arrays and the image where ray_mask holds, in row-major order (rows allocated at
+ * H W); info[0] = their count, info[1..3] = 0.
+ * th_ray_acc: coord int64 [n][2] = (row, col); acc uint8 [n] = 1 where any pixel of msk [H][W] is nonzero in the 25 x 25 window
+ * centred on the coordinate and clipped to the image (cv2.dilate with a 25 x 25 kernel of ones, read at the coordinate).
+ * No atomics: bit-identical from run to run.  No host wait; nothing is allocated.  Limits (argument errors before any launch):
+ * 1 <= H, W <= 4096 (train: 2 <= H, W), 1 <= nrays <= 65536, 0 <= body_ratio, face_ratio, body_ratio + face_ratio <= 1; the
+ * workspace at least th_ray_sample_workspace_bytes(H, W, nrays) (nrays is not read by the test split: pass 0; 0 bytes for sizes out
+ * of range). */
+size_t th_ray_sample_workspace_bytes(int H, int W, int nrays);
+int th_ray_sample_train(th_ctx* ctx, const float* ray_o, const float* ray_d, const float* near, const float* far,
+                        const uint8_t* ray_mask, const uint8_t* msk, const uint8_t* bound_mask, const float* img,
+                        long long pix_stride, long long chan_stride, int H, int W, const double* draws, int nrays, double body_ratio,
+                        double face_ratio, float* out_rgb, float* out_ray_o, float* out_ray_d, float* out_near, float* out_far,
+                        int64_t* out_coord, int32_t* info, void* workspace, size_t workspace_bytes, th_stream stream);
+int th_ray_sample_test(th_ctx* ctx, const float* ray_o, const float* ray_d, const float* near, const float* far,
+                       const uint8_t* ray_mask, const float* img, long long pix_stride, long long chan_stride, int H, int W,
+                       float* out_rgb, float* out_ray_o, float* out_ray_d, float* out_near, float* out_far, int32_t* info,
+                       void* workspace, size_t workspace_bytes, th_stream stream);
+int th_ray_acc(th_ctx* ctx, const int64_t* coord, int n, const uint8_t* msk, int H, int W, uint8_t* acc, th_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,15 @@ def _defaults():
         # host) or "device" (made in Renderer.render from the target view, target_K / target_R / target_T and can_bounds, when the
         # batch has no ray_o; transhuman_amd/train_targets.py, K18)
         target_prep="batch",
+        # which of the dataset's target sides target_prep = "device" makes: "patch" (the patch targets of a training call only) or
+        # "dataset" (what the reference's __getitem__ makes for the call's split, can_smpl.py:507-535: the patch targets for a
+        # training call with patch sampling, else sample_ray_h36m + get_acc -- also for the renderer's no-grad entries, which then
+        # accept a batch without ray_o; transhuman_amd/train_targets.py, K26)
+        target_sampler="patch",
+        # sample_ray_h36m's train split (train_or_eval.yaml / lib/config/config.py: N_rand, body_sample_ratio, face_sample_ratio)
+        N_rand=1024,
+        body_sample_ratio=0.5,
+        face_sample_ratio=0.0,
         # the trainer's loss (lib/train/trainers/if_nerf_clight.py:34-38, train_or_eval.yaml): l2rec_weight * MSE +
         # lpips_weight * mean(LPIPS_vgg) over the rendered patches (transhuman_amd/train_loss.py, K21)
         l2rec_weight=1.0,

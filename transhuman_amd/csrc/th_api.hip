@@ -1868,6 +1868,41 @@ int th_adam_unpack(th_ctx* c, th_adam_plan_t* plan, void* const* dst, const long
                                (hipStream_t)stream);
 }
 
+size_t th_ray_sample_workspace_bytes(int H, int W, int nrays) { return th_ray_sample_ws(H, W, nrays); }
+
+int th_ray_sample_train(th_ctx* c, const float* ray_o, const float* ray_d, const float* near_in, const float* far_in,
+                        const uint8_t* ray_mask, const uint8_t* msk, const uint8_t* bound_mask, const float* img,
+                        long long pix_stride, long long chan_stride, int H, int W, const double* draws, int nrays, double body_ratio,
+                        double face_ratio, float* out_rgb, float* out_ray_o, float* out_ray_d, float* out_near, float* out_far,
+                        int64_t* out_coord, int32_t* info, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c, "null argument");
+    TH_TRY(th_ray_sample_train_check(H, W, nrays, body_ratio, face_ratio));
+    TH_REQUIRE(ray_o && ray_d && near_in && far_in && ray_mask && msk && bound_mask && img && draws, "null argument");
+    TH_REQUIRE(out_rgb && out_ray_o && out_ray_d && out_near && out_far && out_coord && info && ws, "null argument");
+    return th_ray_sample_train_launch(ray_o, ray_d, near_in, far_in, ray_mask, msk, bound_mask, img, pix_stride, chan_stride, H, W,
+                                      draws, nrays, body_ratio, face_ratio, out_rgb, out_ray_o, out_ray_d, out_near, out_far,
+                                      out_coord, info, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int th_ray_sample_test(th_ctx* c, const float* ray_o, const float* ray_d, const float* near_in, const float* far_in,
+                       const uint8_t* ray_mask, const float* img, long long pix_stride, long long chan_stride, int H, int W,
+                       float* out_rgb, float* out_ray_o, float* out_ray_d, float* out_near, float* out_far, int32_t* info, void* ws,
+                       size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c, "null argument");
+    TH_TRY(th_ray_sample_check(H, W));
+    TH_REQUIRE(ray_o && ray_d && near_in && far_in && ray_mask && img, "null argument");
+    TH_REQUIRE(out_rgb && out_ray_o && out_ray_d && out_near && out_far && info && ws, "null argument");
+    return th_ray_sample_test_launch(ray_o, ray_d, near_in, far_in, ray_mask, img, pix_stride, chan_stride, H, W, out_rgb, out_ray_o,
+                                     out_ray_d, out_near, out_far, info, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int th_ray_acc(th_ctx* c, const int64_t* coord, int n, const uint8_t* msk, int H, int W, uint8_t* acc, th_stream stream) {
+    TH_REQUIRE(c, "null argument");
+    TH_TRY(th_ray_sample_check(H, W));
+    TH_REQUIRE(n == 0 || (coord && msk && acc), "null argument");
+    return th_ray_acc_launch(coord, n, msk, H, W, acc, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 static ThProf* prof_of(th_ctx* c) {

@@ -655,6 +655,20 @@ int th_patch_rays_launch(const float* ray_o, const float* ray_d, const float* ne
                          uint8_t* patch_masks_sub, float* target_patches, int32_t* xy_min, int32_t* counts, float* o_rgb,
                          float* o_ray_o, float* o_ray_d, float* o_near, float* o_far, uint8_t* o_sub, int64_t* o_inds, void* ws,
                          size_t ws_bytes, hipStream_t s);
+// K26 (k_raysample.hip): sample_ray_h36m's two splits on the dense arrays of th_gen_rays, and get_acc's window test
+size_t th_ray_sample_ws(int H, int W, int nrays);
+int th_ray_sample_check(int H, int W);
+int th_ray_sample_train_check(int H, int W, int nrays, double body_ratio, double face_ratio);
+int th_ray_sample_train_launch(const float* ray_o, const float* ray_d, const float* near_in, const float* far_in,
+                               const uint8_t* ray_mask, const uint8_t* msk, const uint8_t* bound, const float* img,
+                               long long pix_stride, long long chan_stride, int H, int W, const double* draws, int nrays,
+                               double body_ratio, double face_ratio, float* o_rgb, float* o_ray_o, float* o_ray_d, float* o_near,
+                               float* o_far, int64_t* o_coord, int32_t* info, void* ws, size_t ws_bytes, hipStream_t s);
+int th_ray_sample_test_launch(const float* ray_o, const float* ray_d, const float* near_in, const float* far_in,
+                              const uint8_t* ray_mask, const float* img, long long pix_stride, long long chan_stride, int H, int W,
+                              float* o_rgb, float* o_ray_o, float* o_ray_d, float* o_near, float* o_far, int32_t* info, void* ws,
+                              size_t ws_bytes, hipStream_t s);
+int th_ray_acc_launch(const int64_t* coord, int n, const uint8_t* msk, int H, int W, uint8_t* acc, hipStream_t s);
 int th_segmean_masked_launch(const float* rows, int V, int width, const uint8_t* viz, int nv, const int32_t* off,
                              const int32_t* mem, int nc, float* out, hipStream_t s);
 // k_optim.hip: the gradient exchange's flat buffer over a th_adam_plan_t -- the layout rule, and the checks + launch behind

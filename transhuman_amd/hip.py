@@ -1656,21 +1656,10 @@ def patch_rays(dense, msk, bound_mask, img, draws, subject_ratio, patch_size):
     H, W = (int(n) for n in msk.shape)
     dev = msk.device
     N, P = int(draws.shape[0]), int(patch_size)
-    if img.dim() != 3 or img.dtype is not torch.float32:
-        raise ValueError(f"img must be float32 [H,W,3] or [3,H,W], got {img.dtype} {tuple(img.shape)}")
-    if tuple(img.shape) == (H, W, 3) and (img.stride(0) == W * img.stride(1) or H == 1):
-        pix, chan = img.stride(1), img.stride(2)
-    elif tuple(img.shape) == (3, H, W) and (img.stride(1) == W * img.stride(2) or H == 1):
-        pix, chan = img.stride(2), img.stride(0)
-    else:
-        raise ValueError(f"img {tuple(img.shape)} with strides {img.stride()}: [H,W,3] or [3,H,W] for H, W = {H}, {W}, its rows "
-                         "W pixels apart")
-    rm = dense["mask_at_box"]
-    rm = rm.view(torch.uint8) if rm.dtype is torch.bool else rm
-    ray_o, ray_d, near, far = (_f32(dense[k]) for k in ("ray_o", "ray_d", "near", "far"))
-    assert rm.numel() == H * W and ray_o.numel() == 3 * H * W and near.numel() == H * W and bound_mask.shape == msk.shape
+    (ray_o, ray_d, near, far, rm), pix, chan = _dense_ray_inputs(dense, img, H, W)
+    assert bound_mask.shape == msk.shape
     assert msk.dtype is torch.uint8 and bound_mask.dtype is torch.uint8 and draws.dtype is torch.float64 and draws.shape[1] == 2
-    msk, bound_mask, rm, draws = msk.contiguous(), bound_mask.contiguous(), rm.contiguous(), draws.contiguous()
+    msk, bound_mask, draws = msk.contiguous(), bound_mask.contiguous(), draws.contiguous()
     rows = max(N * P * P, 1)
     e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
     out = dict(patch_masks=e((N, P, P), torch.uint8), patch_masks_sub=e((N, P, P), torch.uint8),
@@ -1684,6 +1673,85 @@ def patch_rays(dense, msk, bound_mask, img, draws, subject_ratio, patch_size):
                                  "patch_masks", "patch_masks_sub", "target_patches", "xy_min", "counts", "rgb", "ray_o", "ray_d",
                                  "near", "far", "sub_mask", "select_inds")), _p(ws), ws.numel(), _stream()))
     return out
+
+
+def _dense_ray_inputs(dense, img, H, W):
+    """the arguments th_patch_rays, th_ray_sample_train and th_ray_sample_test share: the four dense arrays of ``gen_rays`` and its
+    box mask as uint8, and the image's pixel / channel strides"""
+    if img.dim() != 3 or img.dtype is not torch.float32:
+        raise ValueError(f"img must be float32 [H,W,3] or [3,H,W], got {img.dtype} {tuple(img.shape)}")
+    if tuple(img.shape) == (H, W, 3) and (img.stride(0) == W * img.stride(1) or H == 1):
+        pix, chan = img.stride(1), img.stride(2)
+    elif tuple(img.shape) == (3, H, W) and (img.stride(1) == W * img.stride(2) or H == 1):
+        pix, chan = img.stride(2), img.stride(0)
+    else:
+        raise ValueError(f"img {tuple(img.shape)} with strides {img.stride()}: [H,W,3] or [3,H,W] for H, W = {H}, {W}, its rows "
+                         "W pixels apart")
+    rm = dense["mask_at_box"]
+    rm = (rm.view(torch.uint8) if rm.dtype is torch.bool else rm).contiguous()
+    ray_o, ray_d, near, far = (_f32(dense[k]) for k in ("ray_o", "ray_d", "near", "far"))
+    assert rm.numel() == H * W and ray_o.numel() == 3 * H * W and ray_d.numel() == 3 * H * W
+    assert near.numel() == H * W and far.numel() == H * W
+    return (ray_o, ray_d, near, far, rm), pix, chan
+
+
+def ray_sample_train(dense, msk, bound_mask, img, draws, nrays, body_ratio, face_ratio):
+    """th_ray_sample_train (K26): the train split of sample_ray_h36m (if_nerf_data_utils.py:532-598) on the dense arrays of
+    ``gen_rays(..., compact=False)``; the arguments of ``patch_rays``, with ``draws`` float64 [4,3,nrays].  Returns the raw device
+    outputs, the ray rows allocated at their bound nrays + 4: {rgb, ray_o, ray_d [.,3], near, far [.], coord int64 [.,2], info
+    int32 [4] (ray count, iterations, status bits 1 = an iteration added nothing / 2 = unfinished / 4 = a negative class count, the
+    last iteration's candidates)}; only the first info[0] rows are written.  No host wait; sizes outside the kernel's limits raise
+    HipError before any launch."""
+    lib = load_library()
+    H, W = (int(n) for n in msk.shape)
+    dev, nrays = msk.device, int(nrays)
+    arrays, pix, chan = _dense_ray_inputs(dense, img, H, W)
+    assert msk.dtype is torch.uint8 and bound_mask.dtype is torch.uint8 and bound_mask.shape == msk.shape
+    assert draws.dtype is torch.float64 and tuple(draws.shape) == (4, 3, max(nrays, 0))
+    msk, bound_mask, draws = msk.contiguous(), bound_mask.contiguous(), draws.contiguous()
+    rows = max(nrays, 0) + 4
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    out = dict(rgb=e((rows, 3), torch.float32), ray_o=e((rows, 3), torch.float32), ray_d=e((rows, 3), torch.float32),
+               near=e((rows,), torch.float32), far=e((rows,), torch.float32), coord=e((rows, 2), torch.int64),
+               info=e((4,), torch.int32))
+    ws = _ws(lib.th_ray_sample_workspace_bytes(H, W, nrays), dev)
+    _check(lib.th_ray_sample_train(ctx(dev), *(_p(a) for a in arrays), _p(msk), _p(bound_mask), _p(img), pix, chan, H, W, _p(draws),
+                                   nrays, float(body_ratio), float(face_ratio), *(_p(out[k]) for k in (
+                                       "rgb", "ray_o", "ray_d", "near", "far", "coord", "info")), _p(ws), ws.numel(), _stream()))
+    return out
+
+
+def ray_sample_test(dense, img, H, W):
+    """th_ray_sample_test (K26): the test split of sample_ray_h36m (if_nerf_data_utils.py:600-612) -- the rows of the dense arrays
+    of ``gen_rays(..., compact=False)`` and of ``img`` (float32 [H,W,3] or [3,H,W], read through its strides) where mask_at_box
+    holds, in row-major order.  Returns the raw device outputs, the rows allocated at H W: {rgb, ray_o, ray_d [.,3], near, far [.],
+    info int32 [4] (info[0] = the count)}; only the first info[0] rows are written.  No host wait."""
+    lib = load_library()
+    H, W = int(H), int(W)
+    dev = img.device
+    arrays, pix, chan = _dense_ray_inputs(dense, img, H, W)
+    rows = max(H * W, 1)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    out = dict(rgb=e((rows, 3), torch.float32), ray_o=e((rows, 3), torch.float32), ray_d=e((rows, 3), torch.float32),
+               near=e((rows,), torch.float32), far=e((rows,), torch.float32), info=e((4,), torch.int32))
+    ws = _ws(lib.th_ray_sample_workspace_bytes(H, W, 0), dev)
+    _check(lib.th_ray_sample_test(ctx(dev), *(_p(a) for a in arrays), _p(img), pix, chan, H, W, *(_p(out[k]) for k in (
+        "rgb", "ray_o", "ray_d", "near", "far", "info")), _p(ws), ws.numel(), _stream()))
+    return out
+
+
+def ray_acc(coord, msk):
+    """th_ray_acc (K26): get_acc (if_nerf_data_utils.py:635-641).  coord int64 [n,2] = (row, col), msk uint8 [H,W] -- device tensors.
+    Returns uint8 [n]: 1 where any pixel of msk is nonzero in the 25 x 25 window centred on the coordinate, clipped to the image.
+    No host wait."""
+    lib = load_library()
+    H, W = (int(n) for n in msk.shape)
+    assert coord.dtype is torch.int64 and coord.dim() == 2 and coord.shape[1] == 2 and msk.dtype is torch.uint8
+    coord, msk = coord.contiguous(), msk.contiguous()
+    n = int(coord.shape[0])
+    acc = torch.empty(n, dtype=torch.uint8, device=msk.device)
+    _check(lib.th_ray_acc(ctx(msk.device), _p(coord), n, _p(msk), H, W, _p(acc), _stream()))
+    return acc
 
 
 def ssim(a, b):

@@ -14,7 +14,8 @@ What runs where
     DPaRF, pixel gather, MLP,
     compositing                        th_render_rays        (K1,K4,K5,K6,K7)
 Unlike the reference nothing here mutates ``batch`` (:459-462) -- with one documented exception: cfg.target_prep == "device"
-adds the training targets made on the device to it (``render``).
+adds the training targets made on the device to it (``render``), and with cfg.target_sampler == "dataset" the same holds for the
+no-grad entries (``render_fast``, ``render_sequence``, ``render``): a batch without ``ray_o`` gets the test split's keys.
 """
 import os
 import sys
@@ -34,6 +35,17 @@ import torch                                                        # noqa: E402
 
 from transhuman_amd.config import cfg_get, get_cfg                  # noqa: E402
 from transhuman_amd import hip, synth                               # noqa: E402
+
+
+def _test_targets(batch):
+    """cfg.target_prep == "device" with cfg.target_sampler == "dataset": a batch without ``ray_o`` gets the test split of the
+    dataset's targets (rgb, ray_o, ray_d, near, far, acc, mask_at_box) ADDED TO IT from its target view, in front of the first
+    read of ``batch["ray_o"]`` (transhuman_amd.train_targets.add_targets, K26).  Every other setting, and a batch that carries
+    its rays: nothing is touched."""
+    if "ray_o" not in batch and cfg_get("target_prep", "batch") == "device" and cfg_get("target_sampler", "patch") == "dataset":
+        from transhuman_amd import train_targets
+        train_targets.add_targets(batch, split="test")
+    return batch
 
 
 class _PreparedBatch(dict):
@@ -477,8 +489,10 @@ class Renderer:
         Without a ready ``frame`` the ray-only stage (hull mask, compaction) is queued first, then the
         per-frame constants, then the shading: the sample count is on the host by the time it is needed.
         Called on the device's default stream the frame is queued on a stream of the renderer's own (``_own_stream``), ordered
-        behind everything the caller has queued; the caller's stream waits for the frame before this returns."""
-        dev = batch["ray_o"].device
+        behind everything the caller has queued; the caller's stream waits for the frame before this returns.
+        cfg.target_prep == "device" with cfg.target_sampler == "dataset": a batch without ``ray_o`` first gets the test split's
+        targets added to it (``_test_targets``)."""
+        dev = _test_targets(batch)["ray_o"].device
         own = self._own_stream(dev) if dev.type == "cuda" else None
         if own is None:
             return self._render_fast(batch, frame, ray_slice, small_frame_rays)
@@ -583,7 +597,9 @@ class Renderer:
         encoder stem's latents.
         The stem and TransHE of these frames are replayed hipGraphs (encoder.trunk(graph=True), hip.vit_forward(graph=True)):
         the latents and tokens of ``self.last_frame`` live in the graphs' rotating buffers and stay valid until three more
-        frames have been yielded -- ``self.last_frame.rebuild()`` returns a frame that owns its memory."""
+        frames have been yielded -- ``self.last_frame.rebuild()`` returns a frame that owns its memory.
+        cfg.target_prep == "device" with cfg.target_sampler == "dataset": a batch without ``ray_o`` gets the test split's targets
+        added to it at the head of its front (``_test_targets``)."""
         pipe = _FramePipeline(self, batches, ray_slice, small_frame_rays, lookahead, token_exchange, stem_exchange)
         pipe.start()
         # A frame is handed out one step late: its range-guard snapshot (hip.render_rays, defer_guard) is read back
@@ -641,6 +657,9 @@ class Renderer:
         cfg.target_prep == "device": a training call whose batch has no ``ray_o`` gets its rays and patch targets made on the
         device from the target view (transhuman_amd.train_targets.add_targets, K18); they are ADDED TO ``batch`` -- the one
         exception to "nothing here mutates batch", because the trainer reads them from it after this returns.
+        cfg.target_sampler == "dataset" (K26) widens that to what the reference's dataset makes for the call's split: a training
+        call with cfg.patch.use_patch_sampling false gets sample_ray_h36m's train split (rgb, ray_o, ray_d, near, far, acc,
+        mask_at_box), a call without gradients its test split (``_test_targets``), both added to ``batch`` in the same way.
         cfg.input_prep == "device": a training call whose batch has no ``input_imgs`` gets its input views through ``frame_inputs``
         (raw frames, jittered under cfg.input_jitter == "device"); a batch that has ``input_imgs`` is read as it is."""
         cfg = get_cfg()
@@ -653,7 +672,9 @@ class Renderer:
                 raise ValueError(f'cfg.target_prep is {target_prep!r}: "batch" or "device"')
             if wants_grad or randomised:
                 from transhuman_amd import train_targets
-                train_targets.add_targets(batch)
+                train_targets.add_targets(batch, split="train" if wants_grad else "test")
+            else:
+                _test_targets(batch)
         if wants_grad or randomised:
             if not batch["ray_o"].is_cuda:
                 raise hip.HipError("Renderer.render needs the batch on an MI355X (there is no CPU path)")
@@ -733,7 +754,7 @@ class _FramePipeline:
         if first is None:
             return
         r = self.r
-        self.dev = dev = first["ray_o"].device
+        self.dev = dev = _test_targets(first)["ray_o"].device
         self.side = r._stream("side_stream", dev)
         self.side.wait_stream(torch.cuda.current_stream(dev))
         self.hull_side = r._stream("hull_side_stream", dev)
@@ -776,8 +797,11 @@ class _FramePipeline:
         r, side = self.r, self.side
         # the range-guard epoch these constants are built under: a frame whose front was issued before the guard
         # switched a path (fp32 MLP, stock convolutions, fp32 TransHE GEMMs) is rebuilt before it is handed out
-        ep = hip.range_epoch(b["ray_o"].device)
         given = getattr(b, "source", None) or b        # (what the caller handed in: ``self.last_batch``)
+        if "ray_o" not in b:
+            with torch.cuda.stream(side):
+                _test_targets(b)
+        ep = hip.range_epoch(b["ray_o"].device)
         with torch.cuda.stream(side):
             b = r.frame_inputs(b)
             pts = r._points(b, self.ray_slice)
