@@ -1161,6 +1161,34 @@ int th_ray_sample_test(th_ctx* ctx, const float* ray_o, const float* ray_d, cons
                        void* workspace, size_t workspace_bytes, th_stream stream);
 int th_ray_acc(th_ctx* ctx, const int64_t* coord, int n, const uint8_t* msk, int H, int W, uint8_t* acc, th_stream stream);
 
+/* ---- K27: cfg.use_truncation -- skip the samples far from every token centre (additions, ABI 12) ---------------------- */
+/* Network.get_human_representation's mask_preserve = knn_dist.min(-1) < cfg.KNN_SIGMA (cross_transformer.py:175-180) and what
+ * Network.forward does with it (:247-264): the per-point network runs on the preserved samples, raw = 0 for the others.
+ * A sample is kept when sqrtf(d2min) < (float)sigma, d2min = the squared distance to its nearest centre by K4's own
+ * expression -- bit for bit the distance of K4's first neighbour -- over K4's candidate grid where the grid builder takes
+ * these centres (7 <= nc <= 4096, TH_DPARF_NOGRID unset), else over all of them: the same result.  A NaN distance drops.
+ * All pointers are DEVICE pointers.
+ * th_truncate_select: pts_smpl [P,3], centres [nc,3] (nc >= 1) -> mask uint8 [P] (1 = kept), sel int32 (allocated at P): the
+ * kept indices, ascending, in sel[0 .. count), and count int32 [1].  No host wait: the caller reads count.  An ordered
+ * compaction in three launches (+ two for the grid): no atomics, no workgroup waits for another, every output element is stored
+ * once, nothing is cleared and nothing in the outputs or the workspace is read before it is written -- bit-identical from
+ * run to run whatever the buffers held.  P = 0 writes count = 0.
+ * th_truncate_scatter: rows_kept [n_kept,C] -> rows [P,C]: rows[sel[j]] = rows_kept[j], exact zeros in the rows with mask 0,
+ * every element stored once; mask and sel[0 .. n_kept) as th_truncate_select left them.  th_truncate_scatter_bwd, its adjoint:
+ * g_rows_kept[j] = g_rows[sel[j]].  C must be 4.
+ * th_set_truncation: sigma > 0 switches the same rule on for th_render_rays, th_eval_sigma_grid and th_eval_points: behind the
+ * shading and in front of compositing / extraction one more launch zeroes the dense raw rows of the hull-valid samples
+ * whose nearest centre is sigma or farther away -- the reference's raw = 0.  The hull mask, the ray compaction and the
+ * R' <= small_frame_rays rule are untouched.  sigma <= 0 (the default of a new context): off, no launch and no byte differs. */
+int th_set_truncation(th_ctx* ctx, double sigma);
+size_t th_truncate_select_workspace_bytes(int P, int nc);                                       /* pure host call */
+int th_truncate_select(th_ctx* ctx, const float* pts_smpl, int P, const float* centres, int nc, double sigma, uint8_t* mask,
+                       int32_t* sel, int32_t* count, void* workspace, size_t workspace_bytes, th_stream stream);
+int th_truncate_scatter(th_ctx* ctx, const float* rows_kept, const uint8_t* mask, const int32_t* sel, int n_kept, int P, int C,
+                        float* rows, th_stream stream);
+int th_truncate_scatter_bwd(th_ctx* ctx, const float* g_rows, const int32_t* sel, int n_kept, int P, int C, float* g_rows_kept,
+                            th_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

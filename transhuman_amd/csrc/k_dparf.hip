@@ -21,6 +21,7 @@
 // encoding, ONE split-f16 row (64 hi + 64 lo halves) per sample -- it is the same for every view.
 // Bound: L2 gather of 7*V*768 B per sample; HBM write 3 KB per sample.
 #include "th_internal.h"
+#include "k_dparf_near.h"
 
 #define DP_K 7
 #define DP_SAMPLES 128
@@ -77,15 +78,7 @@ __device__ __forceinline__ float dp_sin(float a) {
 // (with the fixed 0.075 m cell the lists of the reference's kmeans_dict_1500 held ~3 x as many: K4 3.1 ms against 0.57 at
 // N_c = 500).  Lists live in slots of DPG_STRIDE entries; a cell whose list does not fit is marked (count -1) and its points
 // take the full scan -- exact either way.
-#define DPG_MAXCELLS 32768
-#define DPG_STRIDE 192
-#define DPG_CELL 0.075f        // cell size asked for at N_c = 500; 0.1: lists of ~70 candidates, 0.075: ~55, K4 0.73 -> 0.71 ms; (dpgrid_setup_kernel grows it until the grid fits DPG_MAXCELLS)
-struct DpGrid {
-    float gmin[3];
-    float g, inv_g;
-    int dim[3];
-    int ncell;          // 0: grid disabled (too many cells)
-};
+// (DPG_MAXCELLS, DPG_STRIDE, DPG_CELL and struct DpGrid: k_dparf_near.h, shared with K27)
 
 __global__ __launch_bounds__(256) void dpgrid_setup_kernel(const float* __restrict__ centres, int nc, float g, float margin,
                                                            DpGrid* __restrict__ gi) {
@@ -273,9 +266,7 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
         }
         for (int j = half; j < nlist; j += 2) {
             const int c = list ? list[j] : j;
-            float dx = x - cen[3 * c], dy = y - cen[3 * c + 1], dz = z - cen[3 * c + 2];
-            float d2 = dx * dx + dy * dy;
-            d2 = d2 + dz * dz;
+            const float d2 = dp_dist2(x, y, z, cen[3 * c], cen[3 * c + 1], cen[3 * c + 2]);   // (k_dparf_near.h: K27 tests the same value)
             if (d2 < bd[DP_K - 1]) dp_insert(bd, bi, d2, c);   // ascending c: a tie never displaces an earlier index
         }
         // merge the partner's list (7 candidates) -> global top-7 ordered by (d2, index)

@@ -360,6 +360,36 @@ int th_set_fused_waves(th_ctx* c, int waves) {
     return 0;
 }
 
+// ---- K27: cfg.use_truncation (k_truncate.hip) ----
+int th_set_truncation(th_ctx* c, double sigma) {
+    TH_REQUIRE(c && sigma == sigma, "th_set_truncation: a context and a number (<= 0: off)");
+    c->trunc_sigma = sigma > 0.0 ? (float)sigma : 0.f;       // the reference's comparison runs in fp32: sigma rounds once, here
+    return 0;
+}
+
+size_t th_truncate_select_workspace_bytes(int P, int nc) { return th_truncate_select_ws(P, nc); }
+
+int th_truncate_select(th_ctx* c, const float* pts_smpl, int P, const float* centres, int nc, double sigma, uint8_t* mask,
+                       int32_t* sel, int32_t* count, void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && centres && count && ws && (P == 0 || (pts_smpl && mask && sel)), "null argument");
+    const bool grid = getenv("TH_DPARF_NOGRID") == nullptr;
+    return th_truncate_select_launch(pts_smpl, P, centres, nc, (float)sigma, mask, sel, count, ws, ws_bytes, grid, (hipStream_t)stream);
+}
+
+int th_truncate_scatter(th_ctx* c, const float* rows_kept, const uint8_t* mask, const int32_t* sel, int n_kept, int P, int C,
+                        float* rows, th_stream stream) {
+    TH_REQUIRE(c && C == 4, "th_truncate_scatter: rows of 4 floats");
+    TH_REQUIRE(P == 0 || (mask && rows && (n_kept == 0 || (rows_kept && sel))), "null argument");
+    return th_truncate_scatter_launch(rows_kept, mask, sel, n_kept, P, rows, (hipStream_t)stream);
+}
+
+int th_truncate_scatter_bwd(th_ctx* c, const float* g_rows, const int32_t* sel, int n_kept, int P, int C, float* g_rows_kept,
+                            th_stream stream) {
+    TH_REQUIRE(c && C == 4, "th_truncate_scatter_bwd: rows of 4 floats");
+    TH_REQUIRE(n_kept == 0 || (g_rows && sel && g_rows_kept), "null argument");
+    return th_truncate_gather_launch(g_rows, sel, n_kept, P, g_rows_kept, (hipStream_t)stream);
+}
+
 int th_set_vit_weights(th_ctx* c, int depth, int dim, int heads, const th_vit_block* blocks, const float* norm_w,
                        const float* norm_b, th_stream stream) {
     TH_REQUIRE(c && blocks && norm_w && norm_b, "null argument");
@@ -1541,6 +1571,13 @@ static int shade_stage(th_ctx* c, const th_frame* f, const ThPointSrc& ps, bool 
         }
         ProfScope ps4(pf, TH_PROF_COMPOSITE, s);
         TH_TRY(th_scatter_raw_launch(cb.raw_c, sel, m, unmasked, w.raw, s));
+    }
+    // th_set_truncation (K27): raw = 0 where the nearest token centre is sigma or farther away, what Network.forward's _forward
+    // leaves for those samples (cross_transformer.py:247-264).  K4's grid where this call built it, else the full scan: same rows.
+    if (c->trunc_sigma > 0.f && n > 0) {
+        ProfScope ps5(pf, TH_PROF_COMPOSITE, s);
+        TH_TRY(th_truncate_zero_launch(ps, f->Rh, f->Th, w.idx, n, f->centres, f->n_clusters, c->trunc_sigma,
+                                       use_grid ? w.gws : nullptr, w.raw, s));
     }
     return 0;
 }

@@ -345,6 +345,7 @@ struct th_ctx {
     int vit_mode = 1;                 // 1: TransHE dense layers on the fp16-split MFMA path (th_gemm_h3), 0: fp32 MFMA
     int tok_gather = 1;               // 1: TH_ROWS_NBR hand-over (token blend inside the fused kernel), 0: TH_ROWS_FOLDED
     int tex_rows = 1;                 // 1: TH_ROWS_TEX hand-over of the pixel features (texel lists, blend inside the fused kernel)
+    float trunc_sigma = 0.f;          // th_set_truncation: > 0: the frame paths zero the raw rows of samples this far from every token centre
     int device = 0;
     void* mlp_store = nullptr;
     void* vit_store = nullptr;
@@ -671,6 +672,16 @@ int th_ray_sample_test_launch(const float* ray_o, const float* ray_d, const floa
 int th_ray_acc_launch(const int64_t* coord, int n, const uint8_t* msk, int H, int W, uint8_t* acc, hipStream_t s);
 int th_segmean_masked_launch(const float* rows, int V, int width, const uint8_t* viz, int nv, const int32_t* off,
                              const int32_t* mem, int nc, float* out, hipStream_t s);
+// K27 (k_truncate.hip): cfg.use_truncation -- the mask / ordered list of the samples whose nearest token centre is closer than
+// sigma, the scatter of their rows back to all samples with its adjoint, and the frame paths' zeroing of the dropped raw rows
+size_t th_truncate_select_ws(int P, int nc);
+int th_truncate_select_launch(const float* pts_smpl, int P, const float* centres, int nc, float sigma, uint8_t* mask, int32_t* sel,
+                              int32_t* count, void* ws, size_t ws_bytes, bool use_grid, hipStream_t s);
+int th_truncate_scatter_launch(const float* rows_c, const uint8_t* mask, const int32_t* sel, int n, int P, float* rows, hipStream_t s);
+int th_truncate_gather_launch(const float* g, const int32_t* sel, int n, int P, float* g_c, hipStream_t s);
+// grid_ws: K4's candidate grid of these centres (th_dparf_grid_build) or nullptr (full scan)
+int th_truncate_zero_launch(const ThPointSrc& ps, const float* Rh, const float* Th, const int32_t* idx, int n, const float* centres,
+                            int nc, float sigma, const void* grid_ws, float* raw, hipStream_t s);
 // k_optim.hip: the gradient exchange's flat buffer over a th_adam_plan_t -- the layout rule, and the checks + launch behind
 // th_adam_pack (unpack = 0; ptrs[i] NULL: zeros) and th_adam_unpack (unpack = 1)
 long long ad_flat_layout(int n_tensors, const long long* counts, const uint8_t* live, long long* offsets_out);

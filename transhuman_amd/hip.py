@@ -84,6 +84,7 @@ class DeviceState:
         self.fallback = {"mlp": False, "conv": False, "vit": False}
         self.epoch = 0                   # number of switches so far (frames queued earlier are re-rendered)
         self.owner = {}                  # "mlp" / "vit" -> (weakref to the module whose weights the ctx holds, version tuple)
+        self.truncation = 0.0            # what set_truncation last handed to th_set_truncation (0: off, a new context's default)
         self.workspaces, self.pools = {}, {}   # slot -> render workspace (_cached_ws) / shading pool, None: the shared one (_shade_pool)
 
 
@@ -1752,6 +1753,65 @@ def ray_acc(coord, msk):
     acc = torch.empty(n, dtype=torch.uint8, device=msk.device)
     _check(lib.th_ray_acc(ctx(msk.device), _p(coord), n, _p(msk), H, W, _p(acc), _stream()))
     return acc
+
+
+def truncate_select(pts_smpl, centres, sigma):
+    """th_truncate_select (K27): cfg.use_truncation's mask_preserve (cross_transformer.py:175-180).  pts_smpl [P,3], centres [N_c,3]
+    -> (mask uint8 [P], sel int32 [P'] = the kept indices, ascending, P').  A sample is kept when the fp32 distance to its nearest
+    centre -- K4's own -- is below fp32(sigma).  One host read: the count (4 bytes)."""
+    lib = load_library()
+    p, c = _f32(pts_smpl).reshape(-1, 3), _f32(centres).reshape(-1, 3)
+    P, nc = p.shape[0], c.shape[0]
+    mask = torch.empty(P, dtype=torch.uint8, device=p.device)
+    sel = torch.empty(P, dtype=torch.int32, device=p.device)
+    count = torch.empty(1, dtype=torch.int32, device=p.device)
+    ws = _ws(lib.th_truncate_select_workspace_bytes(P, nc), p.device)
+    _check(lib.th_truncate_select(ctx(p.device), _p(p), P, _p(c), nc, float(sigma), _p(mask), _p(sel), _p(count), _p(ws),
+                                  ws.numel(), _stream()))
+    n = int(count.item())
+    return mask, sel[:n], n
+
+
+def _truncate_lists(fn, mask, sel):
+    assert mask.is_cuda and mask.dtype is torch.uint8 and mask.dim() == 1 and mask.is_contiguous(), f"{fn}: mask uint8 [P]"
+    assert sel.dtype is torch.int32 and sel.dim() == 1 and sel.is_contiguous() and sel.device == mask.device, f"{fn}: sel int32 [P']"
+    return int(mask.shape[0]), int(sel.shape[0])
+
+
+def truncate_scatter(rows_kept, mask, sel):
+    """th_truncate_scatter (K27): rows_kept [P',4] -> rows [P,4] with rows[sel[j]] = rows_kept[j] and exact zeros where mask is 0
+    (raw[:, mask_preserve, :] = raw_preserved on zeros, cross_transformer.py:256-257); mask, sel from ``truncate_select``."""
+    lib = load_library()
+    P, n = _truncate_lists("truncate_scatter", mask, sel)
+    r = _f32(rows_kept)
+    assert r.shape == (n, 4), "truncate_scatter: one row of 4 floats per kept sample"
+    rows = torch.empty((P, 4), dtype=torch.float32, device=mask.device)
+    _check(lib.th_truncate_scatter(ctx(mask.device), _p(r), _p(mask), _p(sel), n, P, 4, _p(rows), _stream()))
+    return rows
+
+
+def truncate_scatter_bwd(g_rows, sel):
+    """th_truncate_scatter_bwd (K27): the adjoint of ``truncate_scatter``, g_rows [P,4] -> g_rows[sel] [P',4]."""
+    lib = load_library()
+    g = _f32(g_rows)
+    assert g.dim() == 2 and g.shape[1] == 4 and sel.dtype is torch.int32 and sel.is_contiguous() and sel.device == g.device
+    P, n = int(g.shape[0]), int(sel.shape[0])
+    out = torch.empty((n, 4), dtype=torch.float32, device=g.device)
+    _check(lib.th_truncate_scatter_bwd(ctx(g.device), _p(g), _p(sel), n, P, 4, _p(out), _stream()))
+    return out
+
+
+def set_truncation(sigma, device=None):
+    """th_set_truncation (K27): ``sigma`` > 0 = the frame paths of this device (render_rays, eval_sigma_grid, eval_points) zero the
+    raw rows of the hull-valid samples whose nearest token centre is sigma or farther away (cfg.use_truncation at inference);
+    0 or None = off, the default.  A value already in force costs nothing."""
+    sigma = float(sigma or 0.0)
+    st = _state(device)
+    if st.handle is None and sigma <= 0.0:
+        return                                   # (a context is created off)
+    if st.truncation != sigma:
+        _check(load_library().th_set_truncation(ctx(device), sigma))
+        st.truncation = sigma
 
 
 def ssim(a, b):

@@ -44,6 +44,10 @@ The allowed values of these six and of ``cfg.train_gather_bwd`` (the form of the
 ``config.TRAIN_SWITCHES``, and ``_switch`` is their one reader: a value outside the table is a ValueError, a value other than
 the first on CPU tensors a HipError.
 
+``cfg.use_truncation`` (the reference's key, with ``cfg.KNN_SIGMA``; cross_transformer.py:175-180, :247-264) is honoured under every
+combination of the switches: the samples whose nearest token centre is KNN_SIGMA or farther away are taken out once, in front of
+the token blend, the pixel rows and the per-point network, and get raw = 0 (``truncation_lists``).
+
 Pinned by ``oracle/gen_golden_train.py`` (the real reference imported in the survey container: outputs and parameter
 gradients of one training step's forward/backward on a synthetic patch -> ``tests/golden/g18_train_step.npz``) and
 ``tests/test_train_path.py``.  Every function cites the reference lines it follows.
@@ -54,6 +58,7 @@ import torch
 import torch.nn.functional as F
 
 from ..config import TRAIN_SWITCHES, get_cfg
+from ..truncation import sigma_in_force
 
 
 # ---- the switches ------------------------------------------------------------------------------------------------------
@@ -336,6 +341,36 @@ def composite(raw, z, ray_d, raw_noise_std, white_bkgd):
     return rgb, acc, torch.sum(w * z, -1)
 
 
+# ---- cfg.use_truncation --------------------------------------------------------------------------------------------------
+class _Truncation:
+    """the kept samples of a step: ``index`` selects their rows from a [P, ...] tensor, ``scatter`` puts raw rows back"""
+    def __init__(self, index, n, scatter):
+        self.index, self.n, self.scatter = index, n, scatter
+
+
+def truncation_lists(pts_s, centres, sigma, mode):
+    """mask_preserve = knn_dist.min(-1) < cfg.KNN_SIGMA (cross_transformer.py:175-180) over all samples, compared in fp32 like the
+    reference.  mode "device": K27 (hip.truncate_select; the scatter is train_ops.TruncScatterFn); "torch": the same fp32
+    expressions as torch operators, a boolean index (any device)."""
+    if mode == "device":
+        from .. import hip
+        from . import train_ops
+        mask, sel, n = hip.truncate_select(pts_s, centres, sigma)
+        return _Truncation(sel.long(), n, lambda rows, P: train_ops.TruncScatterFn.apply(rows.contiguous(), mask, sel))
+    keep = []
+    for p in pts_s.split(32768):
+        d = p[:, None, :] - centres[None]
+        d2 = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]
+        keep.append((d2 + d[..., 2] * d[..., 2]).min(1)[0].sqrt() < torch.tensor(sigma, dtype=p.dtype, device=p.device))
+    keep = torch.cat(keep)
+
+    def scatter(rows, P):
+        full = rows.new_zeros((P, rows.shape[1]))
+        full[keep] = rows                                          # raw[:, mask_preserve, :] = raw_preserved, :256-257
+        return full
+    return _Truncation(keep, int(keep.sum()), scatter)
+
+
 # ---- the entry -------------------------------------------------------------------------------------------------------------
 def render(renderer, batch, chunk=32768):
     """Renderer.render -> _render (if_clight_renderer.py:486-605) with pts_mask = None: every sample of every ray through
@@ -367,6 +402,16 @@ def render(renderer, batch, chunk=32768):
     R_in, T_in, K_in = (batch[k][0].reshape(V, *sh) for k, sh in (("input_R", (3, 3)), ("input_T", (3, 1)), ("input_K", (3, 3))))
     image_shape = batch["input_imgs"][0].shape[-2:]
     verts_in = batch["input_smpl_vertice"][0][0]
+    nv = verts_in.shape[0]
+    M = pooling_matrix_cached(renderer, nv, dev, torch.float32)
+    centres = M @ batch["tar_smpl_vertice_smplcoord"][0]
+    # cfg.use_truncation (cross_transformer.py:175-180, :247-264): the mask over all P samples once; K4, the pixel rows and the
+    # per-point network then see the kept rows only, raw is scattered back in front of the noise and the compositor
+    P_all, trunc = xyz.shape[0], None
+    sigma = sigma_in_force(cfg)
+    if sigma > 0.0:
+        trunc = truncation_lists(pts_s, centres, sigma, mode)
+        xyz, pts_s, viewdir = xyz[trunc.index], pts_s[trunc.index], viewdir[trunc.index]
     if maps == "latents":
         from .. import hip
         # a 1 x 1 convolution commutes with bilinear sampling: reduction_layer on the gathered rows (k_encoder.hip does the same)
@@ -374,17 +419,14 @@ def render(renderer, batch, chunk=32768):
                                  hip.feat_scale(net.encoder.feat_scale(*images.shape[2:]), image_shape, dev), encoder=encoder,
                                  gather_bwd=gather_bwd)
         painted = _lin(net.encoder.reduction_layer, gather(verts_in)).permute(1, 0, 2)
-        f_lat = gather(xyz)                                # once over all P samples, split per chunk below
+        f_lat = gather(xyz) if xyz.shape[0] > 0 else None  # once over all (kept) samples, split per chunk below
     else:
         hol, pix = encode(net.encoder, images, encoder=encoder)
         painted = sample_map(hol, project(verts_in, R_in, T_in, K_in), net.encoder, image_shape).permute(0, 2, 1)
     if cfg.rasterize:
         painted = painted * batch["input_vizmaps"][0][0][..., None].to(painted.dtype)              # :181-182
-    nv = verts_in.shape[0]
-    M = pooling_matrix_cached(renderer, nv, dev, torch.float32)
     tokens = vit_forward(net.ViT, torch.einsum("cn,vnd->vcd", M, painted), renderer._pe_norm(V, dev),
                          attention=attention, dense=dense)
-    centres = M @ batch["tar_smpl_vertice_smplcoord"][0]
     blend = batch["blend_mtx"][0]
     M64 = pooling_matrix_cached(renderer, nv, dev, blend.dtype)        # (float64 mean, :544)
     rot = (M64 @ blend.reshape(nv, 16)).reshape(-1, 4, 4)[:, :3, :3].to(torch.float32)             # cross_transformer.py:185
@@ -397,14 +439,17 @@ def render(renderer, batch, chunk=32768):
         from . import train_ops
         if int(cfg.KNN) != 7 or float(cfg.KNN_DIST_ALPHA) != 0.5:
             raise hip.HipError("cfg.train_kernels = 'device': K4 is built for KNN = 7, KNN_DIST_ALPHA = 0.5")
-        # K5 and K4 once over all P samples: one map-sized gradient per step, nothing of the blends kept for backward
-        if maps != "latents":
-            scale = hip.feat_scale(net.encoder.feat_scale(*pix.shape[2:]), image_shape, dev)
-            f_lat = train_ops.PixelGatherFn.apply(pix.permute(0, 2, 3, 1).contiguous(), xyz, hip.pack_cams(R_in, T_in, K_in), scale)
-        fs = f_lat.split(chunk)
-        hs = train_ops.HumanRepresentationFn.apply(tokens.contiguous(), pts_s, centres, rot).split(chunk)
-        if point_net != "device":
-            hs = (h[..., :255] for h in hs)                        # (K4's rows carry a zero pad column, point_network_device takes it)
+        # K5 and K4 once over all (kept) samples: one map-sized gradient per step, nothing of the blends kept for backward
+        fs = hs = ()
+        if chunks:                                                 # (none: cfg.use_truncation dropped every sample)
+            if maps != "latents":
+                scale = hip.feat_scale(net.encoder.feat_scale(*pix.shape[2:]), image_shape, dev)
+                f_lat = train_ops.PixelGatherFn.apply(pix.permute(0, 2, 3, 1).contiguous(), xyz, hip.pack_cams(R_in, T_in, K_in),
+                                                      scale)
+            fs = f_lat.split(chunk)
+            hs = train_ops.HumanRepresentationFn.apply(tokens.contiguous(), pts_s, centres, rot).split(chunk)
+            if point_net != "device":
+                hs = (h[..., :255] for h in hs)                    # (K4's rows carry a zero pad column, point_network_device takes it)
         compose = lambda raw: train_ops.CompositeFn.apply(raw.contiguous(), z, ray_d, bool(cfg.white_bkgd))
     else:
         if maps == "latents":
@@ -415,7 +460,10 @@ def render(renderer, batch, chunk=32768):
         compose = lambda raw: composite(raw, z, ray_d, 0.0, bool(cfg.white_bkgd))
 
     raws = [shade(net, h, f, viewdir[c]) for f, h, c in zip(fs, hs, chunks)]       # (the generators run chunk by chunk)
-    raw = torch.cat(raws, 0).view(-1, S, 4)
+    raw = torch.cat(raws, 0) if raws else xyz.new_zeros((0, 4))    # (no kept sample: the reference's else branch, :258-260)
+    if trunc is not None:
+        raw = trunc.scatter(raw, P_all)
+    raw = raw.view(-1, S, 4)
     noise_std = float(getattr(cfg, "raw_noise_std", 0.0))
     if noise_std > 0.0:                                            # nerf_net_utils.py:39-44, drawn by torch
         noise = torch.randn(raw[..., 3].shape).to(raw) * noise_std

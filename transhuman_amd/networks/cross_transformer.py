@@ -29,6 +29,7 @@ import torch                                                        # noqa: E402
 from torch import nn                                                # noqa: E402
 
 from transhuman_amd.config import get_cfg                           # noqa: E402
+from transhuman_amd.truncation import sigma_in_force               # noqa: E402
 from transhuman_amd.networks.encoder import SpatialEncoder, _PEBuffers   # noqa: E402
 from transhuman_amd.networks import vision_transformer as ViT       # noqa: E402
 
@@ -66,8 +67,6 @@ class Network(nn.Module):
         if cfg.KNN != 7 or cfg.KNN_FREQ != 10 or abs(cfg.KNN_DIST_ALPHA - 0.5) > 0:
             raise NotImplementedError("the DPaRF kernel is built for KNN=7, KNN_FREQ=10, KNN_DIST_ALPHA=0.5 "
                                       "(configs/train_or_eval.yaml:63-66)")
-        if getattr(cfg, "use_truncation", False):
-            raise NotImplementedError("cfg.use_truncation=True is a training-only option (cross_transformer.py:249)")
 
     # -- checkpoint compatibility ------------------------------------------------
     def load_state_dict(self, state_dict, strict=True, **kw):
@@ -84,6 +83,21 @@ class Network(nn.Module):
         blend = DPaRF_param_dict["blend_mtx"]
         assert pts.shape[0] == 1, "B = 1 is assumed (cross_transformer.py:222)"
         rot = blend[0][..., :3, :3].type(torch.float32).reshape(-1, 9)    # :185
-        raw = hip.network_forward(self, pixel_feat, sincos_viewdir[0], pts[0], centres[0], rot, holder,
-                                  mask=None if pts_mask is None else pts_mask[0])
+        mask = None if pts_mask is None else pts_mask[0]
+        sigma = sigma_in_force()
+        if sigma > 0.0:
+            # cfg.use_truncation (:175-180, :247-264): the per-point network on the samples closer than KNN_SIGMA to a token
+            # centre (K27), zeros elsewhere -- inside pts_mask on the progressive branch, without one on MLP_forward_ori (:273-278)
+            keep, sel, n = hip.truncate_select(pts[0], centres[0], sigma)
+            if mask is not None:
+                mask = mask.reshape(-1).to(torch.uint8) * keep
+            else:
+                P = pts.shape[1]
+                raw = torch.zeros((0, 4), dtype=torch.float32, device=keep.device)
+                if n > 0:
+                    idx = sel.long()
+                    raw = hip.network_forward(self, pixel_feat[..., idx].contiguous(), sincos_viewdir[0][idx], pts[0][idx],
+                                              centres[0], rot, holder, mask=None)
+                return hip.truncate_scatter(raw, keep, sel).reshape(1, P, 4)
+        raw = hip.network_forward(self, pixel_feat, sincos_viewdir[0], pts[0], centres[0], rot, holder, mask=mask)
         return raw.unsqueeze(0)

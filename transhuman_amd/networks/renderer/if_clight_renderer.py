@@ -35,6 +35,7 @@ import torch                                                        # noqa: E402
 
 from transhuman_amd.config import cfg_get, get_cfg                  # noqa: E402
 from transhuman_amd import hip, synth                               # noqa: E402
+from transhuman_amd.truncation import sigma_in_force               # noqa: E402
 
 
 def _test_targets(batch):
@@ -452,7 +453,8 @@ class Renderer:
                           n_samples=cfg.N_samples, **self._sampling_randoms(batch, sl, cfg))
 
     def _shade(self, frame, pts, **kw):
-        """hip.render_rays over the configuration's background"""
+        """hip.render_rays over the configuration's background, under the cfg.use_truncation / cfg.KNN_SIGMA in force (K27)"""
+        hip.set_truncation(sigma_in_force(), frame.verts.device)
         return hip.render_rays(self.net, frame, pts, white_bkgd=bool(get_cfg().white_bkgd), **kw)
 
     def _hull_front(self, batch, pts, V, feed, hull, small_frame_rays, slot=0, **predemand_args):

@@ -26,6 +26,7 @@ import numpy as np                                                  # noqa: E402
 
 from transhuman_amd.config import get_cfg, cfg_get                  # noqa: E402
 from transhuman_amd import hip                                      # noqa: E402
+from transhuman_amd.truncation import sigma_in_force               # noqa: E402
 from transhuman_amd.networks.renderer.if_clight_renderer import Renderer as Base_Renderer   # noqa: E402
 
 
@@ -38,6 +39,7 @@ class Renderer(Base_Renderer):
         flat = pts.reshape(-1, 3)
         if pts_slice is not None:
             flat = flat[pts_slice]
+        hip.set_truncation(sigma_in_force(cfg), flat.device)         # cfg.use_truncation / cfg.KNN_SIGMA in force (K27)
         sigma, stats = hip.eval_sigma_grid(self.net, frame, flat)
         self.last_stats = stats
         if pts_slice is not None:

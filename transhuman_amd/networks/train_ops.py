@@ -169,6 +169,22 @@ class CompositeFn(torch.autograd.Function):
             None, None, None
 
 
+class TruncScatterFn(torch.autograd.Function):
+    """cfg.use_truncation (cross_transformer.py:256-257): the raw rows of the kept samples [P',4] back into all P samples, exact
+    zeros elsewhere (K27); ``mask`` uint8 [P] and ``sel`` int32 [P'] from hip.truncate_select.  The adjoint is the gather g[sel]."""
+
+    @staticmethod
+    def forward(ctx, rows_kept, mask, sel):
+        _on_device("TruncScatterFn", rows_kept)
+        ctx.save_for_backward(sel)
+        return hip.truncate_scatter(rows_kept, mask, sel)
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        (sel,) = ctx.saved_tensors
+        return hip.truncate_scatter_bwd(grad_rows.contiguous(), sel), None, None
+
+
 class AttentionFn(torch.autograd.Function):
     """Attention.forward (vision_transformer.py:271-278) on the fused qkv layer's output: qkv [V,N,3 C] -> [V,N,C], through the
     attention kernels of the inference path (K3) with the backward of k_vit_bwd.hip.  Kept for the backward: qkv, the output
