@@ -186,18 +186,15 @@ __global__ __launch_bounds__(256) void dpgrid_fill_kernel(const float* __restric
     if (lane == 0) cell_count[cell] = o <= DPG_STRIDE ? o : -1;      // (-1: the list does not fit its slot -> full scan)
 }
 
-size_t th_dparf_grid_ws(int nc) {
-    return th_align(sizeof(DpGrid)) + th_align((size_t)DPG_MAXCELLS * 4) + th_align((size_t)DPG_MAXCELLS * DPG_STRIDE * 4);
-}
+size_t th_dparf_grid_ws(int /* nc: the grid's size is fixed */) { return th_measure(dp_grid_layout); }
 
 int th_dparf_grid_build(const float* centres, int nc, void* ws, size_t ws_bytes, hipStream_t s) {
-    TH_REQUIRE(ws_bytes >= th_dparf_grid_ws(nc), "grid workspace too small");
-    TH_REQUIRE(th_dparf_grid_ok(nc), "too many (or fewer than 7) token centres for the grid builder");
     ThArena ar(ws, ws_bytes);
-    DpGrid* gi = ar.take<DpGrid>(1);
-    int* cnt = ar.take<int>(DPG_MAXCELLS);
-    int* cand = ar.take<int>((size_t)DPG_MAXCELLS * DPG_STRIDE);
-    TH_REQUIRE(cand != nullptr, "grid workspace carve failed");
+    const DpGridView v = dp_grid_layout(ar);
+    TH_REQUIRE(ar.ok(), "grid workspace too small");
+    TH_REQUIRE(th_dparf_grid_ok(nc), "too many (or fewer than 7) token centres for the grid builder");
+    DpGrid* gi = const_cast<DpGrid*>(v.gi);
+    int *cnt = const_cast<int*>(v.cell_count), *cand = const_cast<int*>(v.cand);
     hipLaunchKernelGGL(dpgrid_setup_kernel, dim3(1), dim3(256), 0, s, centres, nc, DPG_CELL, 0.25f, gi);
     hipLaunchKernelGGL(dpgrid_fill_kernel, dim3(DPG_MAXCELLS / 4), dim3(256), (size_t)nc * 16, s, centres, nc, gi, cnt, cand);
     TH_LAUNCH_CHECK();
@@ -544,39 +541,32 @@ int th_dparf_launch(const float* pts_smpl, const ThPointSrc* ps, const float* Rh
     }
     TH_REQUIRE(fmt == TH_ROWS_F32 || fmt == TH_ROWS_REC || ((fmt == TH_ROWS_FOLDED || fmt == TH_ROWS_NBR) && pe_out != nullptr),
                "K4 writes fp32 rows, the folded form or neighbour records");
-    // optional candidate grid (th_dparf_grid_build into grid_ws): same carve as the builder
-    const DpGrid* gi = nullptr;
-    const int *cnt = nullptr, *cand = nullptr;
-    if (grid_ws != nullptr) {
-        ThArena ar(const_cast<void*>(grid_ws), th_dparf_grid_ws(nc));
-        gi = ar.take<DpGrid>(1);
-        cnt = ar.take<int>(DPG_MAXCELLS);
-        cand = ar.take<int>((size_t)DPG_MAXCELLS * DPG_STRIDE);
-    }
+    // optional candidate grid (th_dparf_grid_build into grid_ws)
+    const DpGridView gv = dp_grid_view(grid_ws, nc);
     if (fmt == TH_ROWS_REC) {
         static unsigned long long attrr = 0ull;
         if (th_lds_attr_needed(&attrr))
             TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<false, -2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL((dparf_kernel<false, -2>), dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gi, cnt, cand);
+                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
     } else if (fmt == TH_ROWS_NBR) {
         static unsigned long long attrn = 0ull;
         if (th_lds_attr_needed(&attrn))
             TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<true, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL((dparf_kernel<true, -1>), dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gi, cnt, cand);
+                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
     } else if (fmt == TH_ROWS_FOLDED && V == 3) {
         static unsigned long long attr3 = 0ull;
         if (th_lds_attr_needed(&attr3))
             TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL((dparf_kernel<true, 3>), dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gi, cnt, cand);
+                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
     } else if (fmt == TH_ROWS_FOLDED)
         hipLaunchKernelGGL(dparf_kernel<true>, dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gi, cnt, cand);
+                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
     else
         hipLaunchKernelGGL(dparf_kernel<false>, dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gi, cnt, cand);
+                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
     TH_LAUNCH_CHECK();
     return 0;
 }

@@ -14,21 +14,16 @@ struct DpGrid {
     int ncell;          // 0: grid disabled (too many cells)
 };
 
-// the carve of th_dparf_grid_build's workspace (th_dparf_grid_ws bytes)
-struct DpGridView {
-    const DpGrid* gi;
-    const int* cell_count;
-    const int* cand;
-};
+// th_dparf_grid_build's workspace: the grid's record, every cell's candidate count and list (only the builder casts the const away)
+struct DpGridView { const DpGrid* gi; const int *cell_count, *cand; };
+static inline DpGridView dp_grid_layout(ThArena& ar) {
+    return {ar.take<DpGrid>(1), ar.take<int>(DPG_MAXCELLS), ar.take<int>((size_t)DPG_MAXCELLS * DPG_STRIDE)};
+}
+// the view of a built grid handed on without its size (nullptr: no grid, the scans run over all centres)
 static inline DpGridView dp_grid_view(const void* grid_ws, int nc) {
-    DpGridView v{nullptr, nullptr, nullptr};
-    if (grid_ws != nullptr) {
-        ThArena ar(const_cast<void*>(grid_ws), th_dparf_grid_ws(nc));
-        v.gi = ar.take<DpGrid>(1);
-        v.cell_count = ar.take<int>(DPG_MAXCELLS);
-        v.cand = ar.take<int>((size_t)DPG_MAXCELLS * DPG_STRIDE);
-    }
-    return v;
+    if (grid_ws == nullptr) return {nullptr, nullptr, nullptr};
+    ThArena ar(const_cast<void*>(grid_ws), th_dparf_grid_ws(nc));
+    return dp_grid_layout(ar);
 }
 
 #ifdef __HIPCC__

@@ -388,23 +388,29 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     }
 }
 
-size_t th_bn_ws(int N, int C, int HW) {
+// the plane slices' partial (sum, sum of squares) per channel
+static double* bn_layout(ThArena& ar, int N, int C, int HW) {
     const int splits = (HW + BN_SPLIT_ELEMS - 1) / BN_SPLIT_ELEMS;
-    return th_align((size_t)C * N * splits * 2 * sizeof(double));
+    return ar.take<double>((size_t)C * N * splits * 2);
 }
+size_t th_bn_ws(int N, int C, int HW) { return th_measure(bn_layout, N, C, HW); }
 
 int th_bn_act_launch(const float* x, const float* res, int N, int C, int HW, const float* gamma, const float* beta,
                      float eps, float momentum, float* run_mean, float* run_var, int relu, float* y, void* ws,
                      size_t ws_bytes, hipStream_t s, int eval, const void* conv_stats, int conv_np) {
     TH_REQUIRE(N > 0 && C > 0 && HW > 0, "empty tensor");
-    TH_REQUIRE(eval || conv_stats || ws_bytes >= th_bn_ws(N, C, HW), "workspace too small");
+    double* part = nullptr;          // (eval mode and a convolution's own statistics need no partials)
+    if (!eval && !conv_stats) {
+        ThArena ar(ws, ws_bytes);
+        part = bn_layout(ar, N, C, HW);
+        TH_REQUIRE(ar.ok(), "workspace too small");
+    }
     TH_REQUIRE(!conv_stats || (!eval && conv_np > 0), "convolution statistics: train mode, at least one partial");
     TH_REQUIRE(!eval || (run_mean && run_var), "eval-mode BatchNorm needs the running statistics");
     TH_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) == 0, "tensors must be 16-byte aligned");
     const int splits = (HW + BN_SPLIT_ELEMS - 1) / BN_SPLIT_ELEMS;
     const int NS = N * splits;
     TH_REQUIRE(NS <= 65535, "too many plane slices");
-    double* part = (eval || conv_stats) ? nullptr : (double*)ws;
     if (part) hipLaunchKernelGGL(bn_stats_kernel, dim3(C, NS), dim3(256), 0, s, x, C, HW, splits, part, NS);
     hipLaunchKernelGGL(bn_apply_kernel, dim3(C, NS), dim3(256), 0, s, x, res, C, HW, splits, part, NS,
                        (long long)N * HW, gamma, beta, eps, momentum, run_mean, run_var, relu, y,

@@ -426,9 +426,11 @@ int th_conv2d_wgrad_chunk_internal() { return EB_WG_CHUNK; }
 void th_conv2d_dgrad_tile_internal(int* rows, int* cols) { *rows = EB_TH; *cols = EB_TW; }
 int th_bn_act_bwd_slice_internal() { return EB_BN_SLICE; }
 
+// four partial sums per (slice, channel)
+static double* eb_bn_layout(ThArena& ar, int N, int C, int HW) { return ar.take<double>((size_t)C * eb_bn_plan(N, HW).S * 4); }
 size_t th_bn_act_bwd_ws(int N, int C, int HW) {
     if (N < 1 || C < 1 || HW < 1 || (long long)N * C * HW >= (1LL << 31) || C > 65535) return 0;
-    return th_align((size_t)C * eb_bn_plan(N, HW).S * 4 * sizeof(double));
+    return th_measure(eb_bn_layout, N, C, HW);
 }
 
 int th_bn_act_bwd_launch(const float* y, const float* out, const float* g, int N, int C, int HW, const float* gamma, double eps,
@@ -436,13 +438,15 @@ int th_bn_act_bwd_launch(const float* y, const float* out, const float* g, int N
     TH_REQUIRE(N >= 1 && C >= 1 && C <= 65535 && HW >= 1 && (long long)N * C * HW < (1LL << 31),
                "unsupported shape: N, C, HW >= 1, C <= 65535, fewer than 2^31 elements");
     TH_REQUIRE(eps > 0.0, "eps must be positive");
-    TH_REQUIRE(ws_bytes >= th_bn_act_bwd_ws(N, C, HW), "workspace too small");
+    ThArena ar(ws, ws_bytes);
+    double* sums = eb_bn_layout(ar, N, C, HW);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     TH_REQUIRE((((uintptr_t)ws) & 7) == 0, "the workspace must be 8-byte aligned");
     const EbBnPlan p = eb_bn_plan(N, HW);
     const dim3 grid((unsigned)p.S, (unsigned)C);
-    hipLaunchKernelGGL(eb_bn_sums_kernel, grid, dim3(EB_THREADS), 0, s, y, out, g, C, HW, p.L, p.slice, (double*)ws);
+    hipLaunchKernelGGL(eb_bn_sums_kernel, grid, dim3(EB_THREADS), 0, s, y, out, g, C, HW, p.L, p.slice, sums);
     TH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(eb_bn_apply_kernel, grid, dim3(EB_THREADS), 0, s, y, out, g, C, HW, p.L, p.slice, (const double*)ws, gamma,
+    hipLaunchKernelGGL(eb_bn_apply_kernel, grid, dim3(EB_THREADS), 0, s, y, out, g, C, HW, p.L, p.slice, (const double*)sums, gamma,
                        eps, g_y, g_res, g_gamma, g_beta);
     TH_LAUNCH_CHECK();
     return 0;
@@ -494,25 +498,31 @@ int th_conv2d_dgrad_launch(const float* gy, int N, int cin, int cout, int ks, in
     return 0;
 }
 
+// one partial weight gradient [cout][cin ks ks] per chunk of output positions
+static float* eb_wgrad_layout(ThArena& ar, int N, int cin, int cout, int ks, int stride, int H, int W) {
+    const long long M = (long long)N * eb_out(H, ks, stride) * eb_out(W, ks, stride);
+    return ar.take<float>((size_t)th_cdiv(M, EB_WG_CHUNK) * cout * cin * ks * ks);
+}
 size_t th_conv2d_wgrad_ws(int N, int cin, int cout, int ks, int stride, int H, int W) {
     if (!(eb_supported(cin, cout, ks, stride) & 1) || !eb_dims_ok(N, cin, cout, ks, stride, H, W)) return 0;
-    const long long M = (long long)N * eb_out(H, ks, stride) * eb_out(W, ks, stride);
-    return th_align((size_t)th_cdiv(M, EB_WG_CHUNK) * cout * cin * ks * ks * sizeof(float));
+    return th_measure(eb_wgrad_layout, N, cin, cout, ks, stride, H, W);
 }
 
 int th_conv2d_wgrad_launch(const float* x, const float* gy, int N, int cin, int cout, int ks, int stride, int H, int W, float* gw,
                            void* ws, size_t ws_bytes, hipStream_t s) {
     TH_REQUIRE(eb_supported(cin, cout, ks, stride) & 1, "unsupported shape: no weight gradient is built for this convolution");
     TH_REQUIRE(eb_dims_ok(N, cin, cout, ks, stride, H, W), "unsupported shape: N in 1..16383, H, W >= 1, fewer than 2^31 elements");
-    TH_REQUIRE(ws_bytes >= th_conv2d_wgrad_ws(N, cin, cout, ks, stride, H, W), "workspace too small");
+    ThArena ar(ws, ws_bytes);
+    float* part = eb_wgrad_layout(ar, N, cin, cout, ks, stride, H, W);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     const int Ho = eb_out(H, ks, stride), Wo = eb_out(W, ks, stride), J = cin * ks * ks;
     const int Mtot = N * Ho * Wo, chunks = th_cdiv(Mtot, EB_WG_CHUNK);
     const dim3 grid((unsigned)chunks, (unsigned)th_cdiv(J, EB_WG_TILE), (unsigned)(cout / EB_WG_TILE));
     hipLaunchKernelGGL(eb_wgrad_kernel, grid, dim3(EB_THREADS), 0, s, x, gy, cin, H, W, cout, Ho, Wo, ks, stride, ks / 2, Mtot,
-                       (float*)ws);
+                       part);
     TH_LAUNCH_CHECK();
     const long long elems = (long long)cout * J;
-    hipLaunchKernelGGL(eb_wgrad_reduce_kernel, dim3((unsigned)th_cdiv(elems, 256)), dim3(256), 0, s, (const float*)ws, chunks, elems,
+    hipLaunchKernelGGL(eb_wgrad_reduce_kernel, dim3((unsigned)th_cdiv(elems, 256)), dim3(256), 0, s, (const float*)part, chunks, elems,
                        gw);
     TH_LAUNCH_CHECK();
     return 0;

@@ -327,36 +327,32 @@ __global__ __launch_bounds__(256) void hull_mask_kernel(ThPointSrc ps, long long
     }
 }
 
-size_t th_hull_ws(int n_verts) {
-    return th_align(sizeof(GridInfo)) + 3 * th_align((GRID_MAX_CELLS + 1) * sizeof(int)) +
-           th_align((size_t)n_verts * 3 * sizeof(float)) + th_align((size_t)GRID_MAX_CELLS * 6 * sizeof(float)) +
-           th_align((size_t)GRID_EXT_CELLS * sizeof(unsigned));
+// the vertex grid: record, cell counts / starts / fill cursors, vertices in cell order, cell boxes, extended cells' neighbour masks
+struct HullWs { GridInfo* gi; int *counts, *starts, *cursor; float *sorted, *bbox; unsigned* nbr; };
+static HullWs hull_layout(ThArena& ar, int n_verts) {
+    return {ar.take<GridInfo>(1), ar.take<int>(GRID_MAX_CELLS + 1), ar.take<int>(GRID_MAX_CELLS + 1),
+            ar.take<int>(GRID_MAX_CELLS + 1), ar.take<float>((size_t)n_verts * 3), ar.take<float>((size_t)GRID_MAX_CELLS * 6),
+            ar.take<unsigned>(GRID_EXT_CELLS)};
 }
+size_t th_hull_ws(int n_verts) { return th_measure(hull_layout, n_verts); }
 
 int th_hull_mask_launch(const ThPointSrc& ps, long long P, const float* verts, int nv, float thresh, uint8_t* mask,
                         int32_t* ray_hit, void* ws, size_t ws_bytes, hipStream_t s, int32_t* info_zero) {
-    TH_REQUIRE(ws_bytes >= th_hull_ws(nv), "workspace too small");
     ThArena ar(ws, ws_bytes);
-    GridInfo* gi = ar.take<GridInfo>(1);
-    int* counts = ar.take<int>(GRID_MAX_CELLS + 1);
-    int* starts = ar.take<int>(GRID_MAX_CELLS + 1);
-    int* cursor = ar.take<int>(GRID_MAX_CELLS + 1);
-    float* sorted = ar.take<float>((size_t)nv * 3);
-    float* bbox = ar.take<float>((size_t)GRID_MAX_CELLS * 6);
-    unsigned* nbr = ar.take<unsigned>(GRID_EXT_CELLS);
-    TH_REQUIRE(sorted != nullptr && bbox != nullptr && nbr != nullptr, "workspace carve failed");
+    HullWs w = hull_layout(ar, nv);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     // cell size: thresh plus 5 % so fp rounding of the cell index can never
     // separate a vertex within `thresh` from the 3x3x3 neighbourhood
     float h0 = thresh * 1.05f;
-    hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, s, verts, nv, h0, gi, counts, starts, cursor, sorted, bbox,
-                       ray_hit, ray_hit ? ps.R : 0, info_zero, nbr);
+    hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, s, verts, nv, h0, w.gi, w.counts, w.starts, w.cursor, w.sorted, w.bbox,
+                       ray_hit, ray_hit ? ps.R : 0, info_zero, w.nbr);
     const bool seq = getenv("TH_HULL_SEQ") != nullptr;          // A/B switch, read per launch: one lane per sample throughout
     if (seq)
-        hipLaunchKernelGGL(hull_mask_seq_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, ps, P, gi, starts, sorted, bbox, thresh,
+        hipLaunchKernelGGL(hull_mask_seq_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, ps, P, w.gi, w.starts, w.sorted, w.bbox, thresh,
                            mask, ray_hit);
     else
-        hipLaunchKernelGGL(hull_mask_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, ps, P, gi, starts, sorted, bbox, thresh,
-                           mask, ray_hit, nbr);
+        hipLaunchKernelGGL(hull_mask_kernel, dim3(th_cdiv(P, 256)), dim3(256), 0, s, ps, P, w.gi, w.starts, w.sorted, w.bbox, thresh,
+                           mask, ray_hit, w.nbr);
     TH_LAUNCH_CHECK();
     return 0;
 }
@@ -517,15 +513,17 @@ __global__ __launch_bounds__(256) void cmp_write_kernel(uint8_t* __restrict__ ma
 // blocks over the permuted index space: ceil(R / 16) ray groups x 16 S positions
 static long long cmp_space(long long R, int S) { return (R + CMP_G - 1) / CMP_G * CMP_G * S; }
 // (P + 16 S covers the padded last ray group of any (R, S) factorisation of P with S <= 1024)
-size_t th_compact_ws(long long P) { return th_align((size_t)(th_cdiv(P + 16 * 1024, CMP_ITEMS) + 2) * sizeof(int)); }
+static int* compact_layout(ThArena& ar, long long P) { return ar.take<int>((size_t)(th_cdiv(P + 16 * 1024, CMP_ITEMS) + 2)); }
+size_t th_compact_ws(long long P) { return th_measure(compact_layout, P); }
 
 static int compact_launch(uint8_t* mask, long long P, int32_t* idx_out, int32_t* dev_count, void* ws, size_t ws_bytes,
                           const CmpRule& rule, hipStream_t s) {
     TH_REQUIRE(P < (1LL << 31), "too many points for int32 indices");
     TH_REQUIRE(rule.S >= 1 && rule.S <= 1024 && (long long)rule.R * rule.S == P, "compaction: P must be R x S, S <= 1024");
     int nb = th_cdiv(cmp_space(rule.R, rule.S), CMP_ITEMS);
-    TH_REQUIRE(ws_bytes >= th_compact_ws(P), "workspace too small");
-    int* bcount = (int*)ws;
+    ThArena ar(ws, ws_bytes);
+    int* bcount = compact_layout(ar, P);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     hipLaunchKernelGGL(cmp_count_kernel, dim3(nb), dim3(256), 0, s, mask, P, bcount, rule);
     hipLaunchKernelGGL(cmp_scan_kernel, dim3(1), dim3(1024), 0, s, bcount, nb, dev_count);
     hipLaunchKernelGGL(cmp_write_kernel, dim3(nb), dim3(256), 0, s, mask, P, bcount, idx_out, rule);

@@ -207,10 +207,11 @@ int jt_groups(long long n) {
 
 }  // namespace
 
-size_t th_color_jitter_ws(int V, int H, int W) {
-    if (!jt_size_ok(V, H, W)) return 0;
-    return th_align((size_t)V * jt_groups((long long)H * W) * sizeof(unsigned long long));
+// one slot per (image, pixel group): the group's grey sum for the contrast step
+static unsigned long long* jt_layout(ThArena& ar, int V, int H, int W) {
+    return ar.take<unsigned long long>((size_t)V * jt_groups((long long)H * W));
 }
+size_t th_color_jitter_ws(int V, int H, int W) { return jt_size_ok(V, H, W) ? th_measure(jt_layout, V, H, W) : 0; }
 
 int th_color_jitter_launch(const uint8_t* img, int V, int H, int W, uint32_t order, float brightness, float contrast,
                            float saturation, int hue_shift, uint32_t enabled, uint8_t* out, void* ws, size_t ws_bytes,
@@ -242,9 +243,10 @@ int th_color_jitter_launch(const uint8_t* img, int V, int H, int W, uint32_t ord
     const bool two = (enabled >> 1) & 1u;
     unsigned long long* slots = nullptr;
     if (two) {
-        TH_REQUIRE(ws && ws_bytes >= th_color_jitter_ws(V, H, W), "workspace missing or smaller than th_color_jitter_workspace_bytes");
+        ThArena ar(ws, ws_bytes);
+        slots = jt_layout(ar, V, H, W);
+        TH_REQUIRE(ws && ar.ok(), "workspace missing or smaller than th_color_jitter_workspace_bytes");
         TH_REQUIRE(((uintptr_t)ws & 7) == 0, "workspace must be 8-byte aligned");
-        slots = (unsigned long long*)ws;
         P.steps = contrast_at;
         hipLaunchKernelGGL(jitter_kernel<true>, dim3(G, V), dim3(JT_THREADS), 0, s, img, (uint8_t*)nullptr, n, P, wide, slots);
         TH_LAUNCH_CHECK();

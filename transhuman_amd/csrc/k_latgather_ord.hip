@@ -359,43 +359,27 @@ static int lgo_sum_launch(int nc, int nw, int h, int w, int V, int H, int W, con
 }
 #undef LGO_SUM_ARGS
 
-struct LgoPlan {
-    size_t n, ntile, nchunk, nb;
-    size_t bytes;
-};
-
-static LgoPlan lgo_plan(int V, int H, int W, int P) {
-    LgoPlan p;
-    p.n = (size_t)P * V;
-    p.ntile = (p.n + LGO_TILE - 1) / LGO_TILE;
-    p.nchunk = (p.n + LGO_LIFT_ROWS - 1) / LGO_LIFT_ROWS;
-    p.nb = (size_t)V * H * W;
-    p.bytes = 4 * th_align(p.n * 4) + th_align(256 * p.ntile * 4) + th_align((p.nb + 1) * 4) + th_align(p.nchunk * 512 * 4);
-    return p;
+// the sort's two key / value buffers over the n (sample, view) pairs, its digit counts, the segment starts, the lift's partial sums
+struct LgoWs { size_t n, ntile, nchunk, nb; unsigned *key[2], *val[2]; int *cnt, *start; float* part; };
+static LgoWs lgo_layout(ThArena& ar, int V, int H, int W, int P) {
+    const size_t n = (size_t)P * V, ntile = (n + LGO_TILE - 1) / LGO_TILE, nchunk = (n + LGO_LIFT_ROWS - 1) / LGO_LIFT_ROWS;
+    const size_t nb = (size_t)V * H * W;
+    return {n, ntile, nchunk, nb, {ar.take<unsigned>(n), ar.take<unsigned>(n)}, {ar.take<unsigned>(n), ar.take<unsigned>(n)},
+            ar.take<int>(256 * ntile), ar.take<int>(nb + 1), ar.take<float>(nchunk * 512)};
 }
 
 size_t th_latgather_bwd_ord_ws(int V, int H, int W, int P) {
-    if (V < 1 || H < 1 || W < 1 || P < 0) return 0;
-    return lgo_plan(V, H, W, P).bytes;
+    return (V < 1 || H < 1 || W < 1 || P < 0) ? 0 : th_measure(lgo_layout, V, H, W, P);
 }
 
 int th_latgather_bwd_ord_launch(const int* dims, int V, int H, int W, const float* pts_world, int P, const float* cams,
                                 const float* scale, const float* grad_out, int ldo, const float* rgb_s, float* g0, float* g1,
                                 float* g2, float* g_w, float* g_b, void* ws, size_t ws_bytes, hipStream_t s) {
     TH_TRY(lgo_check(dims, V, H, W, P, ldo));
-    const LgoPlan pl = lgo_plan(V, H, W, P);
-    TH_REQUIRE(ws_bytes >= pl.bytes, "workspace too small (th_latent_gather_bwd_ordered_ws)");
     ThArena ar(ws, ws_bytes);
-    unsigned* key[2];
-    unsigned* val[2];
-    key[0] = ar.take<unsigned>(pl.n);
-    key[1] = ar.take<unsigned>(pl.n);
-    val[0] = ar.take<unsigned>(pl.n);
-    val[1] = ar.take<unsigned>(pl.n);
-    int* cnt = ar.take<int>(256 * pl.ntile);
-    int* start = ar.take<int>(pl.nb + 1);
-    float* part = ar.take<float>(pl.nchunk * 512);
-    TH_REQUIRE(key[0] && key[1] && val[0] && val[1] && cnt && start && part, "workspace too small");
+    const LgoWs pl = lgo_layout(ar, V, H, W, P);
+    TH_REQUIRE(ar.ok(), "workspace too small (th_latent_gather_bwd_ordered_ws)");
+    unsigned *const *key = pl.key, *const *val = pl.val;
     const int N = (int)pl.n, ntile = (int)pl.ntile, nb = (int)pl.nb;
     int cur = 0;
     if (N > 0) {
@@ -405,30 +389,30 @@ int th_latgather_bwd_ord_launch(const int* dims, int V, int H, int W, const floa
         int bits = 1;
         while (bits < 31 && ((long long)nb - 1) >> bits) ++bits;
         for (int shift = 0; shift < bits; shift += 8) {
-            hipLaunchKernelGGL(lgo_hist_kernel, dim3(ntile), dim3(256), 0, s, key[cur], N, shift, ntile, cnt);
+            hipLaunchKernelGGL(lgo_hist_kernel, dim3(ntile), dim3(256), 0, s, key[cur], N, shift, ntile, pl.cnt);
             TH_LAUNCH_CHECK();
-            hipLaunchKernelGGL(lgo_scan_kernel, dim3(1), dim3(1024), 0, s, cnt, 256 * ntile);
+            hipLaunchKernelGGL(lgo_scan_kernel, dim3(1), dim3(1024), 0, s, pl.cnt, 256 * ntile);
             TH_LAUNCH_CHECK();
-            hipLaunchKernelGGL(lgo_scatter_kernel, dim3(ntile), dim3(256), 0, s, key[cur], val[cur], N, shift, ntile, cnt,
+            hipLaunchKernelGGL(lgo_scatter_kernel, dim3(ntile), dim3(256), 0, s, key[cur], val[cur], N, shift, ntile, pl.cnt,
                                key[cur ^ 1], val[cur ^ 1]);
             TH_LAUNCH_CHECK();
             cur ^= 1;
         }
-        hipLaunchKernelGGL(lgo_csr_kernel, dim3(th_cdiv((long long)nb + 1, 256)), dim3(256), 0, s, key[cur], N, nb, start);
+        hipLaunchKernelGGL(lgo_csr_kernel, dim3(th_cdiv((long long)nb + 1, 256)), dim3(256), 0, s, key[cur], N, nb, pl.start);
         TH_LAUNCH_CHECK();
     }
     float* gl[3] = {g0, g1, g2};
     for (int l = 0; l < 3; ++l) {
         const int h = dims[2 * l], w = dims[2 * l + 1];
         TH_TRY(lgo_sum_launch(l == 2 ? 2 : 1, lgo_waves(h, w, H, W), h, w, V, H, W, pts_world, N, cams, scale, grad_out, ldo,
-                              l == 2 ? 128 : 64 * l, val[cur], start, gl[l], s));
+                              l == 2 ? 128 : 64 * l, val[cur], pl.start, gl[l], s));
     }
     if (g_w) {
         if (N > 0) {
-            hipLaunchKernelGGL(lgo_lift_part_kernel, dim3((int)pl.nchunk), dim3(128), 0, s, grad_out, ldo, rgb_s, N, part);
+            hipLaunchKernelGGL(lgo_lift_part_kernel, dim3((int)pl.nchunk), dim3(128), 0, s, grad_out, ldo, rgb_s, N, pl.part);
             TH_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(lgo_lift_sum_kernel, dim3(128), dim3(256), 0, s, part, (int)pl.nchunk, g_w, g_b);
+        hipLaunchKernelGGL(lgo_lift_sum_kernel, dim3(128), dim3(256), 0, s, pl.part, (int)pl.nchunk, g_w, g_b);
         TH_LAUNCH_CHECK();
     }
     return 0;

@@ -517,18 +517,18 @@ LpStatePlan lp_state_plan(int n, int h, int w) {
     p.partial = lp_partial_doubles(n, h, w);
     return p;
 }
-bool lp_state_carve(void* state, size_t bytes, int n, int h, int w, LpDest* d) {
+LpDest lp_state_layout(ThArena& arena, int n, int h, int w) {
+    LpDest d;
     const LpStatePlan p = lp_state_plan(n, h, w);
-    ThArena arena(state, bytes);
-    for (int l = 0; l < LP_NL; ++l) d->layer[l] = arena.take<float>(p.layer[l]);
+    for (int l = 0; l < LP_NL; ++l) d.layer[l] = arena.take<float>(p.layer[l]);
     float* sa = arena.take<float>(p.sa);
     float* sb = arena.take<float>(p.sb);
     float* pool = arena.take<float>(p.pool);
-    d->partial = arena.take<double>(p.partial);
-    for (int l = 0; l < LP_NL; ++l) d->layer1[l] = lp_is_tap(l) ? nullptr : (l == 0 || lp_is_tap(l - 1)) ? sa : sb;
-    d->pool[0] = nullptr;
-    for (int lev = 1; lev < 5; ++lev) d->pool[lev] = pool;
-    return d->partial != nullptr;
+    d.partial = arena.take<double>(p.partial);
+    for (int l = 0; l < LP_NL; ++l) d.layer1[l] = lp_is_tap(l) ? nullptr : (l == 0 || lp_is_tap(l - 1)) ? sa : sb;
+    d.pool[0] = nullptr;
+    for (int lev = 1; lev < 5; ++lev) d.pool[lev] = pool;
+    return d;
 }
 
 // the launches of the forward: 13 convolutions, 4 pools, 5 heads, the finish.  split: the destinations keep the two halves of
@@ -615,16 +615,25 @@ int lp_head_bwd_launch(const float* f0, const float* f1, int N, int hw, int C, c
     return 0;
 }
 
-size_t lp_grad_floats(int n, int h, int w) { return (size_t)n * 64 * h * w; }
+// th_lpips's workspace: two ping-pong activation buffers and the head's partials
+struct LpWs { float* buf[2]; double* partial; };
+LpWs lp_ws_layout(ThArena& arena, int n, int h, int w) {
+    const size_t act = lp_act_floats(n, h, w);
+    return {{arena.take<float>(act), arena.take<float>(act)}, arena.take<double>(lp_partial_doubles(n, h, w))};
+}
+// th_lpips_bwd's workspace: two ping-pong gradient buffers of the largest layer output of one image set
+struct LpGrads { float* gb[2]; };
+LpGrads lp_bwd_layout(ThArena& arena, int n, int h, int w) {
+    const size_t g = (size_t)n * 64 * h * w;
+    return {{arena.take<float>(g), arena.take<float>(g)}};
+}
+bool lp_image_ok(int n, int h, int w) { return n >= 1 && h >= 16 && w >= 16; }
 
 }  // namespace
 
 size_t th_lpips_pack_bytes_internal() { return lp_pack_floats() * sizeof(float); }
 
-size_t th_lpips_ws(int n, int h, int w) {
-    if (n < 1 || h < 16 || w < 16) return 0;
-    return 2 * th_align(lp_act_floats(n, h, w) * sizeof(float)) + th_align(lp_partial_doubles(n, h, w) * sizeof(double));
-}
+size_t th_lpips_ws(int n, int h, int w) { return lp_image_ok(n, h, w) ? th_measure(lp_ws_layout, n, h, w) : 0; }
 
 int th_lpips_pack_launch(const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* packed,
                          size_t bytes, hipStream_t s) {
@@ -652,14 +661,13 @@ int th_lpips_launch(const float* in0, const float* in1, int n, int h, int w, con
                     size_t ws_bytes, hipStream_t s) {
     TH_REQUIRE(h >= 16 && w >= 16, "image smaller than 16 x 16");
     TH_REQUIRE(n >= 1 && 2 * n <= 65535, "bad batch size");
-    TH_REQUIRE(ws_bytes >= th_lpips_ws(n, h, w), "workspace too small");
     ThArena arena(ws, ws_bytes);
-    float* buf[2] = {arena.take<float>(lp_act_floats(n, h, w)), arena.take<float>(lp_act_floats(n, h, w))};
-    double* partial = arena.take<double>(lp_partial_doubles(n, h, w));
-    TH_REQUIRE(buf[0] && buf[1] && partial, "workspace too small");
+    const LpWs lw = lp_ws_layout(arena, n, h, w);
+    TH_REQUIRE(arena.ok(), "workspace too small");
+    float* const* buf = lw.buf;
     // two ping-pong buffers: every convolution and every pool writes the buffer its input is not in
     LpDest d;
-    d.partial = partial;
+    d.partial = lw.partial;
     int k = 0;
     for (int l = 0, lev = 0; l < LP_NL; ++l) {
         if (l > LP_LEVEL_LAST[lev]) d.pool[++lev] = buf[k++ & 1];
@@ -672,19 +680,9 @@ int th_lpips_launch(const float* in0, const float* in1, int n, int h, int w, con
 // ---- training form ----------------------------------------------------------------------------------------------------
 size_t th_lpips_bwd_pack_bytes_internal() { return lp_bwd_woff(LP_NL) * sizeof(float); }
 
-size_t th_lpips_state_bytes(int n, int h, int w) {
-    if (n < 1 || h < 16 || w < 16) return 0;
-    const LpStatePlan p = lp_state_plan(n, h, w);
-    size_t b = th_align(p.partial * sizeof(double)) + th_align(p.sa * sizeof(float)) + th_align(p.sb * sizeof(float)) +
-               th_align(p.pool * sizeof(float));
-    for (int l = 0; l < LP_NL; ++l) b += th_align(p.layer[l] * sizeof(float));
-    return b;
-}
+size_t th_lpips_state_bytes(int n, int h, int w) { return lp_image_ok(n, h, w) ? th_measure(lp_state_layout, n, h, w) : 0; }
 
-size_t th_lpips_bwd_ws(int n, int h, int w) {
-    if (n < 1 || h < 16 || w < 16) return 0;
-    return 2 * th_align(lp_grad_floats(n, h, w) * sizeof(float));
-}
+size_t th_lpips_bwd_ws(int n, int h, int w) { return lp_image_ok(n, h, w) ? th_measure(lp_bwd_layout, n, h, w) : 0; }
 
 int th_lpips_pack_bwd_launch(const float* const* conv_w, void* packed_bwd, size_t bytes, hipStream_t s) {
     TH_REQUIRE(bytes >= th_lpips_bwd_pack_bytes_internal(), "packed buffer too small");
@@ -703,9 +701,9 @@ int th_lpips_train_launch(const float* in0, const float* in1, int n, int h, int 
                           void* state, size_t state_bytes, hipStream_t s) {
     TH_REQUIRE(h >= 16 && w >= 16, "image smaller than 16 x 16");
     TH_REQUIRE(n >= 1 && 2 * n <= 65535, "bad batch size");
-    TH_REQUIRE(state_bytes >= th_lpips_state_bytes(n, h, w), "state buffer too small");
-    LpDest d;
-    TH_REQUIRE(lp_state_carve(state, state_bytes, n, h, w, &d), "state buffer too small");
+    ThArena st(state, state_bytes);
+    const LpDest d = lp_state_layout(st, n, h, w);
+    TH_REQUIRE(st.ok(), "state buffer too small");
     return lp_forward(in0, in1, n, h, w, (const float*)packed, out, d, true, s);
 }
 
@@ -713,13 +711,13 @@ int th_lpips_bwd_launch(const double* g_out, int n, int h, int w, const void* pa
                         const void* state, size_t state_bytes, float* g_in0, void* ws, size_t ws_bytes, hipStream_t s) {
     TH_REQUIRE(h >= 16 && w >= 16, "image smaller than 16 x 16");
     TH_REQUIRE(n >= 1 && 2 * n <= 65535, "bad batch size");
-    TH_REQUIRE(state_bytes >= th_lpips_state_bytes(n, h, w), "state buffer too small");
-    TH_REQUIRE(ws_bytes >= th_lpips_bwd_ws(n, h, w), "workspace too small");
-    LpDest d;
-    TH_REQUIRE(lp_state_carve(const_cast<void*>(state), state_bytes, n, h, w, &d), "state buffer too small");
+    ThArena st(const_cast<void*>(state), state_bytes);
+    const LpDest d = lp_state_layout(st, n, h, w);
+    TH_REQUIRE(st.ok(), "state buffer too small");
     ThArena arena(ws, ws_bytes);
-    float* gb[2] = {arena.take<float>(lp_grad_floats(n, h, w)), arena.take<float>(lp_grad_floats(n, h, w))};
-    TH_REQUIRE(gb[0] && gb[1], "workspace too small");
+    const LpGrads lg = lp_bwd_layout(arena, n, h, w);
+    float* const* gb = lg.gb;
+    TH_REQUIRE(arena.ok(), "workspace too small");
     const float* pk = (const float*)packed;
     const float* pkb = (const float*)packed_bwd;
     int hl[5], wl[5];

@@ -199,33 +199,30 @@ static int mc_tables_upload() {
     return 0;
 }
 
-size_t th_mc_ws(int X, int Y, int Z) {
-    const size_t n = (size_t)X * Y * Z;
-    const size_t nb = (n + MC_SCAN_B - 1) / MC_SCAN_B;
-    return 2 * th_align(n * sizeof(int)) + 2 * th_align((nb + 2) * sizeof(long long));
+// the packed per-point words of the two passes, their block sums, and one block of counters the entry points read back
+// ([0..1]: the totals of th_mc_count_launch, [4..5]: the prefix of th_mc_prefix_launch)
+struct McWs { size_t nb; int *vpack, *tbase; long long *vsums, *tsums, *counters; };
+static McWs mc_layout(ThArena& ar, int X, int Y, int Z) {
+    const size_t n = (size_t)X * Y * Z, nb = (n + MC_SCAN_B - 1) / MC_SCAN_B;
+    return {nb, ar.take<int>(n), ar.take<int>(n), ar.take<long long>(nb + 2), ar.take<long long>(nb + 2), ar.take<long long>(32)};
 }
-
-struct McWs { int *vpack, *tbase; long long *vsums, *tsums; size_t nb; };
-static McWs mc_carve(void* ws, int X, int Y, int Z) {
-    const size_t n = (size_t)X * Y * Z;
-    McWs w;
-    w.nb = (n + MC_SCAN_B - 1) / MC_SCAN_B;
-    char* p = (char*)ws;
-    w.vpack = (int*)p; p += th_align(n * sizeof(int));
-    w.tbase = (int*)p; p += th_align(n * sizeof(int));
-    w.vsums = (long long*)p; p += th_align((w.nb + 2) * sizeof(long long));
-    w.tsums = (long long*)p;
+size_t th_mc_ws(int X, int Y, int Z) { return th_measure(mc_layout, X, Y, Z); }
+// (th_marching_cubes_range / _emit get the workspace without its size: the caller sized it for th_marching_cubes_count)
+static McWs mc_carve(const void* ws, int X, int Y, int Z) {
+    ThArena ar(const_cast<void*>(ws), th_mc_ws(X, Y, Z));
+    McWs w = mc_layout(ar, X, Y, Z);
     return w;
 }
 
-// passes 1 + 2; totals (vertices, triangles) -> counts_dev[0..1]
-int th_mc_count_launch(const float* cube, int X, int Y, int Z, float iso, void* ws, size_t ws_bytes, long long* counts_dev,
+// passes 1 + 2; totals (vertices, triangles) -> (*counts_dev)[0..1], in the workspace
+int th_mc_count_launch(const float* cube, int X, int Y, int Z, float iso, void* ws, size_t ws_bytes, long long** counts_dev,
                        hipStream_t s) {
-    TH_REQUIRE(ws_bytes >= th_mc_ws(X, Y, Z), "workspace too small");
+    ThArena ar(ws, ws_bytes);
+    McWs w = mc_layout(ar, X, Y, Z);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     TH_REQUIRE(X >= 2 && Y >= 2 && Z >= 2, "marching cubes needs at least 2 grid points per axis");
     TH_REQUIRE((long long)X * Y * Z <= 80000000LL, "grid too large for the packed 28-bit vertex prefix (80 M points)");
     TH_TRY(mc_tables_upload());
-    McWs w = mc_carve(ws, X, Y, Z);
     const long long n = (long long)X * Y * Z;
     McDims d{X, Y, Z};
     hipLaunchKernelGGL(mc_count_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, cube, d, iso, w.vpack, w.tbase);
@@ -236,14 +233,15 @@ int th_mc_count_launch(const float* cube, int X, int Y, int Z, float iso, void* 
     hipLaunchKernelGGL(mc_scan_add_kernel<true>, dim3((unsigned)w.nb), dim3(256), 0, s, w.vpack, n, w.vsums);
     hipLaunchKernelGGL(mc_scan_add_kernel<false>, dim3((unsigned)w.nb), dim3(256), 0, s, w.tbase, n, w.tsums);
     TH_LAUNCH_CHECK();
-    TH_HIP(hipMemcpyAsync(counts_dev, w.vsums + w.nb, sizeof(long long), hipMemcpyDeviceToDevice, s));
-    TH_HIP(hipMemcpyAsync(counts_dev + 1, w.tsums + w.nb, sizeof(long long), hipMemcpyDeviceToDevice, s));
+    *counts_dev = w.counters;
+    TH_HIP(hipMemcpyAsync(w.counters, w.vsums + w.nb, sizeof(long long), hipMemcpyDeviceToDevice, s));
+    TH_HIP(hipMemcpyAsync(w.counters + 1, w.tsums + w.nb, sizeof(long long), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
 int th_mc_emit_launch(const float* cube, int X, int Y, int Z, float iso, const void* ws, int x0, int x1, const double* scale,
                       const double* origin, double* verts, int* tris, hipStream_t s) {
-    McWs w = mc_carve(const_cast<void*>(ws), X, Y, Z);
+    McWs w = mc_carve(ws, X, Y, Z);
     McDims d{X, Y, Z};
     x0 = x0 < 0 ? 0 : x0;
     x1 = x1 > X ? X : x1;
@@ -263,11 +261,12 @@ __global__ void mc_prefix_at_kernel(const int* __restrict__ vpack, const int* __
     out[0] = i < n ? (long long)(vpack[i] >> 3) : *vtot;
     out[1] = i < n ? (long long)tbase[i] : *ttot;
 }
-int th_mc_prefix_launch(const void* ws, int X, int Y, int Z, int x, long long* out_dev, hipStream_t s) {
-    McWs w = mc_carve(const_cast<void*>(ws), X, Y, Z);
+int th_mc_prefix_launch(const void* ws, int X, int Y, int Z, int x, long long** out_dev, hipStream_t s) {
+    McWs w = mc_carve(ws, X, Y, Z);
+    *out_dev = w.counters + 4;
     const long long n = (long long)X * Y * Z;
     hipLaunchKernelGGL(mc_prefix_at_kernel, dim3(1), dim3(1), 0, s, w.vpack, w.tbase, (long long)x * Y * Z, n, w.vsums + w.nb,
-                       w.tsums + w.nb, out_dev);
+                       w.tsums + w.nb, *out_dev);
     TH_LAUNCH_CHECK();
     return 0;
 }

@@ -244,24 +244,19 @@ __global__ __launch_bounds__(256) void cc_emit_faces_kernel(const int32_t* __res
 
 // ---- workspace ----
 static size_t cc_nb(long long n) { return (size_t)((n + CC_SCAN_B - 1) / CC_SCAN_B); }
-size_t th_meshcc_ws(int nv, int nf) {
-    if (nv < 0 || nf < 0) return 0;
-    return th_align(CC_CTL_WORDS * sizeof(int)) + 3 * th_align((size_t)nv * sizeof(int)) + 2 * th_align((size_t)nf * sizeof(int)) +
-           th_align((cc_nb(nv) + 2) * sizeof(long long)) + th_align((cc_nb(nf) + 2) * sizeof(long long));
-}
+// control words, the labels' face counts, keep flags and their prefix sums of vertices and faces, the scans' block sums
 struct CcWs { int *ctl, *cnt, *vflag, *vscan, *fflag, *fscan; long long *vsums, *fsums; };
-static CcWs cc_carve(void* ws, int nv, int nf) {
-    CcWs w;
-    char* p = (char*)ws;
-    w.ctl = (int*)p; p += th_align(CC_CTL_WORDS * sizeof(int));
-    w.cnt = (int*)p; p += th_align((size_t)nv * sizeof(int));
-    w.vflag = (int*)p; p += th_align((size_t)nv * sizeof(int));
-    w.vscan = (int*)p; p += th_align((size_t)nv * sizeof(int));
-    w.fflag = (int*)p; p += th_align((size_t)nf * sizeof(int));
-    w.fscan = (int*)p; p += th_align((size_t)nf * sizeof(int));
-    w.vsums = (long long*)p; p += th_align((cc_nb(nv) + 2) * sizeof(long long));
-    w.fsums = (long long*)p;
-    return w;
+static CcWs cc_layout(ThArena& ar, int nv, int nf) {
+    return {ar.take<int>(CC_CTL_WORDS), ar.take<int>((size_t)nv), ar.take<int>((size_t)nv), ar.take<int>((size_t)nv),
+            ar.take<int>((size_t)nf), ar.take<int>((size_t)nf), ar.take<long long>(cc_nb(nv) + 2),
+            ar.take<long long>(cc_nb(nf) + 2)};
+}
+size_t th_meshcc_ws(int nv, int nf) { return (nv < 0 || nf < 0) ? 0 : th_measure(cc_layout, nv, nf); }
+static int cc_carve(const void* ws, size_t ws_bytes, int nv, int nf, CcWs& w) {
+    ThArena ar(const_cast<void*>(ws), ws_bytes);
+    w = cc_layout(ar, nv, nf);
+    TH_REQUIRE(ar.ok(), "workspace too small");
+    return 0;
 }
 
 // first pass: every face index (and, with `label`, every label) inside [0, nv); the error word comes to the host BEFORE
@@ -294,10 +289,10 @@ static int cc_stats(const int32_t* faces, int nf, int nv, const int32_t* label, 
 int th_meshcc_components_launch(const int32_t* faces, int nf, int nv, int32_t* label, void* ws, size_t ws_bytes, int32_t* pinned,
                                 int64_t* info_host, hipStream_t s) {
     TH_REQUIRE(nv >= 0 && nf >= 0, "negative size");
-    TH_REQUIRE(ws_bytes >= th_meshcc_ws(nv, nf), "workspace too small");
+    CcWs w;
+    TH_TRY(cc_carve(ws, ws_bytes, nv, nf, w));
     for (int k = 0; k < 5; ++k) info_host[k] = k == 3 ? -1 : 0;
     if (nv == 0 && nf == 0) return 0;
-    CcWs w = cc_carve(ws, nv, nf);
     TH_TRY(cc_checked(faces, nf, nv, nullptr, w, pinned, s));
     hipLaunchKernelGGL(cc_init_kernel, dim3(th_cdiv(nv, 256)), dim3(256), 0, s, label, nv);
     TH_LAUNCH_CHECK();
@@ -342,10 +337,10 @@ int th_meshcc_components_launch(const int32_t* faces, int nf, int nv, int32_t* l
 int th_meshcc_filter_count_launch(const int32_t* faces, int nf, int nv, const int32_t* label, int min_faces, void* ws,
                                   size_t ws_bytes, int32_t* pinned, int64_t* counts_host, hipStream_t s) {
     TH_REQUIRE(nv >= 0 && nf >= 0 && min_faces >= 0, "negative size");
-    TH_REQUIRE(ws_bytes >= th_meshcc_ws(nv, nf), "workspace too small");
+    CcWs w;
+    TH_TRY(cc_carve(ws, ws_bytes, nv, nf, w));
     for (int k = 0; k < 4; ++k) counts_host[k] = k == 3 ? -1 : 0;
     if (nv == 0 && nf == 0) return 0;
-    CcWs w = cc_carve(ws, nv, nf);
     TH_TRY(cc_checked(faces, nf, nv, label, w, pinned, s));
     if (nv == 0) return 0;
     TH_TRY(cc_stats(faces, nf, nv, label, w, s));
@@ -376,10 +371,12 @@ int th_meshcc_filter_count_launch(const int32_t* faces, int nf, int nv, const in
 }
 
 // the scatter behind th_meshcc_filter_count_launch on the same workspace and arrays.  verts may be null (map and faces only).
-int th_meshcc_filter_emit_launch(const double* verts, const int32_t* faces, int nf, int nv, const void* ws, double* verts_out,
-                                 int32_t* faces_out, int32_t* vert_map, hipStream_t s) {
+int th_meshcc_filter_emit_launch(const double* verts, const int32_t* faces, int nf, int nv, const void* ws, size_t ws_bytes,
+                                 double* verts_out, int32_t* faces_out, int32_t* vert_map, hipStream_t s) {
+    TH_REQUIRE(nv >= 0 && nf >= 0, "negative size");
+    CcWs w;
+    TH_TRY(cc_carve(ws, ws_bytes, nv, nf, w));
     if (nv <= 0) return 0;
-    CcWs w = cc_carve(const_cast<void*>(ws), nv, nf);
     hipLaunchKernelGGL(cc_emit_verts_kernel, dim3(th_cdiv(nv, 256)), dim3(256), 0, s, verts, nv, w.vflag, w.vscan, verts_out, vert_map);
     if (nf > 0)
         hipLaunchKernelGGL(cc_emit_faces_kernel, dim3(th_cdiv(nf, 256)), dim3(256), 0, s, faces, nf, w.fflag, w.fscan, w.vscan, faces_out);

@@ -231,16 +231,16 @@ bool ms_mesh_ok(int nv, int nf) { return nv >= 1 && nf >= 1; }
 
 }  // namespace
 
-size_t th_vertex_normals_ws(int nv, int nf) {
-    if (!ms_mesh_ok(nv, nf)) return 0;
-    return th_align((size_t)nv * 3 * sizeof(unsigned long long));
-}
+// the vertices' exact integer normal sums [nv][3]
+static unsigned long long* normals_layout(ThArena& ar, int nv) { return ar.take<unsigned long long>((size_t)nv * 3); }
+size_t th_vertex_normals_ws(int nv, int nf) { return ms_mesh_ok(nv, nf) ? th_measure(normals_layout, nv) : 0; }
 
 int th_vertex_normals_launch(const float* verts, int nv, const int32_t* faces, int nf, int flip, float* normals, int32_t* status,
                              void* ws, size_t ws_bytes, hipStream_t s) {
     TH_REQUIRE(ms_mesh_ok(nv, nf), "bad mesh (n_verts, n_faces >= 1)");
-    TH_REQUIRE(ws_bytes >= th_vertex_normals_ws(nv, nf), "workspace too small (th_vertex_normals_workspace_bytes)");
-    unsigned long long* sums = (unsigned long long*)ws;
+    ThArena ar(ws, ws_bytes);
+    unsigned long long* sums = normals_layout(ar, nv);
+    TH_REQUIRE(ar.ok(), "workspace too small (th_vertex_normals_workspace_bytes)");
     TH_HIP(hipMemsetAsync(sums, 0, (size_t)nv * 3 * sizeof(unsigned long long), s));
     TH_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(normals_accumulate_kernel, dim3(th_cdiv(nf, MS_THREADS)), dim3(MS_THREADS), 0, s, verts, nv, faces, nf,

@@ -130,19 +130,19 @@ int ssim_tiles(int h, int w) {
 
 }  // namespace
 
-size_t th_ssim_ws(int h, int w, int c) {
-    if (h < SS_WIN || w < SS_WIN || c < 1) return 0;
-    return th_align((size_t)ssim_tiles(h, w) * c * sizeof(double));
-}
+// every tile's partial sum per channel
+static double* ssim_layout(ThArena& ar, int h, int w, int c) { return ar.take<double>((size_t)ssim_tiles(h, w) * c); }
+size_t th_ssim_ws(int h, int w, int c) { return (h < SS_WIN || w < SS_WIN || c < 1) ? 0 : th_measure(ssim_layout, h, w, c); }
 
 int th_ssim_launch(const float* a, const float* b, int h, int w, int c, long long pitch, double* out, void* ws,
                    size_t ws_bytes, hipStream_t s) {
     TH_REQUIRE(h >= SS_WIN && w >= SS_WIN, "image smaller than the 7 x 7 window");
     TH_REQUIRE(c >= 1 && pitch >= (long long)w * c, "bad channel count or row pitch");
-    TH_REQUIRE(ws_bytes >= th_ssim_ws(h, w, c), "workspace too small");
+    ThArena ar(ws, ws_bytes);
+    double* partial = ssim_layout(ar, h, w, c);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     TH_REQUIRE(c <= 65535, "too many channels");
     const int tiles_x = th_cdiv(w - (SS_WIN - 1), SS_TW), n_tiles = ssim_tiles(h, w);
-    double* partial = (double*)ws;
     hipLaunchKernelGGL(ssim_tile_kernel, dim3((unsigned)n_tiles, (unsigned)c), dim3(SS_THREADS), 0, s, a, b, h, w, c, pitch,
                        tiles_x, partial);
     TH_LAUNCH_CHECK();

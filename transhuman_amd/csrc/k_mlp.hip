@@ -158,10 +158,14 @@ int th_scatter_raw_launch(const float* raw_c, const int32_t* sel, int P, int rgb
     return 0;
 }
 
-size_t th_mlp_ws(int V, int P) {
-    size_t rows = (size_t)V * P;
-    return 2 * th_align(rows * 256 * 4) + 2 * th_align(rows * 384 * 4) + 2 * th_align((size_t)P * 256 * 4);
+// per (sample, view) row two 256-wide and two 384-wide activations, per sample two 256-wide ones
+struct MlpWs { float *B1, *B2, *B3, *B4, *M1, *M2; };
+static MlpWs mlp_layout(ThArena& ar, int V, int P) {
+    const size_t rows = (size_t)V * P;
+    return {ar.take<float>(rows * 256), ar.take<float>(rows * 256), ar.take<float>(rows * 384), ar.take<float>(rows * 384),
+            ar.take<float>((size_t)P * 256), ar.take<float>((size_t)P * 256)};
 }
+size_t th_mlp_ws(int V, int P) { return th_measure(mlp_layout, V, P); }
 
 int th_mlp_forward(const ThMlpPacked& W, int V, int P, const float* h, const float* f, int f_ld, const float* vd,
                    float* raw_c, void* ws, size_t ws_bytes, hipStream_t s) {
@@ -174,45 +178,39 @@ int th_mlp_forward(const ThMlpPacked& W, int V, int P, const float* h, const flo
     const ThPacked& L_rr0 = cf ? W.rgb_res_0c : W.rgb_res_0;
     const ThPacked& L_rr1 = cf ? W.rgb_res_1c : W.rgb_res_1;
     TH_REQUIRE(V >= 1 && V <= 4, "supported reference-view counts: 1..4");
-    TH_REQUIRE(ws_bytes >= th_mlp_ws(V, P), "workspace too small");
     ThArena ar(ws, ws_bytes);
+    MlpWs w = mlp_layout(ar, V, P);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     const int rows = V * P;
-    float* B1 = ar.take<float>((size_t)rows * 256);
-    float* B2 = ar.take<float>((size_t)rows * 256);
-    float* B3 = ar.take<float>((size_t)rows * 384);
-    float* B4 = ar.take<float>((size_t)rows * 384);
-    float* M1 = ar.take<float>((size_t)P * 256);
-    float* M2 = ar.take<float>((size_t)P * 256);
-    TH_REQUIRE(M2 != nullptr, "workspace carve failed");
 
     // _multiview_agg :313-322
-    TH_TRY(th_gemm(h, 256, rows, W.fc_0, TH_ACT_RELU, B1, 256, s));              // s
-    TH_TRY(th_gemm(f, f_ld, rows, L_ar0, TH_ACT_RELU, B2, 256, s));       // p
-    TH_TRY(th_gemm(B1, 256, rows, W.kv1, TH_ACT_NONE, B3, 384, s));              // ks|vs
-    TH_TRY(th_gemm(B2, 256, rows, W.kv0, TH_ACT_NONE, B4, 384, s));              // kp|vp
+    TH_TRY(th_gemm(h, 256, rows, W.fc_0, TH_ACT_RELU, w.B1, 256, s));              // s
+    TH_TRY(th_gemm(f, f_ld, rows, L_ar0, TH_ACT_RELU, w.B2, 256, s));       // p
+    TH_TRY(th_gemm(w.B1, 256, rows, W.kv1, TH_ACT_NONE, w.B3, 384, s));              // ks|vs
+    TH_TRY(th_gemm(w.B2, 256, rows, W.kv0, TH_ACT_NONE, w.B4, 384, s));              // kp|vp
     dim3 g4(th_cdiv(P, 4));
     switch (V) {
-        case 1: hipLaunchKernelGGL(xattn_kernel<1>, g4, dim3(256), 0, s, B4, B3, P, B1); break;
-        case 2: hipLaunchKernelGGL(xattn_kernel<2>, g4, dim3(256), 0, s, B4, B3, P, B1); break;
-        case 3: hipLaunchKernelGGL(xattn_kernel<3>, g4, dim3(256), 0, s, B4, B3, P, B1); break;
-        default: hipLaunchKernelGGL(xattn_kernel<4>, g4, dim3(256), 0, s, B4, B3, P, B1); break;
+        case 1: hipLaunchKernelGGL(xattn_kernel<1>, g4, dim3(256), 0, s, w.B4, w.B3, P, w.B1); break;
+        case 2: hipLaunchKernelGGL(xattn_kernel<2>, g4, dim3(256), 0, s, w.B4, w.B3, P, w.B1); break;
+        case 3: hipLaunchKernelGGL(xattn_kernel<3>, g4, dim3(256), 0, s, w.B4, w.B3, P, w.B1); break;
+        default: hipLaunchKernelGGL(xattn_kernel<4>, g4, dim3(256), 0, s, w.B4, w.B3, P, w.B1); break;
     }
-    TH_TRY(th_gemm(B1, 256, rows, W.fc_1, TH_ACT_RELU, B2, 256, s));
-    TH_TRY(th_gemm(B2, 256, rows, W.fc_2, TH_ACT_RELU, B1, 256, s));             // inter
+    TH_TRY(th_gemm(w.B1, 256, rows, W.fc_1, TH_ACT_RELU, w.B2, 256, s));
+    TH_TRY(th_gemm(w.B2, 256, rows, W.fc_2, TH_ACT_RELU, w.B1, 256, s));             // inter
     // _alpha_forward :324-328
-    hipLaunchKernelGGL(view_mean_kernel, dim3(th_cdiv((long long)P * 256, 256)), dim3(256), 0, s, B1, P, V, 256, M1);
-    TH_TRY(th_gemm(M1, 256, P, W.fc_3, TH_ACT_RELU, M2, 256, s));
-    hipLaunchKernelGGL(head_kernel<1>, g4, dim3(256), 0, s, M2, P, 256, W.alpha_w, W.alpha_b, raw_c + 3, 4);
+    hipLaunchKernelGGL(view_mean_kernel, dim3(th_cdiv((long long)P * 256, 256)), dim3(256), 0, s, w.B1, P, V, 256, w.M1);
+    TH_TRY(th_gemm(w.M1, 256, P, W.fc_3, TH_ACT_RELU, w.M2, 256, s));
+    hipLaunchKernelGGL(head_kernel<1>, g4, dim3(256), 0, s, w.M2, P, 256, W.alpha_w, W.alpha_b, raw_c + 3, 4);
     // _RGB_forward :330-353 (evaluated for every compacted sample; the
     // sigma>0 gate is applied when scattering)
-    TH_TRY(th_gemm(B1, 256, rows, W.feature_fc, TH_ACT_NONE, B4, 288, s));
-    TH_TRY(th_gemm(f, f_ld, rows, L_rr0, TH_ACT_NONE | TH_GEMM_ACCUM, B4, 288, s));
-    hipLaunchKernelGGL(viewdir_fill_kernel, dim3(th_cdiv((long long)rows * 32, 256)), dim3(256), 0, s, vd, P, V, B4);
-    TH_TRY(th_gemm(B4, 288, rows, W.view_fc, TH_ACT_RELU, B3, 128, s));
-    TH_TRY(th_gemm(f, f_ld, rows, L_rr1, TH_ACT_NONE | TH_GEMM_ACCUM, B3, 128, s));
-    hipLaunchKernelGGL(view_mean_kernel, dim3(th_cdiv((long long)P * 128, 256)), dim3(256), 0, s, B3, P, V, 128, M1);
-    TH_TRY(th_gemm(M1, 128, P, W.fc_4, TH_ACT_RELU, M2, 128, s));
-    hipLaunchKernelGGL(head_kernel<3>, g4, dim3(256), 0, s, M2, P, 128, W.rgb_w, W.rgb_b, raw_c, 4);
+    TH_TRY(th_gemm(w.B1, 256, rows, W.feature_fc, TH_ACT_NONE, w.B4, 288, s));
+    TH_TRY(th_gemm(f, f_ld, rows, L_rr0, TH_ACT_NONE | TH_GEMM_ACCUM, w.B4, 288, s));
+    hipLaunchKernelGGL(viewdir_fill_kernel, dim3(th_cdiv((long long)rows * 32, 256)), dim3(256), 0, s, vd, P, V, w.B4);
+    TH_TRY(th_gemm(w.B4, 288, rows, W.view_fc, TH_ACT_RELU, w.B3, 128, s));
+    TH_TRY(th_gemm(f, f_ld, rows, L_rr1, TH_ACT_NONE | TH_GEMM_ACCUM, w.B3, 128, s));
+    hipLaunchKernelGGL(view_mean_kernel, dim3(th_cdiv((long long)P * 128, 256)), dim3(256), 0, s, w.B3, P, V, 128, w.M1);
+    TH_TRY(th_gemm(w.M1, 128, P, W.fc_4, TH_ACT_RELU, w.M2, 128, s));
+    hipLaunchKernelGGL(head_kernel<3>, g4, dim3(256), 0, s, w.M2, P, 128, W.rgb_w, W.rgb_b, raw_c, 4);
     TH_LAUNCH_CHECK();
     return 0;
 }

@@ -218,11 +218,13 @@ __global__ __launch_bounds__(PT_THREADS) void patch_gather_kernel(
 
 static bool pt_sizes_ok(int H, int W) { return H >= 1 && W >= 1 && H <= PT_MAX_DIM && W <= PT_MAX_DIM; }
 
-size_t th_patch_ws(int H, int W) {
-    if (!pt_sizes_ok(H, W)) return 0;
+// three counters (and their scans) per block of pixels, and behind them the blocks' bit planes, one word per wave
+struct PtWs { int32_t* cnt; unsigned long long* bits; };
+static PtWs pt_layout(ThArena& ar, int H, int W) {
     const size_t nb = (size_t)th_cdiv((long long)H * W, PT_THREADS);
-    return th_align(3 * (nb + 1) * sizeof(int32_t)) + th_align(nb * PT_WAVES * sizeof(unsigned long long));
+    return {ar.take<int32_t>(3 * (nb + 1)), ar.take<unsigned long long>(nb * PT_WAVES)};
 }
+size_t th_patch_ws(int H, int W) { return pt_sizes_ok(H, W) ? th_measure(pt_layout, H, W) : 0; }
 
 // the limits of the stage, checked before anything else (th_patch_rays reports them ahead of a null pointer)
 int th_patch_check(int H, int W, int N, int P) {
@@ -241,19 +243,19 @@ int th_patch_rays_launch(const float* ray_o, const float* ray_d, const float* ne
                          size_t ws_bytes, hipStream_t s) {
     TH_TRY(th_patch_check(H, W, N, P));
     TH_REQUIRE(pix_stride >= 1 && chan_stride >= 1, "image strides must be positive");
-    TH_REQUIRE(ws_bytes >= th_patch_ws(H, W), "workspace too small");
+    ThArena ar(ws, ws_bytes);
+    PtWs w = pt_layout(ar, H, W);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     const int npix = H * W, nb = th_cdiv(npix, PT_THREADS);
-    int32_t* cnt = (int32_t*)ws;
-    unsigned long long* bits = (unsigned long long*)((char*)ws + th_align(3 * ((size_t)nb + 1) * sizeof(int32_t)));
-    hipLaunchKernelGGL(patch_count_kernel, dim3(nb), dim3(PT_THREADS), 0, s, ray_mask, msk, bound, npix, nb, cnt, bits);
+    hipLaunchKernelGGL(patch_count_kernel, dim3(nb), dim3(PT_THREADS), 0, s, ray_mask, msk, bound, npix, nb, w.cnt, w.bits);
     TH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(patch_scan_kernel, dim3(3), dim3(PT_THREADS), 0, s, cnt, nb);
+    hipLaunchKernelGGL(patch_scan_kernel, dim3(3), dim3(PT_THREADS), 0, s, w.cnt, nb);
     TH_LAUNCH_CHECK();
     hipLaunchKernelGGL(patch_window_kernel, dim3(N), dim3(PT_THREADS), 0, s, ray_mask, msk, bound, img, pix_stride, chan_stride, H,
-                       W, draws, subject_ratio, N, P, nb, cnt, patch_masks, patch_masks_sub, target_patches, xy_min, counts);
+                       W, draws, subject_ratio, N, P, nb, w.cnt, patch_masks, patch_masks_sub, target_patches, xy_min, counts);
     TH_LAUNCH_CHECK();
     hipLaunchKernelGGL(patch_gather_kernel, dim3(N), dim3(PT_THREADS), 0, s, ray_o, ray_d, near_in, far_in, img, pix_stride,
-                       chan_stride, W, N, P, nb, cnt, bits, patch_masks, patch_masks_sub, xy_min, counts, o_rgb, o_ray_o, o_ray_d,
+                       chan_stride, W, N, P, nb, w.cnt, w.bits, patch_masks, patch_masks_sub, xy_min, counts, o_rgb, o_ray_o, o_ray_d,
                        o_near, o_far, o_sub, o_inds);
     TH_LAUNCH_CHECK();
     return 0;

@@ -270,12 +270,14 @@ __global__ __launch_bounds__(RS_THREADS) void rs_acc_kernel(const int64_t* __res
 
 static bool rs_sizes_ok(int H, int W) { return H >= 1 && W >= 1 && H <= RS_MAX_DIM && W <= RS_MAX_DIM; }
 
-static size_t rs_cnt_bytes(size_t nb) { return th_align(3 * (nb + 1) * sizeof(int32_t)); }
-
-size_t th_ray_sample_ws(int H, int W, int nrays) {
-    if (!rs_sizes_ok(H, W) || nrays < 0 || nrays > RS_MAX_RAYS) return 0;
+// three counters (and their scans) per block of pixels, and behind them the three classes' bit planes, one word per wave
+struct RsWs { int32_t* cnt; unsigned long long* bits; };
+static RsWs rs_layout(ThArena& ar, int H, int W) {
     const size_t nb = (size_t)th_cdiv((long long)H * W, RS_THREADS);
-    return rs_cnt_bytes(nb) + th_align(3 * nb * RS_WAVES * sizeof(unsigned long long));
+    return {ar.take<int32_t>(3 * (nb + 1)), ar.take<unsigned long long>(3 * nb * RS_WAVES)};
+}
+size_t th_ray_sample_ws(int H, int W, int nrays) {
+    return (!rs_sizes_ok(H, W) || nrays < 0 || nrays > RS_MAX_RAYS) ? 0 : th_measure(rs_layout, H, W);
 }
 
 // the limits of the stage, checked before anything else
@@ -301,16 +303,16 @@ int th_ray_sample_train_launch(const float* ray_o, const float* ray_d, const flo
                                float* o_far, int64_t* o_coord, int32_t* info, void* ws, size_t ws_bytes, hipStream_t s) {
     TH_TRY(th_ray_sample_train_check(H, W, nrays, body_ratio, face_ratio));
     TH_REQUIRE(pix_stride >= 1 && chan_stride >= 1, "image strides must be positive");
-    TH_REQUIRE(ws_bytes >= th_ray_sample_ws(H, W, nrays), "workspace too small");
+    ThArena ar(ws, ws_bytes);
+    RsWs w = rs_layout(ar, H, W);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     const int npix = H * W, nb = th_cdiv(npix, RS_THREADS);
-    int32_t* cnt = (int32_t*)ws;
-    unsigned long long* bits = (unsigned long long*)((char*)ws + rs_cnt_bytes((size_t)nb));
-    hipLaunchKernelGGL(rs_class_count_kernel, dim3(nb), dim3(RS_THREADS), 0, s, msk, bound, npix, nb, cnt, bits);
+    hipLaunchKernelGGL(rs_class_count_kernel, dim3(nb), dim3(RS_THREADS), 0, s, msk, bound, npix, nb, w.cnt, w.bits);
     TH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rs_scan_kernel, dim3(3), dim3(RS_THREADS), 0, s, cnt, nb);
+    hipLaunchKernelGGL(rs_scan_kernel, dim3(3), dim3(RS_THREADS), 0, s, w.cnt, nb);
     TH_LAUNCH_CHECK();
     hipLaunchKernelGGL(rs_train_loop_kernel, dim3(1), dim3(RS_LOOP_THREADS), 0, s, ray_o, ray_d, near_in, far_in, ray_mask, img,
-                       pix_stride, chan_stride, W, draws, nrays, body_ratio, face_ratio, nb, cnt, bits, nrays + RS_MAX_ITERS, o_rgb,
+                       pix_stride, chan_stride, W, draws, nrays, body_ratio, face_ratio, nb, w.cnt, w.bits, nrays + RS_MAX_ITERS, o_rgb,
                        o_ray_o, o_ray_d, o_near, o_far, o_coord, info);
     TH_LAUNCH_CHECK();
     return 0;
@@ -322,15 +324,16 @@ int th_ray_sample_test_launch(const float* ray_o, const float* ray_d, const floa
                               size_t ws_bytes, hipStream_t s) {
     TH_TRY(th_ray_sample_check(H, W));
     TH_REQUIRE(pix_stride >= 1 && chan_stride >= 1, "image strides must be positive");
-    TH_REQUIRE(ws_bytes >= th_ray_sample_ws(H, W, 0), "workspace too small");
+    ThArena ar(ws, ws_bytes);
+    RsWs w = rs_layout(ar, H, W);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     const int npix = H * W, nb = th_cdiv(npix, RS_THREADS);
-    int32_t* cnt = (int32_t*)ws;
-    hipLaunchKernelGGL(rs_mask_count_kernel, dim3(nb), dim3(RS_THREADS), 0, s, ray_mask, npix, nb, cnt);
+    hipLaunchKernelGGL(rs_mask_count_kernel, dim3(nb), dim3(RS_THREADS), 0, s, ray_mask, npix, nb, w.cnt);
     TH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(RS_THREADS), 0, s, cnt, nb);
+    hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(RS_THREADS), 0, s, w.cnt, nb);
     TH_LAUNCH_CHECK();
     hipLaunchKernelGGL(rs_compact_kernel, dim3(nb), dim3(RS_THREADS), 0, s, ray_o, ray_d, near_in, far_in, ray_mask, img, pix_stride,
-                       chan_stride, npix, nb, cnt, o_rgb, o_ray_o, o_ray_d, o_near, o_far, info);
+                       chan_stride, npix, nb, w.cnt, o_rgb, o_ray_o, o_ray_d, o_near, o_far, info);
     TH_LAUNCH_CHECK();
     return 0;
 }

@@ -147,27 +147,25 @@ __global__ __launch_bounds__(128) void smpl_skin_kernel(const double* __restrict
         verts[3 * v + r] = ((Tm[4 * r] * vp[0] + Tm[4 * r + 1] * vp[1]) + Tm[4 * r + 2] * vp[2]) + Tm[4 * r + 3] * 1.0;
 }
 
-size_t th_smpl_ws(int nv) {
-    return th_align((size_t)nv * 3 * 8) + th_align(SM_J * 3 * 8) + th_align(SM_J * 16 * 8) + th_align(207 * 8) +
-           th_align(SM_J * 9 * 4);
+// shaped vertices, rest joints, the joints' global transforms, the pose feature (23 local rotations - I) and the fp32 rotations
+struct SmplWs { double *v_shaped, *J, *G, *lrot; float* Rf; };
+static SmplWs smpl_layout(ThArena& ar, int nv) {
+    return {ar.take<double>((size_t)nv * 3), ar.take<double>(SM_J * 3), ar.take<double>(SM_J * 16), ar.take<double>(207),
+            ar.take<float>(SM_J * 9)};
 }
+size_t th_smpl_ws(int nv) { return th_measure(smpl_layout, nv); }
 
 int th_smpl_launch(const th_smpl_model& m, const float* pose_aa, const float* R, const double* beta, double* verts,
                    double* joints, double* T, void* ws, size_t ws_bytes, hipStream_t s) {
-    TH_REQUIRE(ws_bytes >= th_smpl_ws(m.n_verts), "workspace too small");
     ThArena ar(ws, ws_bytes);
     const int nv = m.n_verts;
-    double* v_shaped = ar.take<double>((size_t)nv * 3);
-    double* J = ar.take<double>(SM_J * 3);
-    double* G = ar.take<double>(SM_J * 16);
-    double* lrot = ar.take<double>(207);
-    float* Rf = ar.take<float>(SM_J * 9);
-    TH_REQUIRE(Rf != nullptr, "workspace carve failed");
+    SmplWs w = smpl_layout(ar, nv);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     hipLaunchKernelGGL(smpl_shape_kernel, dim3(th_cdiv(nv, 256)), dim3(256), 0, s, m.v_template, m.shapedirs, beta, nv,
-                       v_shaped);
-    hipLaunchKernelGGL(smpl_joint_kernel, dim3(SM_J), dim3(256), 0, s, m.J_regressor, v_shaped, nv, J);
-    hipLaunchKernelGGL(smpl_chain_kernel, dim3(1), dim3(64), 0, s, pose_aa, R, m.parent, J, Rf, G, joints, lrot);
-    hipLaunchKernelGGL(smpl_skin_kernel, dim3(th_cdiv(nv, 128)), dim3(128), 0, s, v_shaped, m.posedirs, m.weights, G, lrot,
+                       w.v_shaped);
+    hipLaunchKernelGGL(smpl_joint_kernel, dim3(SM_J), dim3(256), 0, s, m.J_regressor, w.v_shaped, nv, w.J);
+    hipLaunchKernelGGL(smpl_chain_kernel, dim3(1), dim3(64), 0, s, pose_aa, R, m.parent, w.J, w.Rf, w.G, joints, w.lrot);
+    hipLaunchKernelGGL(smpl_skin_kernel, dim3(th_cdiv(nv, 128)), dim3(128), 0, s, w.v_shaped, m.posedirs, m.weights, w.G, w.lrot,
                        nv, verts, T);
     TH_LAUNCH_CHECK();
     return 0;

@@ -156,33 +156,32 @@ __global__ __launch_bounds__(TR_THREADS) void tr_zero_kernel(ThPointSrc ps, cons
 
 static size_t tr_blocks(long long P) { return (size_t)((P + TR_THREADS - 1) / TR_THREADS); }
 
-size_t th_truncate_select_ws(int P, int nc) {
-    const size_t nb = tr_blocks(P > 0 ? P : 0);
-    return 2 * th_align((nb > 0 ? nb : 1) * 4) + th_dparf_grid_ws(nc > 0 ? nc : 1);
+// per block of samples the kept count and its scanned offset, and K4's candidate grid of the centres
+struct TrWs { int32_t *blk, *off; size_t gws_b; void* gws; };
+static TrWs tr_layout(ThArena& ar, int P, int nc) {
+    const size_t nb = tr_blocks(P > 0 ? P : 0), gws_b = th_dparf_grid_ws(nc > 0 ? nc : 1);
+    return {ar.take<int32_t>(nb > 0 ? nb : 1), ar.take<int32_t>(nb > 0 ? nb : 1), gws_b, ar.take<char>(gws_b)};
 }
+size_t th_truncate_select_ws(int P, int nc) { return th_measure(tr_layout, P, nc); }
 
 int th_truncate_select_launch(const float* pts_smpl, int P, const float* centres, int nc, float sigma, uint8_t* mask, int32_t* sel,
                               int32_t* count, void* ws, size_t ws_bytes, bool use_grid, hipStream_t s) {
     TH_REQUIRE(P >= 0 && nc >= 1, "th_truncate_select: P >= 0 and at least one token centre");
-    TH_REQUIRE(ws_bytes >= th_truncate_select_ws(P, nc), "th_truncate_select: workspace too small");
     const int nb = (int)tr_blocks(P);
     ThArena ar(ws, ws_bytes);
-    int32_t* blk = ar.take<int32_t>(nb > 0 ? nb : 1);
-    int32_t* off = ar.take<int32_t>(nb > 0 ? nb : 1);
-    const size_t gws_b = th_dparf_grid_ws(nc);
-    void* gws = ar.take<char>(gws_b);
-    TH_REQUIRE(gws != nullptr, "th_truncate_select: workspace carve failed");
+    TrWs w = tr_layout(ar, P, nc);
+    TH_REQUIRE(ar.ok(), "th_truncate_select: workspace too small");
     DpGridView gv{nullptr, nullptr, nullptr};
     if (use_grid && P > 0 && th_dparf_grid_ok(nc)) {
-        TH_TRY(th_dparf_grid_build(centres, nc, gws, gws_b, s));
-        gv = dp_grid_view(gws, nc);
+        TH_TRY(th_dparf_grid_build(centres, nc, w.gws, w.gws_b, s));
+        gv = dp_grid_view(w.gws, nc);
     }
     if (nb > 0) {
         hipLaunchKernelGGL(tr_mask_kernel, dim3(nb), dim3(TR_THREADS), 0, s, pts_smpl, P, centres, nc, sigma, gv.gi, gv.cell_count,
-                           gv.cand, mask, blk);
+                           gv.cand, mask, w.blk);
     }
-    hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(TR_SCAN_THREADS), 0, s, blk, nb, off, count);
-    if (nb > 0) hipLaunchKernelGGL(tr_emit_kernel, dim3(nb), dim3(TR_THREADS), 0, s, mask, P, off, sel);
+    hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(TR_SCAN_THREADS), 0, s, w.blk, nb, w.off, count);
+    if (nb > 0) hipLaunchKernelGGL(tr_emit_kernel, dim3(nb), dim3(TR_THREADS), 0, s, mask, P, w.off, sel);
     TH_LAUNCH_CHECK();
     return 0;
 }

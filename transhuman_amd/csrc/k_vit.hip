@@ -478,58 +478,45 @@ static bool attn_shape_ok(int V, int N, int heads) {
     return V > 0 && V <= 65535 && N > 0 && N <= (1 << 24) && heads > 0 && heads <= 1024;
 }
 
-// the split K / V^T planes of one layer (2 x [V][heads][2][Npad][64] halves); 0 for a shape th_attention refuses
-size_t th_attn_ws(int V, int N, int heads) {
-    if (!attn_shape_ok(V, N, heads)) return 0;
-    return 2 * th_align((size_t)V * heads * 2 * vit_npad(N) * 64 * sizeof(_Float16));
+// the split K / V^T planes of one layer (2 x [V][heads][2][Npad][64] halves); size 0 for a shape th_attention refuses
+struct AttnPlanes { _Float16 *Kp, *Vp; };
+static AttnPlanes attn_layout(ThArena& ar, int V, int N, int heads) {
+    const size_t halves = (size_t)V * heads * 2 * vit_npad(N) * 64;
+    return {ar.take<_Float16>(halves), ar.take<_Float16>(halves)};
 }
+size_t th_attn_ws(int V, int N, int heads) { return attn_shape_ok(V, N, heads) ? th_measure(attn_layout, V, N, heads) : 0; }
 
 // The attention of one layer on its own (tests): kv_split_kernel, then the kernel th_vit_launch would pick (form 0) or a forced
 // one (2: attn2_kernel, 3: attn3_kernel).  Every plane element the attention kernels read is written by kv_split_kernel first.
-int th_attention_launch(const float* qkv, int V, int N, int heads, int form, float* out, void* ws, size_t ws_bytes,
-                        hipStream_t s) {
+// lse: nullptr, or (the training form) [V][heads][N], from which k_vit_bwd.hip recomputes the probabilities.
+int th_attention_train_launch(const float* qkv, int V, int N, int heads, int form, float* out, float* lse, void* ws,
+                              size_t ws_bytes, hipStream_t s) {
     TH_REQUIRE(attn_shape_ok(V, N, heads), "th_attention: need 1 <= V <= 65535, 1 <= N <= 2^24, 1 <= heads <= 1024");
     TH_REQUIRE(form == 0 || form == 2 || form == 3,
                "th_attention: form must be 0 (the forward's own choice), 2 (attn2_kernel) or 3 (attn3_kernel)");
-    TH_REQUIRE(ws_bytes >= th_attn_ws(V, N, heads), "workspace too small");
-    TH_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)out) & 15) == 0, "qkv and out must be 16-byte aligned");
-    TH_REQUIRE((((uintptr_t)ws) & 15) == 0, "workspace must be 16-byte aligned");
-    ThArena ar(ws, ws_bytes);
-    const int Npad = vit_npad(N), dim = heads * 64;
-    _Float16* Kp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
-    _Float16* Vp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
-    TH_REQUIRE(Kp != nullptr && Vp != nullptr, "workspace too small");
-    vit_split_attention(qkv, V, N, Npad, dim, heads, true, form == 0 ? vit_attn_tile(N) : form == 3, Kp, Vp, out, s);
-    TH_LAUNCH_CHECK();
-    return 0;
-}
-
-// The training form of the same launch: also writes lse [V][heads][N] (k_vit_bwd.hip recomputes the probabilities from it).
-int th_attention_train_launch(const float* qkv, int V, int N, int heads, int form, float* out, float* lse, void* ws,
-                              size_t ws_bytes, hipStream_t s) {
-    TH_REQUIRE(attn_shape_ok(V, N, heads), "th_attention_train: need 1 <= V <= 65535, 1 <= N <= 2^24, 1 <= heads <= 1024");
-    TH_REQUIRE(form == 0 || form == 2 || form == 3,
-               "th_attention_train: form must be 0 (the forward's own choice), 2 (attn2_kernel) or 3 (attn3_kernel)");
-    TH_REQUIRE(ws_bytes >= th_attn_ws(V, N, heads), "workspace too small");
     TH_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)lse) & 15) == 0,
                "qkv, out and lse must be 16-byte aligned");
     TH_REQUIRE((((uintptr_t)ws) & 15) == 0, "workspace must be 16-byte aligned");
     ThArena ar(ws, ws_bytes);
-    const int Npad = vit_npad(N), dim = heads * 64;
-    _Float16* Kp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
-    _Float16* Vp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
-    TH_REQUIRE(Kp != nullptr && Vp != nullptr, "workspace too small");
-    vit_split_attention(qkv, V, N, Npad, dim, heads, true, form == 0 ? vit_attn_tile(N) : form == 3, Kp, Vp, out, s, lse);
+    const AttnPlanes p = attn_layout(ar, V, N, heads);
+    TH_REQUIRE(ar.ok(), "workspace too small");
+    vit_split_attention(qkv, V, N, vit_npad(N), heads * 64, heads, true, form == 0 ? vit_attn_tile(N) : form == 3, p.Kp, p.Vp, out, s,
+                        lse);
     TH_LAUNCH_CHECK();
     return 0;
 }
-
-size_t th_vit_ws(int V, int N, int dim, int heads) {
-    size_t T = (size_t)V * N;
-    // X, Y, qkv / hidden, and the split K / V^T planes of one layer (2 x [V][heads][2][Npad][64] halves)
-    return 2 * th_align(T * dim * 4) + th_align(T * 4 * dim * 4) +
-           2 * th_align((size_t)V * heads * 2 * vit_npad(N) * 64 * sizeof(_Float16));
+int th_attention_launch(const float* qkv, int V, int N, int heads, int form, float* out, void* ws, size_t ws_bytes,
+                        hipStream_t s) {
+    return th_attention_train_launch(qkv, V, N, heads, form, out, nullptr, ws, ws_bytes, s);
 }
+
+// X, Y, qkv (3 dim) / mlp hidden (4 dim), and the attention planes of one layer
+struct VitWs { float *X, *Y, *Q; AttnPlanes kv; };
+static VitWs vit_layout(ThArena& ar, int V, int N, int dim, int heads) {
+    const size_t T = (size_t)V * N;
+    return {ar.take<float>(T * dim), ar.take<float>(T * dim), ar.take<float>(T * 4 * dim), attn_layout(ar, V, N, heads)};
+}
+size_t th_vit_ws(int V, int N, int dim, int heads) { return th_measure(vit_layout, V, N, dim, heads); }
 
 int th_vit_launch(const ThVitPacked& W, const float* x, const float* pe, int V, int N, float* out, void* ws,
                   size_t ws_bytes, hipStream_t s, unsigned int* range, bool allow_h3) {
@@ -537,20 +524,14 @@ int th_vit_launch(const ThVitPacked& W, const float* x, const float* pe, int V, 
     const int dim = W.dim, heads = W.heads;
     TH_REQUIRE(dim == heads * 64, "attention kernel is built for head_dim 64 (ViT-tiny: 192 = 3 x 64)");
     TH_REQUIRE(dim <= 512, "dim too large for the layernorm kernel");
-    TH_REQUIRE(ws_bytes >= th_vit_ws(V, N, dim, heads), "workspace too small");
     ThArena ar(ws, ws_bytes);
-    const int T = V * N;
-    float* X = ar.take<float>((size_t)T * dim);
-    float* Y = ar.take<float>((size_t)T * dim);
-    float* Q = ar.take<float>((size_t)T * 4 * dim);     // qkv (3*dim) or mlp hidden (4*dim)
-    const int Npad = vit_npad(N);
-    _Float16* Kp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
-    _Float16* Vp = ar.take<_Float16>((size_t)V * heads * 2 * Npad * 64);
-    TH_REQUIRE(Vp != nullptr, "workspace too small");
+    VitWs w = vit_layout(ar, V, N, dim, heads);
+    TH_REQUIRE(ar.ok(), "workspace too small");
+    const int T = V * N, Npad = vit_npad(N);
+    _Float16 *Kp = w.kv.Kp, *Vp = w.kv.Vp;
     const bool attn_tile = vit_attn_tile(N);
-    TH_REQUIRE(Q != nullptr, "workspace carve failed");
     long long n = (long long)T * dim;
-    hipLaunchKernelGGL(add_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, x, pe, n, X);
+    hipLaunchKernelGGL(add_kernel, dim3(th_cdiv(n, 256)), dim3(256), 0, s, x, pe, n, w.X);
     // the two pre-LayerNorms of a block run inside the GEMM that consumes them
     const bool fuse_ln = th_gemm_ln_ok(T, W.blocks[0].qkv) && th_gemm_ln_ok(T, W.blocks[0].fc1);
     // dense layers on the fp16-split MFMA path (th_gemm_h3)
@@ -569,30 +550,30 @@ int th_vit_launch(const ThVitPacked& W, const float* x, const float* pe, int V, 
     for (int b = 0; b < W.depth; ++b) {
         const ThVitBlockPacked& B = W.blocks[b];
         if (h3) {
-            TH_TRY(th_gemm_h3(X, dim, T, B.qkv, B.ln1_w, B.ln1_b, 1e-6f, TH_ACT_NONE, Q, 3 * dim, range, s, fuse_split ? &qs : nullptr));
+            TH_TRY(th_gemm_h3(w.X, dim, T, B.qkv, B.ln1_w, B.ln1_b, 1e-6f, TH_ACT_NONE, w.Q, 3 * dim, range, s, fuse_split ? &qs : nullptr));
         } else if (fuse_ln) {
-            TH_TRY(th_gemm_ln(X, dim, T, B.qkv, B.ln1_w, B.ln1_b, 1e-6f, TH_ACT_NONE, Q, 3 * dim, s));
+            TH_TRY(th_gemm_ln(w.X, dim, T, B.qkv, B.ln1_w, B.ln1_b, 1e-6f, TH_ACT_NONE, w.Q, 3 * dim, s));
         } else {
-            hipLaunchKernelGGL(layernorm_kernel, dim3(th_cdiv(T, 4)), dim3(256), 0, s, X, T, dim, B.ln1_w, B.ln1_b, 1e-6f, Y);
-            TH_TRY(th_gemm(Y, dim, T, B.qkv, TH_ACT_NONE, Q, 3 * dim, s));
+            hipLaunchKernelGGL(layernorm_kernel, dim3(th_cdiv(T, 4)), dim3(256), 0, s, w.X, T, dim, B.ln1_w, B.ln1_b, 1e-6f, w.Y);
+            TH_TRY(th_gemm(w.Y, dim, T, B.qkv, TH_ACT_NONE, w.Q, 3 * dim, s));
         }
-        vit_split_attention(Q, V, N, Npad, dim, heads, !fuse_split, attn_tile, Kp, Vp, Y, s);
+        vit_split_attention(w.Q, V, N, Npad, dim, heads, !fuse_split, attn_tile, Kp, Vp, w.Y, s);
         if (h3) {
-            TH_TRY(th_gemm_h3(Y, dim, T, B.proj, nullptr, nullptr, 0.f, TH_ACT_NONE | TH_GEMM_ACCUM, X, dim, range, s));
-            TH_TRY(th_gemm_h3(X, dim, T, B.fc1, B.ln2_w, B.ln2_b, 1e-6f, TH_ACT_GELU, Q, 4 * dim, range, s));
-            TH_TRY(th_gemm_h3(Q, 4 * dim, T, B.fc2, nullptr, nullptr, 0.f, TH_ACT_NONE | TH_GEMM_ACCUM, X, dim, range, s));
+            TH_TRY(th_gemm_h3(w.Y, dim, T, B.proj, nullptr, nullptr, 0.f, TH_ACT_NONE | TH_GEMM_ACCUM, w.X, dim, range, s));
+            TH_TRY(th_gemm_h3(w.X, dim, T, B.fc1, B.ln2_w, B.ln2_b, 1e-6f, TH_ACT_GELU, w.Q, 4 * dim, range, s));
+            TH_TRY(th_gemm_h3(w.Q, 4 * dim, T, B.fc2, nullptr, nullptr, 0.f, TH_ACT_NONE | TH_GEMM_ACCUM, w.X, dim, range, s));
             continue;
         }
-        TH_TRY(th_gemm(Y, dim, T, B.proj, TH_ACT_NONE | TH_GEMM_ACCUM, X, dim, s));
+        TH_TRY(th_gemm(w.Y, dim, T, B.proj, TH_ACT_NONE | TH_GEMM_ACCUM, w.X, dim, s));
         if (fuse_ln) {
-            TH_TRY(th_gemm_ln(X, dim, T, B.fc1, B.ln2_w, B.ln2_b, 1e-6f, TH_ACT_GELU, Q, 4 * dim, s));
+            TH_TRY(th_gemm_ln(w.X, dim, T, B.fc1, B.ln2_w, B.ln2_b, 1e-6f, TH_ACT_GELU, w.Q, 4 * dim, s));
         } else {
-            hipLaunchKernelGGL(layernorm_kernel, dim3(th_cdiv(T, 4)), dim3(256), 0, s, X, T, dim, B.ln2_w, B.ln2_b, 1e-6f, Y);
-            TH_TRY(th_gemm(Y, dim, T, B.fc1, TH_ACT_GELU, Q, 4 * dim, s));
+            hipLaunchKernelGGL(layernorm_kernel, dim3(th_cdiv(T, 4)), dim3(256), 0, s, w.X, T, dim, B.ln2_w, B.ln2_b, 1e-6f, w.Y);
+            TH_TRY(th_gemm(w.Y, dim, T, B.fc1, TH_ACT_GELU, w.Q, 4 * dim, s));
         }
-        TH_TRY(th_gemm(Q, 4 * dim, T, B.fc2, TH_ACT_NONE | TH_GEMM_ACCUM, X, dim, s));
+        TH_TRY(th_gemm(w.Q, 4 * dim, T, B.fc2, TH_ACT_NONE | TH_GEMM_ACCUM, w.X, dim, s));
     }
-    hipLaunchKernelGGL(layernorm_kernel, dim3(th_cdiv(T, 4)), dim3(256), 0, s, X, T, dim, W.norm_w, W.norm_b, 1e-6f, out);
+    hipLaunchKernelGGL(layernorm_kernel, dim3(th_cdiv(T, 4)), dim3(256), 0, s, w.X, T, dim, W.norm_w, W.norm_b, 1e-6f, out);
     TH_LAUNCH_CHECK();
     return 0;
 }

@@ -253,24 +253,25 @@ static bool attn_bwd_shape_ok(int V, int N, int heads) {
     return V > 0 && V <= 65535 && N > 0 && N <= (1 << 24) && heads > 0 && heads <= 1024;
 }
 
-// the rows' constants 1 / l and D, [V][heads][N] each; 0 for a shape th_attention_bwd refuses
+// the rows' constants 1 / l and D, [V][heads][N] each; size 0 for a shape th_attention_bwd refuses
+struct AttnBwdWs { float *inv_l, *D; };
+static AttnBwdWs attn_bwd_layout(ThArena& ar, int V, int N, int heads) {
+    return {ar.take<float>((size_t)V * heads * N), ar.take<float>((size_t)V * heads * N)};
+}
 size_t th_attn_bwd_ws(int V, int N, int heads) {
-    if (!attn_bwd_shape_ok(V, N, heads)) return 0;
-    return 2 * th_align((size_t)V * heads * N * sizeof(float));
+    return attn_bwd_shape_ok(V, N, heads) ? th_measure(attn_bwd_layout, V, N, heads) : 0;
 }
 
 int th_attention_bwd_launch(const float* qkv, const float* out, const float* lse, const float* g_out, int V, int N, int heads,
                             float* g_qkv, void* ws, size_t ws_bytes, hipStream_t s) {
     TH_REQUIRE(attn_bwd_shape_ok(V, N, heads), "th_attention_bwd: need 1 <= V <= 65535, 1 <= N <= 2^24, 1 <= heads <= 1024");
-    TH_REQUIRE(ws_bytes >= th_attn_bwd_ws(V, N, heads), "workspace too small");
     TH_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)lse) & 15) == 0 &&
                    (((uintptr_t)g_out) & 15) == 0 && (((uintptr_t)g_qkv) & 15) == 0,
                "qkv, out, lse, g_out and g_qkv must be 16-byte aligned");
     TH_REQUIRE((((uintptr_t)ws) & 15) == 0, "workspace must be 16-byte aligned");
     ThArena ar(ws, ws_bytes);
-    float* inv_l = ar.take<float>((size_t)V * heads * N);
-    float* D = ar.take<float>((size_t)V * heads * N);
-    TH_REQUIRE(inv_l != nullptr && D != nullptr, "workspace too small");
+    AttnBwdWs w = attn_bwd_layout(ar, V, N, heads);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     const int dim = heads * 64;
     const float scale = 0.125f;   // head_dim ** -0.5
     if (N == 1) {
@@ -280,8 +281,8 @@ int th_attention_bwd_launch(const float* qkv, const float* out, const float* lse
     }
     const dim3 grid(th_cdiv(N, AB_T), heads, V);
     // (every row's constants are written by the first launch before the second, on the same stream, reads them)
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(256), 0, s, qkv, g_out, lse, N, dim, scale, inv_l, D, g_qkv);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, dim3(256), 0, s, qkv, g_out, lse, inv_l, D, N, dim, scale, g_qkv);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(256), 0, s, qkv, g_out, lse, N, dim, scale, w.inv_l, w.D, g_qkv);
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, dim3(256), 0, s, qkv, g_out, lse, w.inv_l, w.D, N, dim, scale, g_qkv);
     TH_LAUNCH_CHECK();
     return 0;
 }

@@ -401,6 +401,14 @@ static int vd_ln_bwd_launch(const float* x, int ldx, int M, int dim, const float
     return 0;
 }
 
+// the forward's workspace: the packed layer, and for form 2 the GELU of the input rows [M, in_f]
+struct VdFwdWs { void* pack; float* gelu; };
+static VdFwdWs vd_fwd_layout(ThArena& ar, int M, int out_f, int in_f, int form) {
+    return {ar.take<char>(ThPacked::bytes(out_f, in_f)), form == OP_GELU ? ar.take<float>((size_t)M * in_f) : nullptr};
+}
+// the partial column sums of th_layernorm_bwd: [blocks][2][dim]
+static float* vd_ln_bwd_layout(ThArena& ar, int M, int dim) { return ar.take<float>((size_t)vd_ln_blocks(M) * 2 * dim); }
+
 // C = act(op(A) W^T + b): the one forward behind th_linear_train_forward (act = TH_ACT_NONE) and th_linear_relu_forward
 // (form 0, act = TH_ACT_RELU in the GEMM's epilogue)
 static int vd_forward(th_ctx* c, const float* A, int lda, int M, int form, const float* ln_w, const float* ln_b, float ln_eps,
@@ -414,13 +422,15 @@ static int vd_forward(th_ctx* c, const float* A, int lda, int M, int form, const
                "lda / ldc (ldy): >= the row, multiples of 4");
     TH_REQUIRE(vd_al16(A) && vd_al16(C) && vd_al16(ws) && vd_al16(lin->w) && (form != OP_LN || (vd_al16(ln_w) && vd_al16(ln_b))),
                "pointers must be 16-byte aligned");
-    TH_REQUIRE(ws_bytes >= th_linear_train_workspace_bytes(M, lin->out_f, lin->in_f, form), "workspace too small");
+    ThArena ar(ws, ws_bytes);
+    VdFwdWs w = vd_fwd_layout(ar, M, lin->out_f, lin->in_f, form);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     ThPacked P;
-    TH_TRY(th_pack_linear(*lin, ws, &P, s));
+    TH_TRY(th_pack_linear(*lin, w.pack, &P, s));
     if (form == OP_LN) return th_gemm_ln(A, lda, M, P, ln_w, ln_b, ln_eps, TH_ACT_NONE, C, ldc, s);
     if (form == OP_GELU) {
-        float* t = (float*)((char*)ws + ThPacked::bytes(lin->out_f, lin->in_f));
+        float* t = w.gelu;
         hipLaunchKernelGGL(gelu_fwd_kernel, dim3(vd_grid4(M, lin->in_f)), dim3(256), 0, s, A, lda, t, M, lin->in_f);
         TH_LAUNCH_CHECK();
         return th_gemm(t, lin->in_f, M, P, TH_ACT_NONE, C, ldc, s);
@@ -505,8 +515,7 @@ int th_wgrad_chunk_rows(void) { return WG_CHUNK; }
 int th_layernorm_bwd_chunk_rows(void) { return LN_ROWS; }
 
 size_t th_linear_train_workspace_bytes(int M, int out_f, int in_f, int form) {
-    if (!vd_shape_ok(M, out_f, in_f, form)) return 0;
-    return ThPacked::bytes(out_f, in_f) + (form == OP_GELU ? th_align((size_t)M * in_f * sizeof(float)) : 0);
+    return vd_shape_ok(M, out_f, in_f, form) ? th_measure(vd_fwd_layout, M, out_f, in_f, form) : 0;
 }
 
 int th_linear_train_forward(th_ctx* c, const float* A, int lda, int M, int form, const float* ln_w, const float* ln_b,
@@ -561,8 +570,7 @@ int th_layernorm_forward(th_ctx* c, const float* x, int ldx, int M, int dim, con
 }
 
 size_t th_layernorm_bwd_workspace_bytes(int M, int dim) {
-    if (M < 1 || M > (1 << 24) || dim < 16 || dim > 256 || (dim & 15)) return 0;
-    return th_align((size_t)vd_ln_blocks(M) * 2 * dim * sizeof(float));
+    return (M < 1 || M > (1 << 24) || dim < 16 || dim > 256 || (dim & 15)) ? 0 : th_measure(vd_ln_bwd_layout, M, dim);
 }
 
 int th_layernorm_bwd(th_ctx* c, const float* x, int ldx, int M, int dim, const float* w, float eps, const float* g, int ldg,
@@ -573,8 +581,10 @@ int th_layernorm_bwd(th_ctx* c, const float* x, int ldx, int M, int dim, const f
     TH_REQUIRE(ldx >= dim && ldg >= dim && ldgx >= dim && (ldx & 3) == 0 && (ldg & 3) == 0 && (ldgx & 3) == 0,
                "ldx / ldg / ldgx: >= dim, multiples of 4");
     TH_REQUIRE(vd_al16(x) && vd_al16(w) && vd_al16(g) && vd_al16(g_x) && vd_al16(ws), "pointers must be 16-byte aligned");
-    TH_REQUIRE(ws_bytes >= th_layernorm_bwd_workspace_bytes(M, dim), "workspace too small");
-    return vd_ln_bwd_launch(x, ldx, M, dim, w, eps, g, ldg, g_x, ldgx, g_w, g_b, (float*)ws, (hipStream_t)stream);
+    ThArena ar(ws, ws_bytes);
+    float* part = vd_ln_bwd_layout(ar, M, dim);
+    TH_REQUIRE(ar.ok(), "workspace too small");
+    return vd_ln_bwd_launch(x, ldx, M, dim, w, eps, g, ldg, g_x, ldgx, g_w, g_b, part, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -181,6 +181,25 @@ static bool lin_ok(const th_linear& l, int out_f, int in_f) {
     return l.w != nullptr && l.out_f == out_f && l.in_f == in_f;
 }
 
+// The MLP weight store: packed layers in the order of th_set_mlp_weights' item list (kv0 / kv1 = [key ; value] stacked), the
+// colour-folded forms (optional: packed layers + fp32 fold scratch [N,260] + [N]), the token columns of fc_0 (no bias: packed
+// layer + contiguous [256,192] copy), the two tiny heads as plain rows, and the concat scratch of kv0 / kv1.
+static const int kMlpLayers[12][2] = {{256, 255}, {256, 384}, {384, 256}, {384, 256}, {256, 256}, {256, 256},
+                                      {256, 256}, {256, 256}, {256, 384}, {128, 283}, {128, 384}, {128, 128}};
+static const int kFoldedOut[3] = {256, 256, 128};          // alpha_res_0, rgb_res_0, rgb_res_1 with in_f 260
+struct MlpStore { void *layer[12], *folded_pk[3], *tok_pk; float *fold[3], *tok_w, *heads, *kv_tmp[2]; };
+static MlpStore mlp_store_layout(ThArena& ar, bool have_lift) {
+    MlpStore m;
+    for (int i = 0; i < 12; ++i) m.layer[i] = ar.take<char>(ThPacked::bytes(kMlpLayers[i][0], kMlpLayers[i][1]));
+    for (int i = 0; i < 3; ++i) m.folded_pk[i] = have_lift ? ar.take<char>(ThPacked::bytes(kFoldedOut[i], 260)) : nullptr;
+    for (int i = 0; i < 3; ++i) m.fold[i] = have_lift ? ar.take<float>(256 * 260 + 256) : nullptr;
+    m.tok_pk = ar.take<char>(ThPacked::bytes(256, 192));
+    m.tok_w = ar.take<float>(256 * 192);
+    m.heads = ar.take<float>(256 + 1 + 3 * 128 + 3);
+    for (float*& t : m.kv_tmp) t = ar.take<float>(384 * 256 + 384);
+    return m;
+}
+
 int th_set_mlp_weights(th_ctx* c, const th_mlp_weights* w, th_stream stream) {
     TH_REQUIRE(c && w, "null argument");
     hipStream_t s = (hipStream_t)stream;
@@ -192,45 +211,29 @@ int th_set_mlp_weights(th_ctx* c, const th_mlp_weights* w, th_stream stream) {
                    lin_ok(w->rgb_res_0, 256, 384) && lin_ok(w->view_fc, 128, 283) &&
                    lin_ok(w->rgb_res_1, 128, 384) && lin_ok(w->fc_4, 128, 128) && lin_ok(w->rgb_fc, 3, 128),
                "unexpected layer shape (expects the reference Network of cross_transformer.py:96-126)");
-    struct Item { const th_linear* l; ThPacked* dst; int out_f, in_f; };
+    struct Item { const th_linear* l; ThPacked* dst; };
     ThMlpPacked& M = c->mlp;
-    size_t total = 0;
-    Item items[] = {{&w->fc_0, &M.fc_0, 256, 255},          {&w->alpha_res_0, &M.alpha_res_0, 256, 384},
-                    {nullptr, &M.kv0, 384, 256},            {nullptr, &M.kv1, 384, 256},
-                    {&w->fc_1, &M.fc_1, 256, 256},          {&w->fc_2, &M.fc_2, 256, 256},
-                    {&w->fc_3, &M.fc_3, 256, 256},          {&w->feature_fc, &M.feature_fc, 256, 256},
-                    {&w->rgb_res_0, &M.rgb_res_0, 256, 384}, {&w->view_fc, &M.view_fc, 128, 283},
-                    {&w->rgb_res_1, &M.rgb_res_1, 128, 384}, {&w->fc_4, &M.fc_4, 128, 128}};
-    for (auto& it : items) total += ThPacked::bytes(it.out_f, it.in_f);
-    // colour-folded forms (optional): packed layers + fp32 fold scratch [N,260] + [N]
+    const Item items[12] = {{&w->fc_0, &M.fc_0},          {&w->alpha_res_0, &M.alpha_res_0}, {nullptr, &M.kv0},
+                            {nullptr, &M.kv1},            {&w->fc_1, &M.fc_1},               {&w->fc_2, &M.fc_2},
+                            {&w->fc_3, &M.fc_3},          {&w->feature_fc, &M.feature_fc},   {&w->rgb_res_0, &M.rgb_res_0},
+                            {&w->view_fc, &M.view_fc},    {&w->rgb_res_1, &M.rgb_res_1},     {&w->fc_4, &M.fc_4}};
     const bool have_lift = w->upsample_color.w != nullptr;
     if (have_lift) TH_REQUIRE(lin_ok(w->upsample_color, 128, 3), "upsample_color must be a 3 -> 128 layer (encoder.py:95)");
-    const size_t cpk_off = total;
-    if (have_lift) total += 2 * ThPacked::bytes(256, 260) + ThPacked::bytes(128, 260);
-    const size_t cfold_off = total;
-    if (have_lift) total += 3 * th_align((size_t)(256 * 260 + 256) * sizeof(float));
-    // token columns of fc_0 (no bias): packed layer + contiguous [256,192] copy
-    const size_t tokpk_off = total;
-    total += ThPacked::bytes(256, 192);
-    const size_t tokw_off = total;
-    total += th_align((size_t)256 * 192 * sizeof(float));
-    size_t heads_off = total;
-    total += th_align((256 + 1 + 3 * 128 + 3) * sizeof(float));
-    size_t tmp_off = total;
-    total += 2 * th_align((size_t)(384 * 256 + 384) * sizeof(float));   // concat scratch for kv0 / kv1
     if (c->mlp_store) { TH_HIP(hipFree(c->mlp_store)); c->mlp_store = nullptr; }
+    const size_t total = th_measure(mlp_store_layout, have_lift);
     TH_HIP(hipMalloc(&c->mlp_store, total));
-    char* base = (char*)c->mlp_store;
-    size_t off = 0;
+    ThArena ar(c->mlp_store, total);
+    const MlpStore st = mlp_store_layout(ar, have_lift);
+    TH_REQUIRE(ar.ok(), "weight store carve failed");
     int kv_i = 0;
-    for (auto& it : items) {
+    for (int i = 0; i < 12; ++i) {
         th_linear src;
-        if (it.l) src = *it.l;
+        if (items[i].l) src = *items[i].l;
         else {
             // [key_embed ; value_embed] stacked along out_f -> one 256 -> 384 layer
             const th_linear& k = kv_i == 0 ? w->key0 : w->key1;
             const th_linear& v = kv_i == 0 ? w->val0 : w->val1;
-            float* tw = (float*)(base + tmp_off + kv_i * th_align((size_t)(384 * 256 + 384) * sizeof(float)));
+            float* tw = st.kv_tmp[kv_i];
             float* tb = tw + 384 * 256;
             TH_HIP(hipMemcpyAsync(tw, k.w, 128 * 256 * 4, hipMemcpyDeviceToDevice, s));
             TH_HIP(hipMemcpyAsync(tw + 128 * 256, v.w, 256 * 256 * 4, hipMemcpyDeviceToDevice, s));
@@ -241,10 +244,9 @@ int th_set_mlp_weights(th_ctx* c, const th_mlp_weights* w, th_stream stream) {
             src.w = tw; src.b = tb; src.out_f = 384; src.in_f = 256;
             ++kv_i;
         }
-        TH_TRY(th_pack_linear(src, base + off, it.dst, s));
-        off += ThPacked::bytes(it.out_f, it.in_f);
+        TH_TRY(th_pack_linear(src, st.layer[i], items[i].dst, s));
     }
-    float* hd = (float*)(base + heads_off);
+    float* hd = st.heads;
     M.alpha_w = hd; M.alpha_b = hd + 256; M.rgb_w = hd + 257; M.rgb_b = hd + 257 + 384;
     TH_HIP(hipMemcpyAsync(M.alpha_w, w->alpha_fc.w, 256 * 4, hipMemcpyDeviceToDevice, s));
     TH_HIP(hipMemcpyAsync(M.rgb_w, w->rgb_fc.w, 384 * 4, hipMemcpyDeviceToDevice, s));
@@ -253,25 +255,23 @@ int th_set_mlp_weights(th_ctx* c, const th_mlp_weights* w, th_stream stream) {
     if (w->rgb_fc.b) TH_HIP(hipMemcpyAsync(M.rgb_b, w->rgb_fc.b, 12, hipMemcpyDeviceToDevice, s));
     else TH_HIP(hipMemsetAsync(M.rgb_b, 0, 12, s));
     {
-        float* tw = (float*)(base + tokw_off);
+        float* tw = st.tok_w;
         TH_HIP(hipMemcpy2DAsync(tw, 192 * 4, w->fc_0.w, 255 * 4, 192 * 4, 256, hipMemcpyDeviceToDevice, s));
         th_linear tok{tw, nullptr, 256, 192};
-        TH_TRY(th_pack_linear(tok, base + tokpk_off, &M.fc_0tok, s));
+        TH_TRY(th_pack_linear(tok, st.tok_pk, &M.fc_0tok, s));
     }
     th_linear folded[3] = {};
     M.compact_ready = false;
     if (have_lift) {
         const th_linear* src3[3] = {&w->alpha_res_0, &w->rgb_res_0, &w->rgb_res_1};
         ThPacked* dst3[3] = {&M.alpha_res_0c, &M.rgb_res_0c, &M.rgb_res_1c};
-        size_t po = cpk_off;
         for (int i = 0; i < 3; ++i) {
-            float* fw = (float*)(base + cfold_off + i * th_align((size_t)(256 * 260 + 256) * sizeof(float)));
+            float* fw = st.fold[i];
             float* fb = fw + 256 * 260;
             const int N = src3[i]->out_f;
             TH_TRY(th_fold_color_launch(src3[i]->w, src3[i]->b, w->upsample_color.w, w->upsample_color.b, N, fw, fb, s));
             folded[i].w = fw; folded[i].b = fb; folded[i].out_f = N; folded[i].in_f = 260;
-            TH_TRY(th_pack_linear(folded[i], base + po, dst3[i], s));
-            po += ThPacked::bytes(N, 260);
+            TH_TRY(th_pack_linear(folded[i], st.folded_pk[i], dst3[i], s));
         }
         M.compact_ready = true;
     }
@@ -390,47 +390,54 @@ int th_truncate_scatter_bwd(th_ctx* c, const float* g_rows, const int32_t* sel, 
     return th_truncate_gather_launch(g_rows, sel, n_kept, P, g_rows_kept, (hipStream_t)stream);
 }
 
+// The ViT weight store: per block the four packed layers (qkv, proj, fc1, fc2), their fp16-split images (th_gemm_h3: the
+// ViT's small-M GEMMs on the fp16 matrix pipe) and the two LayerNorms' [w | b | w | b]; the final norm's [w | b] behind them.
+struct VitBlockStore { void *pk[4], *pk16[4]; float* ln; };
+struct VitStore { std::vector<VitBlockStore> blk; float* norm; };
+static VitStore vit_store_layout(ThArena& ar, int depth, int dim) {
+    VitStore st{std::vector<VitBlockStore>(depth), nullptr};
+    const int shape[4][2] = {{3 * dim, dim}, {dim, dim}, {4 * dim, dim}, {dim, 4 * dim}};
+    for (VitBlockStore& b : st.blk) {
+        for (int i = 0; i < 4; ++i) b.pk[i] = ar.take<char>(ThPacked::bytes(shape[i][0], shape[i][1]));
+        for (int i = 0; i < 4; ++i) b.pk16[i] = ar.take<char>(ThPacked::bytes_h3(shape[i][0], shape[i][1]));
+        b.ln = ar.take<float>(4 * dim);
+    }
+    st.norm = ar.take<float>(2 * dim);
+    return st;
+}
+
 int th_set_vit_weights(th_ctx* c, int depth, int dim, int heads, const th_vit_block* blocks, const float* norm_w,
                        const float* norm_b, th_stream stream) {
     TH_REQUIRE(c && blocks && norm_w && norm_b, "null argument");
     TH_REQUIRE(depth > 0 && dim == heads * 64, "ViT must have head_dim 64");
     hipStream_t s = (hipStream_t)stream;
-    size_t per = ThPacked::bytes(3 * dim, dim) + ThPacked::bytes(dim, dim) + ThPacked::bytes(4 * dim, dim) +
-                 ThPacked::bytes(dim, 4 * dim) + th_align(4 * dim * sizeof(float)) +
-                 ThPacked::bytes_h3(3 * dim, dim) + ThPacked::bytes_h3(dim, dim) + ThPacked::bytes_h3(4 * dim, dim) +
-                 ThPacked::bytes_h3(dim, 4 * dim);
-    size_t total = per * depth + th_align(2 * dim * sizeof(float));
+    const size_t total = th_measure(vit_store_layout, depth, dim);
     if (c->vit_store) { TH_HIP(hipFree(c->vit_store)); c->vit_store = nullptr; }
     TH_HIP(hipMalloc(&c->vit_store, total));
+    ThArena ar(c->vit_store, total);
+    const VitStore vs = vit_store_layout(ar, depth, dim);
+    TH_REQUIRE(ar.ok(), "weight store carve failed");
     delete[] c->vit.blocks;
     c->vit.blocks = new ThVitBlockPacked[depth];
     c->vit.depth = depth; c->vit.dim = dim; c->vit.heads = heads;
-    char* base = (char*)c->vit_store;
-    size_t off = 0;
     for (int b = 0; b < depth; ++b) {
         const th_vit_block& B = blocks[b];
         ThVitBlockPacked& P = c->vit.blocks[b];
         TH_REQUIRE(lin_ok(B.qkv, 3 * dim, dim) && lin_ok(B.proj, dim, dim) && lin_ok(B.fc1, 4 * dim, dim) &&
                        lin_ok(B.fc2, dim, 4 * dim) && B.ln1_w && B.ln1_b && B.ln2_w && B.ln2_b,
                    "unexpected ViT block shape");
-        TH_TRY(th_pack_linear(B.qkv, base + off, &P.qkv, s)); off += ThPacked::bytes(3 * dim, dim);
-        TH_TRY(th_pack_linear(B.proj, base + off, &P.proj, s)); off += ThPacked::bytes(dim, dim);
-        TH_TRY(th_pack_linear(B.fc1, base + off, &P.fc1, s)); off += ThPacked::bytes(4 * dim, dim);
-        TH_TRY(th_pack_linear(B.fc2, base + off, &P.fc2, s)); off += ThPacked::bytes(dim, 4 * dim);
-        // fp16-split images of the same four layers (th_gemm_h3: the ViT's small-M GEMMs on the fp16 matrix pipe)
-        TH_TRY(th_pack_linear_h3(B.qkv, base + off, &P.qkv, s)); off += ThPacked::bytes_h3(3 * dim, dim);
-        TH_TRY(th_pack_linear_h3(B.proj, base + off, &P.proj, s)); off += ThPacked::bytes_h3(dim, dim);
-        TH_TRY(th_pack_linear_h3(B.fc1, base + off, &P.fc1, s)); off += ThPacked::bytes_h3(4 * dim, dim);
-        TH_TRY(th_pack_linear_h3(B.fc2, base + off, &P.fc2, s)); off += ThPacked::bytes_h3(dim, 4 * dim);
-        float* ln = (float*)(base + off); off += th_align(4 * dim * sizeof(float));
+        const th_linear* src[4] = {&B.qkv, &B.proj, &B.fc1, &B.fc2};
+        ThPacked* dst[4] = {&P.qkv, &P.proj, &P.fc1, &P.fc2};
+        for (int i = 0; i < 4; ++i) TH_TRY(th_pack_linear(*src[i], vs.blk[b].pk[i], dst[i], s));
+        for (int i = 0; i < 4; ++i) TH_TRY(th_pack_linear_h3(*src[i], vs.blk[b].pk16[i], dst[i], s));
+        float* ln = vs.blk[b].ln;
         P.ln1_w = ln; P.ln1_b = ln + dim; P.ln2_w = ln + 2 * dim; P.ln2_b = ln + 3 * dim;
         TH_HIP(hipMemcpyAsync(P.ln1_w, B.ln1_w, dim * 4, hipMemcpyDeviceToDevice, s));
         TH_HIP(hipMemcpyAsync(P.ln1_b, B.ln1_b, dim * 4, hipMemcpyDeviceToDevice, s));
         TH_HIP(hipMemcpyAsync(P.ln2_w, B.ln2_w, dim * 4, hipMemcpyDeviceToDevice, s));
         TH_HIP(hipMemcpyAsync(P.ln2_b, B.ln2_b, dim * 4, hipMemcpyDeviceToDevice, s));
     }
-    float* nf = (float*)(base + off);
-    c->vit.norm_w = nf; c->vit.norm_b = nf + dim;
+    c->vit.norm_w = vs.norm; c->vit.norm_b = vs.norm + dim;
     TH_HIP(hipMemcpyAsync(c->vit.norm_w, norm_w, dim * 4, hipMemcpyDeviceToDevice, s));
     TH_HIP(hipMemcpyAsync(c->vit.norm_b, norm_b, dim * 4, hipMemcpyDeviceToDevice, s));
     TH_HIP(hipMemsetAsync(c->range_dev + TH_RANGE_VIT, 0, sizeof(unsigned int), s));   // new weights: sticky maximum cleared
@@ -531,11 +538,16 @@ int th_upsample_concat_nhwc(th_ctx* c, const float* img, const float* lat0, cons
                                      (hipStream_t)stream, 0, nullptr);
 }
 
+// th_paint_group_nhwc: gathered rows g [nv][V][CR], reduced rows r [nv][V][out_f], the packed layer, its colour fold's fp32 scratch
+struct PaintWs { float *g, *r; void* pk; float* fold; };
+static PaintWs paint_layout(ThArena& ar, int V, int n_verts, int C, int out_f) {
+    const int CR = C == TH_MAP_SPLIT ? TH_MAP_COMPACT : C;       // gathered rows are 260 wide either way
+    const size_t rows = (size_t)V * n_verts;
+    return {ar.take<float>(rows * CR), ar.take<float>(rows * out_f), ar.take<char>(ThPacked::bytes(out_f, CR)),
+            ar.take<float>((size_t)(out_f * 260 + out_f))};
+}
 size_t th_paint_group_nhwc_workspace_bytes(int V, int n_verts, int C, int out_f) {
-    if (C == TH_MAP_SPLIT) C = TH_MAP_COMPACT;       // gathered rows are 260 wide either way
-    size_t rows = (size_t)V * n_verts;
-    return th_align(rows * C * 4) + th_align(rows * out_f * 4) + ThPacked::bytes(out_f, C) +
-           th_align((size_t)(out_f * 260 + out_f) * 4);
+    return th_measure(paint_layout, V, n_verts, C, out_f);
 }
 
 int th_paint_group_nhwc(th_ctx* c, const float* map_nhwc, int V, int H, int W, int C, const float* verts, int nv,
@@ -548,28 +560,24 @@ int th_paint_group_nhwc(th_ctx* c, const float* map_nhwc, int V, int H, int W, i
     TH_REQUIRE(!compact || (color_lift && color_lift->w && lin_ok(*color_lift, 128, 3)),
                "a compact map needs the upsample_color layer (3 -> 128) to fold into the reduction layer");
     const int out_f = reduction->out_f;
-    TH_REQUIRE(ws_bytes >= th_paint_group_nhwc_workspace_bytes(V, nv, C, out_f), "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     ThArena ar(ws, ws_bytes);
+    const PaintWs pw = paint_layout(ar, V, nv, C, out_f);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     const size_t rows = (size_t)V * nv;
     const int CR = C == TH_MAP_SPLIT ? TH_MAP_COMPACT : C;     // width of a gathered row
-    float* g = ar.take<float>(rows * CR);             // [nv][V][CR]
-    float* r = ar.take<float>(rows * out_f);          // [nv][V][out_f]
-    void* pk = ar.take<char>(ThPacked::bytes(out_f, CR));
-    float* fold = ar.take<float>((size_t)out_f * 260 + out_f);
-    TH_REQUIRE(fold != nullptr, "workspace carve failed");
     // sample the channels-last map at the projected vertices, then the 1x1 conv on those rows only
-    TH_TRY(th_pixgather_launch(map_nhwc, V, C, H, W, verts, nullptr, nullptr, nv, cams, scale, g, CR, TH_ROWS_F32, s));
+    TH_TRY(th_pixgather_launch(map_nhwc, V, C, H, W, verts, nullptr, nullptr, nv, cams, scale, pw.g, CR, TH_ROWS_F32, s));
     ThPacked P;
     th_linear red = *reduction;
     if (compact) {
-        TH_TRY(th_fold_color_launch(reduction->w, reduction->b, color_lift->w, color_lift->b, out_f, fold,
-                                    fold + (size_t)out_f * 260, s));
-        red.w = fold; red.b = fold + (size_t)out_f * 260; red.in_f = 260;
+        TH_TRY(th_fold_color_launch(reduction->w, reduction->b, color_lift->w, color_lift->b, out_f, pw.fold,
+                                    pw.fold + (size_t)out_f * 260, s));
+        red.w = pw.fold; red.b = pw.fold + (size_t)out_f * 260; red.in_f = 260;
     }
-    TH_TRY(th_pack_linear(red, pk, &P, s));
-    TH_TRY(th_gemm(g, CR, (int)rows, P, TH_ACT_NONE, r, out_f, s));
-    return th_segmean_masked_launch(r, V, out_f, viz, nv, off, mem, nc, tokens, s);
+    TH_TRY(th_pack_linear(red, pw.pk, &P, s));
+    TH_TRY(th_gemm(pw.g, CR, (int)rows, P, TH_ACT_NONE, pw.r, out_f, s));
+    return th_segmean_masked_launch(pw.r, V, out_f, viz, nv, off, mem, nc, tokens, s);
 }
 
 int th_bn_act_eval(th_ctx* c, const float* x, const float* residual, int N, int C, int HW, const float* gamma, const float* beta,
@@ -959,15 +967,14 @@ int th_lpips_head_bwd(th_ctx* c, const float* f0, const float* f1, int N, int hw
     return th_lpips_head_bwd_launch(f0, f1, N, hw, C, lin, g_out, accumulate, gate, g, (hipStream_t)stream);
 }
 
-size_t th_marching_cubes_workspace_bytes(int X, int Y, int Z) { return th_mc_ws(X, Y, Z) + 256; }
+size_t th_marching_cubes_workspace_bytes(int X, int Y, int Z) { return th_mc_ws(X, Y, Z); }
 
 int th_marching_cubes_count(th_ctx* c, const float* cube, int X, int Y, int Z, float iso, void* ws, size_t ws_bytes,
                             int64_t* counts_host, th_stream stream) {
     TH_REQUIRE(c && cube && ws && counts_host, "null argument");
-    TH_REQUIRE(ws_bytes >= th_marching_cubes_workspace_bytes(X, Y, Z), "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    long long* cnt = (long long*)((char*)ws + th_mc_ws(X, Y, Z));
-    TH_TRY(th_mc_count_launch(cube, X, Y, Z, iso, ws, th_mc_ws(X, Y, Z), cnt, s));
+    long long* cnt = nullptr;
+    TH_TRY(th_mc_count_launch(cube, X, Y, Z, iso, ws, ws_bytes, &cnt, s));
     long long h[2];
     TH_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, s));
     TH_HIP(hipStreamSynchronize(s));
@@ -978,8 +985,8 @@ int th_marching_cubes_count(th_ctx* c, const float* cube, int X, int Y, int Z, f
 int th_marching_cubes_range(th_ctx* c, const void* ws, int X, int Y, int Z, int x, int64_t* prefix_host, th_stream stream) {
     TH_REQUIRE(c && ws && prefix_host && x >= 0 && x <= X, "bad argument");
     hipStream_t s = (hipStream_t)stream;
-    long long* cnt = (long long*)((char*)ws + th_mc_ws(X, Y, Z)) + 4;
-    TH_TRY(th_mc_prefix_launch(ws, X, Y, Z, x, cnt, s));
+    long long* cnt = nullptr;
+    TH_TRY(th_mc_prefix_launch(ws, X, Y, Z, x, &cnt, s));
     long long h[2];
     TH_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, s));
     TH_HIP(hipStreamSynchronize(s));
@@ -1016,9 +1023,9 @@ int th_mesh_filter_count(th_ctx* c, const int32_t* faces, int n_faces, int n_ver
 int th_mesh_filter_emit(th_ctx* c, const double* verts, const int32_t* faces, int n_faces, int n_verts, const void* ws,
                         size_t ws_bytes, double* verts_out, int32_t* faces_out, int32_t* vert_map, th_stream stream) {
     TH_REQUIRE(c && ws, "null argument");
-    TH_REQUIRE(n_verts >= 0 && n_faces >= 0 && ws_bytes >= th_meshcc_ws(n_verts, n_faces), "workspace too small");
     TH_REQUIRE((faces || n_faces <= 0) && (vert_map || n_verts <= 0), "null argument");
-    return th_meshcc_filter_emit_launch(verts, faces, n_faces, n_verts, ws, verts_out, faces_out, vert_map, (hipStream_t)stream);
+    return th_meshcc_filter_emit_launch(verts, faces, n_faces, n_verts, ws, ws_bytes, verts_out, faces_out, vert_map,
+                                        (hipStream_t)stream);
 }
 
 size_t th_smpl_workspace_bytes(int n_verts) { return th_smpl_ws(n_verts); }
@@ -1179,29 +1186,24 @@ static int mlp_dispatch(th_ctx* c, int V, int m, const ChunkBufs& cb, int f_ld, 
     return th_mlp_forward(c->mlp, V, m, cb.h, cb.f, f_ld, vd, cb.raw_c, cb.mlp_ws, cb.mlp_ws_bytes, s);
 }
 
-static size_t chunk_bytes(int V, int CH) {
-    size_t rows = (size_t)V * CH;
-    return th_align(rows * 256 * 4) + th_align(rows * 384 * 4) + th_align((size_t)CH * 27 * 4) +
-           th_align((size_t)CH * 4 * 4) + th_align((size_t)CH * 64 * 4) + th_mlp_ws(V, CH);
-}
-static int chunk_carve(ThArena& ar, int V, int CH, ChunkBufs* b) {
-    size_t rows = (size_t)V * CH;
-    b->h = ar.take<float>(rows * 256);
-    b->f = ar.take<float>(rows * 384);
-    b->vdc = ar.take<float>((size_t)CH * 27);
-    b->raw_c = ar.take<float>((size_t)CH * 4);
-    b->pe = ar.take<float>((size_t)CH * 64);
-    b->mlp_ws_bytes = th_mlp_ws(V, CH);
-    b->mlp_ws = ar.take<char>(b->mlp_ws_bytes);
-    TH_REQUIRE(b->mlp_ws != nullptr, "workspace too small");
-    return 0;
+static ChunkBufs chunk_layout(ThArena& ar, int V, int CH) {
+    ChunkBufs b;
+    const size_t rows = (size_t)V * CH;
+    b.h = ar.take<float>(rows * 256), b.f = ar.take<float>(rows * 384), b.vdc = ar.take<float>((size_t)CH * 27);
+    b.raw_c = ar.take<float>((size_t)CH * 4), b.pe = ar.take<float>((size_t)CH * 64);
+    b.mlp_ws_bytes = th_mlp_ws(V, CH);
+    b.mlp_ws = ar.take<char>(b.mlp_ws_bytes);
+    return b;
 }
 
-size_t th_network_workspace_bytes(int V, int P) {
-    int CH = P < TH_CHUNK ? (P > 0 ? P : 1) : TH_CHUNK;
-    return chunk_bytes(V, CH) + th_align((size_t)P * 4) + th_compact_ws(P) + th_align(64) +
-           th_align(TPRIME_FLOATS(V) * 4);
+// th_network_forward: a chunk's buffers, the token table, and (with a mask only) the sample list, compaction scratch and count
+struct NetWs { ChunkBufs cb; float* tprime; int32_t* idx; size_t cws_b; void* cws; int32_t* dcount; };
+static NetWs network_layout(ThArena& ar, int V, int P) {
+    const size_t cws_b = th_compact_ws(P);
+    return {chunk_layout(ar, V, P < TH_CHUNK ? (P > 0 ? P : 1) : TH_CHUNK), ar.take<float>(TPRIME_FLOATS(V)),
+            ar.take<int32_t>((size_t)P), cws_b, ar.take<char>(cws_b), ar.take<int32_t>(16)};
 }
+size_t th_network_workspace_bytes(int V, int P) { return th_measure(network_layout, V, P); }
 
 int th_network_forward(th_ctx* c, const float* pixel_feat, const float* viewdir, const float* pts_smpl,
                        const uint8_t* mask, int P, const float* centres, const float* rot, const float* tokens,
@@ -1209,26 +1211,20 @@ int th_network_forward(th_ctx* c, const float* pixel_feat, const float* viewdir,
     TH_REQUIRE(c && pixel_feat && viewdir && pts_smpl && centres && rot && tokens && raw_out && ws, "null argument");
     hipStream_t s = (hipStream_t)stream;
     if (P <= 0) return 0;
-    TH_REQUIRE(ws_bytes >= th_network_workspace_bytes(V, P), "workspace too small");
     ThArena ar(ws, ws_bytes);
-    int CH = P < TH_CHUNK ? P : TH_CHUNK;
-    ChunkBufs cb;
-    TH_TRY(chunk_carve(ar, V, CH, &cb));
+    NetWs w = network_layout(ar, V, P);
+    TH_REQUIRE(ar.ok(), "workspace too small");
+    const int CH = P < TH_CHUNK ? P : TH_CHUNK;
+    const ChunkBufs& cb = w.cb;
     TH_REQUIRE(nc <= TH_MAX_CLUSTERS, "too many token clusters");
-    float* tprime = ar.take<float>(TPRIME_FLOATS(V));
-    TH_REQUIRE(tprime != nullptr, "workspace too small");
     const float* table = nullptr;
-    TH_TRY(token_table(c, tokens, V, nc, tprime, &table, s));
-    int32_t* idx = nullptr;
+    TH_TRY(token_table(c, tokens, V, nc, w.tprime, &table, s));
+    const int32_t* idx = mask ? w.idx : nullptr;      // (the sample list is used with a mask only)
     int n = P;
     if (mask) {
-        idx = ar.take<int32_t>((size_t)P);
-        void* cws = ar.take<char>(th_compact_ws(P));
-        int32_t* dcount = ar.take<int32_t>(16);
-        TH_REQUIRE(dcount != nullptr, "workspace too small");
-        TH_TRY(th_compact_mask(mask, P, idx, dcount, cws, th_compact_ws(P), s));
+        TH_TRY(th_compact_mask(mask, P, w.idx, w.dcount, w.cws, w.cws_b, s));
         TH_HIP(hipMemsetAsync(raw_out, 0, (size_t)P * 16, s));     // raw_temp zeros, :231
-        TH_HIP(hipMemcpyAsync(c->host_pinned, dcount, 4, hipMemcpyDeviceToHost, s));
+        TH_HIP(hipMemcpyAsync(c->host_pinned, w.dcount, 4, hipMemcpyDeviceToHost, s));
         TH_HIP(hipStreamSynchronize(s));                           // the reference syncs here too (:232)
         n = c->host_pinned[0];
     }
@@ -1241,8 +1237,8 @@ int th_network_forward(th_ctx* c, const float* pixel_feat, const float* viewdir,
                                dparf_row_format(c, V), nullptr, s));
         if (idx) TH_TRY(th_gather_chan_major_launch(pixel_feat, V, 384, P, sel, m, cb.f, fmt, s, c->range_dev));
         else TH_TRY(th_gather_chan_major_launch(pixel_feat + o, V, 384, P, nullptr, m, cb.f, fmt, s, c->range_dev));
-        if (idx) TH_TRY(mlp_dispatch(c, V, m, cb, 384, viewdir, sel, 1, 0, s, tprime, nc));
-        else TH_TRY(mlp_dispatch(c, V, m, cb, 384, viewdir + 27LL * o, nullptr, 1, 1, s, tprime, nc));
+        if (idx) TH_TRY(mlp_dispatch(c, V, m, cb, 384, viewdir, sel, 1, 0, s, w.tprime, nc));
+        else TH_TRY(mlp_dispatch(c, V, m, cb, 384, viewdir + 27LL * o, nullptr, 1, 1, s, w.tprime, nc));
         if (idx) TH_TRY(th_scatter_raw_launch(cb.raw_c, sel, m, 0, raw_out, s));
         else TH_TRY(th_scatter_raw_launch(cb.raw_c, nullptr, m, 1, raw_out + 4LL * o, s));
     }
@@ -1264,33 +1260,23 @@ static int frame_ok(const th_frame* f) {
 
 // ray-stage workspace (per frame in flight): hull mask, hit flags, grid, compaction scratch, sample list, counts, view
 // embeddings, dense raw, the per-frame token table and K4's candidate grid.  Nothing here scales with the VALID samples.
-static size_t shade_ws_bytes(const th_frame* f, long long P, int R) {
-    return th_align((size_t)P) + th_align((size_t)R * 4) + th_hull_ws(f->n_verts) + th_compact_ws(P) +
-           th_align((size_t)P * 4) + th_align(64) + th_align((size_t)R * 27 * 4) + th_align((size_t)P * 16) +
-           th_align(TPRIME_FLOATS(f->V) * 4) + th_dparf_grid_ws(f->n_clusters > 0 ? f->n_clusters : 1);
-}
-// (one prologue for every entry point that works in a ray workspace: size check, arena, carve)
 struct ShadeWs {
-    uint8_t* mask; int32_t* ray_hit; void* hws; size_t hws_b; void* cws; size_t cws_b; int32_t* idx; int32_t* info;
-    float* vd_all; float* raw; float* tprime; void* gws; size_t gws_b;
+    uint8_t* mask; int32_t* ray_hit; size_t hws_b; void* hws; size_t cws_b; void* cws; int32_t *idx, *info;
+    float *vd_all, *raw, *tprime; size_t gws_b; void* gws;
 };
+static ShadeWs shade_layout(ThArena& ar, const th_frame* f, long long P, int R) {
+    const size_t hws_b = th_hull_ws(f->n_verts), cws_b = th_compact_ws(P);
+    const size_t gws_b = th_dparf_grid_ws(f->n_clusters > 0 ? f->n_clusters : 1);
+    return {ar.take<uint8_t>((size_t)P), ar.take<int32_t>((size_t)R), hws_b, ar.take<char>(hws_b), cws_b, ar.take<char>(cws_b),
+            ar.take<int32_t>((size_t)P), ar.take<int32_t>(16), ar.take<float>((size_t)R * 27), ar.take<float>((size_t)P * 4),
+            ar.take<float>(TPRIME_FLOATS(f->V)), gws_b, ar.take<char>(gws_b)};
+}
+static size_t shade_ws_bytes(const th_frame* f, long long P, int R) { return th_measure(shade_layout, f, P, R); }
+// (one prologue for every entry point that works in a ray workspace: arena, layout, size check)
 static int carve_shade_ws(const th_frame* f, long long P, int R, void* ws, size_t ws_bytes, ShadeWs& w) {
-    TH_REQUIRE(ws_bytes >= shade_ws_bytes(f, P, R), "workspace too small");
     ThArena ar(ws, ws_bytes);
-    w.mask = ar.take<uint8_t>((size_t)P);
-    w.ray_hit = ar.take<int32_t>((size_t)R);
-    w.hws_b = th_hull_ws(f->n_verts);
-    w.hws = ar.take<char>(w.hws_b);
-    w.cws_b = th_compact_ws(P);
-    w.cws = ar.take<char>(w.cws_b);
-    w.idx = ar.take<int32_t>((size_t)P);
-    w.info = ar.take<int32_t>(16);
-    w.vd_all = ar.take<float>((size_t)R * 27);
-    w.raw = ar.take<float>((size_t)P * 4);
-    w.tprime = ar.take<float>(TPRIME_FLOATS(f->V));
-    w.gws_b = th_dparf_grid_ws(f->n_clusters > 0 ? f->n_clusters : 1);
-    w.gws = ar.take<char>(w.gws_b);
-    TH_REQUIRE(w.raw != nullptr && w.tprime != nullptr && w.gws != nullptr, "workspace too small");
+    w = shade_layout(ar, f, P, R);
+    TH_REQUIRE(ar.ok(), "workspace too small");
     return 0;
 }
 static int frame_f_ld(const th_frame* f) {

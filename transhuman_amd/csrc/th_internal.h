@@ -8,6 +8,7 @@
 #include <string>
 
 #include "transhuman_hip.h"
+#include "th_arena.h"      // th_align, ThArena, th_measure
 
 #define TH_WAVE 64
 
@@ -37,23 +38,7 @@ void th_set_error(const std::string& msg);
         if (r__ != 0) return r__;                                                   \
     } while (0)
 
-static inline size_t th_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int th_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-
-// Bump allocator over the caller-supplied workspace.
-struct ThArena {
-    char* base;
-    size_t cap, off;
-    ThArena(void* p, size_t n) : base((char*)p), cap(n), off(0) {}
-    template <typename T>
-    T* take(size_t count) {
-        size_t bytes = th_align(count * sizeof(T));
-        if (off + bytes > cap) return nullptr;
-        T* r = (T*)(base + off);
-        off += bytes;
-        return r;
-    }
-};
 
 // ---- packed dense layer (MFMA 16x16x4 f32 B-operand image) --------------------
 // w: [NB][KB][64 lanes][4] with lane = (kq<<4)|j, value = W[nb*16+j][kb*16+4*kq+e]
@@ -541,11 +526,11 @@ int th_gen_rays_launch(const float* K, const float* R, const float* T, const flo
                        float* ray_d, float* near_out, float* far_out, uint8_t* mask, hipStream_t s);
 // k_mcubes.hip
 size_t th_mc_ws(int X, int Y, int Z);
-int th_mc_count_launch(const float* cube, int X, int Y, int Z, float iso, void* ws, size_t ws_bytes, long long* counts_dev,
+int th_mc_count_launch(const float* cube, int X, int Y, int Z, float iso, void* ws, size_t ws_bytes, long long** counts_dev,
                        hipStream_t s);
 int th_mc_emit_launch(const float* cube, int X, int Y, int Z, float iso, const void* ws, int x0, int x1, const double* scale,
                       const double* origin, double* verts, int* tris, hipStream_t s);
-int th_mc_prefix_launch(const void* ws, int X, int Y, int Z, int x, long long* out_dev, hipStream_t s);
+int th_mc_prefix_launch(const void* ws, int X, int Y, int Z, int x, long long** out_dev, hipStream_t s);
 int th_bound_mask_launch(const int32_t* corners_xy /* host [8][2] */, int H, int W, uint8_t* mask, hipStream_t s);
 // k_meshcc.hip (K24).  `pinned`: 8 int32 words of pinned host memory the calls read their flags / counts through (they wait).
 size_t th_meshcc_ws(int nv, int nf);
@@ -553,8 +538,8 @@ int th_meshcc_components_launch(const int32_t* faces, int nf, int nv, int32_t* l
                                 int64_t* info_host /* [5] */, hipStream_t s);
 int th_meshcc_filter_count_launch(const int32_t* faces, int nf, int nv, const int32_t* label, int min_faces, void* ws,
                                   size_t ws_bytes, int32_t* pinned, int64_t* counts_host /* [4] */, hipStream_t s);
-int th_meshcc_filter_emit_launch(const double* verts, const int32_t* faces, int nf, int nv, const void* ws, double* verts_out,
-                                 int32_t* faces_out, int32_t* vert_map, hipStream_t s);
+int th_meshcc_filter_emit_launch(const double* verts, const int32_t* faces, int nf, int nv, const void* ws, size_t ws_bytes,
+                                 double* verts_out, int32_t* faces_out, int32_t* vert_map, hipStream_t s);
 // k_encoder.hip
 int th_upsample_concat_launch(const float* img, const float* lat0, const float* lat1, const float* lat2,
                               const int* dims, int V, int H, int W, const float* wc, const float* bc, float* out,
