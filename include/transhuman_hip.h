@@ -1082,6 +1082,14 @@ int th_adam_pack(th_ctx* ctx, th_adam_plan_t* plan, const void* const* grads, co
                  float* flat, long long flat_elems, th_stream stream);
 int th_adam_unpack(th_ctx* ctx, th_adam_plan_t* plan, void* const* dst, const long long* offsets, int n_tensors, const float* flat,
                    long long flat_elems, th_stream stream);
+/* K28, th_rank_sum: the sum of a reduce-scatter whose order this library owns (GradExchange(reduce="rank_ordered")).  parts
+ * [world][slice_elems] is slice r of every rank's flat buffer as all_to_all_single delivers it to rank r;
+ *   out[e] = ((parts[0][e] + parts[1][e]) + parts[2][e]) + ...     fp32, one rounding per addition, in rank order
+ * (subnormals kept; NaN, +-inf and -0.0 as IEEE says; world == 1 copies the bits).  128-bit accesses when parts and out are 16-byte
+ * aligned and slice_elems is a multiple of 4, 32-bit ones otherwise; no atomics, no LDS; two calls write identical bytes.  `out` may
+ * be parts + r * slice_elems for any r (an element is read from every part and then written by one lane); any other overlap is
+ * undefined.  Refused: world outside 1 .. 64, slice_elems < 1, null or misaligned (4-byte) pointers. */
+int th_rank_sum(th_ctx* ctx, const float* parts, int world, long long slice_elems, float* out, th_stream stream);
 
 /* ---- K23: the backward of the encoder trunk in training (additions, ABI 12) ---- */
 /* The sites of SpatialEncoder.trunk (encoder.py:114-126: conv1 / bn1 / relu, the 3x3 / 2 max pool, layer1, layer2), backward only: the
@@ -1096,6 +1104,8 @@ int th_adam_unpack(th_ctx* ctx, th_adam_plan_t* plan, void* const* dst, const lo
  * ReLU.  y: the BatchNorm's input; out: the site's output, read for the gate [out > 0] (NULL: no ReLU); g: the gradient of the
  * site's output; gamma NULL: 1.  g_y: the gradient of y; g_res (optional): the gated gradient, which is the residual's; g_gamma /
  * g_beta [C] (optional).  Statistics and sums are fp64 (th_bn_act_bwd_slice_elems: the least slice of a channel one workgroup sums).
+ * The statistics are those of the call's own batch: a SyncBatchNorm site, whose statistics are those of all ranks, takes the split
+ * pair th_bn_act_bwd_sums / th_bn_act_bwd_apply declared below, which is this function bit for bit with one rank.
  *
  * th_conv2d_dgrad: g_y [N, cout, Ho, Wo] -> g_x [N, cin, H, W], every element written, from an image of the weights that
  * th_conv2d_dgrad_pack writes into caller-owned memory (th_conv2d_dgrad_pack_bytes, 16-byte aligned; pack again when the weights
@@ -1115,6 +1125,21 @@ size_t th_bn_act_bwd_workspace_bytes(int N, int C, int HW);                     
 int th_bn_act_bwd(th_ctx* ctx, const float* y, const float* out_or_null, const float* g, int N, int C, int HW,
                   const float* gamma_or_null, double eps, float* g_y, float* g_res_or_null, float* g_gamma_or_null,
                   float* g_beta_or_null, void* workspace, size_t workspace_bytes, th_stream stream);
+/* The same backward for a SyncBatchNorm site (statistics of all ranks), split around the caller's collective (additions, ABI 12):
+ * th_bn_act_bwd_sums: pass A over this rank's N images and the fixed-order sum of its slices -> record [C][6] fp64 on the device:
+ * a0 a1 a2 a3 against the rank's own pivot p = y[0, c, 0, 0], then p and L = N HW.  The workspace is th_bn_act_bwd_workspace_bytes.
+ * The caller gathers the ranks' records in rank order (one all_gather of C * 48 bytes).
+ * th_bn_act_bwd_apply: records [world][C][6] -> the global sums, added over the ranks in rank order with d_r = p_r - p_0:
+ *   A0 = sum (a0_r + L_r d_r), A1 = sum ((a1_r + (2 d_r) a0_r) + (L_r d_r) d_r), A2 = sum a2_r, A3 = sum (a3_r + d_r a2_r), L = sum L_r
+ * then m, var, invstd, mg, mx, k as th_bn_act_bwd from A0..A3 and L, xhat = ((y - p_r) - (m - d_r)) invstd per element, and g_y, g_res
+ * as th_bn_act_bwd.  g_beta = fp32(a2_r) and g_gamma = fp32((a3_r - (m - d_r) a2_r) invstd) are this rank's LOCAL sums (torch's
+ * SyncBatchNorm returns the same; the gradient exchange averages them).  y, out, g, N are this rank's; world = 1, rank = 0 is
+ * th_bn_act_bwd bit for bit.  No atomics, no wait on the host: DESIGN.md 4, K23. */
+int th_bn_act_bwd_sums(th_ctx* ctx, const float* y, const float* out_or_null, const float* g, int N, int C, int HW,
+                       double* record /* [C][6]: a0 a1 a2 a3 p L */, void* workspace, size_t workspace_bytes, th_stream stream);
+int th_bn_act_bwd_apply(th_ctx* ctx, const float* y, const float* out_or_null, const float* g, int N, int C, int HW,
+                        const float* gamma_or_null, double eps, const double* records /* [world][C][6] */, int world, int rank,
+                        float* g_y, float* g_res_or_null, float* g_gamma_or_null, float* g_beta_or_null, th_stream stream);
 int th_maxpool3x3s2_bwd(th_ctx* ctx, const float* x, const float* g, int planes, int H, int W, float* g_x, th_stream stream);
 size_t th_conv2d_dgrad_pack_bytes(int cin, int cout, int ks, int stride);                     /* pure host call; 0: unsupported */
 int th_conv2d_dgrad_pack(th_ctx* ctx, const float* w, int cin, int cout, int ks, int stride, void* packed, size_t packed_bytes,

@@ -1,6 +1,6 @@
 """Time the gradient exchange of data-parallel training (transhuman_amd/train_dist.py) on one MI355X, in one process:
 
-    timeout -k 10 900 python tools/dp_step_time.py [--rounds 5] [--reps 20] [--steps 5] [--warmup 2] [--only pack|step]
+    timeout -k 10 900 python tools/dp_step_time.py [--rounds 5] [--reps 20] [--steps 5] [--warmup 2] [--only pack|rank_sum|sync_bn|step]
 
 (a) "pack": adam_pack_kernel alone on the product Network's parameter list with a seeded gradient on every tensor, once for the
     live set (the tensors the reference trains: no layer3 / layer4, dead tokens or PE buffers) and once for all tensors, at
@@ -14,6 +14,14 @@
       ddp        torch DistributedDataParallel(find_unused_parameters=True) around the same computation, clip_grad_value_(., 40)
                  + torch.optim.Adam over one group per tensor: the reference's form (lib/train/trainers/trainer.py:23-33, :84-86)
       single     the single-process step: forward + backward, DeviceAdam(clip 40)
+      rank_ordered_sync   as "exchange" with GradExchange(reduce="rank_ordered") on a network converted to SyncBatchNorm under
+                 cfg.train_sync_bn = "device": at world 1 no collective runs, what differs from "exchange" (the step as it was
+                 before these options) is the BatchNorm backward's split launches (train_ops.SyncBnActFn)
+(c) "rank_sum": th_rank_sum (K28) at world 2, 3 and 8 on the live set's flat buffer -- the parts emulated on one device, the sum
+    written over rank 0's part -- as device time per call and GB/s over (world + 1) * slice * 4 bytes, beside a copy_ that moves
+    the same bytes.  As in (a), buffers of this size live in the Infinity Cache: these are its rates, not HBM's.
+(d) "sync_bn": th_bn_act_bwd_sums + th_bn_act_bwd_apply (world 1) against th_bn_act_bwd at the trunk's five BatchNorm sites'
+    shapes for V = 3 views of 512 x 512.
 Per figure: the median of --rounds alternating rounds with the lowest and the highest round beside it.  Prints one JSON line.
 No threshold on any figure.  One rank on one device: what a multi-GPU node adds is the transport, which this does not measure."""
 import argparse
@@ -91,6 +99,72 @@ def pack_times(dev, rounds, reps):
     return out
 
 
+def live_flat_elems():
+    import torch
+    from transhuman_amd.networks.cross_transformer import Network
+    from transhuman_amd.train_dist import flat_layout
+    torch.manual_seed(0)
+    net = Network()
+    names = [k for k, _ in net.named_parameters()]
+    dead = [k.endswith(("cls_token", "mask_token")) or ".layer3." in k or ".layer4." in k or "PE" in k for k in names]
+    return flat_layout([p.numel() for p in net.parameters()], [not d for d in dead])[1]
+
+
+def timed_rounds(forms, rounds, reps):
+    ms = {f: [] for f in forms}
+    for f in forms.values():
+        f()
+    for r in range(rounds):
+        for f in (list(forms) if r % 2 == 0 else list(forms)[::-1]):
+            ms[f].append(device_ms(forms[f], reps))
+    return ms
+
+
+def rank_sum_times(dev, rounds, reps):
+    import torch
+    from transhuman_amd import hip
+    from transhuman_amd.train_dist import rank_slice
+    n = live_flat_elems()
+    out = {"flat_elems": int(n)}
+    gen = torch.Generator().manual_seed(2)
+    for world in (2, 3, 8):
+        sl = rank_slice(n, world)
+        parts = torch.randn(world * sl, generator=gen).to(dev)
+        half = (world + 1) * sl // 2                                          # a copy_ that reads and writes the same bytes in all
+        a, b = torch.zeros(half, device=dev), torch.zeros(half, device=dev)
+        ms = timed_rounds({"rank_sum": lambda: hip.rank_sum(parts, world, sl, parts[:sl]), "copy": lambda: b.copy_(a)}, rounds, reps)
+        moved = (world + 1) * sl * 4
+        out[f"world{world}"] = {"slice_elems": int(sl), "MB_moved": round(moved / 1e6, 2)}
+        for f, v in ms.items():
+            out[f"world{world}"][f] = {"device_ms": spread(v), "GB_per_s": round(moved / float(np.median(v)) / 1e6, 1)}
+    return out
+
+
+def sync_bn_times(dev, rounds, reps):
+    import torch
+    from transhuman_amd import hip
+    sites = {"bn1 64@256x256 relu": (64, 256, True, False), "layer1.bn1 64@128x128 relu": (64, 128, True, False),
+             "layer1.bn2 64@128x128 residual relu": (64, 128, True, True), "layer2.bn2 128@64x64 residual relu": (128, 64, True, True),
+             "layer2.downsample 128@64x64": (128, 64, False, False)}
+    gen = torch.Generator().manual_seed(3)
+    out = {}
+    for label, (C, hw, relu, res) in sites.items():
+        y, g = (torch.randn((3, C, hw, hw), generator=gen).to(dev) for _ in range(2))
+        o = torch.relu(torch.randn((3, C, hw, hw), generator=gen)).to(dev) if relu else None
+        gamma = torch.rand(C, generator=gen).to(dev) + 0.5
+
+        def split():
+            rec = hip.bn_act_bwd_sums(y, o, g)
+            return hip.bn_act_bwd_apply(y, o, g, gamma, 1e-5, rec[None], 0, need_residual=res and relu)
+
+        ms = timed_rounds({"bn_act_bwd": lambda: hip.bn_act_bwd(y, o, g, gamma, 1e-5, need_residual=res and relu),
+                           "sums_apply": split}, rounds, reps)
+        assert all(a is None or torch.equal(a, b) for a, b in zip(split(), hip.bn_act_bwd(y, o, g, gamma, 1e-5,
+                                                                                            need_residual=res and relu)))
+        out[label] = {f: {"device_ms": spread(v)} for f, v in ms.items()}
+    return out
+
+
 def step_times(dev, rounds, steps, warmup):
     import torch
     import torch.distributed as dist
@@ -121,8 +195,10 @@ def step_times(dev, rounds, steps, warmup):
         d = np.load(os.path.join(ROOT, "tests", "golden", "synth_assign.npz"))
         assign = d["assign_500"].astype(np.int64) if "assign_500" in d.files else synth.kmeans_assign(body, 500).astype(np.int64)
         forms = {}
-        for form in ("exchange", "ddp", "single"):
+        for form in ("exchange", "ddp", "single", "rank_ordered_sync"):
             net = net0 if form == "single" else copy.deepcopy(net0)
+            if form == "rank_ordered_sync":
+                net = torch.nn.SyncBatchNorm.convert_sync_batchnorm(net)
             r = r0 if form == "single" else Renderer(net, vertex_can=body.astype(np.float64) * 1.02 + 0.001, pc2voxel_ind=assign)
             mod = Step(net, r)
             params = [p for p in net.parameters() if p.requires_grad]
@@ -140,7 +216,9 @@ def step_times(dev, rounds, steps, warmup):
                     opt.step()
             else:
                 opt = DeviceAdam(groups, 7e-4, clip_value=40.0)
-                ex = GradExchange(params) if form == "exchange" else None
+                ex = None
+                if form != "single":
+                    ex = GradExchange(params, reduce="rank_ordered" if form == "rank_ordered_sync" else None)
 
                 def one(mod=mod, opt=opt, ex=ex):
                     loss = mod(b, target)
@@ -151,7 +229,7 @@ def step_times(dev, rounds, steps, warmup):
                     opt.step()
             forms[form] = one
         ms = {f: [] for f in forms}
-        with override(**{k: v[1] for k, v in TRAIN_SWITCHES.items()}):
+        with override(**{k: v[1] for k, v in TRAIN_SWITCHES.items()}, train_sync_bn="device"):
             for f in forms.values():
                 for _ in range(warmup):
                     f()
@@ -177,7 +255,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20, help="pack: calls per timed round")
     ap.add_argument("--steps", type=int, default=5, help="step: steps per timed round")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default="", help="'pack' or 'step'")
+    ap.add_argument("--only", default="", help="'pack', 'rank_sum', 'sync_bn' or 'step'")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -186,6 +264,10 @@ def main():
     res = {"gpu": torch.cuda.get_device_name(0), "rounds": args.rounds}
     if args.only in ("", "pack"):
         res["pack"] = pack_times(dev, args.rounds, args.reps)
+    if args.only in ("", "rank_sum"):
+        res["rank_sum"] = rank_sum_times(dev, args.rounds, args.reps)
+    if args.only in ("", "sync_bn"):
+        res["sync_bn"] = sync_bn_times(dev, args.rounds, args.reps)
     if args.only in ("", "step"):
         res["step"] = step_times(dev, args.rounds, args.steps, args.warmup)
     print(json.dumps(res))

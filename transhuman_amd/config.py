@@ -26,6 +26,9 @@ TRAIN_SWITCHES = {
 }
 
 
+TRAIN_SYNC_BN = ("torch", "device")
+
+
 def _defaults():
     return SimpleNamespace(
         # sampling / compositing (train_or_eval.yaml:17-43, run.py:22)
@@ -115,9 +118,14 @@ def _defaults():
         # the ResNet18 trunk of the encoder (conv1 / bn1, the max pool, layer1, layer2) in the training entry: "torch" runs the stock
         # modules under torch autograd; "device" runs the same torch operators in the forward, site by site without a graph, and
         # HIP backwards with fixed-order sums (autograd_path.trunk_device: train_ops.ConvFn / BnActFn / MaxPoolFn, K23).  The
-        # device backward is that of batch statistics: a trunk with a BatchNorm site in eval mode, or converted to SyncBatchNorm,
-        # runs under torch autograd whatever this says
+        # device backward is that of batch statistics: a trunk with a BatchNorm site in eval mode runs under torch autograd
+        # whatever this says; one converted to SyncBatchNorm follows train_sync_bn
         train_encoder="torch",
+        # read only with train_encoder = "device" when a trunk site is a train-mode SyncBatchNorm with a momentum: "torch" runs
+        # such a trunk under torch autograd as a whole; "device" keeps it on K23, the BatchNorm backward split around ONE
+        # all_gather of a [C, 6] float64 record per site and the ranks' sums combined in rank order (train_ops.SyncBnActFn).
+        # Not one of TRAIN_SWITCHES: it selects nothing in a single process
+        train_sync_bn="torch",
         # patch sampling of the training targets (train_or_eval.yaml:70-75)
         patch=SimpleNamespace(use_patch_sampling=True, sample_subject_ratio=0.8, N_patches=6, size=20),
         # where the training entry's rays and patch targets come from: "batch" (as the reference: its dataset samples them on the

@@ -16,6 +16,8 @@
 //       g_beta = fp32(a2),  g_gamma = fp32(s * invstd),  mg = a2 / L,  mx = s * invstd / L,  k = gamma * invstd  (gamma NULL: 1)
 //     per element, fp64, rounded to fp32 once at the end:
 //       xhat = ((y - p) - m) * invstd,   g_y = fp32(k * ((g' - mg) - xhat * mx)),   g_res = g' (when asked for)
+//     eb_bn_record_kernel / eb_bn_apply_sync_kernel: the same backward for a SyncBatchNorm site, split around the caller's
+//     all_gather of one record per rank (th_bn_act_bwd_sums / th_bn_act_bwd_apply; the definition stands beside the kernels).
 //
 // eb_dgrad_kernel   the input gradient of a 3x3 / pad 1 or 1x1 / pad 0 convolution of stride 1 or 2 as an implicit GEMM on the
 //     fp32-input MFMA (v_mfma_f32_32x32x2_f32): no reduced-precision operand, no range guard.  Input pixel (iy, ix) receives
@@ -125,6 +127,31 @@ __global__ __launch_bounds__(EB_THREADS) void eb_bn_sums_kernel(const float* __r
         for (int k = 0; k < 4; ++k) partial[((size_t)c * S + s) * 4 + k] = a[k];
 }
 
+// the per-element part of pass B over slice s of channel c: xhat = ((y - p) - m) * invstd with this rank's pivot and the mean
+// relative to it
+__device__ __forceinline__ void eb_bn_apply_slice(const float* __restrict__ y, const float* __restrict__ out,
+                                                  const float* __restrict__ g, int C, int HW, long long L, long long slice, int c,
+                                                  int s, double p, double m, double invstd, double k, double mg, double mx,
+                                                  float* __restrict__ g_y, float* __restrict__ g_res) {
+    const long long lo = (long long)s * slice, hi = lo + slice < L ? lo + slice : L;
+    long long i = lo + threadIdx.x;
+    int n = (int)(i / HW), r = (int)(i - (long long)n * HW);      // (one division per thread: the loop steps (n, r) along)
+    for (; i < hi; i += EB_THREADS) {
+        const size_t o = ((size_t)n * C + c) * HW + (size_t)r;
+        float gv = g[o];
+        if (out != nullptr) gv = out[o] > 0.f ? gv : 0.f;
+        const double xhat = (((double)y[o] - p) - m) * invstd;
+        g_y[o] = (float)(k * (((double)gv - mg) - xhat * mx));
+        if (g_res != nullptr) g_res[o] = gv;
+        r += EB_THREADS;
+        if (r >= HW) {
+            const int q = r / HW;
+            n += q;
+            r -= q * HW;
+        }
+    }
+}
+
 // grid (S, C), the same slices
 __global__ __launch_bounds__(EB_THREADS) void eb_bn_apply_kernel(const float* __restrict__ y, const float* __restrict__ out,
                                                                  const float* __restrict__ g, int C, int HW, long long L,
@@ -149,23 +176,66 @@ __global__ __launch_bounds__(EB_THREADS) void eb_bn_apply_kernel(const float* __
         if (g_beta != nullptr) g_beta[c] = (float)a[2];
         if (g_gamma != nullptr) g_gamma[c] = (float)(sgy * invstd);
     }
-    const long long lo = (long long)s * slice, hi = lo + slice < L ? lo + slice : L;
-    long long i = lo + threadIdx.x;
-    int n = (int)(i / HW), r = (int)(i - (long long)n * HW);      // (one division per thread: the loop steps (n, r) along)
-    for (; i < hi; i += EB_THREADS) {
-        const size_t o = ((size_t)n * C + c) * HW + (size_t)r;
-        float gv = g[o];
-        if (out != nullptr) gv = out[o] > 0.f ? gv : 0.f;
-        const double xhat = (((double)y[o] - p) - m) * invstd;
-        g_y[o] = (float)(k * (((double)gv - mg) - xhat * mx));
-        if (g_res != nullptr) g_res[o] = gv;
-        r += EB_THREADS;
-        if (r >= HW) {
-            const int q = r / HW;
-            n += q;
-            r -= q * HW;
-        }
+    eb_bn_apply_slice(y, out, g, C, HW, L, slice, c, s, p, m, invstd, k, mg, mx, g_y, g_res);
+}
+
+// ---- the split form for SyncBatchNorm sites: pass A ends in a record per channel, the ranks' records are gathered by the caller,
+// pass B combines them in rank order.  record [C][6] = a0 a1 a2 a3 p L, every sum against the rank's OWN pivot p_r.  With
+// d_r = p_r - p_0 (fp64) the sums against rank 0's pivot are, added over r in rank order (rank 0's terms taken as they are: d_0 = 0),
+//   A0 = sum (a0_r + L_r d_r)     A1 = sum ((a1_r + (2 d_r) a0_r) + (L_r d_r) d_r)     A2 = sum a2_r     A3 = sum (a3_r + d_r a2_r)
+// and L = sum L_r; m, var, invstd, mg, mx, k follow from them as in pass B above.  Per element xhat = ((y - p_r) - (m - d_r)) invstd;
+// g_beta = fp32(a2_r) and g_gamma = fp32((a3_r - (m - d_r) a2_r) invstd) are the rank's LOCAL sums (the exchange averages them, as
+// with torch's SyncBatchNorm).  One rank: every correction is absent and the launch pair IS th_bn_act_bwd, bit for bit.
+constexpr int EB_BN_REC = 6;
+
+// one thread per (channel, sum): the slices of pass A added in slice order, as eb_bn_apply_kernel adds them
+__global__ __launch_bounds__(EB_THREADS) void eb_bn_record_kernel(const float* __restrict__ y, int C, int HW, long long L, int S,
+                                                                  const double* __restrict__ partial, double* __restrict__ record) {
+    const int i = blockIdx.x * EB_THREADS + threadIdx.x, c = i >> 2, k = i & 3;
+    if (c >= C) return;
+    double a = 0.0;
+    for (int t = 0; t < S; ++t) a += partial[((size_t)c * S + t) * 4 + k];
+    double* rec = record + (size_t)c * EB_BN_REC;
+    rec[k] = a;
+    if (k == 0) rec[4] = (double)y[(size_t)c * HW];
+    if (k == 1) rec[5] = (double)L;
+}
+
+// grid (S, C), the slices of pass A
+__global__ __launch_bounds__(EB_THREADS) void eb_bn_apply_sync_kernel(const float* __restrict__ y, const float* __restrict__ out,
+                                                                      const float* __restrict__ g, int C, int HW, long long L,
+                                                                      long long slice, const double* __restrict__ records, int world,
+                                                                      int rank, const float* __restrict__ gamma, double eps,
+                                                                      float* __restrict__ g_y, float* __restrict__ g_res,
+                                                                      float* __restrict__ g_gamma, float* __restrict__ g_beta) {
+    const int c = blockIdx.y, s = blockIdx.x;
+    const double* r0 = records + (size_t)c * EB_BN_REC;
+    const double p0 = r0[4];
+    double A0 = r0[0], A1 = r0[1], A2 = r0[2], A3 = r0[3], Ld = r0[5];
+    for (int r = 1; r < world; ++r) {
+        const double* q = records + ((size_t)r * C + c) * EB_BN_REC;
+        const double d = q[4] - p0, Lr = q[5];
+        A0 += q[0] + Lr * d;
+        A1 += (q[1] + (2.0 * d) * q[0]) + (Lr * d) * d;
+        A2 += q[2];
+        A3 += q[3] + d * q[2];
+        Ld += Lr;
     }
+    const double m = A0 / Ld;
+    double var = A1 / Ld - m * m;
+    var = var > 0.0 ? var : 0.0;
+    const double invstd = 1.0 / sqrt(var + eps);
+    const double sgy = A3 - m * A2;
+    const double mg = A2 / Ld, mx = sgy * invstd / Ld;
+    const double k = (gamma != nullptr ? (double)gamma[c] : 1.0) * invstd;
+    const double* own = records + ((size_t)rank * C + c) * EB_BN_REC;
+    const double p = own[4];
+    const double ml = m - (p - p0);                              // the mean relative to this rank's pivot (rank 0: m - 0)
+    if (s == 0 && threadIdx.x == 0) {
+        if (g_beta != nullptr) g_beta[c] = (float)own[2];
+        if (g_gamma != nullptr) g_gamma[c] = (float)((own[3] - ml * own[2]) * invstd);
+    }
+    eb_bn_apply_slice(y, out, g, C, HW, L, slice, c, s, p, ml, invstd, k, mg, mx, g_y, g_res);
 }
 
 // ---- max pool 3x3 / 2 / 1 -----------------------------------------------------------------------------------------------------
@@ -448,6 +518,41 @@ int th_bn_act_bwd_launch(const float* y, const float* out, const float* g, int N
     TH_LAUNCH_CHECK();
     hipLaunchKernelGGL(eb_bn_apply_kernel, grid, dim3(EB_THREADS), 0, s, y, out, g, C, HW, p.L, p.slice, (const double*)sums, gamma,
                        eps, g_y, g_res, g_gamma, g_beta);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+// pass A of th_bn_act_bwd (the same slices, the same workspace) and the record of this rank
+int th_bn_act_bwd_sums_launch(const float* y, const float* out, const float* g, int N, int C, int HW, double* record, void* ws,
+                              size_t ws_bytes, hipStream_t s) {
+    TH_REQUIRE(N >= 1 && C >= 1 && C <= 65535 && HW >= 1 && (long long)N * C * HW < (1LL << 31),
+               "unsupported shape: N, C, HW >= 1, C <= 65535, fewer than 2^31 elements");
+    ThArena ar(ws, ws_bytes);
+    double* sums = eb_bn_layout(ar, N, C, HW);
+    TH_REQUIRE(ar.ok(), "workspace too small");
+    TH_REQUIRE((((uintptr_t)ws) & 7) == 0 && (((uintptr_t)record) & 7) == 0, "the workspace and the record must be 8-byte aligned");
+    const EbBnPlan p = eb_bn_plan(N, HW);
+    hipLaunchKernelGGL(eb_bn_sums_kernel, dim3((unsigned)p.S, (unsigned)C), dim3(EB_THREADS), 0, s, y, out, g, C, HW, p.L, p.slice,
+                       sums);
+    TH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(eb_bn_record_kernel, dim3((unsigned)th_cdiv(4LL * C, EB_THREADS)), dim3(EB_THREADS), 0, s, y, C, HW, p.L, p.S,
+                       (const double*)sums, record);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_bn_act_bwd_apply_launch(const float* y, const float* out, const float* g, int N, int C, int HW, const float* gamma, double eps,
+                               const double* records, int world, int rank, float* g_y, float* g_res, float* g_gamma, float* g_beta,
+                               hipStream_t s) {
+    TH_REQUIRE(N >= 1 && C >= 1 && C <= 65535 && HW >= 1 && (long long)N * C * HW < (1LL << 31),
+               "unsupported shape: N, C, HW >= 1, C <= 65535, fewer than 2^31 elements");
+    TH_REQUIRE(eps > 0.0, "eps must be positive");
+    TH_REQUIRE(world >= 1 && world <= 4096 && rank >= 0 && rank < world,
+               "rank " + std::to_string(rank) + " of " + std::to_string(world) + ": world in 1 .. 4096, rank in 0 .. world - 1");
+    TH_REQUIRE((((uintptr_t)records) & 7) == 0, "the records must be 8-byte aligned");
+    const EbBnPlan p = eb_bn_plan(N, HW);
+    hipLaunchKernelGGL(eb_bn_apply_sync_kernel, dim3((unsigned)p.S, (unsigned)C), dim3(EB_THREADS), 0, s, y, out, g, C, HW, p.L,
+                       p.slice, records, world, rank, gamma, eps, g_y, g_res, g_gamma, g_beta);
     TH_LAUNCH_CHECK();
     return 0;
 }

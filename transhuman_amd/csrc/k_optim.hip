@@ -27,6 +27,7 @@
 //   adam_unpack_kernel   dst_i[e] = flat[off_i + e]
 // with a per-call table of (pointer, slot offset) per tensor that travels through the same ring of staging buffers into a
 // region of its own behind the chunk table.  The slots follow ad_flat_layout, the one statement of the layout rule in C.
+//   rank_sum_kernel      K28, at the end of the file: the rank-ordered sum of the slices a reduce-scatter delivered
 #include "th_internal.h"
 
 #include <string.h>
@@ -472,4 +473,49 @@ int th_adam_flat_launch(th_ctx* c, th_adam_plan_t* pl, int unpack, const void* c
                            (float)world, world == 1 ? 1 : 0);
     TH_LAUNCH_CHECK();
     return ad_stage_done(pl, last_of_half, s);
+}
+
+// ---- K28: the rank-ordered sum of the exchange's reduce-scatter ----
+// parts [world][slice_elems] holds slice r of every rank's flat buffer, as all_to_all_single delivers it to rank r:
+//   out[e] = ((parts[0][e] + parts[1][e]) + parts[2][e]) + ...      fp32, one rounding per addition, in rank order
+// which is grad_exchange_oracle's sum for any world, whatever order a collective would take.  One lane owns an element (a group
+// of four on the 128-bit path): it reads the element of every part and then writes it, so `out` may BE any of the parts.  No
+// atomics, no LDS; subnormals are kept (the library's default), NaN, +-inf and -0.0 are the adder's; world == 1 copies the bits.
+// The 128-bit path needs parts and out on the 16-byte grid and slice_elems a multiple of 4 (every part then starts on the grid).
+template <typename T, typename G>
+__global__ __launch_bounds__(AD_THREADS) void rank_sum_kernel(const float* parts_, int world, long long stride, long long n,
+                                                               float* out_) {
+    const long long i = (long long)blockIdx.x * AD_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const G* parts = (const G*)(uintptr_t)parts_ + i;                             // (stride and n count T's)
+    T acc = parts[0];
+    int r = 1;
+    for (; r + 4 <= world; r += 4) {                                              // four loads in flight, added in rank order
+        const T a = parts[(long long)r * stride], b = parts[(long long)(r + 1) * stride], c = parts[(long long)(r + 2) * stride],
+                d = parts[(long long)(r + 3) * stride];
+        acc = acc + a;
+        acc = acc + b;
+        acc = acc + c;
+        acc = acc + d;
+    }
+    for (; r < world; ++r) acc = acc + parts[(long long)r * stride];
+    ((G*)(uintptr_t)out_)[i] = acc;
+}
+
+int th_rank_sum_launch(const float* parts, int world, long long slice_elems, float* out, hipStream_t s) {
+    TH_REQUIRE(parts && out, "null argument");
+    TH_REQUIRE(world >= 1 && world <= 64, "world is " + std::to_string(world) + ": 1 .. 64");
+    TH_REQUIRE(slice_elems >= 1 && slice_elems <= (1LL << 36), "slice_elems is " + std::to_string(slice_elems) + ": 1 .. 2^36");
+    TH_REQUIRE(((((uintptr_t)parts) | ((uintptr_t)out)) & 3) == 0, "parts and out must be 4-byte aligned");
+    const bool wide = ((((uintptr_t)parts) | ((uintptr_t)out)) & 15) == 0 && slice_elems % 4 == 0;
+    if (wide) {
+        const long long n4 = slice_elems / 4;
+        hipLaunchKernelGGL((rank_sum_kernel<AdF4, AdGlobalF4>), dim3((unsigned)((n4 + AD_THREADS - 1) / AD_THREADS)), dim3(AD_THREADS),
+                           0, s, parts, world, n4, n4, out);
+    } else {
+        hipLaunchKernelGGL((rank_sum_kernel<float, AdGlobalF>), dim3((unsigned)((slice_elems + AD_THREADS - 1) / AD_THREADS)),
+                           dim3(AD_THREADS), 0, s, parts, world, slice_elems, slice_elems, out);
+    }
+    TH_LAUNCH_CHECK();
+    return 0;
 }

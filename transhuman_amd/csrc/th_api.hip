@@ -1841,6 +1841,20 @@ int th_bn_act_bwd(th_ctx* c, const float* y, const float* out_or_null, const flo
                                 g_beta_or_null, ws, ws_bytes, (hipStream_t)stream);
 }
 
+int th_bn_act_bwd_sums(th_ctx* c, const float* y, const float* out_or_null, const float* g, int N, int C, int HW, double* record,
+                       void* ws, size_t ws_bytes, th_stream stream) {
+    TH_REQUIRE(c && y && g && record && ws, "null argument");
+    return th_bn_act_bwd_sums_launch(y, out_or_null, g, N, C, HW, record, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int th_bn_act_bwd_apply(th_ctx* c, const float* y, const float* out_or_null, const float* g, int N, int C, int HW,
+                        const float* gamma_or_null, double eps, const double* records, int world, int rank, float* g_y,
+                        float* g_res_or_null, float* g_gamma_or_null, float* g_beta_or_null, th_stream stream) {
+    TH_REQUIRE(c && y && g && records && g_y, "null argument");
+    return th_bn_act_bwd_apply_launch(y, out_or_null, g, N, C, HW, gamma_or_null, eps, records, world, rank, g_y, g_res_or_null,
+                                      g_gamma_or_null, g_beta_or_null, (hipStream_t)stream);
+}
+
 int th_maxpool3x3s2_bwd(th_ctx* c, const float* x, const float* g, int planes, int H, int W, float* g_x, th_stream stream) {
     TH_REQUIRE(c && x && g && g_x, "null argument");
     return th_maxpool3x3s2_bwd_launch(x, g, planes, H, W, g_x, (hipStream_t)stream);
@@ -1889,6 +1903,11 @@ int th_adam_unpack(th_ctx* c, th_adam_plan_t* plan, void* const* dst, const long
     TH_REQUIRE(c && plan && dst && offsets && flat, "null argument");
     return th_adam_flat_launch(c, plan, 1, (const void* const*)dst, offsets, n_tensors, 1, const_cast<float*>(flat), flat_elems,
                                (hipStream_t)stream);
+}
+
+int th_rank_sum(th_ctx* c, const float* parts, int world, long long slice_elems, float* out, th_stream stream) {
+    TH_REQUIRE(c && parts && out, "null argument");
+    return th_rank_sum_launch(parts, world, slice_elems, out, (hipStream_t)stream);
 }
 
 size_t th_ray_sample_workspace_bytes(int H, int W, int nrays) { return th_ray_sample_ws(H, W, nrays); }

@@ -601,6 +601,12 @@ int th_bn_act_bwd_slice_internal();
 size_t th_bn_act_bwd_ws(int N, int C, int HW);
 int th_bn_act_bwd_launch(const float* y, const float* out, const float* g, int N, int C, int HW, const float* gamma, double eps,
                          float* g_y, float* g_res, float* g_gamma, float* g_beta, void* ws, size_t ws_bytes, hipStream_t s);
+// the split form for SyncBatchNorm sites: record [C][6] = a0 a1 a2 a3 p L of this rank; records [world][C][6] in rank order
+int th_bn_act_bwd_sums_launch(const float* y, const float* out, const float* g, int N, int C, int HW, double* record, void* ws,
+                              size_t ws_bytes, hipStream_t s);
+int th_bn_act_bwd_apply_launch(const float* y, const float* out, const float* g, int N, int C, int HW, const float* gamma, double eps,
+                               const double* records, int world, int rank, float* g_y, float* g_res, float* g_gamma, float* g_beta,
+                               hipStream_t s);
 int th_maxpool3x3s2_bwd_launch(const float* x, const float* g, int planes, int H, int W, float* gx, hipStream_t s);
 size_t th_conv2d_dgrad_pack_size(int cin, int cout, int ks, int stride);
 int th_conv2d_dgrad_pack_launch(const float* w, int cin, int cout, int ks, int stride, void* packed, size_t bytes, hipStream_t s);
@@ -672,3 +678,5 @@ int th_truncate_zero_launch(const ThPointSrc& ps, const float* Rh, const float* 
 long long ad_flat_layout(int n_tensors, const long long* counts, const uint8_t* live, long long* offsets_out);
 int th_adam_flat_launch(th_ctx* c, th_adam_plan_t* pl, int unpack, const void* const* ptrs, const long long* offsets, int n_tensors,
                         int world, float* flat, long long flat_elems, hipStream_t s);
+// K28: out[e] = the parts' elements e added in rank order (parts [world][slice_elems]; out may be any of the parts)
+int th_rank_sum_launch(const float* parts, int world, long long slice_elems, float* out, hipStream_t s);

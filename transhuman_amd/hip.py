@@ -1046,6 +1046,51 @@ def bn_act_bwd(y, out, g, gamma, eps, need_residual=False, need_affine=True):
     return g_y, g_res, g_gamma, g_beta
 
 
+BN_RECORD = 6       # a0 a1 a2 a3 p L per channel (th_bn_act_bwd_sums)
+
+
+def _bn_site(fn, y, out, g):
+    y2, g2 = _nchw(fn, "y", y), _nchw(fn, "g", g)
+    o2 = None if out is None else _nchw(fn, "out", out)
+    if g2.shape != y2.shape or (o2 is not None and o2.shape != y2.shape):
+        raise ValueError(f"{fn}: y, out and g must have one shape")
+    return y2, o2, g2
+
+
+def bn_act_bwd_sums(y, out, g):
+    """th_bn_act_bwd_sums: pass A of bn_act_bwd over this rank's batch -> the rank's record, float64 [C, 6] = a0 a1 a2 a3 p L
+    on the device, for the all_gather of a SyncBatchNorm site"""
+    lib = load_library()
+    y2, o2, g2 = _bn_site("bn_act_bwd_sums", y, out, g)
+    N, Cc, H, W = (int(n) for n in y2.shape)
+    record = torch.empty((Cc, BN_RECORD), dtype=torch.float64, device=y2.device)
+    ws = _ws(lib.th_bn_act_bwd_workspace_bytes(N, Cc, H * W), y2.device)
+    _check(lib.th_bn_act_bwd_sums(ctx(y2.device), _p(y2), _p(o2), _p(g2), N, Cc, H * W, _p(record), _p(ws), ws.numel(), _stream()))
+    return record
+
+
+def bn_act_bwd_apply(y, out, g, gamma, eps, records, rank, need_residual=False, need_affine=True):
+    """th_bn_act_bwd_apply: ``records`` float64 [world, C, 6], the ranks' bn_act_bwd_sums in rank order; y, out, g are rank
+    ``rank``'s -> (g_y, g_residual or None, g_gamma or None, g_beta or None) as bn_act_bwd, with the statistics of all ranks and
+    the LOCAL g_gamma / g_beta.  world 1 is bn_act_bwd bit for bit."""
+    lib = load_library()
+    fn = "bn_act_bwd_apply"
+    y2, o2, g2 = _bn_site(fn, y, out, g)
+    N, Cc, H, W = (int(n) for n in y2.shape)
+    if not (isinstance(records, torch.Tensor) and records.dtype is torch.float64 and records.dim() == 3 and records.is_contiguous()
+            and records.device == y2.device and tuple(records.shape[1:]) == (Cc, BN_RECORD)):
+        raise ValueError(f"{fn}: 'records' must be a contiguous float64 [world, {Cc}, {BN_RECORD}] tensor on {y2.device}")
+    world = int(records.shape[0])
+    gm = None if gamma is None else _train_vec(fn, gamma, Cc)
+    g_y = torch.empty_like(y2)
+    g_res = torch.empty_like(y2) if need_residual else None
+    g_gamma = torch.empty(Cc, dtype=torch.float32, device=y2.device) if need_affine else None
+    g_beta = torch.empty(Cc, dtype=torch.float32, device=y2.device) if need_affine else None
+    _check(lib.th_bn_act_bwd_apply(ctx(y2.device), _p(y2), _p(o2), _p(g2), N, Cc, H * W, _p(gm), float(eps), _p(records), world,
+                                   int(rank), _p(g_y), _p(g_res), _p(g_gamma), _p(g_beta), _stream()))
+    return g_y, g_res, g_gamma, g_beta
+
+
 def maxpool3x3s2_bwd(x, g):
     """th_maxpool3x3s2_bwd: x [N,C,H,W] (the input of nn.MaxPool2d(3, 2, 1)), g [N,C,Ho,Wo] -> g_x; torch's routing rule"""
     x2, g2 = _nchw("maxpool3x3s2_bwd", "x", x), _nchw("maxpool3x3s2_bwd", "g", g)
@@ -1086,6 +1131,23 @@ def adam_flat_layout(counts, live=None):
     if end < 0:
         raise HipError("adam_flat_layout: sizes out of range")
     return offsets, end
+
+
+def rank_sum(parts, world, slice_elems, out):
+    """th_rank_sum (K28): out[e] = ((parts[0][e] + parts[1][e]) + ...) in fp32, in rank order.  ``parts``: a contiguous fp32 device
+    tensor of at least world * slice_elems elements, read as [world, slice_elems]; ``out``: at least slice_elems elements, and may
+    be the view of any one part."""
+    world, slice_elems = int(world), int(slice_elems)
+    for name, t, need in (("parts", parts, max(world, 1) * slice_elems), ("out", out, slice_elems)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
+            raise HipError(f"rank_sum: '{name}' must be a contiguous float32 device tensor (there is no CPU path)")
+        if t.numel() < need:
+            raise HipError(f"rank_sum: '{name}' holds {t.numel()} elements, the call reads or writes {need}")
+    if out.device != parts.device:
+        raise HipError("rank_sum: parts and out live on different devices")
+    with torch.cuda.device(parts.device):
+        _check(load_library().th_rank_sum(ctx(parts.device), _p(parts), world, slice_elems, _p(out), _stream()))
+    return out
 
 
 def adam_check_tensor(t, what):

@@ -38,7 +38,10 @@ gradient is bit-identical from run to run.  The residual adds and the positional
 (default) is ``SpatialEncoder.trunk(fused_bn=False)`` under torch autograd; "device" is ``trunk_device``: the same torch
 operators in the forward, site by site without a graph -- latents, running statistics and num_batches_tracked are the "torch"
 mode's bit for bit --, and HIP backwards with fixed-order sums (``train_ops.ConvFn`` / ``BnActFn`` / ``MaxPoolFn``, DESIGN.md
-K23).  The upsamples, ``upsample_color`` and ``reduction_layer`` stay what ``cfg.train_maps`` makes them.
+K23).  The upsamples, ``upsample_color`` and ``reduction_layer`` stay what ``cfg.train_maps`` makes them.  A trunk converted to
+SyncBatchNorm (data-parallel training) runs under torch autograd as a whole under "device" too, unless ``cfg.train_sync_bn`` =
+"device" (default "torch"; its own check, ``_sync_bn_mode``: the key is not in the table below), which runs the converted sites
+on ``train_ops.SyncBnActFn``: the BatchNorm backward split around one all_gather of a [C, 6] float64 record per site.
 
 The allowed values of these six and of ``cfg.train_gather_bwd`` (the form of the latent gather's adjoint) are one table,
 ``config.TRAIN_SWITCHES``, and ``_switch`` is their one reader: a value outside the table is a ValueError, a value other than
@@ -57,7 +60,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from ..config import TRAIN_SWITCHES, get_cfg
+from ..config import TRAIN_SWITCHES, TRAIN_SYNC_BN, get_cfg
 from ..truncation import sigma_in_force
 
 
@@ -73,6 +76,14 @@ def _switch(key, value, on_device, noun="batch"):
         from .. import hip
         raise hip.HipError(f"cfg.{key} = '{mode}' needs the {noun} on an MI355X (the HIP kernels have no CPU form); "
                            f"use '{allowed[0]}' for a CPU batch")
+    return mode
+
+
+def _sync_bn_mode(value):
+    """cfg.train_sync_bn, which is not one of TRAIN_SWITCHES (it selects nothing in a single process): one of config.TRAIN_SYNC_BN"""
+    mode = str(value)
+    if mode not in TRAIN_SYNC_BN:
+        raise ValueError(f"cfg.train_sync_bn must be {TRAIN_SYNC_BN[0]!r} or {TRAIN_SYNC_BN[1]!r}, not {mode!r}")
     return mode
 
 
@@ -102,25 +113,36 @@ def embed_view(ray_d, view_res):
 def _trunk_sites_have_batch_statistics(enc):
     """every BatchNorm site of the trunk is a train-mode nn.BatchNorm2d with a momentum: what th_bn_act_bwd is the backward of
     (eval mode normalises with the running statistics; SyncBatchNorm, after the reference trainer's conversion, with the
-    statistics of all ranks)"""
+    statistics of all ranks: ``_trunk_sync_sites``)"""
     return all(isinstance(b, torch.nn.BatchNorm2d) and b.training and b.momentum is not None for b in enc._bn_sites())
+
+
+def _trunk_sync_sites(enc):
+    """every BatchNorm site is a train-mode BatchNorm2d or SyncBatchNorm with a momentum, and at least one is a SyncBatchNorm:
+    the trunk th_bn_act_bwd_sums / _apply are the backward of at the converted sites"""
+    sites = list(enc._bn_sites())
+    return (all(isinstance(b, (torch.nn.BatchNorm2d, torch.nn.SyncBatchNorm)) and b.training and b.momentum is not None
+                for b in sites) and any(isinstance(b, torch.nn.SyncBatchNorm) for b in sites))
 
 
 def trunk_device(enc, images):
     """SpatialEncoder.trunk(images, fused_bn=False) (encoder.walk_trunk) on the per-site Functions of train_ops: the same torch
     operators in the forward, called without recording a graph, and k_encoder_bwd.hip in the backward (K23).  A trunk whose
-    BatchNorm sites do not all use batch statistics runs under torch autograd as a whole."""
+    BatchNorm sites do not all use batch statistics runs under torch autograd as a whole; so does one with SyncBatchNorm sites,
+    unless cfg.train_sync_bn = "device" (read only then), which runs them on train_ops.SyncBnActFn."""
     from .. import hip
     from . import train_ops as T
     from .encoder import walk_trunk
     _switch("train_encoder", "device", images.is_cuda)
     if not _trunk_sites_have_batch_statistics(enc):
-        return enc.trunk(images, fused_bn=False)
+        if not (_trunk_sync_sites(enc) and _sync_bn_mode(getattr(get_cfg(), "train_sync_bn", TRAIN_SYNC_BN[0])) == "device"):
+            return enc.trunk(images, fused_bn=False)
 
     def conv_bn(conv, bn, t, residual=None, relu=True):
         if conv.bias is not None:
             raise hip.HipError("cfg.train_encoder = 'device': the trunk's convolutions have no bias in the HIP backward")
-        return T.BnActFn.apply(T.ConvFn.apply(t, conv.weight, conv.stride[0]), bn, residual, relu, bn.weight, bn.bias)
+        site = T.SyncBnActFn if isinstance(bn, torch.nn.SyncBatchNorm) else T.BnActFn
+        return site.apply(T.ConvFn.apply(t, conv.weight, conv.stride[0]), bn, residual, relu, bn.weight, bn.bias)
 
     return walk_trunk(enc.model, images, conv_bn, T.MaxPoolFn.apply)
 

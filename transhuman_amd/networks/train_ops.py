@@ -48,6 +48,8 @@ the "torch" mode bit for bit; the backward is k_encoder_bwd.hip (DESIGN.md K23; 
     ConvFn                  x, W, stride         -> conv2d(x, W)       keeps x, W       gradient: x (not conv1's images), W
     BnActFn                 y, bn, residual, relu, gamma, beta -> relu(bn(y) + residual)   keeps y, the output (with a ReLU), gamma
     MaxPoolFn               x                    -> max_pool2d(x, 3, 2, 1)   keeps x
+    SyncBnActFn             as BnActFn, `bn` a train-mode nn.SyncBatchNorm (cfg.train_sync_bn = "device"): the backward is split
+                            around one all_gather of the ranks' [C, 6] float64 records (th_bn_act_bwd_sums / _apply)
 
 K4 and K5 are linear in the tensor that gets the gradient, so nothing of the forward is kept for the backward but the
 geometry (points, centres, cameras): the [P,7,255] blend operands and the per-chunk map-sized gradients of the torch
@@ -382,6 +384,99 @@ class BnActFn(torch.autograd.Function):
         if need_res and not ctx.relu:
             g_res = g                                          # (no gate: the residual's gradient is the arriving one)
         return g_y, None, g_res, None, g_gamma, g_beta
+
+
+def _bn_group(bn):
+    """(torch.distributed or None, the group, world, rank) of a SyncBatchNorm: its process_group, the default one without"""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return None, None, 1, 0
+    group = bn.process_group if bn.process_group is not None else dist.group.WORLD
+    return dist, group, dist.get_world_size(group), dist.get_rank(group)
+
+
+class SyncBnActFn(torch.autograd.Function):
+    """BnActFn for a site whose ``bn`` is a train-mode nn.SyncBatchNorm.  Forward: the stock module call, made without a graph (it
+    runs the module's own collective and updates the running statistics as always), torch's add and ReLU.  Backward:
+    th_bn_act_bwd_sums over this rank's batch, ONE all_gather of the [C, 6] float64 record on bn.process_group (the list form on
+    gloo, as torch's own SyncBatchNorm; skipped with one rank), th_bn_act_bwd_apply, which adds the ranks' sums in rank order.
+    g_gamma / g_beta are the rank's local sums, as torch's SyncBatchNorm returns them: the gradient exchange averages them.
+    ``calls`` counts the backward runs of the process."""
+
+    calls = 0
+
+    @staticmethod
+    def forward(ctx, y, bn, residual, relu, gamma, beta):
+        _trunk_input("SyncBnActFn", "y", y)
+        if not (isinstance(bn, torch.nn.SyncBatchNorm) and bn.training and bn.momentum is not None):
+            raise ValueError("SyncBnActFn: the backward is defined for a train-mode nn.SyncBatchNorm with a momentum (batch statistics)")
+        out = bn(y.detach())
+        if residual is not None:
+            out = out + residual.detach()
+        if relu:
+            out = torch.relu_(out)
+        ctx.relu, ctx.eps, ctx.has_res = bool(relu), float(bn.eps), residual is not None
+        ctx.dist, ctx.group, ctx.world, ctx.rank = _bn_group(bn)
+        ctx.save_for_backward(y, out if relu else None, gamma)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        y, out, gamma = ctx.saved_tensors
+        g, yc = grad_out.contiguous(), y.contiguous()
+        record = hip.bn_act_bwd_sums(yc, out, g)
+        if ctx.world == 1:
+            records = record[None]
+        elif ctx.dist.get_backend(ctx.group) == "gloo":
+            parts = [torch.empty_like(record) for _ in range(ctx.world)]
+            ctx.dist.all_gather(parts, record, group=ctx.group)
+            records = torch.stack(parts)
+        else:
+            records = record.new_empty((ctx.world, *record.shape))
+            ctx.dist.all_gather_into_tensor(records, record, group=ctx.group)
+        need_res = ctx.has_res and ctx.needs_input_grad[2]
+        g_y, g_res, g_gamma, g_beta = hip.bn_act_bwd_apply(yc, out, g, gamma, ctx.eps, records, ctx.rank,
+                                                           need_residual=need_res and ctx.relu, need_affine=gamma is not None)
+        if need_res and not ctx.relu:
+            g_res = g                                          # (no gate: the residual's gradient is the arriving one)
+        SyncBnActFn.calls += 1
+        return g_y, None, g_res, None, g_gamma, g_beta
+
+
+def sync_bn_act_bwd_oracle(ys, outs, gs, gamma, eps):
+    """th_bn_act_bwd_sums / _apply in float64 numpy.  ys, outs, gs: per rank, y [N_r,C,H,W], the site's output (None: no ReLU) and
+    the arriving gradient; gamma [C] or None -> per rank (g_y, g', g_gamma, g_beta), g' the gated gradient (the residual's) and
+    g_gamma / g_beta the rank's LOCAL sums.  The sums are taken against each rank's own pivot and moved to rank 0's in rank order,
+    as the kernels do."""
+    recs, gates = [], []
+    for y, out, g in zip(ys, outs, gs):
+        y, g = _np64(y), _np64(g)
+        gp = g if out is None else g * (_np64(out) > 0)
+        p = y[0, :, 0, 0]
+        d = y - p[None, :, None, None]
+        recs.append((d.sum((0, 2, 3)), (d * d).sum((0, 2, 3)), gp.sum((0, 2, 3)), (gp * d).sum((0, 2, 3)), p,
+                     float(y.shape[0] * y.shape[2] * y.shape[3])))
+        gates.append(gp)
+    p0 = recs[0][4]
+    A0, A1, A2, A3, L = recs[0][0].copy(), recs[0][1].copy(), recs[0][2].copy(), recs[0][3].copy(), recs[0][5]
+    for a0, a1, a2, a3, p, Lr in recs[1:]:
+        d = p - p0
+        A0 += a0 + Lr * d
+        A1 += (a1 + (2.0 * d) * a0) + (Lr * d) * d
+        A2 += a2
+        A3 += a3 + d * a2
+        L += Lr
+    m = A0 / L
+    invstd = 1.0 / np.sqrt(np.maximum(A1 / L - m * m, 0.0) + eps)
+    mg, mx = A2 / L, (A3 - m * A2) * invstd / L
+    k = (1.0 if gamma is None else _np64(gamma)) * invstd
+    res = []
+    for (a0, a1, a2, a3, p, Lr), y, gp in zip(recs, ys, gates):
+        ml = m - (p - p0)
+        sh = (None, slice(None), None, None)
+        xhat = ((_np64(y) - p[sh]) - ml[sh]) * invstd[sh]
+        res.append((k[sh] * ((gp - mg[sh]) - xhat * mx[sh]), gp, (a3 - ml * a2) * invstd, a2))
+    return res
 
 
 class MaxPoolFn(torch.autograd.Function):

@@ -25,6 +25,20 @@ no order.  ``grad_exchange_oracle`` is the rank-ordered statement the tests hold
 ranks; with three, one all_reduce cannot meet 2 * 2^-24 * sum_r |g_r / 3| against it (two orders of one three-term sum are each
 two roundings from the exact sum: up to 4 * 2^-24 * sum apart; measured over gloo, 0.47 % of 7.4 M elements beyond the former,
 none beyond the latter).  ``reduce="ordered"`` is the form that does meet it, at world times the traffic, on request only.
+
+``reduce="rank_ordered"`` meets it at the traffic of a ring all-reduce: a reduce-scatter whose additions this project owns,
+then an all-gather.  With slice = ceil(flat_elems / world / 4) * 4 (``rank_slice``) the buffer is world slices long (its tail
+past flat_elems is zero and stays zero), and a step is
+
+    pack        as above
+    scatter     all_to_all_single with equal splits: rank r receives slice r of every rank's buffer, parts [world, slice]
+    sum         one launch (csrc/k_optim.hip, rank_sum_kernel, K28): ((parts[0] + parts[1]) + parts[2]) + ... in fp32, in rank
+                order -- the oracle's sum, for any world
+    gather      all_gather_into_tensor of the summed slices back into the flat buffer
+    views       as above
+
+A rank receives 2 * (world - 1) * slice * 4 bytes (``GradExchange.bytes_received`` counts them), "ordered"
+(world - 1) * flat_elems * 4.
 """
 import math
 
@@ -49,6 +63,11 @@ def flat_layout(counts, live=None):
         else:
             offsets.append(-1)
     return np.array(offsets, dtype=np.int64), end
+
+
+def rank_slice(flat_elems, world):
+    """elements per rank of the rank-ordered exchange: the flat buffer cut into ``world`` equal slices of whole float4 groups"""
+    return (int(flat_elems) + 4 * int(world) - 1) // (4 * int(world)) * 4
 
 
 def grad_exchange_oracle(per_rank_grads, world):
@@ -135,11 +154,14 @@ def _dist():
 class _Layout:
     """the flat buffer of one bitmap: offsets, the buffer, a view of it per live tensor in the tensor's shape"""
 
-    def __init__(self, params, counts, live):
+    def __init__(self, params, counts, live, slices=1):
         self.offsets, self.flat_elems = flat_layout(counts, live)
         self.live = [i for i, l in enumerate(live) if l]
         ref = params[0]
-        self.flat = torch.zeros(max(self.flat_elems, 4), dtype=torch.float32, device=ref.device)
+        # (slices > 1, the rank-ordered exchange: `slices` whole slices; pack never writes the tail, which stays zero)
+        self.slice = rank_slice(self.flat_elems, slices)
+        self.flat = torch.zeros(max(self.flat_elems, 4, slices * self.slice), dtype=torch.float32, device=ref.device)
+        self.parts = None                # (rank-ordered exchange) what the scatter delivers, [slices * slice]
         self.views, self.pads = {}, []
         for i in self.live:
             o, n = int(self.offsets[i]), counts[i]
@@ -166,6 +188,11 @@ class GradExchange:
     SOME order, which can differ from the oracle by up to 4 * 2^-24 * sum_r |g_r / world| with three ranks (gloo's ring
     starts every chunk at another rank).  "ordered", only ever on request, gathers the ranks' buffers (all_gather: world times
     the traffic) and adds them in rank order, which IS the oracle, bit for bit, for any world: a yardstick, not a way to train.
+    "rank_ordered" is the oracle bit for bit as well, at a ring all-reduce's traffic (module docstring): all_to_all_single, the
+    rank-ordered sum of the received slices (th_rank_sum on the device back end, torch additions on the host one),
+    all_gather_into_tensor.  Over RCCL the device buffers are the collectives' own operands; over gloo, which is only the test
+    transport, device buffers are staged through host memory.  ``bytes_received`` counts what the gathers and scatters of
+    "ordered" and "rank_ordered" delivered to this rank from the others (the all_reduce's share is the collective's business).
 
     Liveness with DeviceAdam(zero_grad=True): a zeroed view stays ``p.grad``, so "has a gradient" stays true for a tensor
     that once had a slot, and the bitmap only grows.  A branch that stops taking part keeps its slot and is stepped on zero
@@ -196,7 +223,7 @@ class GradExchange:
         if backend not in (None, "device", "torch"):
             raise ValueError(f"GradExchange: backend = {backend!r}")
         self.backend = backend or ("device" if first.is_cuda else "torch")
-        if reduce not in (None, "collective", "ordered"):
+        if reduce not in (None, "collective", "ordered", "rank_ordered"):
             raise ValueError(f"GradExchange: reduce = {reduce!r}")
         self.reduce = reduce or "collective"
         for i, p in enumerate(self.params):
@@ -209,6 +236,7 @@ class GradExchange:
         self._world_t = torch.tensor(float(self.world), dtype=torch.float32, device=first.device)
         self.layout = None               # the layout of the last exchange
         self.exchanges = 0
+        self.bytes_received = 0
 
     # -- layouts -----------------------------------------------------------------------------------------------------
     def _bitmap(self):
@@ -222,7 +250,8 @@ class GradExchange:
         key = live.tobytes()
         lay = self._layouts.get(key)
         if lay is None:
-            lay = self._layouts[key] = _Layout(self.params, self.counts, live)
+            slices = self.world if self.reduce == "rank_ordered" and self.dist is not None else 1
+            lay = self._layouts[key] = _Layout(self.params, self.counts, live, slices)
         return lay
 
     # -- pack --------------------------------------------------------------------------------------------------------
@@ -249,6 +278,35 @@ class GradExchange:
                 torch.div(g, self._world_t, out=slot)          # (a tensor divisor: a true division, not a reciprocal's product)
         for a, b in lay.pads:
             lay.flat[a:b] = 0
+
+    # -- the rank-ordered reduce-scatter + all-gather ------------------------------------------------------------------
+    def _rank_ordered(self, lay):
+        dist, world, n = self.dist, self.world, lay.slice
+        full = lay.flat[:world * n]
+        if lay.parts is None:
+            lay.parts = torch.empty_like(full)
+        parts = lay.parts
+        # the sum lands on one of the parts: the rank's own on the device, rank 0's (only ever the first term) on the host
+        mine = parts[self.rank * n:(self.rank + 1) * n] if self.backend == "device" else parts[:n]
+        staged = full.is_cuda and dist.get_backend(self.group) == "gloo"
+        if staged:
+            host = torch.empty(world * n, dtype=torch.float32)
+            dist.all_to_all_single(host, full.cpu(), group=self.group)
+            parts.copy_(host)
+        else:
+            dist.all_to_all_single(parts, full, group=self.group)
+        if self.backend == "device":
+            from . import hip
+            hip.rank_sum(parts, world, n, mine)
+        else:
+            for r in range(1, world):                          # one fp32 addition per rank, in rank order
+                mine.add_(parts[r * n:(r + 1) * n])
+        if staged:
+            dist.all_gather_into_tensor(host, mine.cpu(), group=self.group)
+            full.copy_(host)
+        else:
+            dist.all_gather_into_tensor(full, mine, group=self.group)
+        self.bytes_received += 2 * (world - 1) * n * 4
 
     # -- the step ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -280,6 +338,9 @@ class GradExchange:
                 flat.copy_(parts[0])
                 for part in parts[1:]:
                     flat.add_(part)                            # one fp32 addition per rank, in rank order
+                self.bytes_received += (self.world - 1) * lay.flat_elems * 4
+            elif self.reduce == "rank_ordered" and self.world > 1:
+                self._rank_ordered(lay)
             else:
                 self.dist.all_reduce(flat, op=self.dist.ReduceOp.SUM, group=self.group)
         for i in lay.live:

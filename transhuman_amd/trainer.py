@@ -7,9 +7,11 @@ transhuman_amd.trainer`` sets one up from RANK / WORLD_SIZE / LOCAL_RANK) every 
 buffers, trains on its own batches, and the gradients are averaged between ``loss.backward()`` and the step by
 train_dist.GradExchange -- one pack launch, one all-reduce, DeviceAdam stepping out of the flat buffer -- in the place of the
 reference's DistributedDataParallel(find_unused_parameters=True) (lib/train/trainers/trainer.py:23-33).  The reference also
-converts every BatchNorm to SyncBatchNorm; ``sync_bn`` does the same (default: when distributed on a device), and the converted
-encoder trunk then runs under torch autograd whatever cfg.train_encoder says: the HIP backward of the trunk (K23) is that of
-rank-local batch statistics.  Without a group nothing differs from a single process.  The data loaders
+converts every BatchNorm to SyncBatchNorm; ``sync_bn`` does the same (default: when distributed on a device).  With
+cfg.train_encoder = "device" the converted encoder trunk runs under torch autograd unless cfg.train_sync_bn = "device", which
+keeps it on the HIP backward of the trunk (K23) with the ranks' statistics combined in rank order (train_ops.SyncBnActFn,
+DESIGN.md section 4).  ``reduce`` is GradExchange's: "rank_ordered" makes an N-rank step the rank-ordered oracle bit for bit.
+Without a group nothing differs from a single process.  The data loaders
 are out of scope; a ``data_loader`` is any sized iterable of batches (train_dist.DistributedSampler deals a data set to the
 ranks as the reference's sampler does).
 
@@ -108,11 +110,12 @@ class Trainer:
     step, so DeviceAdam's in-kernel clip clips the averaged gradient as :84-86 does.  Only rank 0 records and logs (:88-89).
     With DeviceAdam(zero_grad=True) a tensor that once had a gradient keeps its slot (train_dist.GradExchange, "Liveness").
     sync_bn: convert BatchNorm to SyncBatchNorm (:24-26); None: when distributed and on a device, as the reference.  A
-    converted encoder trunk runs under torch autograd whatever cfg.train_encoder says (autograd_path._trunk_sites_have_batch_statistics)."""
+    converted encoder trunk under cfg.train_encoder = "device" follows cfg.train_sync_bn (autograd_path.trunk_device).
+    reduce: passed to GradExchange (None: its default, one all_reduce)."""
 
     clip_value = 40.0                                          # trainer.py:85
 
-    def __init__(self, network, device=None, group=None, sync_bn=None):
+    def __init__(self, network, device=None, group=None, sync_bn=None, reduce=None):
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.device = torch.device(device)
@@ -129,7 +132,7 @@ class Trainer:
         self.rank = dist.get_rank(group)
         if sync_bn:
             self.network = torch.nn.SyncBatchNorm.convert_sync_batchnorm(self.network, process_group=group)
-        self.exchange = GradExchange([p for p in self.network.parameters() if p.requires_grad], group=group)
+        self.exchange = GradExchange([p for p in self.network.parameters() if p.requires_grad], group=group, reduce=reduce)
         self.exchange.broadcast_parameters(self.network, src=dist.get_global_rank(group, 0))
 
     @staticmethod
@@ -324,13 +327,14 @@ def load_model(net, optim, scheduler, recorder, model_dir, resume=True, epoch=-1
 # ---------------------------------------------------------------------------
 # the epoch loop
 # ---------------------------------------------------------------------------
-def fit(cfg, network, data_loader, log=print, group=None):
+def fit(cfg, network, data_loader, log=print, group=None, reduce=None):
     """train_net.py:31-87: ``network`` is a NetworkWrapper (its ``net`` holds the trained parameters, as in the reference,
     where the optimiser and the checkpoints are built on network.net), ``data_loader`` a sized iterable that yields at most
     cfg.ep_iter batches per pass (train_dist.iterations_per_rank of them on each rank of a job).  With a process group every
-    rank loads the checkpoint, only rank 0 writes one (:76-82) and logs, and the loader's sampler is told the epoch (:68-69)."""
+    rank loads the checkpoint, only rank 0 writes one (:76-82) and logs, and the loader's sampler is told the epoch (:68-69).
+    ``reduce`` is the Trainer's."""
     net = network.net if hasattr(network, "net") else network
-    trainer = Trainer(network, group=group)
+    trainer = Trainer(network, group=group, reduce=reduce)
     optimizer = make_optimizer(cfg, net)
     scheduler = make_lr_scheduler(cfg, optimizer)
     recorder = Recorder()
