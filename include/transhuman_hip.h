@@ -1150,6 +1150,25 @@ size_t th_conv2d_wgrad_workspace_bytes(int N, int cin, int cout, int ks, int str
 int th_conv2d_wgrad(th_ctx* ctx, const float* x, const float* g_y, int N, int cin, int cout, int ks, int stride, int H, int W,
                     float* g_w, void* workspace, size_t workspace_bytes, th_stream stream);
 
+/* ---- K29: the forward convolutions of the encoder trunk in training (additions, ABI 12) ---- */
+/* nn.Conv2d(cin, cout, ks, stride, ks / 2, bias=False), x [N, cin, H, W] -> y [N, cout, Ho, Wo], NCHW fp32 contiguous, Ho = (H + 2 (ks / 2)
+ * - ks) / stride + 1, for the trunk's five shapes: 7x7/2 3->64, 3x3/1 64->64, 3x3/2 64->128, 1x1/2 64->128, 3x3/1 128->128
+ * (th_conv2d_fwd32_supported: 1 for these, 0 otherwise).  An implicit GEMM on the fp32-input MFMA: no reduced-precision operand, no
+ * range guard (th_conv2d, the inference stem's fp16-split convolution, is another function and stays what it is).  w is torch's layout
+ * [cout][cin][ks][ks], read directly: nothing is packed or cached, there is no workspace.  A workgroup owns th_conv2d_fwd32_tile_rows x
+ * th_conv2d_fwd32_tile_cols output pixels x 64 output channels of one image.  The reduction is cut into chunks of
+ * th_conv2d_fwd32_chunk_channels input channels; a chunk is a fresh MFMA chain (taps kh outer, kw inner, channel pairs ascending; 7x7:
+ * one chain per kernel row, channels outer, tap pairs inner, the eighth tap a zero on both operands), the chains are added in order in
+ * fp64 and rounded to fp32 once.  No atomics; every output element is stored once and y is never read: two calls write identical
+ * bytes.  Refused with a negative status and th_last_error: another shape, a null pointer, N outside 1 .. 16383, H or W < 1, 2^31 or
+ * more elements in x or y.  DESIGN.md 4, K29. */
+int th_conv2d_fwd32_supported(int cin, int cout, int ks, int stride);                          /* pure host call */
+int th_conv2d_fwd32_tile_rows(void);
+int th_conv2d_fwd32_tile_cols(void);
+int th_conv2d_fwd32_chunk_channels(void);
+int th_conv2d_fwd32(th_ctx* ctx, const float* x, int N, int cin, int H, int W, const float* w, int cout, int ks, int stride,
+                    float* y, th_stream stream);
+
 /* ---- K26: the dataset's other targets -- sample_ray_h36m, both splits, and get_acc (additions, ABI 12) ---------------- */
 /* sample_ray_h36m (lib/utils/if_nerf/if_nerf_data_utils.py:516-614) and get_acc (:635-641), which the reference's dataset runs in
  * numpy for every test / evaluation batch and for the training batch without patch sampling (can_smpl.py:518-535), on the dense

@@ -9,8 +9,10 @@ gradient on both row tensors standing in for the rest of the network.
   "full"     autograd_path.encode (upsample, concatenate, 1 x 1 reduction: the two full-size maps) + sample_map twice
   "latents"  autograd_path.latent_features (K19, train_ops.LatentGatherFn on the three latents) + the reduction on the rows
 --encoder torch,device repeats every mode with cfg.train_encoder's "device" form of the trunk (K23: autograd_path.trunk_device, the
-same forward, HIP backwards; keys gain '+encoder'); --gather-bwd atomic,ordered repeats the "latents" modes with cfg.train_gather_bwd's
-"ordered" form of K19's backward (k_latgather_ord.hip: no float atomic; keys gain '+ordered', before '+encoder'); --maps picks the
+same forward, HIP backwards; keys gain '+encoder'); --encoder-fwd torch,device repeats the '+encoder' modes with cfg.train_encoder_fwd's
+"device" form of the trunk's forward (K29: th_conv2d_fwd32, th_bn_act, th_maxpool3x3s2; keys gain '+fwd', and the "torch" value --
+MIOpen's forward -- is the yardstick in the same process); --gather-bwd atomic,ordered repeats the "latents" modes with
+cfg.train_gather_bwd's "ordered" form of K19's backward (k_latgather_ord.hip: no float atomic; keys gain '+ordered', before '+encoder'); --maps picks the
 modes.  --rocprof DIR first runs a fresh child process under
 `rocprofv3 --kernel-trace` (last --maps value, last --encoder value) and reports, per step, the number of kernel launches of the
 stage and the device time of its ten slowest kernel names (DIR keeps the trace).
@@ -60,11 +62,17 @@ def setup(dev, size):
 
 
 def step(mode, enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix):
-    from transhuman_amd.networks import autograd_path as A
+    from transhuman_amd.config import override
     parts = mode.split("+")
     maps, encoder, gather_bwd = parts[0], "device" if "encoder" in parts else "torch", "ordered" if "ordered" in parts else "atomic"
     enc.zero_grad(set_to_none=True)
     image_shape = images.shape[-2:]
+    with override(train_encoder_fwd="device" if "fwd" in parts else "torch"):
+        return _step(maps, encoder, gather_bwd, image_shape, enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix)
+
+
+def _step(maps, encoder, gather_bwd, image_shape, enc, images, verts, xyz, rtk, cams, scale, g_paint, g_pix):
+    from transhuman_amd.networks import autograd_path as A
     if maps == "latents":
         gather = A.latent_features(enc, images, cams, scale, encoder=encoder, gather_bwd=gather_bwd)
         painted, f = A._lin(enc.reduction_layer, gather(verts)).permute(1, 0, 2), gather(xyz)
@@ -124,7 +132,7 @@ def kernel_times(enc, images, xyz, cams, scale, g_pix, reps=20, ordered=False):
     return res
 
 
-MARKER = "maxpool3x3s2_kernel"      # the inference path's pooling kernel: no training stage launches it
+MARKER = "rank_sum_kernel"          # the gradient exchange's kernel (K28): no stage of a single-process step launches it
 
 
 def traced_child(mode, size, steps):
@@ -133,12 +141,12 @@ def traced_child(mode, size, steps):
     from transhuman_amd import hip
     dev = torch.device("cuda:0")
     a = setup(dev, size)
-    mark = torch.zeros((1, 1, 2, 2), device=dev)
+    mark = torch.zeros(4, device=dev)
     step(mode, *a)
     for _ in range(steps):
-        hip.maxpool3x3s2(mark)
+        hip.rank_sum(mark, 1, 4, mark)
         step(mode, *a)
-    hip.maxpool3x3s2(mark)
+    hip.rank_sum(mark, 1, 4, mark)
     torch.cuda.synchronize()
 
 
@@ -175,14 +183,16 @@ def main():
     ap.add_argument("--maps", default="full,latents", help="comma list of cfg.train_maps values")
     ap.add_argument("--encoder", default="torch", help="comma list of cfg.train_encoder values (results of 'device' are keyed "
                                                        "'<maps>+encoder')")
+    ap.add_argument("--encoder-fwd", default="torch", help="comma list of cfg.train_encoder_fwd values, for the '+encoder' modes "
+                                                           "(results of 'device' are keyed '<maps>...+encoder+fwd')")
     ap.add_argument("--gather-bwd", default="atomic", help="comma list of cfg.train_gather_bwd values, for the 'latents' modes "
                                                            "(results of 'ordered' are keyed '<maps>+ordered')")
     ap.add_argument("--rocprof", default=None, metavar="DIR", help="also trace a short run of the last mode under rocprofv3 into DIR")
     ap.add_argument("--traced-child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
-    modes = tuple(m + ("" if g == "atomic" else "+ordered") + ("" if e == "torch" else "+encoder")
+    modes = tuple(m + ("" if g == "atomic" else "+ordered") + ("" if e == "torch" else "+encoder") + ("" if f == "torch" else "+fwd")
                   for m in args.maps.split(",") for g in (args.gather_bwd.split(",") if m == "latents" else ["atomic"])
-                  for e in args.encoder.split(","))
+                  for e in args.encoder.split(",") for f in (args.encoder_fwd.split(",") if e == "device" else ["torch"]))
     if args.traced_child:
         return traced_child(args.traced_child, args.size, 3)
     traced = None
@@ -238,6 +248,10 @@ def main():
         if m.endswith("+encoder") and m[:-8] in grads:
             assert set(grads[m]) == set(grads[m[:-8]])
             res[m + "_vs_torch_encoder"] = {"grads_max_rel_to_own_max": rel(m[:-8], m)}
+    for m in modes:
+        if m.endswith("+fwd") and m[:-4] in grads:
+            assert set(grads[m]) == set(grads[m[:-4]])
+            res[m + "_vs_torch_forward"] = {"grads_max_rel_to_own_max": rel(m[:-4], m)}
     for m in modes:
         q = m.replace("+ordered", "")
         if q != m and q in grads:

@@ -8,7 +8,8 @@ the HIP adjoints of K17, transhuman_amd/networks/train_ops.py).
 --maps full,latents repeats every mode with cfg.train_maps = "latents" (K19: the encoder's latents sampled directly) in the same
 process; --point-net torch,device does the same with cfg.train_point_net = "device" (K20: the per-point network layer by layer
 on the device; keys gain '+pointnet'); --encoder torch,device with cfg.train_encoder = "device" (K23: the encoder trunk's backward as
-HIP kernels; keys gain '+encoder'); --gather-bwd atomic,ordered with cfg.train_gather_bwd = "ordered" for the "latents" runs (K19's
+HIP kernels; keys gain '+encoder'); --encoder-fwd torch,device with cfg.train_encoder_fwd = "device" for the runs with the encoder on
+the device (K29: the trunk's forward as HIP kernels too; keys gain '+fwd' after '+encoder'); --gather-bwd atomic,ordered with cfg.train_gather_bwd = "ordered" for the "latents" runs (K19's
 backward without float atomics, k_latgather_ord.hip; keys gain '+ordered' after '+latents'); --rounds N repeats the whole sweep N
 times in alternating order, so the forms are timed in turn in one process (per key then: the median of the rounds' medians with
 the lowest and the highest); --attention / --vit-dense set cfg.train_attention / cfg.train_vit_dense for the whole run.
@@ -150,6 +151,9 @@ def main():
                                                          "(results of 'device' are keyed '<mode>[+<maps>]+pointnet')")
     ap.add_argument("--encoder", default="torch", help="comma list of cfg.train_encoder values; every mode runs once per value "
                                                        "(results of 'device' are keyed '<mode>[+<maps>][+pointnet]+encoder')")
+    ap.add_argument("--encoder-fwd", default="torch", help="comma list of cfg.train_encoder_fwd values; every run with the encoder on "
+                                                           "the device runs once per value (results of 'device' are keyed "
+                                                           "'...+encoder+fwd')")
     ap.add_argument("--gather-bwd", default="atomic", help="comma list of cfg.train_gather_bwd values; every 'latents' mode runs once "
                                                            "per value (results of 'ordered' are keyed '<mode>+latents+ordered...')")
     ap.add_argument("--rounds", type=int, default=1, help="repeat the sweep this many times, in alternating order")
@@ -183,11 +187,13 @@ def main():
             for gather_bwd in (args.gather_bwd.split(",") if maps == "latents" else ["atomic"]):
                 for point_net in args.point_net.split(","):
                     for encoder in args.encoder.split(","):
-                        for mode in args.modes.split(","):
-                            key = (mode if maps == "full" else f"{mode}+{maps}") + ("" if gather_bwd == "atomic" else "+ordered") + \
-                                ("" if point_net == "torch" else "+pointnet") + ("" if encoder == "torch" else "+encoder")
-                            sweep.append((key, dict(train_kernels=mode, train_maps=maps, train_gather_bwd=gather_bwd,
-                                                    train_point_net=point_net, train_encoder=encoder)))
+                        for fwd in (args.encoder_fwd.split(",") if encoder == "device" else ["torch"]):
+                            for mode in args.modes.split(","):
+                                key = (mode if maps == "full" else f"{mode}+{maps}") + ("" if gather_bwd == "atomic" else "+ordered") + \
+                                    ("" if point_net == "torch" else "+pointnet") + ("" if encoder == "torch" else "+encoder") + \
+                                    ("" if fwd == "torch" else "+fwd")
+                                sweep.append((key, dict(train_kernels=mode, train_maps=maps, train_gather_bwd=gather_bwd,
+                                                        train_point_net=point_net, train_encoder=encoder, train_encoder_fwd=fwd)))
         rounds = {}
         for rnd in range(max(args.rounds, 1)):
             for key, switches in (sweep if rnd % 2 == 0 else sweep[::-1]):
@@ -216,6 +222,12 @@ def main():
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
             "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0
                                             if not k.endswith("spatial_key_value_0.key_embed.bias"))}
+    for key in [k for k in seen if k.endswith("+fwd") and k[:-4] in seen]:
+        (o0, g0), (o1, g1) = seen[key[:-4]], seen[key]
+        res[key + "_vs_torch_forward"] = {
+            "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
+            "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0
+                                            if not k.endswith("spatial_key_value_0.key_embed.bias"))}
     for key in [k for k in seen if k.endswith("+pointnet") and k[:-9] in seen]:
         (o0, g0), (o1, g1) = seen[key[:-9]], seen[key]
         res[key + "_vs_torch_point_net"] = {
@@ -227,7 +239,7 @@ def main():
         res[key + "_vs_atomic"] = {
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),
             "grads_max_rel_to_own_max": max(float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-30) for k in g0)}
-    for key in [k for k in seen if "+" in k and not k.endswith(("+pointnet", "+encoder", "+ordered")) and k.split("+")[0] in seen]:
+    for key in [k for k in seen if "+" in k and not k.endswith(("+pointnet", "+encoder", "+ordered", "+fwd")) and k.split("+")[0] in seen]:
         (o0, g0), (o1, g1) = seen[key.split("+")[0]], seen[key]
         res[key + "_vs_full"] = {
             "outputs_max_abs": max(float((o0[k] - o1[k]).abs().max()) for k in o0),

@@ -28,6 +28,10 @@ TRAIN_SWITCHES = {
 
 TRAIN_SYNC_BN = ("torch", "device")
 
+# cfg.train_encoder_fwd: the forward of the trunk's sites under train_encoder = "device".  Not a row of TRAIN_SWITCHES either: it
+# selects nothing unless that switch is on its device value (autograd_path.encoder_fwd_mode is its reader)
+TRAIN_ENCODER_FWD = ("torch", "device")
+
 
 def _defaults():
     return SimpleNamespace(
@@ -126,6 +130,12 @@ def _defaults():
         # all_gather of a [C, 6] float64 record per site and the ranks' sums combined in rank order (train_ops.SyncBnActFn).
         # Not one of TRAIN_SWITCHES: it selects nothing in a single process
         train_sync_bn="torch",
+        # read only with train_encoder = "device": the FORWARD of the trunk's sites.  "torch" calls the stock torch operators
+        # (MIOpen's convolutions, torch's batch norm and pool); "device" runs th_conv2d_fwd32 (K29: exact fp32 on the MFMA,
+        # fixed-order sums), th_bn_act (K11; running statistics and num_batches_tracked updated as the module does) and
+        # th_maxpool3x3s2 -- no vendor-library kernel is left in the trunk.  A SyncBatchNorm site keeps the module call for its
+        # BatchNorm (the statistics span ranks); the convolutions around it follow this key.  Not one of TRAIN_SWITCHES
+        train_encoder_fwd="torch",
         # patch sampling of the training targets (train_or_eval.yaml:70-75)
         patch=SimpleNamespace(use_patch_sampling=True, sample_subject_ratio=0.8, N_patches=6, size=20),
         # where the training entry's rays and patch targets come from: "batch" (as the reference: its dataset samples them on the

@@ -1884,6 +1884,26 @@ int th_conv2d_wgrad(th_ctx* c, const float* x, const float* g_y, int N, int cin,
     return th_conv2d_wgrad_launch(x, g_y, N, cin, cout, ks, stride, H, W, g_w, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- K29: the forward convolutions of the encoder trunk in training (k_encoder_fwd.hip) ----
+int th_conv2d_fwd32_supported(int cin, int cout, int ks, int stride) { return th_conv2d_fwd32_supported_internal(cin, cout, ks, stride); }
+int th_conv2d_fwd32_tile_rows(void) {
+    int r, c;
+    th_conv2d_fwd32_tile_internal(&r, &c);
+    return r;
+}
+int th_conv2d_fwd32_tile_cols(void) {
+    int r, c;
+    th_conv2d_fwd32_tile_internal(&r, &c);
+    return c;
+}
+int th_conv2d_fwd32_chunk_channels(void) { return th_conv2d_fwd32_chunk_internal(); }
+
+int th_conv2d_fwd32(th_ctx* c, const float* x, int N, int cin, int H, int W, const float* w, int cout, int ks, int stride, float* y,
+                    th_stream stream) {
+    TH_REQUIRE(c && x && w && y, "null argument");
+    return th_conv2d_fwd32_launch(x, N, cin, H, W, w, cout, ks, stride, y, (hipStream_t)stream);
+}
+
 // ---- the gradient exchange's flat buffer (k_optim.hip) ----
 long long th_adam_flat_layout(int n_tensors, const long long* counts, const uint8_t* live, long long* offsets_out) {
     if (n_tensors < 1 || n_tensors > (1 << 20) || !counts) return -1;

@@ -615,6 +615,12 @@ int th_conv2d_dgrad_launch(const float* gy, int N, int cin, int cout, int ks, in
 size_t th_conv2d_wgrad_ws(int N, int cin, int cout, int ks, int stride, int H, int W);
 int th_conv2d_wgrad_launch(const float* x, const float* gy, int N, int cin, int cout, int ks, int stride, int H, int W, float* gw,
                            void* ws, size_t ws_bytes, hipStream_t s);
+// k_encoder_fwd.hip (K29): the forward convolutions of the encoder trunk in training, exact fp32 on the fp32-input MFMA
+int th_conv2d_fwd32_supported_internal(int cin, int cout, int ks, int stride);
+void th_conv2d_fwd32_tile_internal(int* rows, int* cols);
+int th_conv2d_fwd32_chunk_internal();
+int th_conv2d_fwd32_launch(const float* x, int N, int cin, int H, int W, const float* w, int cout, int ks, int stride, float* y,
+                           hipStream_t s);
 // k_raster.hip: z-buffer rasteriser of a triangle mesh into V views, and the two vertex-visibility rules on top of it
 size_t th_raster_ws(int V, int nv, int nf, int H, int W);
 int th_raster_launch(const float* verts, int nv, const int32_t* faces, int nf, const float* cams, int V, int H, int W,

@@ -1103,6 +1103,41 @@ def maxpool3x3s2_bwd(x, g):
 
 
 # ---------------------------------------------------------------------------
+# K29: the forward convolutions of the encoder trunk in training (k_encoder_fwd.hip); NCHW fp32
+# ---------------------------------------------------------------------------
+def conv2d_fwd32_supported(cin, cout, ks, stride):
+    """th_conv2d_fwd32_supported: True for the five convolutions of the trunk conv2d_fwd32 is built for"""
+    return bool(load_library().th_conv2d_fwd32_supported(int(cin), int(cout), int(ks), int(stride)))
+
+
+def conv2d_fwd32_tile():
+    """(rows, columns) of output pixels that a workgroup of conv2d_fwd32 owns"""
+    lib = load_library()
+    return int(lib.th_conv2d_fwd32_tile_rows()), int(lib.th_conv2d_fwd32_tile_cols())
+
+
+def conv2d_fwd32_chunk_channels():
+    return int(load_library().th_conv2d_fwd32_chunk_channels())
+
+
+def conv2d_fwd32(x, weight, stride):
+    """th_conv2d_fwd32: nn.Conv2d(cin, cout, ks, stride, ks // 2, bias=False) on x [N,cin,H,W] with torch's weight
+    [cout,cin,ks,ks] -> y [N,cout,Ho,Wo], exact fp32 operands on the MFMA, fixed-order sums.  Bit-identical from run to run."""
+    lib = load_library()
+    x2 = _nchw("conv2d_fwd32", "x", x)
+    w, cin, cout, ks = _conv_weight("conv2d_fwd32", weight)
+    if x2.shape[1] != cin or w.device != x2.device:
+        raise ValueError(f"conv2d_fwd32: 'x' has {x2.shape[1]} channels on {x2.device}, the weight takes {cin} on {w.device}")
+    N, _, H, W = (int(n) for n in x2.shape)
+    st = int(stride)
+    if not lib.th_conv2d_fwd32_supported(cin, cout, ks, st):
+        raise HipError(f"conv2d_fwd32: no HIP forward is built for a {ks}x{ks}/{st} convolution {cin}->{cout}")
+    y = torch.empty((N, cout, _conv_out(H, ks, st), _conv_out(W, ks, st)), dtype=torch.float32, device=x2.device)
+    _check(lib.th_conv2d_fwd32(ctx(x2.device), _p(x2), N, cin, H, W, _p(w), cout, ks, st, _p(y), _stream()))
+    return y
+
+
+# ---------------------------------------------------------------------------
 # K22: the optimiser step (th_adam_plan / th_adam_step)
 # ---------------------------------------------------------------------------
 ADAM_CLIP, ADAM_ZERO_GRAD, ADAM_COUNT_NONFINITE, ADAM_CHECK_POINTERS, ADAM_T_DECOUPLED = (

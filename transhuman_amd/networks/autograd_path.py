@@ -38,7 +38,10 @@ gradient is bit-identical from run to run.  The residual adds and the positional
 (default) is ``SpatialEncoder.trunk(fused_bn=False)`` under torch autograd; "device" is ``trunk_device``: the same torch
 operators in the forward, site by site without a graph -- latents, running statistics and num_batches_tracked are the "torch"
 mode's bit for bit --, and HIP backwards with fixed-order sums (``train_ops.ConvFn`` / ``BnActFn`` / ``MaxPoolFn``, DESIGN.md
-K23).  The upsamples, ``upsample_color`` and ``reduction_layer`` stay what ``cfg.train_maps`` makes them.  A trunk converted to
+K23).  ``cfg.train_encoder_fwd`` = "device" (default "torch"; read only under ``cfg.train_encoder`` = "device"; its own check,
+``encoder_fwd_mode``) replaces those torch operators by HIP forwards: ``hip.conv2d_fwd32`` (K29: exact fp32 operands on the MFMA,
+fixed-order sums), ``hip.bn_act`` (K11) and ``hip.maxpool3x3s2``; the backwards are the same.
+The upsamples, ``upsample_color`` and ``reduction_layer`` stay what ``cfg.train_maps`` makes them.  A trunk converted to
 SyncBatchNorm (data-parallel training) runs under torch autograd as a whole under "device" too, unless ``cfg.train_sync_bn`` =
 "device" (default "torch"; its own check, ``_sync_bn_mode``: the key is not in the table below), which runs the converted sites
 on ``train_ops.SyncBnActFn``: the BatchNorm backward split around one all_gather of a [C, 6] float64 record per site.
@@ -60,7 +63,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from ..config import TRAIN_SWITCHES, TRAIN_SYNC_BN, get_cfg
+from ..config import TRAIN_ENCODER_FWD, TRAIN_SWITCHES, TRAIN_SYNC_BN, get_cfg
 from ..truncation import sigma_in_force
 
 
@@ -84,6 +87,18 @@ def _sync_bn_mode(value):
     mode = str(value)
     if mode not in TRAIN_SYNC_BN:
         raise ValueError(f"cfg.train_sync_bn must be {TRAIN_SYNC_BN[0]!r} or {TRAIN_SYNC_BN[1]!r}, not {mode!r}")
+    return mode
+
+
+def encoder_fwd_mode(value=None):
+    """cfg.train_encoder_fwd, which is not one of TRAIN_SWITCHES (it selects nothing unless cfg.train_encoder = "device"): one of
+    config.TRAIN_ENCODER_FWD.  Without an argument the live cfg's value, the default where the key is absent.  Read by
+    ``trunk_device`` and by the trunk's Functions of train_ops in their forward, nowhere else."""
+    if value is None:
+        value = getattr(get_cfg(), "train_encoder_fwd", TRAIN_ENCODER_FWD[0])
+    mode = str(value)
+    if mode not in TRAIN_ENCODER_FWD:
+        raise ValueError(f"cfg.train_encoder_fwd must be {TRAIN_ENCODER_FWD[0]!r} or {TRAIN_ENCODER_FWD[1]!r}, not {mode!r}")
     return mode
 
 
@@ -127,7 +142,8 @@ def _trunk_sync_sites(enc):
 
 def trunk_device(enc, images):
     """SpatialEncoder.trunk(images, fused_bn=False) (encoder.walk_trunk) on the per-site Functions of train_ops: the same torch
-    operators in the forward, called without recording a graph, and k_encoder_bwd.hip in the backward (K23).  A trunk whose
+    operators in the forward, called without recording a graph -- or, under cfg.train_encoder_fwd = "device", k_encoder_fwd.hip
+    (K29), th_bn_act and th_maxpool3x3s2 --, and k_encoder_bwd.hip in the backward (K23).  A trunk whose
     BatchNorm sites do not all use batch statistics runs under torch autograd as a whole; so does one with SyncBatchNorm sites,
     unless cfg.train_sync_bn = "device" (read only then), which runs them on train_ops.SyncBnActFn."""
     from .. import hip
@@ -137,6 +153,7 @@ def trunk_device(enc, images):
     if not _trunk_sites_have_batch_statistics(enc):
         if not (_trunk_sync_sites(enc) and _sync_bn_mode(getattr(get_cfg(), "train_sync_bn", TRAIN_SYNC_BN[0])) == "device"):
             return enc.trunk(images, fused_bn=False)
+    encoder_fwd_mode()                                       # (a bad value raises here, before the first site)
 
     def conv_bn(conv, bn, t, residual=None, relu=True):
         if conv.bias is not None:

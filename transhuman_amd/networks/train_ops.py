@@ -43,7 +43,9 @@ The loss the trainer back-propagates through (lib/train/trainers/if_nerf_clight.
 
 ``cfg.train_encoder = "device"`` does it for the encoder trunk (SpatialEncoder.trunk, encoder.py:114-126): the forward of every
 site is the stock torch operator, called without recording a graph, so the latents and the BatchNorm statistics are those of
-the "torch" mode bit for bit; the backward is k_encoder_bwd.hip (composed by ``autograd_path.trunk_device``):
+the "torch" mode bit for bit; the backward is k_encoder_bwd.hip (composed by ``autograd_path.trunk_device``).
+``cfg.train_encoder_fwd = "device"`` (read only then) makes the forwards HIP as well: th_conv2d_fwd32 (k_encoder_fwd.hip, K29),
+th_bn_act and th_maxpool3x3s2; a SyncBatchNorm site keeps the module call for its BatchNorm:
 
     ConvFn                  x, W, stride         -> conv2d(x, W)       keeps x, W       gradient: x (not conv1's images), W
     BnActFn                 y, bn, residual, relu, gamma, beta -> relu(bn(y) + residual)   keeps y, the output (with a ReLU), gamma
@@ -316,6 +318,12 @@ class CrossViewAttentionFn(torch.autograd.Function):
         return hip.xview_attention_bwd(kvp, kvs, grad_out.contiguous())
 
 
+def _encoder_fwd():
+    """cfg.train_encoder_fwd through its checked reader: "torch" (the stock operators) or "device" (HIP forwards)"""
+    from .autograd_path import encoder_fwd_mode
+    return encoder_fwd_mode()
+
+
 def _trunk_input(fn, name, t):
     _on_device(fn, t)
     if t.dtype is not torch.float32 or t.dim() != 4:
@@ -324,7 +332,7 @@ def _trunk_input(fn, name, t):
 
 class ConvFn(torch.autograd.Function):
     """nn.Conv2d(cin, cout, ks, stride, ks // 2, bias=False) of the encoder trunk.  Forward: torch's own convolution (the call the
-    module makes).  Backward: th_conv2d_dgrad / th_conv2d_wgrad (fp32-input MFMA, fixed-order sums).  conv1 (7x7/2 on the images)
+    module makes), or th_conv2d_fwd32 (K29) under cfg.train_encoder_fwd = "device".  Backward: th_conv2d_dgrad / th_conv2d_wgrad (fp32-input MFMA, fixed-order sums).  conv1 (7x7/2 on the images)
     has no input gradient: images that require one raise."""
 
     @staticmethod
@@ -339,6 +347,8 @@ class ConvFn(torch.autograd.Function):
                              "gradient here (the images come from the batch)")
         ctx.stride = int(stride)
         ctx.save_for_backward(x, weight)
+        if _encoder_fwd() == "device":
+            return hip.conv2d_fwd32(x.detach().contiguous(), weight.detach().contiguous(), int(stride))
         return torch.nn.functional.conv2d(x.detach(), weight.detach(), None, int(stride), ks // 2)
 
     @staticmethod
@@ -357,7 +367,8 @@ class ConvFn(torch.autograd.Function):
 class BnActFn(torch.autograd.Function):
     """The tail of a ``conv -> bn [-> += identity] [-> relu]`` site: relu(bn(y) + residual) with `bn` a train-mode
     nn.BatchNorm2d.  Forward: the stock module call (it updates the running statistics and num_batches_tracked as always), torch's
-    add and ReLU.  Backward: th_bn_act_bwd from y, the output (the gate) and gamma.  ``gamma`` / ``beta`` are bn.weight / bn.bias
+    add and ReLU; under cfg.train_encoder_fwd = "device" th_bn_act (K11: float64 statistics, the running statistics updated with the
+    module's momentum) and num_batches_tracked incremented here.  Backward: th_bn_act_bwd from y, the output (the gate) and gamma.  ``gamma`` / ``beta`` are bn.weight / bn.bias
     (None without affine), passed so that autograd sees them."""
 
     @staticmethod
@@ -365,11 +376,17 @@ class BnActFn(torch.autograd.Function):
         _trunk_input("BnActFn", "y", y)
         if not (isinstance(bn, torch.nn.BatchNorm2d) and bn.training and bn.momentum is not None):
             raise ValueError("BnActFn: the backward is defined for a train-mode nn.BatchNorm2d with a momentum (batch statistics)")
-        out = bn(y.detach())
-        if residual is not None:
-            out = out + residual.detach()
-        if relu:
-            out = torch.relu_(out)
+        if _encoder_fwd() == "device":
+            # th_bn_act writes a buffer of its own (y is kept for the backward) and updates running_mean / running_var
+            out = hip.bn_act(y.detach().contiguous(), bn, None if residual is None else residual.detach(), bool(relu))
+            if bn.track_running_stats and bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+        else:
+            out = bn(y.detach())
+            if residual is not None:
+                out = out + residual.detach()
+            if relu:
+                out = torch.relu_(out)
         ctx.relu, ctx.eps, ctx.has_res = bool(relu), float(bn.eps), residual is not None
         ctx.save_for_backward(y, out if relu else None, gamma)
         return out
@@ -480,13 +497,15 @@ def sync_bn_act_bwd_oracle(ys, outs, gs, gamma, eps):
 
 
 class MaxPoolFn(torch.autograd.Function):
-    """nn.MaxPool2d(3, 2, 1).  Forward: torch's.  Backward: th_maxpool3x3s2_bwd, which finds the element torch recorded again from
+    """nn.MaxPool2d(3, 2, 1).  Forward: torch's, or th_maxpool3x3s2 under cfg.train_encoder_fwd = "device".  Backward: th_maxpool3x3s2_bwd, which finds the element torch recorded again from
     the input (nothing but the input is kept)."""
 
     @staticmethod
     def forward(ctx, x):
         _trunk_input("MaxPoolFn", "x", x)
         ctx.save_for_backward(x)
+        if _encoder_fwd() == "device":
+            return hip.maxpool3x3s2(x.detach().contiguous())
         return torch.nn.functional.max_pool2d(x.detach(), 3, 2, 1)
 
     @staticmethod
