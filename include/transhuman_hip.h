@@ -1233,6 +1233,18 @@ int th_truncate_scatter(th_ctx* ctx, const float* rows_kept, const uint8_t* mask
 int th_truncate_scatter_bwd(th_ctx* ctx, const float* g_rows, const int32_t* sel, int n_kept, int P, int C, float* g_rows_kept,
                             th_stream stream);
 
+/* ---- DPaRF's hyper-parameters: cfg.KNN, cfg.KNN_FREQ, cfg.KNN_DIST_ALPHA (addition, ABI 12) ---------------------------- */
+/* th_set_dparf: the number of neighbouring tokens (cross_transformer.py:170), the octave count of the local positional
+ * encoding (:106) and the softmax temperature of the distances (:154) of EVERY entry of this context that runs K4 or its
+ * backward: th_dparf_encode, th_dparf_encode_bwd, th_network_forward, th_render_rays, th_render_pregather, th_eval_sigma_grid,
+ * th_eval_points.  A new context has (7, 10, 0.5).  knn 1..7 (a neighbour record holds seven (index, weight) pairs), n_freq
+ * 1..10 (3 + 6 n_freq <= 63 PE channels inside fc_0's 256 padded columns; 0 octaves are not supported), alpha finite
+ * and > 0, rounded to fp32 once; anything else is an error that names the values.  Fewer than knn token centres is an error of
+ * the entry that runs K4.  w = softmax((-sqrt(d2)) / alpha), a true fp32 division.  Columns 195 + 6 n_freq .. 255 of an fp32
+ * row are exact zero.  th_set_mlp_weights takes fc_0 of 256 x (195 + 6 n_freq) of the n_freq in force; changing n_freq
+ * invalidates the uploaded MLP weights (upload again).  Workspace sizes do not depend on these values. */
+int th_set_dparf(th_ctx* ctx, int knn, int n_freq, double alpha);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@
 // fp32 [sample][view][256] (64 lanes x float4: every lane busy), and pe_out = the blended 63-wide positional
 // encoding, ONE split-f16 row (64 hi + 64 lo halves) per sample -- it is the same for every view.
 // Bound: L2 gather of 7*V*768 B per sample; HBM write 3 KB per sample.
+// The numbers above are the defaults of cfg.KNN (7), cfg.KNN_FREQ (10 octaves: 63 PE channels) and cfg.KNN_DIST_ALPHA (0.5);
+// th_set_dparf hands in others -- K 1..7 as a template parameter, 3 + 6 F live PE channels and alpha as arguments (dparf_kernel).
 #include "th_internal.h"
 #include "k_dparf_near.h"
 
@@ -34,9 +36,10 @@ struct DpNbr {
 };
 
 // insert (cd, ci) into the ascending list; on equal distance the smaller index stays first
-__device__ __forceinline__ void dp_insert(float (&bd)[DP_K], int (&bi)[DP_K], float cd, int ci) {
+template <int K>
+__device__ __forceinline__ void dp_insert(float (&bd)[K], int (&bi)[K], float cd, int ci) {
 #pragma unroll
-    for (int k = 0; k < DP_K; ++k) {
+    for (int k = 0; k < K; ++k) {
         bool sw = (cd < bd[k]) || (cd == bd[k] && ci < bi[k]);
         float td = sw ? bd[k] : cd;
         int ti = sw ? bi[k] : ci;
@@ -201,7 +204,12 @@ int th_dparf_grid_build(const float* centres, int nc, void* ws, size_t ws_bytes,
     return 0;
 }
 
-template <bool FOLDED, int VT = 0>
+// K = cfg.KNN (1..7): the length of the register lists, of the pair merge, of the softmax and of every blend chain.  The LDS
+// record (DpNbr) and the 16-word hand-over records keep their seven pairs; a record's unused pairs are idx = 0xffffffff,
+// w = +0.0 (word 7 with them), which the fused kernels' slot test and K17's `c < 0` drop as they stand.
+// DEF = true: cfg.KNN_FREQ = 10, all 63 PE channels live (a literal); DEF = false: channel c is live for c < npe_rt =
+// 3 + 6 cfg.KNN_FREQ, every other channel of the 64-wide PE row (column 192 + c of an fp32 row) is exact zero.
+template <bool FOLDED, int VT = 0, int K = DP_K, bool DEF = true>
 __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restrict__ pts_smpl, ThPointSrc ps,
                                                            const float* __restrict__ Rh, const float* __restrict__ Th,
                                                            const int32_t* __restrict__ sel, int P,
@@ -211,8 +219,10 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
                                                            float alpha, float* __restrict__ out,
                                                            float* __restrict__ pe_out, const DpGrid* __restrict__ gi,
                                                            const int* __restrict__ cell_count,
-                                                           const int* __restrict__ cand) {
+                                                           const int* __restrict__ cand, int npe_rt) {
+    static_assert(K >= 1 && K <= DP_K, "a record holds seven (index, weight) pairs");
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int npe = DEF ? 63 : npe_rt;                  // live PE channels
     float* cen = lds;                                   // [nc*3]
     DpNbr* nb = reinterpret_cast<DpNbr*>(lds + ((nc * 3 + 3) & ~3));
     // TH_ROWS_NBR: per 32-sample tile of the fused kernel (4 per workgroup) a bitmap over the centre indices and the slot
@@ -242,10 +252,10 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
             y = fmaf(az, Rh[7], fmaf(ay, Rh[4], ax * Rh[1]));
             z = fmaf(az, Rh[8], fmaf(ay, Rh[5], ax * Rh[2]));
         }
-        float bd[DP_K];
-        int bi[DP_K];
+        float bd[K];
+        int bi[K];
 #pragma unroll
-        for (int k = 0; k < DP_K; ++k) { bd[k] = 3.0e38f; bi[k] = 0x7fffffff; }
+        for (int k = 0; k < K; ++k) { bd[k] = 3.0e38f; bi[k] = 0x7fffffff; }
         // candidate list of this point's grid cell (exact superset of its 7 nearest centres), else all centres
         const int* list = nullptr;
         int nlist = nc;
@@ -264,30 +274,30 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
         for (int j = half; j < nlist; j += 2) {
             const int c = list ? list[j] : j;
             const float d2 = dp_dist2(x, y, z, cen[3 * c], cen[3 * c + 1], cen[3 * c + 2]);   // (k_dparf_near.h: K27 tests the same value)
-            if (d2 < bd[DP_K - 1]) dp_insert(bd, bi, d2, c);   // ascending c: a tie never displaces an earlier index
+            if (d2 < bd[K - 1]) dp_insert(bd, bi, d2, c);   // ascending c: a tie never displaces an earlier index
         }
         // merge the partner's list (7 candidates) -> global top-7 ordered by (d2, index)
-        float od[DP_K];
-        int oi[DP_K];
+        float od[K];
+        int oi[K];
 #pragma unroll
-        for (int k = 0; k < DP_K; ++k) { od[k] = __shfl_xor(bd[k], 1); oi[k] = __shfl_xor(bi[k], 1); }
+        for (int k = 0; k < K; ++k) { od[k] = __shfl_xor(bd[k], 1); oi[k] = __shfl_xor(bi[k], 1); }
 #pragma unroll
-        for (int k = 0; k < DP_K; ++k)
-            if (od[k] < bd[DP_K - 1] || (od[k] == bd[DP_K - 1] && oi[k] < bi[DP_K - 1])) dp_insert(bd, bi, od[k], oi[k]);
+        for (int k = 0; k < K; ++k)
+            if (od[k] < bd[K - 1] || (od[k] == bd[K - 1] && oi[k] < bi[K - 1])) dp_insert(bd, bi, od[k], oi[k]);
         if (half == 0) {
             // softmax(-d/alpha) over the K neighbours
-            float xs[DP_K], mx = -3.0e38f;
+            float xs[K], mx = -3.0e38f;
 #pragma unroll
-            for (int k = 0; k < DP_K; ++k) {
+            for (int k = 0; k < K; ++k) {
                 xs[k] = (-__fsqrt_rn(bd[k])) / alpha;              // cross_transformer.py:153-154
                 mx = fmaxf(mx, xs[k]);
             }
             float se = 0.f;
 #pragma unroll
-            for (int k = 0; k < DP_K; ++k) { xs[k] = expf(xs[k] - mx); se = se + xs[k]; }
+            for (int k = 0; k < K; ++k) { xs[k] = expf(xs[k] - mx); se = se + xs[k]; }
             DpNbr& o = nb[ls];
 #pragma unroll
-            for (int k = 0; k < DP_K; ++k) {
+            for (int k = 0; k < K; ++k) {
                 int c = bi[k];
                 o.w[k] = xs[k] / se;
                 o.idx[k] = c;
@@ -336,8 +346,9 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
             const long long gp = (long long)blockIdx.x * DP_SAMPLES + lp;
             if (gp >= P) break;
             unsigned rec = 0u;
-            if (j < DP_K) rec = (unsigned)nb[lp].idx[j];
-            else if (j >= 8 && j < 8 + DP_K) rec = __builtin_bit_cast(unsigned, nb[lp].w[j - 8]);
+            if (j < K) rec = (unsigned)nb[lp].idx[j];
+            else if (K < DP_K && j < 8) rec = 0xffffffffu;          // unused pairs: no centre
+            else if (j >= 8 && j < 8 + K) rec = __builtin_bit_cast(unsigned, nb[lp].w[j - 8]);
             reinterpret_cast<unsigned*>(out)[gp * 16 + j] = rec;
         }
         return;
@@ -359,7 +370,7 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
             int a = 0, oc = 0;
             float ph0 = 0.f;
             if (ch < 3) a = ch;
-            else if (ch < 63) {
+            else if (ch < npe) {
                 const int qq = ch - 3, r = qq % 6;
                 oc = qq / 6;
                 a = r % 3;
@@ -376,7 +387,7 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
             const DpNbr& n = nb[lp];
             float pe[4];
 #pragma unroll
-            for (int k = 0; k < DP_K; ++k) {
+            for (int k = 0; k < K; ++k) {
                 const float wk = n.w[k];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -386,12 +397,19 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
                     pe[q] = (k == 0) ? wk * val : fmaf(wk, val, pe[q]);
                 }
             }
-            if (l16 == 15) pe[3] = 0.f;                                     // channel 63: pad
+            if constexpr (DEF) {
+                if (l16 == 15) pe[3] = 0.f;                                 // channel 63: pad
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (4 * l16 + q >= npe) pe[q] = 0.f;                    // channels 3 + 6 F .. 63: pad
+            }
             unsigned rec = 0u;                                              // the neighbour record (16 dwords)
-            if (l16 < 7) {
+            if (l16 < K) {
                 const int c = n.idx[l16], t = lp >> 5;
                 rec = ubw[t * 128 + (c >> 5)] + __popc(ubm[t * 128 + (c >> 5)] & ((1u << (c & 31)) - 1u));   // slot of centre c
-            } else if (l16 >= 8 && l16 < 15) rec = __builtin_bit_cast(unsigned, n.w[l16 - 8]);
+            } else if (K < DP_K && l16 < 8) rec = 0xffffffffu;              // unused pairs: no slot
+            else if (l16 >= 8 && l16 < 8 + K) rec = __builtin_bit_cast(unsigned, n.w[l16 - 8]);
             reinterpret_cast<unsigned*>(out)[(long long)gp * 16 + l16] = rec;
             dp_h4 hi, lo;
 #pragma unroll
@@ -411,7 +429,7 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
     int axis = 0, oct = 0;
     float phase = 0.f;
     if (lane < 3) axis = lane;
-    else if (lane < 63) {
+    else if (lane < npe) {
         int qq = lane - 3;
         oct = qq / 6;
         int r = qq % 6;
@@ -423,19 +441,19 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
         int gp = blockIdx.x * DP_SAMPLES + lp;
         if (gp >= P) break;
         const DpNbr& n = nb[lp];
-        float w[DP_K];
-        int id[DP_K];
+        float w[K];
+        int id[K];
 #pragma unroll
-        for (int k = 0; k < DP_K; ++k) {
+        for (int k = 0; k < K; ++k) {
             // wave-uniform (one sample per wave): keep them in scalar registers so the row addresses are scalar
             // arithmetic and the weights are scalar operands of the FMAs
             w[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, n.w[k])));
             id[k] = __builtin_amdgcn_readfirstlane(n.idx[k]);
         }
         float pe = 0.f;
-        if (lane < 63) {
+        if (lane < npe) {
 #pragma unroll
-            for (int k = 0; k < DP_K; ++k) {
+            for (int k = 0; k < K; ++k) {
                 float xv = n.def[k][axis];
                 float val = (lane < 3) ? xv : dp_sin(fmaf(xv, freq, phase));
                 pe = (k == 0) ? w[k] * val : fmaf(w[k], val, pe);
@@ -445,15 +463,16 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
             // TH_ROWS_NBR: the neighbour record (16 dwords) + the positional-encoding row; no table access
             if (lane < 16) {
                 unsigned rec = 0u;
-                if (lane < 7) {
+                if (lane < K) {
                     const int c = n.idx[lane], t = lp >> 5;
                     rec = ubw[t * 128 + (c >> 5)] + __popc(ubm[t * 128 + (c >> 5)] & ((1u << (c & 31)) - 1u));   // slot of centre c
-                } else if (lane >= 8 && lane < 15) rec = __builtin_bit_cast(unsigned, n.w[lane - 8]);
+                } else if (K < DP_K && lane < 8) rec = 0xffffffffu;
+                else if (lane >= 8 && lane < 8 + K) rec = __builtin_bit_cast(unsigned, n.w[lane - 8]);
                 reinterpret_cast<unsigned*>(out)[(long long)gp * 16 + lane] = rec;
             }
             _Float16* ph = reinterpret_cast<_Float16*>(pe_out) + (long long)gp * 128;
             _Float16 x, y;
-            dp_split((lane < 63) ? pe : 0.f, x, y);
+            dp_split((lane < npe) ? pe : 0.f, x, y);
             ph[lane] = x;
             ph[64 + lane] = y;
             continue;
@@ -461,17 +480,17 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
         if constexpr (FOLDED && VT > 0) {
             // all VT * 7 row loads of the sample in flight before the first blend (one exposed round trip per sample
             // instead of one per view)
-            float4 r[VT > 0 ? VT : 1][DP_K];
+            float4 r[VT > 0 ? VT : 1][K];
 #pragma unroll
             for (int v = 0; v < VT; ++v)
 #pragma unroll
-                for (int k = 0; k < DP_K; ++k)
+                for (int k = 0; k < K; ++k)
                     r[v][k] = *reinterpret_cast<const float4*>(tokens + ((long long)v * nc + id[k]) * 256 + 4 * lane);
 #pragma unroll
             for (int v = 0; v < VT; ++v) {
                 float4 acc = make_float4(w[0] * r[v][0].x, w[0] * r[v][0].y, w[0] * r[v][0].z, w[0] * r[v][0].w);
 #pragma unroll
-                for (int k = 1; k < DP_K; ++k) {
+                for (int k = 1; k < K; ++k) {
                     acc.x = fmaf(w[k], r[v][k].x, acc.x); acc.y = fmaf(w[k], r[v][k].y, acc.y);
                     acc.z = fmaf(w[k], r[v][k].z, acc.z); acc.w = fmaf(w[k], r[v][k].w, acc.w);
                 }
@@ -479,7 +498,7 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
             }
             _Float16* ph = reinterpret_cast<_Float16*>(pe_out) + (long long)gp * 128;
             _Float16 x, y;
-            dp_split((lane < 63) ? pe : 0.f, x, y);
+            dp_split((lane < npe) ? pe : 0.f, x, y);
             ph[lane] = x;
             ph[64 + lane] = y;
             continue;
@@ -487,12 +506,12 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
         if (FOLDED) {
             for (int v = 0; v < V; ++v) {
                 const float* tv = tokens + (long long)v * nc * 256;
-                float4 r[DP_K];
+                float4 r[K];
 #pragma unroll
-                for (int k = 0; k < DP_K; ++k) r[k] = *reinterpret_cast<const float4*>(tv + (long long)id[k] * 256 + 4 * lane);
+                for (int k = 0; k < K; ++k) r[k] = *reinterpret_cast<const float4*>(tv + (long long)id[k] * 256 + 4 * lane);
                 float4 acc = make_float4(w[0] * r[0].x, w[0] * r[0].y, w[0] * r[0].z, w[0] * r[0].w);
 #pragma unroll
-                for (int k = 1; k < DP_K; ++k) {
+                for (int k = 1; k < K; ++k) {
                     acc.x = fmaf(w[k], r[k].x, acc.x); acc.y = fmaf(w[k], r[k].y, acc.y);
                     acc.z = fmaf(w[k], r[k].z, acc.z); acc.w = fmaf(w[k], r[k].w, acc.w);
                 }
@@ -500,7 +519,7 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
             }
             _Float16* ph = reinterpret_cast<_Float16*>(pe_out) + (long long)gp * 128;
             _Float16 x, y;
-            dp_split((lane < 63) ? pe : 0.f, x, y);
+            dp_split((lane < npe) ? pe : 0.f, x, y);
             ph[lane] = x;
             ph[64 + lane] = y;
             continue;
@@ -509,64 +528,85 @@ __global__ __launch_bounds__(DP_THREADS) void dparf_kernel(const float* __restri
             const float* tv = tokens + (long long)v * nc * 192;
             float* o = out + ((long long)gp * V + v) * 256;
             if (lane < 48) {
-                float4 r[DP_K];
+                float4 r[K];
 #pragma unroll
-                for (int k = 0; k < DP_K; ++k) r[k] = *reinterpret_cast<const float4*>(tv + (long long)id[k] * 192 + 4 * lane);
+                for (int k = 0; k < K; ++k) r[k] = *reinterpret_cast<const float4*>(tv + (long long)id[k] * 192 + 4 * lane);
                 float4 acc = make_float4(w[0] * r[0].x, w[0] * r[0].y, w[0] * r[0].z, w[0] * r[0].w);
 #pragma unroll
-                for (int k = 1; k < DP_K; ++k) {
+                for (int k = 1; k < K; ++k) {
                     acc.x = fmaf(w[k], r[k].x, acc.x); acc.y = fmaf(w[k], r[k].y, acc.y);
                     acc.z = fmaf(w[k], r[k].z, acc.z); acc.w = fmaf(w[k], r[k].w, acc.w);
                 }
                 *reinterpret_cast<float4*>(o + 4 * lane) = acc;
             }
-            o[192 + lane] = (lane < 63) ? pe : 0.f;
+            o[192 + lane] = (lane < npe) ? pe : 0.f;
         }
     }
 }
 
+// one instantiation: its LDS attribute (once per device) and the launch
+struct DpLaunch {
+    const float* pts_smpl; ThPointSrc src; const float *Rh, *Th; const int32_t* sel; int P; const float *centres, *rot, *tokens;
+    int V, nc; float alpha; float *out, *pe_out; DpGridView gv; int npe; size_t lds; hipStream_t s;
+};
+template <bool FOLDED, int VT, int K, bool DEF>
+static int dp_launch_one(const DpLaunch& a) {
+    static unsigned long long attr = 0ull;
+    if (th_lds_attr_needed(&attr))
+        TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<FOLDED, VT, K, DEF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL((dparf_kernel<FOLDED, VT, K, DEF>), dim3(th_cdiv(a.P, DP_SAMPLES)), dim3(DP_THREADS), a.lds, a.s, a.pts_smpl,
+                       a.src, a.Rh, a.Th, a.sel, a.P, a.centres, a.rot, a.tokens, a.V, a.nc, a.alpha, a.out, a.pe_out, a.gv.gi,
+                       a.gv.cell_count, a.gv.cand, a.npe);
+    return 0;
+}
+// cfg.KNN / cfg.KNN_FREQ away from (7, 10): the instantiation of this neighbour count with the live PE channels as an argument.
+// (DEF_PE: the form writes no PE -- TH_ROWS_REC -- so the octave count does not reach it.)
+template <bool FOLDED, int VT, bool DEF_PE>
+static int dp_launch_k(int knn, const DpLaunch& a) {
+    switch (knn) {
+    case 1: return dp_launch_one<FOLDED, VT, 1, DEF_PE>(a);
+    case 2: return dp_launch_one<FOLDED, VT, 2, DEF_PE>(a);
+    case 3: return dp_launch_one<FOLDED, VT, 3, DEF_PE>(a);
+    case 4: return dp_launch_one<FOLDED, VT, 4, DEF_PE>(a);
+    case 5: return dp_launch_one<FOLDED, VT, 5, DEF_PE>(a);
+    case 6: return dp_launch_one<FOLDED, VT, 6, DEF_PE>(a);
+    default: return dp_launch_one<FOLDED, VT, 7, DEF_PE>(a);
+    }
+}
+
+bool th_dparf_params_ok(int knn, int n_freq, double alpha) {
+    return knn >= 1 && knn <= DP_K && n_freq >= 1 && n_freq <= 10 && alpha > 0.0 && alpha <= 3.0e38 && (float)alpha > 0.f;
+}
+
 int th_dparf_launch(const float* pts_smpl, const ThPointSrc* ps, const float* Rh, const float* Th,
                     const int32_t* sel, int P, const float* centres, const float* rot, const float* tokens, int V,
-                    int nc, float alpha, float* out, float* pe_out, int fmt, const void* grid_ws, hipStream_t s) {
+                    int nc, const ThDparfParams& dp, float* out, float* pe_out, int fmt, const void* grid_ws, hipStream_t s) {
     if (P <= 0) return 0;
-    TH_REQUIRE(nc >= DP_K, "need at least 7 token centres");
-    ThPointSrc src;
-    if (ps) src = *ps; else { src = ThPointSrc{}; }
-    size_t lds = ((size_t)((nc * 3 + 3) & ~3)) * sizeof(float) + DP_SAMPLES * sizeof(DpNbr) + 2 * 4 * 128 * sizeof(unsigned);
-    TH_REQUIRE(lds <= 160 * 1024, "too many token centres for LDS staging");
-    static unsigned long long attr_set = 0ull;
-    if (th_lds_attr_needed(&attr_set)) {
-        TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    TH_REQUIRE(th_dparf_params_ok(dp.knn, dp.n_freq, dp.alpha), "K4: KNN 1..7, KNN_FREQ 1..10, KNN_DIST_ALPHA finite and > 0");
+    if (nc < dp.knn) TH_FAIL("need at least " + std::to_string(dp.knn) + " token centres (KNN), got " + std::to_string(nc));
+    DpLaunch a;
+    a.pts_smpl = pts_smpl;
+    if (ps) a.src = *ps; else { a.src = ThPointSrc{}; }
+    a.Rh = Rh; a.Th = Th; a.sel = sel; a.P = P; a.centres = centres; a.rot = rot; a.tokens = tokens; a.V = V; a.nc = nc;
+    a.alpha = dp.alpha; a.out = out; a.pe_out = pe_out; a.npe = 3 + 6 * dp.n_freq; a.s = s;
+    a.lds = ((size_t)((nc * 3 + 3) & ~3)) * sizeof(float) + DP_SAMPLES * sizeof(DpNbr) + 2 * 4 * 128 * sizeof(unsigned);
+    TH_REQUIRE(a.lds <= 160 * 1024, "too many token centres for LDS staging");
     TH_REQUIRE(fmt == TH_ROWS_F32 || fmt == TH_ROWS_REC || ((fmt == TH_ROWS_FOLDED || fmt == TH_ROWS_NBR) && pe_out != nullptr),
                "K4 writes fp32 rows, the folded form or neighbour records");
-    // optional candidate grid (th_dparf_grid_build into grid_ws)
-    const DpGridView gv = dp_grid_view(grid_ws, nc);
+    // optional candidate grid (th_dparf_grid_build into grid_ws): the exact superset for seven neighbours, so for any K <= 7
+    a.gv = dp_grid_view(grid_ws, nc);
+    const bool def = dp.knn == DP_K && dp.n_freq == 10;
     if (fmt == TH_ROWS_REC) {
-        static unsigned long long attrr = 0ull;
-        if (th_lds_attr_needed(&attrr))
-            TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<false, -2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((dparf_kernel<false, -2>), dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
+        TH_TRY((dp_launch_k<false, -2, true>(dp.knn, a)));
     } else if (fmt == TH_ROWS_NBR) {
-        static unsigned long long attrn = 0ull;
-        if (th_lds_attr_needed(&attrn))
-            TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<true, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((dparf_kernel<true, -1>), dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
-    } else if (fmt == TH_ROWS_FOLDED && V == 3) {
-        static unsigned long long attr3 = 0ull;
-        if (th_lds_attr_needed(&attr3))
-            TH_HIP(hipFuncSetAttribute((const void*)dparf_kernel<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((dparf_kernel<true, 3>), dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
-    } else if (fmt == TH_ROWS_FOLDED)
-        hipLaunchKernelGGL(dparf_kernel<true>, dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
-    else
-        hipLaunchKernelGGL(dparf_kernel<false>, dim3(th_cdiv(P, DP_SAMPLES)), dim3(DP_THREADS), lds, s, pts_smpl, src, Rh,
-                           Th, sel, P, centres, rot, tokens, V, nc, alpha, out, pe_out, gv.gi, gv.cell_count, gv.cand);
+        TH_TRY(def ? (dp_launch_one<true, -1, DP_K, true>(a)) : (dp_launch_k<true, -1, false>(dp.knn, a)));
+    } else if (fmt == TH_ROWS_FOLDED && V == 3 && def) {
+        TH_TRY((dp_launch_one<true, 3, DP_K, true>(a)));
+    } else if (fmt == TH_ROWS_FOLDED) {
+        TH_TRY(def ? (dp_launch_one<true, 0, DP_K, true>(a)) : (dp_launch_k<true, 0, false>(dp.knn, a)));
+    } else {
+        TH_TRY(def ? (dp_launch_one<false, 0, DP_K, true>(a)) : (dp_launch_k<false, 0, false>(dp.knn, a)));
+    }
     TH_LAUNCH_CHECK();
     return 0;
 }

@@ -5,8 +5,10 @@
 // -- 7 P contribution rows onto N_c destination rows (2.5 GB onto 500 rows at the training shape).  A float-atomic scatter
 // onto so few rows runs an order of magnitude under the atomic rate and its sums depend on arrival order, so the sum is done
 // per DESTINATION through an inverted index, without any float atomic:
-//   1. records  the forward's own selection (dparf_kernel<false, -2>, TH_ROWS_REC): idx[7], w[7] per sample -- the same
-//               statements as the forward that produced the loss, so no neighbour can differ between the two;
+//   1. records  the forward's own selection (dparf_kernel<false, -2, K>, TH_ROWS_REC): idx[7], w[7] per sample -- the same
+//               statements as the forward that produced the loss, so no neighbour can differ between the two.  With
+//               cfg.KNN = K < 7 the record's pairs K..6 are idx = -1, w = 0: the rank pass drops them (`c >= 0`) while the
+//               workspace stays sized for 7 P entries;
 //   2. count    one wave per unit of 256 consecutive samples: how many records of the unit name each centre -> cnt[c][unit];
 //   3. scan     exclusive prefix over (centre major, unit minor): the start of every (centre, unit) segment; the start of a
 //               centre's list is the start of its first segment;
@@ -183,9 +185,10 @@ __global__ __launch_bounds__(64) void dpb_reduce_kernel(const int* __restrict__ 
     *reinterpret_cast<float4*>(gtok + ((long long)v * nc + c) * 192 + 4 * lane) = acc;
 }
 
-int th_dparf_bwd_launch(const float* pts_smpl, int P, const float* centres, const float* rot, int V, int nc, float alpha,
+int th_dparf_bwd_launch(const float* pts_smpl, int P, const float* centres, const float* rot, int V, int nc, const ThDparfParams& dp,
                         const float* grad_out, float* grad_tokens, void* ws, size_t ws_bytes, hipStream_t s) {
-    TH_REQUIRE(P >= 0 && V >= 1 && nc >= DPB_K, "need P >= 0, V >= 1 and at least 7 token centres");
+    TH_REQUIRE(dp.knn >= 1 && dp.knn <= DPB_K, "KNN 1..7");
+    if (!(P >= 0 && V >= 1 && nc >= dp.knn)) TH_FAIL("need P >= 0, V >= 1 and at least " + std::to_string(dp.knn) + " token centres");
     TH_REQUIRE(P <= (1 << 27) && V <= 65535, "too many samples or views");
     TH_REQUIRE((size_t)nc * 4 <= 64 * 1024, "too many token centres for the counting pass (16384)");
     if (P == 0) {
@@ -201,7 +204,7 @@ int th_dparf_bwd_launch(const float* pts_smpl, int P, const float* centres, cons
     int* nch = (int*)(b + pl.nch);
     int2* ent = (int2*)(b + pl.ent);
     float* part = (float*)(b + pl.part);
-    TH_TRY(th_dparf_launch(pts_smpl, nullptr, nullptr, nullptr, nullptr, P, centres, rot, nullptr, V, nc, alpha, (float*)rec,
+    TH_TRY(th_dparf_launch(pts_smpl, nullptr, nullptr, nullptr, nullptr, P, centres, rot, nullptr, V, nc, dp, (float*)rec,
                            nullptr, TH_ROWS_REC, nullptr, s));
     hipLaunchKernelGGL(dpb_rank_kernel<false>, dim3(pl.units), dim3(64), (size_t)nc * 4, s, rec, P, nc, pl.units, off, ent);
     hipLaunchKernelGGL(dpb_scan_kernel, dim3(1), dim3(DPB_SCAN_T), 0, s, off, (long long)nc * pl.units);

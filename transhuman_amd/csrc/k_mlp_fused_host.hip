@@ -270,8 +270,12 @@ int th_fused_pack(const th_mlp_weights* w, const th_linear* folded, void* store,
     float* st = XRc + 128 * 260;
     float* stb = st + 256 * 384;
     float* tw = stb + 256;
-    {   // fc_0: only the 63 positional-encoding columns [192, 255) stay in the kernel (token columns -> T', th_api.hip)
-        TH_HIP(hipMemcpy2DAsync(wpe, 63 * 4, w->fc_0.w + 192, 255 * 4, 63 * 4, 256, hipMemcpyDeviceToDevice, s));
+    {   // fc_0: only the positional-encoding columns [192, in_f) stay in the kernel (token columns -> T', th_api.hip): 63 at
+        // KNN_FREQ = 10; with fewer octaves the rest of wpe's 63 columns is zero, like the PE channels K4 writes for them
+        const int npe = w->fc_0.in_f - 192;
+        TH_REQUIRE(npe >= 9 && npe <= 63, "fc_0 is 256 x (195 + 6 KNN_FREQ), KNN_FREQ 1..10");
+        if (npe < 63) TH_HIP(hipMemsetAsync(wpe, 0, 256 * 63 * 4, s));
+        TH_HIP(hipMemcpy2DAsync(wpe, 63 * 4, w->fc_0.w + 192, (size_t)w->fc_0.in_f * 4, (size_t)npe * 4, 256, hipMemcpyDeviceToDevice, s));
         TH_TRY(layer_scale_log2(wpe, 256LL * 63, amax, &sl2, s));
         TH_TRY(pack_layer(wpe, w->fc_0.b, 256, 63, 2, c256, sl2, cur, &out->fc_0pe, s));
         TH_TRY(pack_layer16(wpe, 256, 63, 2, c256_16, out->fc_0pe, sl2, cur, &out->w16.fc_0pe, s));

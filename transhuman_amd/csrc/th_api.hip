@@ -204,7 +204,12 @@ int th_set_mlp_weights(th_ctx* c, const th_mlp_weights* w, th_stream stream) {
     TH_REQUIRE(c && w, "null argument");
     hipStream_t s = (hipStream_t)stream;
     // shapes of cross_transformer.py:96-126
-    TH_REQUIRE(lin_ok(w->fc_0, 256, 255) && lin_ok(w->alpha_res_0, 256, 384) && lin_ok(w->key0, 128, 256) &&
+    // fc_0 reads [token (192) | PE (3 + 6 KNN_FREQ)]: its width follows the context's octave count (th_set_dparf)
+    const int fc0_in = 195 + 6 * c->dparf.n_freq;
+    if (w->fc_0.w != nullptr && w->fc_0.out_f == 256 && w->fc_0.in_f != fc0_in)
+        TH_FAIL("fc_0 is 256 x " + std::to_string(w->fc_0.in_f) + ", the context's KNN_FREQ = " + std::to_string(c->dparf.n_freq) +
+                " wants 256 x " + std::to_string(fc0_in) + " (th_set_dparf)");
+    TH_REQUIRE(lin_ok(w->fc_0, 256, fc0_in) && lin_ok(w->alpha_res_0, 256, 384) && lin_ok(w->key0, 128, 256) &&
                    lin_ok(w->val0, 256, 256) && lin_ok(w->key1, 128, 256) && lin_ok(w->val1, 256, 256) &&
                    lin_ok(w->fc_1, 256, 256) && lin_ok(w->fc_2, 256, 256) && lin_ok(w->fc_3, 256, 256) &&
                    lin_ok(w->alpha_fc, 1, 256) && lin_ok(w->feature_fc, 256, 256) &&
@@ -256,7 +261,7 @@ int th_set_mlp_weights(th_ctx* c, const th_mlp_weights* w, th_stream stream) {
     else TH_HIP(hipMemsetAsync(M.rgb_b, 0, 12, s));
     {
         float* tw = st.tok_w;
-        TH_HIP(hipMemcpy2DAsync(tw, 192 * 4, w->fc_0.w, 255 * 4, 192 * 4, 256, hipMemcpyDeviceToDevice, s));
+        TH_HIP(hipMemcpy2DAsync(tw, 192 * 4, w->fc_0.w, (size_t)fc0_in * 4, 192 * 4, 256, hipMemcpyDeviceToDevice, s));
         th_linear tok{tw, nullptr, 256, 192};
         TH_TRY(th_pack_linear(tok, st.tok_pk, &M.fc_0tok, s));
     }
@@ -357,6 +362,24 @@ int th_set_mlp_mode(th_ctx* c, int mode) {
 int th_set_fused_waves(th_ctx* c, int waves) {
     TH_REQUIRE(c && (waves == 4 || waves == 8), "th_set_fused_waves: 4 (one wave per SIMD) or 8 (two per SIMD)");
     c->fused.waves = waves;
+    return 0;
+}
+
+// ---- DPaRF's hyper-parameters: cfg.KNN, cfg.KNN_FREQ, cfg.KNN_DIST_ALPHA (k_dparf.hip, k_dparf_bwd.hip) ----
+int th_set_dparf(th_ctx* c, int knn, int n_freq, double alpha) {
+    TH_REQUIRE(c, "null ctx");
+    if (!th_dparf_params_ok(knn, n_freq, alpha))
+        TH_FAIL("KNN = " + std::to_string(knn) + ", KNN_FREQ = " + std::to_string(n_freq) + ", KNN_DIST_ALPHA = " +
+                std::to_string(alpha) + ": K4 takes KNN 1..7 (a record's seven pairs), KNN_FREQ 1..10 (63 PE channels inside "
+                "fc_0's 256 padded columns) and a finite KNN_DIST_ALPHA > 0");
+    if (n_freq != c->dparf.n_freq) {
+        // fc_0's width follows the octave count: the weight images in the context belong to the other width
+        c->mlp.ready = false;
+        c->fused_ready = false;
+    }
+    c->dparf.knn = knn;
+    c->dparf.n_freq = n_freq;
+    c->dparf.alpha = (float)alpha;                        // the reference's distances are fp32: alpha rounds once, here
     return 0;
 }
 
@@ -685,7 +708,7 @@ int th_attention_bwd(th_ctx* c, const float* qkv, const float* out, const float*
 int th_dparf_encode(th_ctx* c, const float* pts, const int32_t* sel, int P, const float* centres, const float* rot,
                     const float* tokens, int V, int nc, float* out, th_stream stream) {
     TH_REQUIRE(c && pts && centres && rot && tokens && out, "null argument");
-    return th_dparf_launch(pts, nullptr, nullptr, nullptr, sel, P, centres, rot, tokens, V, nc, 0.5f, out, nullptr,
+    return th_dparf_launch(pts, nullptr, nullptr, nullptr, sel, P, centres, rot, tokens, V, nc, c->dparf, out, nullptr,
                            TH_ROWS_F32, nullptr, (hipStream_t)stream);
 }
 
@@ -751,7 +774,7 @@ int th_dparf_encode_bwd(th_ctx* c, const float* pts, int P, const float* centres
                         const float* grad_out, float* grad_tokens, void* ws, size_t ws_bytes, th_stream stream) {
     TH_REQUIRE(c && centres && rot && grad_tokens, "null argument");
     TH_REQUIRE(P == 0 || (pts && grad_out && ws), "null argument");
-    return th_dparf_bwd_launch(pts, P, centres, rot, V, nc, 0.5f, grad_out, grad_tokens, ws, ws_bytes, (hipStream_t)stream);
+    return th_dparf_bwd_launch(pts, P, centres, rot, V, nc, c->dparf, grad_out, grad_tokens, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int th_pixel_gather_bwd(th_ctx* c, int V, int C, int H, int W, const float* pts, int P, const float* cams, const float* scale,
@@ -1233,7 +1256,7 @@ int th_network_forward(th_ctx* c, const float* pixel_feat, const float* viewdir,
         const int32_t* sel = idx ? idx + o : nullptr;
         const float* pts = idx ? pts_smpl : pts_smpl + 3LL * o;
         const int fmt = mlp_row_format(c, V);
-        TH_TRY(th_dparf_launch(pts, nullptr, nullptr, nullptr, sel, m, centres, rot, table, V, nc, 0.5f, cb.h, cb.pe,
+        TH_TRY(th_dparf_launch(pts, nullptr, nullptr, nullptr, sel, m, centres, rot, table, V, nc, c->dparf, cb.h, cb.pe,
                                dparf_row_format(c, V), nullptr, s));
         if (idx) TH_TRY(th_gather_chan_major_launch(pixel_feat, V, 384, P, sel, m, cb.f, fmt, s, c->range_dev));
         else TH_TRY(th_gather_chan_major_launch(pixel_feat + o, V, 384, P, nullptr, m, cb.f, fmt, s, c->range_dev));
@@ -1439,7 +1462,7 @@ static int pregather_stage(th_ctx* c, const th_frame* f, const ThPointSrc& ps, c
     t.grid_centres = nullptr;                 // (th_render_pregrid's grid is consumed: chunks beyond the stage rebuild)
     if (rc == 0) {
         ProfScope ps1(pf, TH_PROF_DPARF, s4);
-        rc = th_dparf_launch(nullptr, &ps, f->Rh, f->Th, w.idx, m, f->centres, f->rot, nullptr, V, f->n_clusters, 0.5f, a_h,
+        rc = th_dparf_launch(nullptr, &ps, f->Rh, f->Th, w.idx, m, f->centres, f->rot, nullptr, V, f->n_clusters, c->dparf, a_h,
                              a_pe, TH_ROWS_NBR, grid ? w.gws : nullptr, s4);
     }
     if (rc == 0) {
@@ -1542,7 +1565,7 @@ static int shade_stage(th_ctx* c, const th_frame* f, const ThPointSrc& ps, bool 
         {
             ProfScope ps1(pf, TH_PROF_DPARF, s);
             TH_TRY(th_dparf_launch(nullptr, &ps, f->Rh, f->Th, sel, m, f->centres, f->rot, table, V,
-                                   f->n_clusters, 0.5f, cb.h, cb.pe, dparf_row_format(c, V), use_grid ? w.gws : nullptr, s));
+                                   f->n_clusters, c->dparf, cb.h, cb.pe, dparf_row_format(c, V), use_grid ? w.gws : nullptr, s));
         }
         {
             ProfScope ps3(pf, TH_PROF_MLP, s);

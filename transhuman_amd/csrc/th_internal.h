@@ -322,6 +322,11 @@ int th_pixtex_launch(int V, int H, int W, const ThPointSrc* ps, const int32_t* s
 // maximum's bits).  A non-finite table raises the guard's TH_RANGE_VIT slot (its producer is the ViT).
 int th_tok_split(float* tprime, int rows, float* sc, unsigned int* range, hipStream_t s);
 
+// cfg.KNN (1..7), cfg.KNN_FREQ (1..10) and (float)cfg.KNN_DIST_ALPHA (> 0): th_set_dparf keeps them in the context.  For knn < 7
+// the unused pairs of a TH_ROWS_NBR / TH_ROWS_REC record are idx = 0xffffffff (words knn..7), w = +0.0; the PE channels
+// 3 + 6 n_freq .. 63 (columns 195 + 6 n_freq .. 255 of an fp32 row) are exact zero.
+struct ThDparfParams { int knn = 7, n_freq = 10; float alpha = 0.5f; };
+
 struct th_ctx {
     void* fused_store = nullptr;
     FusedParams fused{};
@@ -330,6 +335,7 @@ struct th_ctx {
     int vit_mode = 1;                 // 1: TransHE dense layers on the fp16-split MFMA path (th_gemm_h3), 0: fp32 MFMA
     int tok_gather = 1;               // 1: TH_ROWS_NBR hand-over (token blend inside the fused kernel), 0: TH_ROWS_FOLDED
     int tex_rows = 1;                 // 1: TH_ROWS_TEX hand-over of the pixel features (texel lists, blend inside the fused kernel)
+    ThDparfParams dparf{};            // th_set_dparf: cfg.KNN, cfg.KNN_FREQ, cfg.KNN_DIST_ALPHA of every K4 / K17 launch of this context
     float trunc_sigma = 0.f;          // th_set_truncation: > 0: the frame paths zero the raw rows of samples this far from every token centre
     int device = 0;
     void* mlp_store = nullptr;
@@ -443,9 +449,10 @@ int th_nchw_to_nhwc_launch(const float* src, int V, int C, int H, int W, float* 
 //                  sample -- int idx[7] (token-centre indices in (distance, index) order), 0, float w[7], 0 -- nothing else
 enum { TH_ROWS_F32 = 0, TH_ROWS_SPLIT = 1, TH_ROWS_FOLDED = 2, TH_ROWS_NBR = 3, TH_ROWS_REC = 4 };
 // k_dparf.hip
+bool th_dparf_params_ok(int knn, int n_freq, double alpha);
 int th_dparf_launch(const float* pts_smpl, const ThPointSrc* ps, const float* Rh, const float* Th,
                     const int32_t* sel, int P, const float* centres, const float* rot, const float* tokens,
-                    int V, int nc, float alpha, float* out, float* pe_out, int fmt, const void* grid_ws,
+                    int V, int nc, const ThDparfParams& dp, float* out, float* pe_out, int fmt, const void* grid_ws,
                     hipStream_t s);
 // exact candidate grid over the token centres for the 7-NN scan of K4 (per frame); grid_ws = nullptr: full scan
 // (the grid builder keeps four cells' squared distances in the default 64 KiB of dynamic LDS: nc <= 4096)
@@ -455,7 +462,7 @@ int th_dparf_grid_build(const float* centres, int nc, void* ws, size_t ws_bytes,
 // k_dparf_bwd.hip: grad_tokens [V,nc,192] = adjoint of the token blend applied to grad_out [P,V,256] (columns 192.. ignored);
 // every element is written; bit-identical from run to run
 size_t th_dparf_bwd_ws(int P, int V, int nc);
-int th_dparf_bwd_launch(const float* pts_smpl, int P, const float* centres, const float* rot, int V, int nc, float alpha,
+int th_dparf_bwd_launch(const float* pts_smpl, int P, const float* centres, const float* rot, int V, int nc, const ThDparfParams& dp,
                         const float* grad_out, float* grad_tokens, void* ws, size_t ws_bytes, hipStream_t s);
 // k_pixfeat_bwd.hip: grad_map [V,H,W,C] = adjoint of the fp32-row gather applied to grad_out [P,V,ldo]; clears the map itself
 int th_pixgather_bwd_launch(int V, int C, int H, int W, const float* pts_world, int P, const float* cams, const float* scale,

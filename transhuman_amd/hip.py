@@ -85,6 +85,7 @@ class DeviceState:
         self.epoch = 0                   # number of switches so far (frames queued earlier are re-rendered)
         self.owner = {}                  # "mlp" / "vit" -> (weakref to the module whose weights the ctx holds, version tuple)
         self.truncation = 0.0            # what set_truncation last handed to th_set_truncation (0: off, a new context's default)
+        self.dparf = (7, 10, 0.5)        # what set_dparf last handed to th_set_dparf (cfg.KNN, KNN_FREQ, KNN_DIST_ALPHA; a new context's default)
         self.workspaces, self.pools = {}, {}   # slot -> render workspace (_cached_ws) / shading pool, None: the shared one (_shade_pool)
 
 
@@ -169,7 +170,11 @@ def set_mlp_weights(net):
         lin, k = _linear(mod.weight, mod.bias)
         keep.append(k)
         setattr(W, name, lin)
-    _check(lib.th_set_mlp_weights(ctx(net.fc_0.weight.device), C.byref(W), _stream()))
+    # fc_0 is 256 x (195 + 6 KNN_FREQ): the context checks it against the octave count in force, which is this network's
+    dev = net.fc_0.weight.device
+    st = _state(dev)
+    set_dparf(st.dparf[0], net.PE_relative.num_freqs, st.dparf[2], dev)
+    _check(lib.th_set_mlp_weights(ctx(dev), C.byref(W), _stream()))
 
 
 def set_vit_weights(vit):
@@ -1909,6 +1914,29 @@ def set_truncation(sigma, device=None):
     if st.truncation != sigma:
         _check(load_library().th_set_truncation(ctx(device), sigma))
         st.truncation = sigma
+
+
+def set_dparf(knn, n_freq, alpha, device=None):
+    """th_set_dparf: cfg.KNN (1..7), the octave count of the network's PE_relative (1..10) and cfg.KNN_DIST_ALPHA (finite, > 0) of
+    every later call on this device that runs K4 or its backward (dparf_encode, dparf_encode_bwd, network_forward, the frame
+    paths).  A new context has (7, 10, 0.5); values already in force cost nothing.  Another octave count means another fc_0 width:
+    the context's MLP weights are dropped with it and the next call that needs them uploads its network's again."""
+    want = (int(knn), int(n_freq), float(alpha))
+    st = _state(device)
+    if st.dparf != want:
+        if st.dparf[1] != want[1] and st.owner.get("mlp") is not None:
+            # (the weight image of the other width is about to be rewritten: frames queued on other streams may still read it;
+            # rare -- another network -- so it simply drains the device, like _sync_weights)
+            torch.cuda.synchronize(st.index)
+        _check(load_library().th_set_dparf(ctx(device), want[0], want[1], want[2]))
+        if st.dparf[1] != want[1]:
+            st.owner.pop("mlp", None)
+        st.dparf = want
+
+
+def dparf_in_force(device=None):
+    """(knn, n_freq, alpha) that the K4 calls of ``device`` run under: what set_dparf last set, (7, 10, 0.5) before that"""
+    return _state(device).dparf
 
 
 def ssim(a, b):

@@ -20,6 +20,7 @@ import torch
 from . import hip
 from . import mesh_render
 from .truncation import sigma_in_force
+from .dparf_params import params_in_force
 
 
 def colors_from_raw(raw, as_float=False):
@@ -67,6 +68,7 @@ def vertex_colors(renderer, batch, mesh_or_verts, faces=None, view="normal", fra
         return (out, dict(no_rgb=0, valid_samples=0)) if return_info else out
     d = view_directions(v, faces, view)
     hip.set_truncation(sigma_in_force(), v.device)                   # cfg.use_truncation / cfg.KNN_SIGMA in force (K27)
+    hip.set_dparf(*params_in_force(renderer.net), v.device)          # cfg.KNN / KNN_FREQ / KNN_DIST_ALPHA in force (K4)
     raw, stats = hip.eval_points(renderer.net, frame, v, d)
     col, n_default = colors_from_raw(raw, as_float=as_float)
     return (col, dict(no_rgb=n_default, valid_samples=int(stats["valid_samples"]))) if return_info else col

@@ -65,6 +65,7 @@ import torch.nn.functional as F
 
 from ..config import TRAIN_ENCODER_FWD, TRAIN_SWITCHES, TRAIN_SYNC_BN, get_cfg
 from ..truncation import sigma_in_force
+from ..dparf_params import check_centres, params_in_force
 
 
 # ---- the switches ------------------------------------------------------------------------------------------------------
@@ -292,7 +293,7 @@ def _lin(mod, x):
 
 
 def human_representation(net, pts_s, centres, rot, tokens, K, alpha):
-    """get_human_representation (cross_transformer.py:158-205) -> [P,V,255]"""
+    """get_human_representation (cross_transformer.py:158-205) -> [P,V,195 + 6 KNN_FREQ] (255 at the default 10 octaves)"""
     d2 = ((pts_s[:, None, :] - centres[None]) ** 2).sum(-1)
     d2k, idx = torch.topk(d2, K, dim=1, largest=False)
     w = F.softmax(-d2k.clamp_min(0).sqrt() / alpha, dim=1)
@@ -338,18 +339,19 @@ def point_network_torch_ops():
 def point_network_device(net, h, f, viewdir, ops=None):
     """point_network (same arguments, same result) as th_mlp_forward composes it (k_mlp.hip): one GEMM per layer with the ReLU
     in its epilogue, the key and value embeddings of a branch as one 384-row layer, the cross-view attention as one kernel.
-    h may carry K4's zero pad column ([P,V,256]).  The GEMMs take multiples of 16: the odd layers are padded with zeros here,
+    h is [P,V,195 + 6 KNN_FREQ] or K4's zero-padded [P,V,256] row.  The GEMMs take multiples of 16: the odd layers are padded with zeros here,
     by differentiable operators, so autograd slices the gradients of the Parameters back.  ``ops``: the three operators
     (default: the HIP Functions of train_ops)."""
     ops = ops or _point_net_device_ops()
     lin, rlin = ops["linear"], ops["relu_linear"]
     w = lambda m: m.weight.reshape(m.weight.shape[0], -1)
     P, V = f.shape[:2]
-    if h.shape[-1] == 255:
-        h = F.pad(h, (0, 1))
+    n_in = net.fc_0.weight.shape[1]                                # 195 + 6 KNN_FREQ
+    if h.shape[-1] == n_in:
+        h = F.pad(h, (0, 256 - n_in))
     h, f = h.contiguous(), f.contiguous()
     kv0, kv1 = net.spatial_key_value_0, net.spatial_key_value_1
-    s = rlin(h, F.pad(w(net.fc_0), (0, 1)), net.fc_0.bias)                                      # 255 -> 256 columns
+    s = rlin(h, F.pad(w(net.fc_0), (0, 256 - n_in)), net.fc_0.bias)                             # 195 + 6 F -> 256 columns
     p = rlin(f, w(net.alpha_res_0), net.alpha_res_0.bias)
     kvp = lin(p, torch.cat([w(kv0.key_embed), w(kv0.value_embed)]), torch.cat([kv0.key_embed.bias, kv0.value_embed.bias]))
     kvs = lin(s, torch.cat([w(kv1.key_embed), w(kv1.value_embed)]), torch.cat([kv1.key_embed.bias, kv1.value_embed.bias]))
@@ -473,11 +475,12 @@ def render(renderer, batch, chunk=32768):
     # chosen once: the per-chunk providers of the pixel rows f and the token rows h, the point network, the compositor
     chunks = [slice(s0, s0 + chunk) for s0 in range(0, xyz.shape[0], chunk)]       # batchify_rays :607-656 without a mask
     shade = point_network_device if point_net == "device" else point_network
+    dparf = params_in_force(net, cfg)                              # (cfg.KNN, the network's octave count, cfg.KNN_DIST_ALPHA), read per call
+    check_centres(dparf[0], centres.shape[0])
     if mode == "device":
         from .. import hip
         from . import train_ops
-        if int(cfg.KNN) != 7 or float(cfg.KNN_DIST_ALPHA) != 0.5:
-            raise hip.HipError("cfg.train_kernels = 'device': K4 is built for KNN = 7, KNN_DIST_ALPHA = 0.5")
+        hip.set_dparf(*dparf, dev)                                 # cfg.KNN / KNN_FREQ / KNN_DIST_ALPHA in force: K4 and K17 follow the context
         # K5 and K4 once over all (kept) samples: one map-sized gradient per step, nothing of the blends kept for backward
         fs = hs = ()
         if chunks:                                                 # (none: cfg.use_truncation dropped every sample)
@@ -488,14 +491,14 @@ def render(renderer, batch, chunk=32768):
             fs = f_lat.split(chunk)
             hs = train_ops.HumanRepresentationFn.apply(tokens.contiguous(), pts_s, centres, rot).split(chunk)
             if point_net != "device":
-                hs = (h[..., :255] for h in hs)                    # (K4's rows carry a zero pad column, point_network_device takes it)
+                hs = (h[..., :195 + 6 * dparf[1]] for h in hs)     # (K4's rows are zero padded to 256 columns, point_network_device takes them)
         compose = lambda raw: train_ops.CompositeFn.apply(raw.contiguous(), z, ray_d, bool(cfg.white_bkgd))
     else:
         if maps == "latents":
             fs = (f_lat[c] for c in chunks)
         else:
             fs = (sample_map(pix, project(xyz[c], R_in, T_in, K_in), net.encoder, image_shape).permute(2, 0, 1) for c in chunks)
-        hs = (human_representation(net, pts_s[c], centres, rot, tokens, int(cfg.KNN), float(cfg.KNN_DIST_ALPHA)) for c in chunks)
+        hs = (human_representation(net, pts_s[c], centres, rot, tokens, dparf[0], dparf[2]) for c in chunks)
         compose = lambda raw: composite(raw, z, ray_d, 0.0, bool(cfg.white_bkgd))
 
     raws = [shade(net, h, f, viewdir[c]) for f, h, c in zip(fs, hs, chunks)]       # (the generators run chunk by chunk)

@@ -30,6 +30,7 @@ from torch import nn                                                # noqa: E402
 
 from transhuman_amd.config import get_cfg                           # noqa: E402
 from transhuman_amd.truncation import sigma_in_force               # noqa: E402
+from transhuman_amd.dparf_params import check_dparf_params, check_centres, params_in_force   # noqa: E402
 from transhuman_amd.networks.encoder import SpatialEncoder, _PEBuffers   # noqa: E402
 from transhuman_amd.networks import vision_transformer as ViT       # noqa: E402
 
@@ -45,6 +46,13 @@ class Network(nn.Module):
     def __init__(self):
         super().__init__()
         cfg = get_cfg()
+        # cfg.KNN_FREQ 1..10 sizes fc_0; cfg.KNN_DIST_ALPHA finite > 0 (dparf_params.py says what is refused and why).  cfg.KNN is
+        # read per call (forward, the renderers, the training entry: 1..7 there); the constructor keeps its refusal of a cfg
+        # that holds another value than 7 at construction time, which tests/test_dropin.py pins
+        check_dparf_params(cfg.KNN, cfg.KNN_FREQ, cfg.KNN_DIST_ALPHA)
+        if int(cfg.KNN) != 7:
+            raise NotImplementedError(f"KNN = {cfg.KNN} at construction: Network() is built under KNN = 7 "
+                                      "(configs/train_or_eval.yaml:63); set cfg.KNN (1..7) afterwards -- it is read on every call")
         self.ViT = ViT.vit_tiny(depth=cfg.vit_depth)
         cfg.embed_size = self.ViT.embed_dim                       # :91
         self.encoder = SpatialEncoder()
@@ -64,9 +72,6 @@ class Network(nn.Module):
         self.alpha_res_0 = nn.Conv1d(cfg.img_feat_size, 256, 1)
         self.rgb_res_0 = nn.Conv1d(cfg.img_feat_size, 256, 1)
         self.rgb_res_1 = nn.Conv1d(cfg.img_feat_size, 128, 1)
-        if cfg.KNN != 7 or cfg.KNN_FREQ != 10 or abs(cfg.KNN_DIST_ALPHA - 0.5) > 0:
-            raise NotImplementedError("the DPaRF kernel is built for KNN=7, KNN_FREQ=10, KNN_DIST_ALPHA=0.5 "
-                                      "(configs/train_or_eval.yaml:63-66)")
 
     # -- checkpoint compatibility ------------------------------------------------
     def load_state_dict(self, state_dict, strict=True, **kw):
@@ -84,6 +89,9 @@ class Network(nn.Module):
         assert pts.shape[0] == 1, "B = 1 is assumed (cross_transformer.py:222)"
         rot = blend[0][..., :3, :3].type(torch.float32).reshape(-1, 9)    # :185
         mask = None if pts_mask is None else pts_mask[0]
+        knn, n_freq, alpha = params_in_force(self)                 # cfg.KNN and cfg.KNN_DIST_ALPHA per call (:154, :170)
+        check_centres(knn, centres.shape[1])
+        hip.set_dparf(knn, n_freq, alpha, pts.device)
         sigma = sigma_in_force()
         if sigma > 0.0:
             # cfg.use_truncation (:175-180, :247-264): the per-point network on the samples closer than KNN_SIGMA to a token

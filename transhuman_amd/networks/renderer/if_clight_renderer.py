@@ -36,6 +36,7 @@ import torch                                                        # noqa: E402
 from transhuman_amd.config import cfg_get, get_cfg                  # noqa: E402
 from transhuman_amd import hip, synth                               # noqa: E402
 from transhuman_amd.truncation import sigma_in_force               # noqa: E402
+from transhuman_amd.dparf_params import params_in_force            # noqa: E402
 
 
 def _test_targets(batch):
@@ -236,6 +237,9 @@ class Renderer:
         # the weight image (and with it the sticky range slot of the stem convolutions, which belongs to the same
         # parameter set) is brought up to date BEFORE the stem runs and on the stream that runs it: a frame's own
         # convolutions are then never queued in front of the clear that new weights trigger
+        # (cfg.KNN / KNN_FREQ / KNN_DIST_ALPHA first: the frame's pre-gathered neighbour records are K4's, and fc_0's width
+        # follows the octave count)
+        hip.set_dparf(*params_in_force(self.net, cfg), self.net.fc_0.weight.device)
         hip._sync_weights(self.net, "mlp")
         v = _Views(batch, t)
         cams = v.cams()
@@ -455,6 +459,7 @@ class Renderer:
     def _shade(self, frame, pts, **kw):
         """hip.render_rays over the configuration's background, under the cfg.use_truncation / cfg.KNN_SIGMA in force (K27)"""
         hip.set_truncation(sigma_in_force(), frame.verts.device)
+        hip.set_dparf(*params_in_force(self.net), frame.verts.device)
         return hip.render_rays(self.net, frame, pts, white_bkgd=bool(get_cfg().white_bkgd), **kw)
 
     def _hull_front(self, batch, pts, V, feed, hull, small_frame_rays, slot=0, **predemand_args):

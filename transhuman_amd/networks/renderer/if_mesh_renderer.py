@@ -27,6 +27,7 @@ import numpy as np                                                  # noqa: E402
 from transhuman_amd.config import get_cfg, cfg_get                  # noqa: E402
 from transhuman_amd import hip                                      # noqa: E402
 from transhuman_amd.truncation import sigma_in_force               # noqa: E402
+from transhuman_amd.dparf_params import params_in_force            # noqa: E402
 from transhuman_amd.networks.renderer.if_clight_renderer import Renderer as Base_Renderer   # noqa: E402
 
 
@@ -40,6 +41,7 @@ class Renderer(Base_Renderer):
         if pts_slice is not None:
             flat = flat[pts_slice]
         hip.set_truncation(sigma_in_force(cfg), flat.device)         # cfg.use_truncation / cfg.KNN_SIGMA in force (K27)
+        hip.set_dparf(*params_in_force(self.net, cfg), flat.device)  # cfg.KNN / KNN_FREQ / KNN_DIST_ALPHA in force (K4)
         sigma, stats = hip.eval_sigma_grid(self.net, frame, flat)
         self.last_stats = stats
         if pts_slice is not None:

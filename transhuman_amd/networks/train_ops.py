@@ -79,19 +79,23 @@ def _on_device(fn, t):
 
 
 class HumanRepresentationFn(torch.autograd.Function):
-    """get_human_representation (cross_transformer.py:158-205) -> [P,V,256] (255 features + one zero column).  The gradient
-    reaches the tokens only: columns 192.. (positional encoding of the point, pad) do not depend on them."""
+    """get_human_representation (cross_transformer.py:158-205) -> [P,V,256] (195 + 6 KNN_FREQ features, zeros behind them).
+    The gradient reaches the tokens only: columns 192.. (positional encoding of the point, pad) do not depend on them.
+    cfg.KNN / KNN_FREQ / KNN_DIST_ALPHA are those of the device's context (hip.set_dparf); the backward runs under the
+    forward's, whatever was set in between."""
 
     @staticmethod
     def forward(ctx, tokens, pts_smpl, centres, rot):
         _no_grad_inputs("HumanRepresentationFn", pts_smpl=pts_smpl, centres=centres, rot=rot)
         _on_device("HumanRepresentationFn", tokens)
         ctx.save_for_backward(pts_smpl, centres, rot)
+        ctx.dparf = hip.dparf_in_force(tokens.device)
         return hip.dparf_encode(pts_smpl, centres, rot, tokens)
 
     @staticmethod
     def backward(ctx, grad_out):
         pts_smpl, centres, rot = ctx.saved_tensors
+        hip.set_dparf(*ctx.dparf, grad_out.device)
         return hip.dparf_encode_bwd(pts_smpl, centres, rot, grad_out), None, None, None
 
 
